@@ -202,6 +202,29 @@ def plumbing_rehearsal(args, rank, world):
     return 0
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each tensor as ``out_dir/<name>.npy`` in float32 (the headline's is 2 MB at the default size).
+    A tensor larger than its share of DUMP_BYTES is cut to a fixed sample of its leading (batch) rows, drawn with seed 0
+    and kept in ascending order, so that two runs with the same arguments write the same rows."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        t = t.detach().float()
+        rows = t.shape[0]
+        keep = max(1, min(rows, budget // max(1, 4 * t[0].numel())))
+        if keep < rows:
+            idx = torch.randperm(rows, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            t = t[idx.to(t.device)]
+        a = t.cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        print(f"[bench] dumped {name} {tuple(a.shape)} float32 ({keep} of {rows} rows) -> {out_dir}",
+              file=sys.stderr, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -222,7 +245,13 @@ def main():
     ap.add_argument("--headline-only", action="store_true",
                     help="profile runs: only the headline loop (dense key sweep), no extras -- every attention "
                          "launch in a rocprofv3 trace of this command is then the launch `roofline` describes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline loop's last step returned (the next state "
+                         "x_{t-1}, [batch, seq-len, 8]) as DIR/x_next.npy (float32; x_next_rank<r>.npy per rank for "
+                         "N > 1); the inputs depend only on the arguments, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without an external launcher: this process never touches the GPU, it only
@@ -303,6 +332,9 @@ def main():
         timed(full_step, args.warmup)
         elapsed = timed(full_step, args.steps)
         by_mode[args.gemm_mode] = elapsed / args.steps
+        if args.dump_outputs:
+            # x is what the last timed step returned; the legs below reuse its buffer, so it is copied out now
+            dump_outputs(args.dump_outputs, {"x_next" if world == 1 else f"x_next_rank{rank}": x})
         lib.e3d_attn_skip_padded_tiles(1)
         elapsed_skip = float("nan")
         if not args.headline_only:
