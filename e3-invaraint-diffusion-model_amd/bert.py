@@ -216,13 +216,20 @@ def _attention_output(att, ctx, x, p_hidden=0.0):
                                        att.output.LayerNorm.bias, att.eps, p_hidden)
 
 
-def run_self_attention(att, x, mask, B, L, drop=(0.0, 0.0)):
+def run_self_attention(att, x, mask, B, L, drop=(0.0, 0.0), layout=None):
     """BertAttention on x [B*L,H] with key padding mask [B,L] (1/0): fused QKV GEMM ->
-    fused relative-key attention -> out-proj GEMM -> residual + LayerNorm."""
+    fused relative-key attention -> out-proj GEMM -> residual + LayerNorm.  ``layout`` (packing.PackedLayout,
+    inference): x holds the packed rows [layout.rows, H] and ``mask``, ``B``, ``L`` are not read."""
     sa = att.self
     w, b = qkv_weights(sa)
     qkv = F.linear(x, w, b, absmax=ops.absmax_slot(sa, "qkv", x.device))
     relkey = sa.position_embedding_type == "relative_key"
+    if layout is not None:
+        H = att.num_heads * 64
+        ctx = ops.attention_varlen(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], layout, layout, att.num_heads,
+                                   dist_emb=sa.distance_embedding.weight if relkey else None,
+                                   max_pos=sa.max_position_embeddings)
+        return _attention_output(att, ctx, x)
     ctx = F.attention(qkv, None, B, att.num_heads, L, L, key_mask=mask,
                       dist_emb=sa.distance_embedding.weight if relkey else None,
                       max_pos=sa.max_position_embeddings, drop_p=drop[1])
@@ -237,31 +244,43 @@ def project_cross_kv(att, enc):
     return F.linear(enc, w, b, absmax=torch.zeros(1, device=enc.device, dtype=torch.float32))
 
 
-def run_cross_attention(att, x, kv, enc_mask, B, Lq, Lk, drop=(0.0, 0.0)):
+def run_cross_attention(att, x, kv, enc_mask, B, Lq, Lk, drop=(0.0, 0.0), layout=None, enc_layout=None):
+    """``layout`` / ``enc_layout`` (inference): segments of the packed query rows x and of the key rows kv -- packed too,
+    or a padded cache (``enc_layout.padded_frame``); ``enc_mask``, ``B``, ``Lq``, ``Lk`` are then not read."""
     q = F.linear(x, att.self.query.weight, att.self.query.bias, absmax=ops.absmax_slot(att.self, "q", x.device))
+    if layout is not None:
+        H = att.num_heads * 64
+        ctx = ops.attention_varlen(q, kv[:, :H], kv[:, H:], layout, enc_layout, att.num_heads)
+        return _attention_output(att, ctx, x)
     ctx = F.attention(q, kv, B, att.num_heads, Lq, Lk, key_mask=enc_mask, drop_p=drop[1])
     return _attention_output(att, ctx, x, drop[0])
 
 
-def run_layer(layer, x, mask, B, L, cross_kv=None, enc_mask=None, Lk=None, drop=(0.0, 0.0)):
-    """``drop`` = (hidden, attention-probability) dropout rates of this call (training only)."""
-    x = run_self_attention(layer.attention, x, mask, B, L, drop)
+def run_layer(layer, x, mask, B, L, cross_kv=None, enc_mask=None, Lk=None, drop=(0.0, 0.0), layout=None,
+              enc_layout=None):
+    """``drop`` = (hidden, attention-probability) dropout rates of this call (training only).  ``layout`` /
+    ``enc_layout``: packed rows (run_self_attention, run_cross_attention)."""
+    x = run_self_attention(layer.attention, x, mask, B, L, drop, layout=layout)
     if hasattr(layer, "crossattention"):
         if cross_kv is None:
             raise ValueError("decoder layer needs encoder states")
-        x = run_cross_attention(layer.crossattention, x, cross_kv, enc_mask, B, L, Lk, drop)
+        x = run_cross_attention(layer.crossattention, x, cross_kv, enc_mask, B, L, Lk, drop, layout=layout,
+                                enc_layout=enc_layout)
     inter = F.linear(x, layer.intermediate.dense.weight, layer.intermediate.dense.bias, ops.ACT_GELU)
     return F.linear_residual_layernorm(inter, layer.output.dense.weight, layer.output.dense.bias, x,
                                        layer.output.LayerNorm.weight, layer.output.LayerNorm.bias, layer.eps, drop[0])
 
 
-def run_encoder(encoder, x, mask, B, L, enc=None, enc_mask=None, Lk=None, cross_kv=None):
+def run_encoder(encoder, x, mask, B, L, enc=None, enc_mask=None, Lk=None, cross_kv=None, layout=None, enc_layout=None):
     """BertEncoder(...).last_hidden_state on flat activations.  ``cross_kv`` (list, one per
-    layer) short-cuts the per-layer K/V projection of ``enc``."""
+    layer) short-cuts the per-layer K/V projection of ``enc``.  ``layout`` / ``enc_layout`` (packing.PackedLayout,
+    inference): x (and enc) hold packed rows; the masks, B, L and Lk are then not read."""
     drop = dropout_rates(encoder)
+    if layout is not None and drop != (0.0, 0.0):
+        raise RuntimeError("packed layouts are inference-only: put the model in eval mode")
     for i, layer in enumerate(encoder.layer):
         kv = None
         if hasattr(layer, "crossattention"):
             kv = cross_kv[i] if cross_kv is not None else project_cross_kv(layer.crossattention, enc)
-        x = run_layer(layer, x, mask, B, L, kv, enc_mask, Lk, drop)
+        x = run_layer(layer, x, mask, B, L, kv, enc_mask, Lk, drop, layout=layout, enc_layout=enc_layout)
     return x

@@ -33,16 +33,22 @@ class SELayer(nn.Module):
         m0, m2 = self.adaLN_modulation[0], self.adaLN_modulation[2]
         return F.linear(F.linear(c, m0.weight, m0.bias, ops.ACT_SILU), m2.weight, m2.bias)
 
-    def run(self, x, c, mask, B, L, mod=None):
+    def run(self, x, c, mask, B, L, mod=None, layout=None):
         """x [B*L,H]; c [B*L,H] (per token) or [B,H] (one conditioning row per item).  ``mod``: the rows
         ``modulation(c)`` would give, computed by the caller ([B*L,6H], [B,6H], or ONE row [1,6H] shared by every
-        item: samplers precompute it per timestep) -- ``c`` is then not read."""
+        item: samplers precompute it per timestep) -- ``c`` is then not read.  ``layout`` (packing.PackedLayout,
+        inference): x holds packed rows [layout.rows, H] (pass B = 1, L = layout.rows) and the conditioning is per
+        token ([rows,H]) or ONE row shared by every item (a sampler's single timestep); ``mask`` is not read."""
         if mod is None:
             mod = self.modulation(c)
+        if layout is not None:
+            assert mod.shape[0] in (1, x.shape[0]), ("a packed batch takes per-token conditioning or one shared row",
+                                                     tuple(mod.shape))
+            assert bert.dropout_rates(self.attn) == (0.0, 0.0), "packed layouts are inference-only"
         rows_per_cond = x.shape[0] // mod.shape[0]
         assert rows_per_cond in (1, L, B * L) and rows_per_cond * mod.shape[0] == x.shape[0], (x.shape, mod.shape)
         drop = bert.dropout_rates(self.attn)   # (hidden, attention) rates in training, zeros in eval
-        att = bert.run_self_attention(self.attn, x, mask, B, L, drop)
+        att = bert.run_self_attention(self.attn, x, mask, B, L, drop, layout=layout)
         x = F.adaln_gate(x, att, mod, 0, rows_per_cond)
         h = F.dropout(F.linear(x, self.mlp[0].weight, self.mlp[0].bias, ops.ACT_GELU), self.mlp[2].p, self.training)
         h = F.dropout(F.linear(h, self.mlp[3].weight, self.mlp[3].bias), self.mlp[4].p, self.training)

@@ -10,7 +10,7 @@ from ctypes import c_char_p, c_float, c_int, c_int64, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("E3D_HIP_LIB", os.path.join(_HERE, "libe3d_hip.so"))   # override: kernel experiments
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 _P = c_void_p
 _SIGNATURES = {
@@ -96,6 +96,9 @@ _SIGNATURES = {
     "e3d_adamw_step_dev": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P]),
     "e3d_dropout_set_epoch_ptr": (c_int, [_P]),
     "e3d_adamw_step": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, _P, c_float, c_float, c_float, c_float, c_float, c_int, _P]),
+    # attention over variable-length segments (ABI v5)
+    "e3d_attn_varlen_fwd": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, _P, _P, _P, _P, _P, c_int, _P, c_int, _P,
+                                    c_int64, c_int, c_int, c_int, c_int, _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

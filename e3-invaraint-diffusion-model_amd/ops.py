@@ -454,6 +454,43 @@ def attention(q, k, v, B, nh, Lq, Lk, key_mask=None, dist_emb=None, max_pos=0, w
     return (out, lse) if want_lse else out
 
 
+def attention_varlen(q, k, v, q_layout, k_layout, nh, dist_emb=None, max_pos=0, mode=None):
+    """Attention over the segments of packed batches (packing.PackedLayout; include/e3d_hip.h, e3d_attn_varlen_fwd).
+    q [q_layout.rows, >= nh*64] and k, v [k_layout.rows, ...] are row-strided 2-D views (e.g. slices of a fused QKV
+    buffer).  Segment s of the queries attends to segment s of the keys -- a packed buffer, or a padded cache when
+    ``k_layout.padded_frame``.  With ``dist_emb`` (rel-key self-attention) both layouts must have the same lengths.
+    Returns ctx [q_layout.rows, nh*64]; rows of no segment are zero.  Inference only (no backward exists): raises when
+    grad mode is on and an input requires grad -- a call that autograd would have to differentiate.
+    Arithmetic (``mode``, default ATTN_MODE): bf16x3 / bf16x6 / f16x3 as ``attention``; "f32" runs the fp32-grade bf16x6
+    form here (there is no exact-fp32 varlen kernel), while ``attention`` runs its exact fp32 MFMA kernel -- a packed
+    chain under E3D_GEMM_MODE=f32 therefore differs from the padded one by bf16x6 rounding (~1e-6) in attention."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k, v, dist_emb)):
+        raise RuntimeError("attention_varlen is inference-only: run it under torch.no_grad()")
+    for n, t in (("q", q), ("k", k), ("v", v), ("dist_emb", dist_emb)):
+        _chk(t, "attention_varlen." + n)
+    assert q.dim() == 2 and q.stride(1) == 1 and k.stride(1) == 1 and v.stride(1) == 1
+    if q.shape[0] != q_layout.rows or k.shape[0] != k_layout.rows or v.shape[0] != k_layout.rows:
+        raise ValueError(f"attention_varlen: rows q {q.shape[0]} / k {k.shape[0]} / v {v.shape[0]} against layouts of "
+                         f"{q_layout.rows} / {k_layout.rows} rows")
+    if q_layout.B != k_layout.B:
+        raise ValueError(f"attention_varlen: {q_layout.B} query segments against {k_layout.B} key segments")
+    if dist_emb is not None:
+        assert dist_emb.is_contiguous() and dist_emb.shape == (2 * max_pos - 1, 64), dist_emb.shape
+        if not q_layout.same_segments(k_layout):
+            raise ValueError("attention_varlen: relative_key self-attention needs q_len == k_len for every segment")
+    alloc = torch.zeros if q_layout.padded_frame else torch.empty   # (a packed layout's kernel writes every row)
+    out = alloc((q_layout.rows, nh * 64), device=q.device, dtype=torch.float32)
+    terms = GEMM_MODES[ATTN_MODE if mode is None else mode]
+    if q_layout.n_tiles == 0:
+        return out
+    with _timed("attn_varlen", (q_layout.B, nh, q_layout.rows, k_layout.rows)):
+        hip.check(hip.lib().e3d_attn_varlen_fwd(
+            _p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(q_layout.start_dev), _p(q_layout.len_dev),
+            _p(k_layout.start_dev), _p(k_layout.len_dev), _p(q_layout.tiles), q_layout.n_tiles, _p(dist_emb), max_pos,
+            _p(out), q_layout.rows, nh, q_layout.max_len, k_layout.max_len, terms, _stream()), "e3d_attn_varlen_fwd")
+    return out
+
+
 def residual_layernorm(x, residual, gamma, beta, eps, want_s=False, drop=None):
     """LayerNorm(x + residual); ``drop`` = (p, seed): LayerNorm(dropout(x) + residual) with the multipliers of
     ``dropout(x, p, seed)`` applied inside the kernel."""

@@ -83,6 +83,30 @@ class ConditionalBertForDiffusionBase(nn.Module):
         return self.amino_acid_predictor.run(x).view(B, L, -1)
 
 
+    def forward_packed(self, timestep, noised_ligand_seq, ligand_angle, receptor_seq, receptor_angle, layout,
+                       receptor_layout):
+        """``forward`` on packed rows (packing.PackedLayout, inference): every input holds its batch's valid rows back
+        to back -- ligand rows [layout.rows, C] / [layout.rows, 8], pocket rows [receptor_layout.rows, 20] /
+        [receptor_layout.rows, 8] -- and every item shares ONE timestep (``timestep`` has one element: the sampler's
+        step).  Returns the logits of the packed ligand rows [layout.rows, 20]; valid rows equal ``forward``'s to fp32
+        rounding, rows of the packed tail are finite and meaningless."""
+        require_gpu(timestep, noised_ligand_seq, ligand_angle, receptor_seq, receptor_angle)
+        if timestep.numel() != 1:
+            raise ValueError(f"a packed batch shares one timestep: got {timestep.numel()} values")
+        rows, rows_r = layout.rows, receptor_layout.rows
+        ops.reset_absmax(noised_ligand_seq.device)
+        temb = self.timestep_projector(timestep.reshape(-1)).contiguous()                 # [1,H]
+        lig_seq = self.ligand_seq_embedding.run(flat2d(noised_ligand_seq))
+        lig_ang = self.ligand_angle_embedding.run(flat2d(ligand_angle), post_add=temb, rows_per_add=rows)
+        lig = self.ligand_feature_emb.run(lig_seq, lig_ang, None, 1, rows, layout=layout)
+        rec_seq = self.receptor_seq_embedding.run(flat2d(receptor_seq))
+        rec_ang = self.receptor_angle_embedding.run(flat2d(receptor_angle), post_add=temb, rows_per_add=rows_r)
+        rec = self.ligand_feature_emb.run(rec_seq, rec_ang, None, 1, rows_r, layout=receptor_layout)
+        x = bert.run_encoder(self.decoder, lig, None, 1, rows, enc=rec, layout=layout, enc_layout=receptor_layout)
+        x = self.decoder_normalize.run(x, temb, None, 1, rows, layout=layout)
+        return self.amino_acid_predictor.run(x)
+
+
 def onehot_to_index(onehot: torch.Tensor) -> torch.Tensor:
     """[.., C] one-hot (all-zero rows = padding) -> int32 class index, -1 for all-zero rows."""
     idx = onehot.argmax(dim=-1).to(torch.int32)

@@ -13,12 +13,13 @@ if __package__ in (None, ""):  # executed as a script from inside this directory
     __package__ = "e3diff_amd.sequence_model"
 
 import os
+import warnings
 
 import torch
 from torch.nn import functional as F
 from torch.utils.data import DataLoader
 
-from .. import ops
+from .. import ops, packing
 from ..bert import BertConfig
 from .dataset import AA_VOCAB, LigandBindingSiteDataset
 from .model import PeptideDiff, onehot_to_index
@@ -30,6 +31,9 @@ THREAD_NUM = 16
 DATA_PATH = "./data/biolip.pt"
 MODEL_PATH = ""  # trained state_dict (reference checkpoint key names)
 OUTPUT_PATH = "./data/from_generated_angles/output.pkl"
+# Packed chains (denoise(pack=True)): the batch runs on its valid rows only; off by default, E3D_SAMPLE_PACK=1 turns it
+# on for ``run()``.
+PACK = os.environ.get("E3D_SAMPLE_PACK", "0") == "1"
 
 CONFIG = {
     "pocket_ext": 0,
@@ -134,9 +138,13 @@ class GraphedDenoiseStep:
     150 launches per step): default for at most ``GRAPH_MAX_ROWS`` token rows, ``use_graph`` / E3D_SAMPLE_GRAPH override."""
 
     def __init__(self, model, x_like, ligand_angles, ligand_mask, receptor_seq, receptor_angles, receptor_mask, noise_schedule,
-                 transition, diverse, T, inject_u=False):
+                 transition, diverse, T, inject_u=False, layouts=None):
+        """``layouts`` = (ligand, pocket) packing.PackedLayout: the step runs ``model.forward_packed`` on packed rows
+        (``x_like`` [1, rows, C], packed angles and pocket inputs; the masks are not read).  The layouts' device tables
+        are fixed for the chain, so the capture holds them like any other argument."""
         dev = x_like.device
         self.args = (ligand_angles, ligand_mask, receptor_seq, receptor_angles, receptor_mask)
+        self.layouts = layouts
         self.model, self.schedule, self.transition, self.diverse, self.T = model, noise_schedule, transition, diverse, T
         self.x = x_like.clone()
         self.s = torch.zeros((x_like.shape[0], 1), device=dev)
@@ -158,7 +166,11 @@ class GraphedDenoiseStep:
             self.out = self._body()
 
     def _body(self):
-        logits = self.model.forward(self.s, self.x, *self.args)
+        if self.layouts is None:
+            logits = self.model.forward(self.s, self.x, *self.args)
+        else:
+            ang, _, rseq, rang, _ = self.args
+            logits = self.model.forward_packed(self.s, self.x, ang, rseq, rang, *self.layouts)[None]
         return sample_p_zs_given_zt_discrete((self.s + 1) / self.T, self.s / self.T, self.x, logits, self.schedule, self.transition,
                                              self.diverse, is_last_step=False, u=self.u)
 
@@ -187,11 +199,19 @@ def _use_graph(x):
 
 @torch.no_grad()
 def denoise(batch, model: PeptideDiff, noise_schedule, transition, diverse, x_T=None, us=None,
-            generated_angles=None, timesteps=None, trim_padding=False, use_graph=None):
+            generated_angles=None, timesteps=None, trim_padding=False, use_graph=None, pack=False):
     """Full reverse chain over CONFIG["timesteps"] steps + recovery metrics (reference
     sample.py:181-229).  ``x_T`` / ``us`` inject the initial one-hot noise and the per-step
     uniforms (parity tests); ``generated_angles`` replaces the dataset's ligand angles
-    (sample_by_generated_angles.py:202)."""
+    (sample_by_generated_angles.py:202).
+
+    ``pack=True``: the chain runs on the packed valid rows of the batch -- ligand and pocket (packing.PackedLayout,
+    varlen attention, ``model.forward_packed``; every item shares the step's timestep) -- so its cost follows the
+    residues the items have.  The results have the same form as the padded chain's.  ``x_T`` and ``us`` (padded layout)
+    are gathered to the packed rows; the default initial noise is drawn in the padded frame as before, the default
+    uniforms of ``diverse`` chains are drawn for the packed rows, i.e. from a different place in the random stream.
+    Masks that are not prefix masks run the trimmed frame instead (with a warning); an item with ligand rows but an
+    empty pocket raises ``ValueError``."""
     T = CONFIG["timesteps"] if timesteps is None else timesteps
     B, max_len, C = batch["ligand_seq"].shape
     dev = next(model.parameters()).device
@@ -202,35 +222,45 @@ def denoise(batch, model: PeptideDiff, noise_schedule, transition, diverse, x_T=
     receptor_seq = batch["receptor_seq"].to(dev)
     receptor_angles = batch["receptor_angles"].to(dev)
     receptor_mask = batch["receptor_attn_mask"].to(dev)
-    if trim_padding:
-        # as structure_model/sample.py::p_sample_loop(trim_padding=True): padding cannot influence valid positions,
-        # and only valid positions are read below, so the chain runs on the frame of the longest ligand / pocket
-        from ..structure_model.sample import trimmed_length
-        Ll, Lr = trimmed_length(ligand_mask), trimmed_length(receptor_mask)
-        x, ligand_seq, ligand_mask = x[:, :Ll].contiguous(), ligand_seq[:, :Ll], ligand_mask[:, :Ll].contiguous()
-        ligand_angles = ligand_angles[:, :Ll].contiguous()
-        receptor_seq, receptor_angles = receptor_seq[:, :Lr].contiguous(), receptor_angles[:, :Lr].contiguous()
-        receptor_mask = receptor_mask[:, :Lr].contiguous()
-        if us is not None:
-            us = [u[:, :Ll] if u is not None and u.dim() >= 2 else u for u in us]
-    graphed = None
-    if (_use_graph(x) if use_graph is None else use_graph) and T > 4:
-        try:
-            graphed = GraphedDenoiseStep(model, x, ligand_angles.contiguous(), ligand_mask, receptor_seq, receptor_angles, receptor_mask,
-                                         noise_schedule, transition, diverse, T, inject_u=us is not None)
-        except Exception as e:   # noqa: BLE001 -- any capture problem: eager launches are always correct
-            import warnings
-            warnings.warn(f"HIP-graph capture of the sequence reverse step failed ({type(e).__name__}: {e}); using eager launches")
-    for n, s_int in enumerate(reversed(range(T))):
-        if graphed is not None and s_int > 0:
-            u_n = None if us is None else us[n]
-            x = graphed.step(s_int, x, None if u_n is None else u_n.to(dev).float())
-            continue
-        s_array = s_int * torch.ones((B, 1), device=dev)
-        t_array = s_array + 1
-        logits = model.forward(s_array, x, ligand_angles, ligand_mask, receptor_seq, receptor_angles, receptor_mask)
-        x = sample_p_zs_given_zt_discrete(t_array / T, s_array / T, x, logits, noise_schedule, transition,
-                                          diverse, is_last_step=s_int == 0, u=None if us is None else us[n])
+    layouts = None
+    if pack:
+        layouts = packing.layouts_or_none(ligand_mask, receptor_mask)
+        if layouts is None:
+            warnings.warn("pack=True: a padding mask is not a prefix mask, so the batch cannot be packed; running the "
+                          "trimmed frame instead")
+            trim_padding = True
+    if layouts is not None:
+        x = _denoise_packed(model, layouts, x, ligand_angles, receptor_seq, receptor_angles, noise_schedule, transition,
+                            diverse, T, us, use_graph)
+    else:
+        if trim_padding:
+            # as structure_model/sample.py::p_sample_loop(trim_padding=True): padding cannot influence valid positions,
+            # and only valid positions are read below, so the chain runs on the frame of the longest ligand / pocket
+            from ..structure_model.sample import trimmed_length
+            Ll, Lr = trimmed_length(ligand_mask), trimmed_length(receptor_mask)
+            x, ligand_seq, ligand_mask = x[:, :Ll].contiguous(), ligand_seq[:, :Ll], ligand_mask[:, :Ll].contiguous()
+            ligand_angles = ligand_angles[:, :Ll].contiguous()
+            receptor_seq, receptor_angles = receptor_seq[:, :Lr].contiguous(), receptor_angles[:, :Lr].contiguous()
+            receptor_mask = receptor_mask[:, :Lr].contiguous()
+            if us is not None:
+                us = [u[:, :Ll] if u is not None and u.dim() >= 2 else u for u in us]
+        graphed = None
+        if (_use_graph(x) if use_graph is None else use_graph) and T > 4:
+            try:
+                graphed = GraphedDenoiseStep(model, x, ligand_angles.contiguous(), ligand_mask, receptor_seq, receptor_angles, receptor_mask,
+                                             noise_schedule, transition, diverse, T, inject_u=us is not None)
+            except Exception as e:   # noqa: BLE001 -- any capture problem: eager launches are always correct
+                warnings.warn(f"HIP-graph capture of the sequence reverse step failed ({type(e).__name__}: {e}); using eager launches")
+        for n, s_int in enumerate(reversed(range(T))):
+            if graphed is not None and s_int > 0:
+                u_n = None if us is None else us[n]
+                x = graphed.step(s_int, x, None if u_n is None else u_n.to(dev).float())
+                continue
+            s_array = s_int * torch.ones((B, 1), device=dev)
+            t_array = s_array + 1
+            logits = model.forward(s_array, x, ligand_angles, ligand_mask, receptor_seq, receptor_angles, receptor_mask)
+            x = sample_p_zs_given_zt_discrete(t_array / T, s_array / T, x, logits, noise_schedule, transition,
+                                              diverse, is_last_step=s_int == 0, u=None if us is None else us[n])
     pred_idx, true_idx = x.argmax(dim=-1).cpu(), ligand_seq.argmax(dim=-1).cpu()
     mask = ligand_mask.bool().cpu()
     ids, true_sequences, pred_sequences, recovery_rates = [], [], [], []
@@ -245,6 +275,37 @@ def denoise(batch, model: PeptideDiff, noise_schedule, transition, diverse, x_T=
     return ids, true_sequences, pred_sequences, recovery_rates
 
 
+def _denoise_packed(model, layouts, x, ligand_angles, receptor_seq, receptor_angles, noise_schedule, transition, diverse, T,
+                    us, use_graph):
+    """The chain of ``denoise`` on packed rows: state [1, rows, C] (the posterior kernel sees B = 1, L = rows with one
+    Q pair: every item shares the step), returned as [B, L, C] with zeros at the padding positions."""
+    lay, lay_r = layouts
+    dev = x.device
+    xp = lay.pack(x.float())[None]
+    ang = lay.pack(ligand_angles.float())
+    rseq, rang = lay_r.pack(receptor_seq.float()), lay_r.pack(receptor_angles.float())
+    if us is not None:
+        us = [lay.pack(u.to(dev).float())[None] if u is not None and u.dim() >= 2 else u for u in us]
+    graphed = None
+    if (_use_graph(xp) if use_graph is None else use_graph) and T > 4:
+        try:
+            graphed = GraphedDenoiseStep(model, xp, ang, None, rseq, rang, None, noise_schedule, transition, diverse, T,
+                                         inject_u=us is not None, layouts=layouts)
+        except Exception as e:   # noqa: BLE001 -- any capture problem: eager launches are always correct
+            warnings.warn(f"HIP-graph capture of the packed sequence reverse step failed ({type(e).__name__}: {e}); using "
+                          "eager launches")
+    for n, s_int in enumerate(reversed(range(T))):
+        if graphed is not None and s_int > 0:
+            u_n = None if us is None else us[n]
+            xp = graphed.step(s_int, xp, u_n)
+            continue
+        s_array = torch.full((1, 1), float(s_int), device=dev)
+        logits = model.forward_packed(s_array, xp, ang, rseq, rang, lay, lay_r)[None]
+        xp = sample_p_zs_given_zt_discrete((s_array + 1) / T, s_array / T, xp, logits, noise_schedule, transition, diverse,
+                                           is_last_step=s_int == 0, u=None if us is None else us[n])
+    return lay.unpack(xp[0])
+
+
 def run(transition, diverse=True):
     import pandas as pd
     loader = get_dataloader(DATA_PATH)
@@ -253,7 +314,7 @@ def run(transition, diverse=True):
     cols = ([], [], [], [])
     for idx, batch in enumerate(loader):
         print(f"Generating Batch {idx}")
-        for acc, part in zip(cols, denoise(batch, model, schedule, transition, diverse)):
+        for acc, part in zip(cols, denoise(batch, model, schedule, transition, diverse, pack=PACK)):
             acc.extend(part)
     res = pd.DataFrame(zip(*cols), columns=["structure_ids", "true_sequence", "predict_sequence", "recovery_rate"])
     res.to_pickle(OUTPUT_PATH)

@@ -25,8 +25,9 @@ class ReceptorCache:
     noised ligand (reference model.py:191-200), so a sampler computes it once per batch instead
     of once per reverse step (41 % of per-step FLOPs + the cross K/V projections)."""
 
-    def __init__(self, encoder_states, cross_kv, mask, B, L):
+    def __init__(self, encoder_states, cross_kv, mask, B, L, layout=None):
         self.encoder_states, self.cross_kv, self.mask, self.B, self.L = encoder_states, cross_kv, mask, B, L
+        self.layout = layout   # packing.PackedLayout of the pocket rows, or None (padded frame)
 
 
 class ConditionalBertForDiffusionBase(nn.Module):
@@ -48,11 +49,20 @@ class ConditionalBertForDiffusionBase(nn.Module):
 
     # -- the two halves of forward ------------------------------------------------------------
     def encode_receptor(self, receptor_seq, receptor_angles, receptor_attention_masks,
-                        project_cross_kv=True) -> ReceptorCache:
-        """reference model.py:191-200 (+ the decoder layers' cross K/V projections)."""
+                        project_cross_kv=True, layout=None) -> ReceptorCache:
+        """reference model.py:191-200 (+ the decoder layers' cross K/V projections).  ``layout``
+        (packing.PackedLayout of the pocket mask, inference): the padded inputs are packed and the pocket runs on its
+        valid rows only; the cache then holds packed rows and carries the layout."""
         require_gpu(receptor_seq, receptor_angles, receptor_attention_masks)
         B, L = receptor_angles.shape[:2]
         ops.reset_absmax(receptor_angles.device)   # |Q|, |K| bounds of the attention calls: fresh per batch / chain
+        if layout is not None:
+            ang = self.receptor_angle_emb.run(flat2d(layout.pack(receptor_angles)))
+            seq = self.receptor_seq_emb.run(flat2d(layout.pack(receptor_seq)))
+            x = self.receptor_emb.run(ang, seq, None, 1, layout.rows, layout=layout)
+            x = bert.run_encoder(self.encoder, x, None, 1, layout.rows, layout=layout)
+            kv = [bert.project_cross_kv(layer.crossattention, x) for layer in self.decoder.layer] if project_cross_kv else None
+            return ReceptorCache(x, kv, None, B, L, layout=layout)
         mask = receptor_attention_masks.contiguous().float()
         ang = self.receptor_angle_emb.run(flat2d(receptor_angles))
         seq = self.receptor_seq_emb.run(flat2d(receptor_seq))
@@ -70,9 +80,15 @@ class ConditionalBertForDiffusionBase(nn.Module):
         temb = self.timestep_projector(timesteps.reshape(-1)).contiguous()
         return self.timestep_emb.modulation(temb)
 
-    def decode(self, timestep, noised_ligand_angles, ligand_attention_masks, receptor: ReceptorCache, mod=None):
+    def decode(self, timestep, noised_ligand_angles, ligand_attention_masks, receptor: ReceptorCache, mod=None,
+               layout=None):
         """reference model.py:202-214.  ``mod`` ([1,6H] or [B,6H]): ``timestep_modulation`` of this step's timestep,
-        if the caller has it already (``timestep`` is then not read)."""
+        if the caller has it already (``timestep`` is then not read).
+        ``layout`` (packing.PackedLayout of the ligand mask, inference): ``noised_ligand_angles`` are the packed rows
+        [layout.rows, F], the receptor cache must be packed too (``encode_receptor(..., layout=)``), every item shares
+        one timestep (``mod`` [1,6H]) and the result is packed [layout.rows, F]; ``ligand_attention_masks`` is not read."""
+        if layout is not None:
+            return self._decode_packed(timestep, noised_ligand_angles, receptor, mod, layout)
         require_gpu(timestep, noised_ligand_angles, ligand_attention_masks)
         B, L = noised_ligand_angles.shape[:2]
         mask = ligand_attention_masks.contiguous().float()
@@ -83,6 +99,22 @@ class ConditionalBertForDiffusionBase(nn.Module):
         x = bert.run_encoder(self.decoder, x, mask, B, L, enc=receptor.encoder_states,
                              enc_mask=receptor.mask, Lk=receptor.L, cross_kv=receptor.cross_kv)
         return self.angles_predictor.run(x).view(B, L, -1)
+
+    def _decode_packed(self, timestep, x_packed, receptor, mod, layout):
+        require_gpu(x_packed)
+        if receptor.layout is None:
+            raise ValueError("a packed decode needs the pocket packed as well: encode_receptor(..., layout=)")
+        assert x_packed.dim() == 2 and x_packed.shape[0] == layout.rows, (tuple(x_packed.shape), layout.rows)
+        if mod is None:
+            t = timestep.reshape(-1)
+            assert bool((t == t[0]).all()), "a packed batch shares one timestep"
+            mod = self.timestep_modulation(t[:1])
+        assert mod.shape[0] == 1, "a packed batch shares one timestep: mod must be one row [1,6H]"
+        x = self.ligand_angle_emb.run(x_packed.contiguous().float())
+        x = self.timestep_emb.run(x, None, None, 1, layout.rows, mod=mod, layout=layout)
+        x = bert.run_encoder(self.decoder, x, None, 1, layout.rows, enc=receptor.encoder_states,
+                             cross_kv=receptor.cross_kv, layout=layout, enc_layout=receptor.layout)
+        return self.angles_predictor.run(x)
 
     def forward(self, timestep, noised_ligand_angles, ligand_attention_masks,
                 receptor_seq, receptor_angles, receptor_attention_masks,

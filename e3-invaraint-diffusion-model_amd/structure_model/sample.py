@@ -23,7 +23,7 @@ import warnings
 import torch
 from torch import nn
 
-from .. import ops
+from .. import ops, packing
 from ..bert import BertConfig
 from .dataset import LigandBindingSiteDataset, NoisedAnglesDataset
 from .model import ConditionalBertForDiffusion
@@ -39,6 +39,9 @@ STEP = 1  # stride over timesteps; >1 trades quality for speed (reference sample
 # samples at full fp32: ``sample()`` runs the fp32-grade f16x3 kernels (two fp16 terms per operand, see ops.py; 4.9e-6
 # from the CPU oracle end to end vs 3.2e-6 for the exact fp32 MFMA path) unless E3D_GEMM_MODE says otherwise.
 ARITHMETIC = "f16x3"
+# Packed chains (p_sample_loop(pack=True)): the batch runs on its valid rows only; off by default, E3D_SAMPLE_PACK=1 turns
+# it on for ``sample()``.
+PACK = os.environ.get("E3D_SAMPLE_PACK", "0") == "1"
 
 CONFIG = {
     "pocket_ext": 0,
@@ -86,7 +89,7 @@ def p_sample(model, ligand_mask, ligand_angle_noise, receptor_seq, receptor_mask
 
 
 def _reverse_step(model, ligand_mask, x_t, receptor_seq, receptor_mask, receptor_angle, timestep,
-                  betas, noise, receptor_cache, out, wrap, mod=None):
+                  betas, noise, receptor_cache, out, wrap, mod=None, layout=None):
     tab = _tables(betas)
     if isinstance(timestep, int):
         t_index = timestep
@@ -97,7 +100,10 @@ def _reverse_step(model, ligand_mask, x_t, receptor_seq, receptor_mask, receptor
         t_index = int(t_unique.item())
     if receptor_cache is None:
         receptor_cache = model.encode_receptor(receptor_seq, receptor_angle, receptor_mask)
-    eps_hat = model.decode(timestep, x_t, ligand_mask, receptor_cache, mod=mod)
+    if layout is None:
+        eps_hat = model.decode(timestep, x_t, ligand_mask, receptor_cache, mod=mod)
+    else:
+        eps_hat = model.decode(timestep, x_t, ligand_mask, receptor_cache, mod=mod, layout=layout)
     sra = float(tab.sqrt_recip_alphas[t_index])
     beta = float(tab.betas[t_index])
     s1m = float(tab.sqrt_one_minus_alphas_cumprod[t_index])
@@ -124,11 +130,14 @@ class GraphedReverseStep:
     busy with dependent kernels, the graph had nothing to remove.  Round 2, K-sliced small-M GEMMs of ~7 us per product
     (csrc/gemm_skinny.hip): eager launches are now host-bound at 2.4 ms per step, a replay takes 1.5 ms."""
 
-    def __init__(self, model, ligand_mask, cache, tab, x_like, wrap=True, draw=True, mod_table=None):
+    def __init__(self, model, ligand_mask, cache, tab, x_like, wrap=True, draw=True, mod_table=None, layout=None):
         """``draw``: the graph draws its own N(0,1) noise each replay; False: ``step`` takes the draw (parity tests).
-        ``mod_table`` [T,6H]: row t = model.timestep_modulation(t), read on the device by the step index."""
+        ``mod_table`` [T,6H]: row t = model.timestep_modulation(t), read on the device by the step index.
+        ``layout``: the step runs on packed ligand rows (``x_like`` [rows,F]; a packed ``cache``); its segment and tile
+        tables are device tensors fixed for the chain, so the capture holds them like any other argument."""
         dev = x_like.device
         self.model, self.mask, self.cache, self.wrap, self.mod_table = model, ligand_mask, cache, wrap, mod_table
+        self.layout = layout
         self.x = torch.empty_like(x_like)
         self.out = torch.empty_like(x_like)
         self.noise = torch.zeros_like(x_like)
@@ -148,7 +157,10 @@ class GraphedReverseStep:
 
     def _body(self):
         mod = None if self.mod_table is None else self.mod_table.index_select(0, self.t[:1])
-        eps_hat = self.model.decode(self.t, self.x, self.mask, self.cache, mod=mod)
+        if self.layout is None:
+            eps_hat = self.model.decode(self.t, self.x, self.mask, self.cache, mod=mod)
+        else:
+            eps_hat = self.model.decode(self.t, self.x, self.mask, self.cache, mod=mod, layout=self.layout)
         if self.draw:
             self.noise.normal_()
         ops.ddpm_step_wrap_table(self.x, eps_hat.contiguous(), self.noise, self.coef, self.t, wrap=self.wrap, out=self.out)
@@ -173,7 +185,7 @@ def _use_graph(x):
     env = os.environ.get("E3D_SAMPLE_GRAPH")
     if env in ("0", "1"):
         return env == "1"
-    return x.shape[0] * x.shape[1] <= GRAPH_MAX_ROWS
+    return x.shape[:-1].numel() <= GRAPH_MAX_ROWS    # (token rows: B x L, or the rows of a packed state)
 
 
 def trimmed_length(mask, multiple=32):
@@ -192,16 +204,32 @@ def trimmed_length(mask, multiple=32):
 def p_sample_loop(model: nn.Module, ligand_mask, ligand_angle_noise, receptor_seq, receptor_mask,
                   receptor_angle, total_timesteps: int, betas, disable_pbar: bool = False,
                   noises=None, return_device: bool = False, step: int = None, use_graph: bool = None,
-                  trim_padding: bool = False) -> torch.Tensor:
+                  trim_padding: bool = False, pack: bool = False) -> torch.Tensor:
     """Full reverse chain; returns [T/STEP, B, L, n_ft] (on the host like the reference,
     sample.py:101-144, unless ``return_device``).  ``noises`` [T/STEP,B,L,n_ft] injects the draws.
     ``use_graph``: replay one captured HIP graph per step (None: by size, E3D_SAMPLE_GRAPH=0/1 overrides -- see
-    GraphedReverseStep); falls back to eager launches if the capture fails."""
+    GraphedReverseStep); falls back to eager launches if the capture fails.
+
+    ``pack=True``: the chain runs on the packed valid rows of the batch -- ligand and pocket (packing.PackedLayout,
+    varlen attention) -- so its cost follows the residues the items have instead of the longest item.  Valid positions
+    agree with the padded and trimmed chains to fp32 rounding; every padding position comes back as 0, in the same
+    [T/STEP, B, L, n_ft] shape.  Injected ``noises`` (padded layout) are gathered to the packed rows; default draws are
+    made for the packed rows, i.e. they come from a different place in the random stream than the padded chain's.
+    Masks that are not prefix masks cannot be packed: the chain then runs the trimmed frame (with a warning).  An item
+    with ligand rows but an empty pocket raises ``ValueError``."""
     step = STEP if step is None else step
     tab = _tables(betas)
     order = list(reversed(range(0, total_timesteps, step)))
     x = ligand_angle_noise.contiguous().float()
     full_traj = None
+    if pack:
+        layouts = packing.layouts_or_none(ligand_mask, receptor_mask)
+        if layouts is not None:
+            return _p_sample_loop_packed(model, layouts, x, receptor_seq, receptor_angle, receptor_mask, total_timesteps,
+                                         tab, order, noises, return_device, use_graph)
+        warnings.warn("pack=True: a padding mask is not a prefix mask, so the batch cannot be packed; running the "
+                      "trimmed frame instead")
+        trim_padding = True
     if trim_padding:
         # Padding positions cannot influence valid ones (their keys carry the -10000 bias, whose softmax weight
         # underflows to exactly 0.0f; every other op is row-wise), so the chain only needs the rows up to the longest
@@ -228,7 +256,6 @@ def p_sample_loop(model: nn.Module, ligand_mask, ligand_angle_noise, receptor_se
             graphed = GraphedReverseStep(model, ligand_mask.contiguous().float(), cache, tab, x, draw=noises is None,
                                          mod_table=mod_table)
         except Exception as e:   # noqa: BLE001 -- any capture problem: eager launches are always correct
-            import warnings
             warnings.warn(f"HIP-graph capture of the reverse step failed ({type(e).__name__}: {e}); using eager launches")
             graphed = None
     for n, i in enumerate(order):
@@ -241,6 +268,36 @@ def p_sample_loop(model: nn.Module, ligand_mask, ligand_angle_noise, receptor_se
     if full_traj is not None:
         full_traj[:, :, :traj.shape[2]] = traj
         traj = full_traj
+    return traj if return_device else traj.cpu()
+
+
+def _p_sample_loop_packed(model, layouts, x, receptor_seq, receptor_angle, receptor_mask, total_timesteps, tab, order,
+                          noises, return_device, use_graph):
+    lay, lay_r = layouts
+    cache = model.encode_receptor(receptor_seq, receptor_angle, receptor_mask, layout=lay_r)
+    xp = lay.pack(x)                                                      # [rows, F], zero tail
+    noises_p = None if noises is None else lay.pack(noises.to(x.device).float(), dim=1)   # [T/STEP, rows, F]
+    traj = torch.empty((len(order),) + tuple(xp.shape), device=x.device, dtype=torch.float32)
+    mod_rows = model.timestep_modulation(torch.tensor(order, device=x.device, dtype=torch.long))
+    mod_table = torch.zeros((total_timesteps, mod_rows.shape[1]), device=x.device, dtype=torch.float32)
+    mod_table[order] = mod_rows
+    graphed = None
+    if (_use_graph(xp) if use_graph is None else use_graph) and len(order) > 4:
+        try:
+            graphed = GraphedReverseStep(model, None, cache, tab, xp, draw=noises is None, mod_table=mod_table,
+                                         layout=lay)
+        except Exception as e:   # noqa: BLE001 -- any capture problem: eager launches are always correct
+            warnings.warn(f"HIP-graph capture of the packed reverse step failed ({type(e).__name__}: {e}); using eager "
+                          "launches")
+            graphed = None
+    for n, i in enumerate(order):
+        if graphed is not None:
+            xp = graphed.step(i, graphed.out if n else xp, None if noises_p is None else noises_p[n])
+            traj[n].copy_(xp)
+        else:
+            xp = _reverse_step(model, None, xp, None, None, None, i, tab, None if noises_p is None else noises_p[n],
+                               cache, traj[n], wrap=True, mod=mod_table[i:i + 1], layout=lay)
+    traj = lay.unpack(traj, dim=1)                                        # [T/STEP, B, L, F], zeros at padding
     return traj if return_device else traj.cpu()
 
 
@@ -299,7 +356,8 @@ def sample(model, test_angle_ds, all_batches: bool = False):
                     model=model, ligand_mask=lm.to(DEVICE), ligand_angle_noise=x_T.to(DEVICE),
                     receptor_seq=receptor_seq[idx].to(DEVICE), receptor_mask=receptor_mask[idx].to(DEVICE),
                     receptor_angle=receptor_angle[idx].to(DEVICE), total_timesteps=test_angle_ds.timesteps,
-                    betas=test_angle_ds.alpha_beta_terms["betas"], trim_padding=True)   # sliced to l_i right below
+                    betas=test_angle_ds.alpha_beta_terms["betas"], trim_padding=True,   # sliced to l_i right below
+                    pack=PACK)
 
         sampled = chain(ARITHMETIC)
         if ops.GEMM_MODES.get(ARITHMETIC) == 19 and "E3D_GEMM_MODE" not in os.environ and not bool(torch.isfinite(sampled).all()):

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define E3D_ABI_VERSION 4
+#define E3D_ABI_VERSION 5
 
 /* ``terms`` of the split-operand entry points: how an fp32 operand enters the 16-bit matrix cores.
  *   3  (bf16x3): 2 bf16 terms, 3 cross products, ~2^-17 per product, fp32 exponent range;
@@ -335,6 +335,25 @@ int e3d_relkey_attn_fwd_split_ex(const float* q, int64_t q_bs, int64_t q_rs, con
                                  float* lse, int B, int nh, int Lq, int Lk, int terms, float drop_p,
                                  uint64_t drop_seed, void* e_scratch, int e_scratch_ready, const float* q_absmax,
                                  const float* k_absmax, float* e_absmax, void* stream);
+
+/* ---- attention over variable-length segments (ABI v5; packed batches, inference) ------------------------------------
+ * Segment s owns query rows q_start[s] .. q_start[s] + q_len[s] - 1 (rows of q: q + row * q_rs + h * 64) and key /
+ * value rows k_start[s] .. k_start[s] + k_len[s] - 1; the int32 arrays live on the device.  Each segment computes what
+ * e3d_relkey_attn_fwd_split computes on one item with Lq = q_len[s], Lk = k_len[s] and no key mask: keys outside the
+ * segment do not exist for its rows.  This equals the padded frame on the valid rows for the reason that makes
+ * trimming exact (e3d_attn_skip_padded_tiles): a padded key's weight exp(s - 10000 - m) is 0.0f as long as the row's
+ * scores spread over less than ~9900.  With dist_emb ([2P-1, 64]) the rel-key term uses positions measured from the
+ * segment start and needs q_len[s] == k_len[s] <= P.  K rows can be a packed buffer (k_start = prefix sums) or a padded
+ * [B, Lr] cache (k_start[s] = s * Lr).
+ * ``tiles`` [n_tiles, 2] int32 (device): (segment, q0) for every 32-query tile of every segment (sum ceil(q_len / 32)
+ * entries), plus (-1, row0) for each 32-row block of query rows that belong to no segment (a packed buffer's tail):
+ * those rows of ``out`` are written as zeros.  ``out`` [out_rows, nh * 64] contiguous.  max_q_len / max_k_len bound the
+ * lengths (host-side checks only: max_k_len x row stride < 2^30).  ``terms`` 3 / 6 / 19 as above; 0 (f32) runs bf16x6.
+ * One wave per (tile entry, head); no dropout, no lse; nothing is allocated and nothing is read back (graph-capturable). */
+int e3d_attn_varlen_fwd(const float* q, int64_t q_rs, const float* k, int64_t k_rs, const float* v, int64_t v_rs,
+                        const int* q_start, const int* q_len, const int* k_start, const int* k_len, const int* tiles,
+                        int n_tiles, const float* dist_emb, int P, float* out, int64_t out_rows, int nh, int max_q_len,
+                        int max_k_len, int terms, void* stream);
 
 /* e3d_relkey_attn_bwd for a forward that used (drop_p, drop_seed). */
 int e3d_relkey_attn_bwd_drop(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs,

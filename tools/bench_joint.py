@@ -3,7 +3,7 @@
 (L = 128): stage 1 = structure p_sample_loop over T = 1000 steps, stage 2 = sequence denoise over 50 steps
 (DiscreteUniformTransition, diverse=True) on the generated last-step angles, handed over on the device.
 
-    python tools/bench_joint.py [--batch 128] [--seq-len 128] [--t-structure 1000] [--t-sequence 50]
+    python tools/bench_joint.py [--batch 128] [--seq-len 128] [--t-structure 1000] [--t-sequence 50] [--trim | --pack]
 """
 import argparse
 import os
@@ -24,7 +24,7 @@ from e3diff_amd.bert import BertConfig  # noqa: E402
 DEV = "cuda:0"
 
 
-def run(batch=128, seq_len=128, t_structure=1000, t_sequence=50, trim=False, device=DEV):
+def run(batch=128, seq_len=128, t_structure=1000, t_sequence=50, trim=False, device=DEV, pack=False):
     """One GPU's share of BASELINE config 5 (sequence_model/sample_by_generated_angles.py:196-278): structure chain ->
     hand-over on the device -> sequence chain.  Returns a dict (also the ``joint`` key of bench.py's line)."""
     B, L = batch, seq_len
@@ -55,22 +55,23 @@ def run(batch=128, seq_len=128, t_structure=1000, t_sequence=50, trim=False, dev
 
     # warm-up (first launches, allocator)
     SS.p_sample_loop(smodel, dpk["ligand_attn_mask"], x_T, dpk["receptor_seq"], dpk["receptor_attn_mask"],
-                     dpk["receptor_angles"], 4, CosineTables(4), disable_pbar=True, return_device=True, step=1, trim_padding=trim)
+                     dpk["receptor_angles"], 4, CosineTables(4), disable_pbar=True, return_device=True, step=1, trim_padding=trim,
+                     pack=pack)
     t0 = sync()
     traj = SS.p_sample_loop(smodel, dpk["ligand_attn_mask"], x_T, dpk["receptor_seq"], dpk["receptor_attn_mask"],
                             dpk["receptor_angles"], t_structure, tab, disable_pbar=True, return_device=True, step=1,
-                            trim_padding=trim)
+                            trim_padding=trim, pack=pack)
     t1 = sync()
     angles = QJ.angles_from_trajectory(traj, dpk["ligand_attn_mask"])
     schedule = PredefinedNoiseScheduleDiscrete("cosine", t_sequence).to(device)
     ids, true_s, pred_s, rec = QJ.denoise(pk, angles, qmodel, schedule, DiscreteUniformTransition(20), True, trim_padding=trim,
-                                          timesteps=t_sequence)
+                                          timesteps=t_sequence, pack=pack)
     t2 = sync()
     assert len(pred_s) == B and bool(torch.isfinite(traj[-1]).all())
     mib = traj.numel() * 4 / 2 ** 20
     del traj, smodel, qmodel
     torch.cuda.empty_cache()
-    return {"pockets": B, "seq_len": L, "frames": "trimmed to the longest ligand / pocket" if trim else "padded to seq_len",
+    return {"pockets": B, "seq_len": L, "frames": "packed valid rows" if pack else "trimmed to the longest ligand / pocket" if trim else "padded to seq_len",
             "structure_steps": t_structure, "structure_s": t1 - t0, "structure_pocket_steps_per_s": B * t_structure / (t1 - t0),
             "sequence_steps": t_sequence, "sequence_s": t2 - t1, "sequence_pocket_steps_per_s": B * t_sequence / (t2 - t1),
             "total_s": t2 - t0, "pockets_per_s": B / (t2 - t0), "trajectory_MiB_on_device": mib}
@@ -83,8 +84,9 @@ def main():
     ap.add_argument("--t-structure", type=int, default=1000)
     ap.add_argument("--t-sequence", type=int, default=50)
     ap.add_argument("--trim", action="store_true", help="trim_padding=True in both chains (frame of the longest ligand / pocket)")
+    ap.add_argument("--pack", action="store_true", help="pack=True in both chains (the valid rows of every item back to back)")
     a = ap.parse_args()
-    r = run(a.batch, a.seq_len, a.t_structure, a.t_sequence, a.trim)
+    r = run(a.batch, a.seq_len, a.t_structure, a.t_sequence, a.trim, pack=a.pack)
     print(f"joint sampling ({r['frames']}), {r['pockets']} pockets x L={r['seq_len']} on one GPU: structure {r['structure_steps']} steps "
           f"{r['structure_s']:.2f} s ({r['structure_pocket_steps_per_s']:.0f} pocket-steps/s, encoder cached), sequence "
           f"{r['sequence_steps']} steps {r['sequence_s']:.2f} s ({r['sequence_pocket_steps_per_s']:.0f} pocket-steps/s); total "
