@@ -270,7 +270,9 @@ def _skinny_ok(terms, M, N, K, a):
 
 
 def gemm(a, weight, bias=None, act=ACT_NONE, out=None, mode=None, absmax=None, prescale=True):
-    """out[M,N] = act(a[M,K] @ weight[N,K]^T + bias).  ``a`` may be a row-strided 2-D view.  ``absmax`` (1-element
+    """out[M,N] = act(a[M,K] @ weight[N,K]^T + bias).  ``a`` may be a row-strided 2-D view; its start and row stride must
+    stay 16-byte aligned (the kernels load float4s): a view that starts off alignment (``x[:, 1:1+K]``) raises a
+    RuntimeError naming the alignment, nothing is copied.  ``absmax`` (1-element
     device tensor, act = none): raised to the largest |out| by the kernel's epilogue (split arithmetics; the exact-f32
     kernels have no use for it -- their attention twin never skips key tiles).  ``prescale`` (f16x3 only): run the
     product on the cached power-of-two-scaled copy of the weight (``f16_weight``); False for weights that change every
@@ -544,8 +546,11 @@ def weight_planes(weight, terms):
     return planes, scale
 
 
-def rowln_ok(terms, M, H, K, a):
-    return (terms in (3, 19) and M >= ROWLN_MIN_M and a.stride(1) == 1
+def rowln_ok(terms, M, H, K, a, residual=None):
+    """Whether the row-complete kernel takes this call: its staging needs A (and the residual) 16-byte aligned, so a view
+    that starts off alignment goes to the pair instead."""
+    return (terms in (3, 19) and M >= ROWLN_MIN_M and a.stride(1) == 1 and a.data_ptr() % 16 == 0
+            and (residual is None or (residual.stride(1) == 1 and residual.stride(0) % 4 == 0 and residual.data_ptr() % 16 == 0))
             and bool(hip.lib().e3d_gemm_residual_layernorm_supported(M, H, K, a.stride(0))))
 
 
@@ -556,7 +561,7 @@ def linear_residual_layernorm(a, weight, bias, residual, gamma, beta, eps, mode=
     M, K = a.shape
     H = weight.shape[0]
     terms = GEMM_MODES[GEMM_MODE if mode is None else mode]
-    if rowln_ok(terms, M, H, K, a) and (residual is None or (residual.stride(1) == 1 and residual.stride(0) % 4 == 0)):
+    if rowln_ok(terms, M, H, K, a, residual):
         for t, n in ((a, "a"), (weight, "weight"), (bias, "bias"), (residual, "residual"), (gamma, "gamma"), (beta, "beta")):
             _chk(t, "linear_residual_layernorm." + n)
         assert weight.is_contiguous() and weight.shape[1] == K and (residual is None or residual.shape == (M, H))
