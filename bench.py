@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: denoising-steps/sec of batched structure-model sampling on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     (N>1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
 
 Workload (BASELINE.json configs[2]): structure_model sampling, batch 256 x 256-residue synthetic
@@ -9,9 +9,14 @@ BioLiP-shaped pockets per GPU, full 12+12-layer 768-wide model, fp32, random-ini
 One "step" = one reverse-diffusion step of the whole per-GPU batch: the full denoiser forward as
 the reference computes it (pocket encoder included, nothing cached) + DDPM update + wrap, inputs
 resident in HBM.  value = pockets * steps / second over all ranks ("pocket-steps/s"; weak scaling:
-every rank owns its own pockets, no collective on the data path).  The sampler's real loop
-(encoder + cross-K/V computed once per batch -- same results) is timed too and reported as
-``value_encoder_cached``; it is NOT the headline because it skips work the reference does.
+every rank owns its own pockets, no collective on the data path).
+
+A plain run does only what the headline needs: set up, W warm-up steps, K timed steps, the
+--dump-outputs arrays, one JSON line.  ``--full`` adds everything else on the same line, after the
+headline steps: the padding skip, the other GEMM arithmetics, the sampler's real loop (encoder +
+cross-K/V computed once per batch -- same results; ``value_encoder_cached``, NOT the headline
+because it skips work the reference does), trimmed frames, the headline re-timed after all that,
+per-kernel roofline figures, the training / single-pocket / joint legs and the CPU baseline.
 """
 import argparse
 import json
@@ -225,6 +230,37 @@ def dump_outputs(out_dir, arrays):
               file=sys.stderr, flush=True)
 
 
+def headline_line(args, world, elapsed):
+    """The result line of a plain run: the headline figure of the K timed steps (``elapsed`` = the slowest rank's
+    seconds for them) and what it was measured on.  A --full run adds its other figures to this dict."""
+    B, L = args.batch, args.seq_len
+    return {
+        "metric": "denoising-steps/sec (batched pocket graphs)",
+        "value": B * world * args.steps / elapsed,
+        "unit": "pocket-steps/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps,
+        "ms_per_step_note": "ms_per_step / value: the W + K steps run FIRST in the process",
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": {"f32": "f32", "bf16x3": "f32 storage and accumulation, bf16x3 products",
+                  "bf16x6": "f32 storage and accumulation, bf16x6 products (fp32 grade)",
+                  "f16x3": "f32 storage and accumulation, f16x3 products (fp32 grade)"}[args.gemm_mode],
+        "data": "synthetic",
+        "gemm_mode": {"f32": "exact fp32 MFMA (v_mfma_f32_32x32x2_f32)",
+                      "bf16x3": "fp32 operands split into 2 bf16 terms, 3 cross products on the bf16 MFMA, fp32 accumulate",
+                      "bf16x6": "fp32 operands split into 3 bf16 terms, 6 cross products on the bf16 MFMA, fp32 accumulate "
+                                "(fp32-grade)",
+                      "f16x3": "fp32 operands split into 2 fp16 terms (11 + 11 bits), 3 cross products on the fp16 MFMA, fp32 "
+                               "accumulate (fp32-grade: 3.8e-6 end to end at L=256 vs 2.6e-6 for the exact fp32 MFMA path, both against "
+                               "the fp64 oracle; weights pre-scaled by an exact power of two so that both terms are normal "
+                               "fp16 numbers, activations must lie inside the fp16 range -- beyond it the outputs are inf/NaN)"}[args.gemm_mode],
+        "config": {"workload": f"structure_model sampling step, {B} x {L}-residue pockets per GPU, "
+                               "12+12 layers x 768, T=1000 schedule, encoder recomputed every step (as the reference)",
+                   "pockets_per_gpu": B, "seq_len": L, "parallelism": f"pocket-sharded x{world}, no collective"},
+        "model_tflops": structure_flops_per_pocket(L) * B * world * args.steps / elapsed / 1e12,
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -232,6 +268,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=256, help="pockets per GPU")
     ap.add_argument("--seq-len", type=int, default=256)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps, also run and report every other figure of the benchmark (padding "
+                         "skip, other GEMM modes, encoder-cached and trimmed loops, roofline figures, training / "
+                         "single-pocket / joint legs, CPU baseline); the --no-* / --only-* / --headline-only options "
+                         "below narrow this")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-train-leg", action="store_true", help="skip the extra training-step timings")
     ap.add_argument("--no-joint-leg", action="store_true", help="skip the joint structure -> sequence chain (config 5 share)")
@@ -243,8 +284,9 @@ def main():
                     help="GEMM arithmetic of the headline value (see DESIGN.md section 3)")
     ap.add_argument("--only-default-mode", action="store_true", help="skip timing the other GEMM modes")
     ap.add_argument("--headline-only", action="store_true",
-                    help="profile runs: only the headline loop (dense key sweep), no extras -- every attention "
-                         "launch in a rocprofv3 trace of this command is then the launch `roofline` describes")
+                    help="profile runs with --full: only the headline loop (dense key sweep) and the roofline pass, no "
+                         "other extras -- every attention launch in a rocprofv3 trace of this command is then the "
+                         "launch `roofline` describes")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the headline loop's last step returned (the next state "
                          "x_{t-1}, [batch, seq-len, 8]) as DIR/x_next.npy (float32; x_next_rank<r>.npy per rank for "
@@ -319,14 +361,11 @@ def main():
     by_mode = {}
     lib = pkg.hip.lib()
     with torch.no_grad():
-        # product default: the attention key sweep stops after the last valid key's tile (bit-identical
-        # results).  Timed first as an extra; the headline below runs the DENSE sweep over all padded keys,
-        # i.e. every flop the reference does.
         pkg.ops.set_gemm_mode(args.gemm_mode)
         pkg.ops.set_attn_mode(args.gemm_mode)
-        # THE HEADLINE FIRST (round 4): W untimed + K timed steps of the dense sweep, before any of the extras below touches
-        # the card.  The extras take about a minute of full load, and a card that has been busy that long holds a 3-5 %
-        # lower clock (DVFS); the same K steps are timed AGAIN after them and reported beside the headline as
+        # THE HEADLINE FIRST (round 4): W untimed + K timed steps of the dense sweep, before any of the --full extras below
+        # touches the card.  The extras take about a minute of full load, and a card that has been busy that long holds a
+        # 3-5 % lower clock (DVFS); the same K steps are timed AGAIN after them and reported beside the headline as
         # ``ms_per_step_after_extras`` (what a long chain sustains), never as ``value``.
         lib.e3d_attn_skip_padded_tiles(0)
         timed(full_step, args.warmup)
@@ -335,6 +374,23 @@ def main():
         if args.dump_outputs:
             # x is what the last timed step returned; the legs below reuse its buffer, so it is copied out now
             dump_outputs(args.dump_outputs, {"x_next" if world == 1 else f"x_next_rank{rank}": x})
+
+    if not args.full:
+        if dist is not None:
+            t = torch.tensor([elapsed], device=device if dist.get_backend() == "nccl" else "cpu", dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            elapsed = float(t.item())
+        if rank == 0:
+            print(json.dumps(headline_line(args, world, elapsed)), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    with torch.no_grad():
+        # product default: the attention key sweep stops after the last valid key's tile (bit-identical
+        # results).  Timed as an extra; the headline above runs the DENSE sweep over all padded keys,
+        # i.e. every flop the reference does.
         lib.e3d_attn_skip_padded_tiles(1)
         elapsed_skip = float("nan")
         if not args.headline_only:
@@ -446,33 +502,12 @@ def main():
         a_tf = attn_flops(B, L) / (attn_ms * 1e-3) / 1e12
         gemm_peak = {"f32": PEAK_F32_MATRIX_TFLOPS, "bf16x3": 2500.0 / 3, "bf16x6": 2500.0 / 6, "f16x3": 2500.0 / 3}[args.gemm_mode]
         a_gb = attn_bytes(B, L) / (attn_ms * 1e-3) / 1e9
-        out = {
-            "metric": "denoising-steps/sec (batched pocket graphs)",
-            "value": B * world * args.steps / elapsed,
-            "unit": "pocket-steps/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": 1e3 * elapsed / args.steps,
+        out = headline_line(args, world, elapsed)
+        out.update({
             "ms_per_step_after_extras": None if (args.headline_only or elapsed_after != elapsed_after) else 1e3 * elapsed_after / args.steps,
             "ms_per_step_note": "ms_per_step / value: the W + K steps run FIRST in the process; ms_per_step_after_extras: the same K steps "
                                 "timed again after the other legs of this command (~1 min of full load: the card then holds a lower clock)",
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": {"f32": "f32", "bf16x3": "f32 storage and accumulation, bf16x3 products",
-                      "bf16x6": "f32 storage and accumulation, bf16x6 products (fp32 grade)",
-                      "f16x3": "f32 storage and accumulation, f16x3 products (fp32 grade)"}[args.gemm_mode],
-            "data": "synthetic",
-            "gemm_mode": {"f32": "exact fp32 MFMA (v_mfma_f32_32x32x2_f32)",
-                          "bf16x3": "fp32 operands split into 2 bf16 terms, 3 cross products on the bf16 MFMA, fp32 accumulate",
-                          "bf16x6": "fp32 operands split into 3 bf16 terms, 6 cross products on the bf16 MFMA, fp32 accumulate "
-                                    "(fp32-grade)",
-                          "f16x3": "fp32 operands split into 2 fp16 terms (11 + 11 bits), 3 cross products on the fp16 MFMA, fp32 "
-                                   "accumulate (fp32-grade: 3.8e-6 end to end at L=256 vs 2.6e-6 for the exact fp32 MFMA path, both against "
-                                   "the fp64 oracle; weights pre-scaled by an exact power of two so that both terms are normal "
-                                   "fp16 numbers, activations must lie inside the fp16 range -- beyond it the outputs are inf/NaN)"}[args.gemm_mode],
             "value_by_gemm_mode": {m: B * world / by_mode[m] for m in modes},
-            "config": {"workload": f"structure_model sampling step, {B} x {L}-residue pockets per GPU, "
-                                   "12+12 layers x 768, T=1000 schedule, encoder recomputed every step (as the reference)",
-                       "pockets_per_gpu": B, "seq_len": L, "parallelism": f"pocket-sharded x{world}, no collective"},
-            "model_tflops": structure_flops_per_pocket(L) * B * world * args.steps / elapsed / 1e12,
             "value_encoder_cached": None if args.headline_only else B * world * args.steps / elapsed_cached,
             "value_padding_skip": None if args.headline_only else B * world / elapsed_skip,
             "value_trimmed": None if args.headline_only else B * world * args.steps / elapsed_trimmed,
@@ -539,7 +574,7 @@ def main():
                               "frac": gemm_flops / (gemm_ms * 1e-3) / 1e12 / gemm_peak,
                               "peak_note": "fp32 MFMA 157.3 for f32; bf16 dense 2500 / terms for the split modes",
                               "ms_per_step": gemm_ms},
-        }
+        })
         if world == 1 and not args.headline_only and not args.no_train_leg:
             # extra keys (never the headline): one training step of BASELINE configs 2 and 4, one GPU's share
             del model

@@ -76,7 +76,7 @@ def test_on_device_forward_noising_matches_dataset_path(pkg, hip):
 
 
 def test_bench_two_rank_rehearsal_reports_the_data_parallel_training_leg():
-    """`python bench.py --gpus 2` with E3D_BENCH_REHEARSAL=1: both ranks on cuda:0, gloo for the collectives -- the control
+    """`python bench.py --gpus 2 --full` with E3D_BENCH_REHEARSAL=1: both ranks on cuda:0, gloo for the collectives -- the control
     path of the multi-GPU line on a one-GPU box (never a measurement).  Rank 0's single JSON line must carry the headline
     keys AND the ``train_ddp`` extra key (BASELINE config 4, the sequence model's DDP step with the
     overlapped GradientAverager), and the ranks must still hold identical weights after the timed steps (asserted inside
@@ -88,7 +88,7 @@ def test_bench_two_rank_rehearsal_reports_the_data_parallel_training_leg():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["E3D_BENCH_REHEARSAL"] = "1"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--batch", "4", "--seq-len", "64", "--only-default-mode", "--train-ddp-batch", "4",
+                        "--batch", "4", "--seq-len", "64", "--full", "--only-default-mode", "--train-ddp-batch", "4",
                         "--train-ddp-seq-len", "64", "--train-ddp-layers", "2"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]

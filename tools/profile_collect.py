@@ -53,7 +53,7 @@ traffic = {
                    "(no trace domains); x2 = the gfx950 FETCH_SIZE correction of MI355X_MICROARCH.md (HBM section)",
         "attn": {"kernel": "attn_coop_kernel<4 waves, rel-key, default arithmetic>, tools/bench_kernels.py attn_pmc", "FETCH_SIZE_KiB_raw_avg": afm,
                  "WRITE_SIZE_KiB_avg": awm, "algorithmic_bytes": (4 * L * H * 4 + (2 * L - 1) * 256 + 4 * L) * B},
-        "gemm": {"kernel": f"{GEMM[0]}, ...>: every launch of one bench.py --headline-only step ({ng} dispatches incl. the untimed "
+        "gemm": {"kernel": f"{GEMM[0]}, ...>: every launch of one bench.py --full --headline-only step ({ng} dispatches incl. the untimed "
                            "trace pass)", "FETCH_SIZE_KiB_raw_avg": gfm, "WRITE_SIZE_KiB_avg": gwm},
         "command": "bash tools/profile_round.sh && python tools/profile_collect.py",
     },

@@ -72,7 +72,7 @@ def row(what, value, source):
 
 
 if final:
-    src = f"`profiles/{tag}_bench_line_final.json` (`python bench.py`, steps {final['steps']}, warm-up {final['warmup']})"
+    src = f"`profiles/{tag}_bench_line_final.json` (`python bench.py --full`, steps {final['steps']}, warm-up {final['warmup']})"
     by = final.get("value_by_gemm_mode", {})
     row("`value` (f16x3, dense key sweep, encoder recomputed every step)",
         f"**{final['value']:.0f} pocket-steps/s** = {final['ms_per_step']:.1f} ms per step of 256 pockets"
@@ -117,7 +117,7 @@ if final:
     if cb:
         row("`cpu_baseline` (oracle, kind = port)", f"{cb['value']:.1f} {cb['unit']} on {cb['cores']} threads ({cb['sample']}) → GPU ÷ CPU ≈ {final['value'] / cb['value']:.0f}×", src)
 if under and bench:
-    src = f"`profiles/{tag}_bench_B256_L256_kernel_stats.csv`, `{tag}_bench_line_under_rocprof.json` (`rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --headline-only`)"
+    src = f"`profiles/{tag}_bench_B256_L256_kernel_stats.csv`, `{tag}_bench_line_under_rocprof.json` (`rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --headline-only`)"
     g = either(bench, ("gemm_split256p_kernelILi0E",), ("gemm_split256p_kernel<0",))
     g1 = either(bench, ("gemm_split256p_kernelILi1E",), ("gemm_split256p_kernel<1",))
     rl = either(bench, ("gemm_rowln_kernel",))
