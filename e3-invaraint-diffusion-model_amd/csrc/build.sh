@@ -10,7 +10,7 @@ pids=()
 for s in $SRCS; do
   o="${s%.hip}.o"
   OBJS="$OBJS $o"
-  if [ ! -f "$o" ] || [ "$s" -nt "$o" ] || [ e3d_common.h -nt "$o" ] || [ attn_split_frag.h -nt "$o" ] || [ ../../include/e3d_hip.h -nt "$o" ]; then
+  if [ ! -f "$o" ] || [ "$s" -nt "$o" ] || [ e3d_common.h -nt "$o" ] || [ attn_split_frag.h -nt "$o" ] || [ e3d_philox.h -nt "$o" ] || [ ../../include/e3d_hip.h -nt "$o" ]; then
     $HIPCC --offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wall -Wno-unused-function -c "$s" -o "$o" &
     pids+=($!)
   fi

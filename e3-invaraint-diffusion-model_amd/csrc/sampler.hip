@@ -1,6 +1,8 @@
 // Diffusion-process kernels: DDPM ancestral update + angular wrap, forward noising, and the
 // discrete (BLOSUM / uniform transition) posterior + categorical draw.  All HBM-bound.
+// The keyed forms (seeded chains) generate their draws in-register from (seed, row key, step): e3d_philox.h.
 #include "e3d_common.h"
+#include "e3d_philox.h"
 
 namespace {
 
@@ -88,10 +90,14 @@ __device__ __forceinline__ int pick_class(const float (&p)[CMAX], int C, float t
 
 // One workgroup per batch item: the three CxC matrices of the item live in LDS, each thread
 // walks rows l = tid, tid+256, ...
+// KEYED: the uniform of row n = b * L + l is drawn from stream 3 at step s_dev[0] with the row's key (row_keys[n]);
+// rows of no item draw u = 0.
+template <bool KEYED>
 __global__ __launch_bounds__(256) void discrete_posterior_kernel(
     const int32_t* __restrict__ xt_idx, const float* __restrict__ logits, const float* __restrict__ Qsb,
     const float* __restrict__ Qtb, const float* __restrict__ u, int mode, int32_t* __restrict__ out_idx,
-    float* __restrict__ prob_out, int L, int C) {
+    float* __restrict__ prob_out, int L, int C, const int64_t* __restrict__ row_keys, uint64_t seed,
+    const int64_t* __restrict__ s_dev) {
     __shared__ float s_qsb[CMAX * CMAX], s_qtb[CMAX * CMAX], s_qt[CMAX * CMAX], s_rs[CMAX];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int CC = C * C;
@@ -162,7 +168,16 @@ __global__ __launch_bounds__(256) void discrete_posterior_kernel(
             for (int c = 0; c < CMAX; ++c)
                 if (c < C) prob_out[n * C + c] = prob[c];
         }
-        out_idx[n] = pick_class(prob, C, ntot, mode, u ? u[n] : 0.f);
+        float un = 0.f;
+        if (KEYED) {
+            const int64_t pos = row_keys[2 * n + 1];
+            if (pos >= 0)
+                un = e3d_keyed_uniform(e3d_keyed_words(seed, (uint64_t)row_keys[2 * n], E3D_STREAM_SEQ_U,
+                                                       (uint32_t)s_dev[0], (uint32_t)pos, 0).w[0]);
+        } else if (u) {
+            un = u[n];
+        }
+        out_idx[n] = pick_class(prob, C, ntot, mode, un);
     }
 }
 
@@ -182,6 +197,83 @@ __global__ __launch_bounds__(256) void discrete_q_sample_kernel(
         tot += p[c];
     }
     out_idx[n] = pick_class(p, C, tot, mode, u ? u[n] : 0.f);
+}
+
+// ---------------------------------------------------------------- keyed (seeded) draws
+// One thread per (row, block j of 4 features): one Philox call gives the 4 normals of features 4j .. 4j+3.
+__device__ __forceinline__ bool keyed_row(const int64_t* __restrict__ row_keys, int64_t row, uint64_t& item,
+                                          uint32_t& pos) {
+    const int64_t p = row_keys[2 * row + 1];
+    item = (uint64_t)row_keys[2 * row];
+    pos = (uint32_t)p;
+    return p >= 0;
+}
+
+// ddpm_step_wrap_kernel's table form with the noise generated from stream 1 at step t_dev[0]; same arithmetic per
+// element, so the result equals the table form fed with these normals (rows of no item: no noise term).
+__global__ __launch_bounds__(256) void keyed_ddpm_step_wrap_kernel(
+    const float* __restrict__ x, const float* __restrict__ eps_hat, const float* __restrict__ coef_table,
+    const int64_t* __restrict__ t_dev, const int64_t* __restrict__ row_keys, uint64_t seed, int wrap,
+    float* __restrict__ out, int64_t n4, int nb) {
+    const int64_t t = t_dev[0];
+    const float sra = coef_table[4 * t], beta = coef_table[4 * t + 1], s1m = coef_table[4 * t + 2],
+                sigma = coef_table[4 * t + 3];
+    const bool noisy = sigma != 0.f;   // t == 0: the mean, exactly as the table form
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        const f32x4 xv = reinterpret_cast<const f32x4*>(x)[i];
+        const f32x4 ev = reinterpret_cast<const f32x4*>(eps_hat)[i];
+        const int64_t row = i / nb;
+        uint64_t item;
+        uint32_t pos;
+        const bool has = noisy && keyed_row(row_keys, row, item, pos);
+        float nv[4] = {0.f, 0.f, 0.f, 0.f};
+        if (has) e3d_keyed_normal4(e3d_keyed_words(seed, item, E3D_STREAM_STRUCT_STEP, (uint32_t)t, pos,
+                                                   (uint32_t)(i - row * nb)), nv);
+        f32x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float mean = sra * (xv[j] - beta * ev[j] / s1m);
+            if (has) mean = mean + sigma * nv[j];
+            o[j] = wrap ? wrap_pi(mean) : mean;
+        }
+        reinterpret_cast<f32x4*>(out)[i] = o;
+    }
+}
+
+// Raw keyed draws of one (stream, step) over a key table (rows of no item: zeros):
+//   kind 0: wrap ? wrap_pi(scale * z) : z, z the normals  -> float [rows, 4 nb]   (wrap + stream 0: keyed x_T)
+//   kind 1: uniforms from word 0 of block 0                -> float [rows]
+//   kind 2: classes from word 0 of block 0, as one-hot     -> float [rows, C]     (stream 2: keyed sequence x_T)
+//   kind 3: classes from word 0 of block 0                 -> int32 [rows]
+__global__ __launch_bounds__(256) void keyed_draws_kernel(
+    const int64_t* __restrict__ row_keys, uint64_t seed, int stream, uint32_t t, int kind, int nb, int C, int wrap,
+    float scale, void* __restrict__ out, int64_t n) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const int64_t row = kind == 0 ? i / nb : i;
+        const uint32_t block = kind == 0 ? (uint32_t)(i - row * nb) : 0u;
+        uint64_t item;
+        uint32_t pos;
+        const bool has = keyed_row(row_keys, row, item, pos);
+        const E3dU32x4 w = has ? e3d_keyed_words(seed, item, stream, t, pos, block) : E3dU32x4{{0u, 0u, 0u, 0u}};
+        if (kind == 0) {
+            float z[4] = {0.f, 0.f, 0.f, 0.f};
+            if (has) e3d_keyed_normal4(w, z);
+            f32x4 o;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = (has && wrap) ? wrap_pi(scale * z[j]) : z[j];
+            reinterpret_cast<f32x4*>(out)[i] = o;
+        } else if (kind == 1) {
+            reinterpret_cast<float*>(out)[i] = has ? e3d_keyed_uniform(w.w[0]) : 0.f;
+        } else if (kind == 2) {
+            const int k = has ? e3d_keyed_class(w.w[0], C) : -1;
+            float* o = reinterpret_cast<float*>(out) + i * C;
+            for (int c = 0; c < C; ++c) o[c] = c == k ? 1.f : 0.f;
+        } else {
+            reinterpret_cast<int32_t*>(out)[i] = has ? e3d_keyed_class(w.w[0], C) : 0;
+        }
+    }
 }
 
 }  // namespace
@@ -234,8 +326,8 @@ extern "C" int e3d_discrete_posterior_sample(const int32_t* xt_idx, const float*
     E3D_REQUIRE(xt_idx && logits && Qsb && Qtb && out_idx && B > 0 && L > 0, "discrete_posterior: bad arguments");
     E3D_REQUIRE(C >= 2 && C <= CMAX, "discrete_posterior: C must be in [2,%d] (C=%d)", CMAX, C);
     E3D_REQUIRE(mode == 0 || (mode == 1 && u), "discrete_posterior: mode 1 needs uniforms");
-    hipLaunchKernelGGL(discrete_posterior_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, xt_idx, logits, Qsb, Qtb,
-                       u, mode, out_idx, prob_out, L, C);
+    hipLaunchKernelGGL(discrete_posterior_kernel<false>, dim3(B), dim3(256), 0, (hipStream_t)stream, xt_idx, logits, Qsb,
+                       Qtb, u, mode, out_idx, prob_out, L, C, nullptr, 0ull, nullptr);
     return e3d_launch_status("e3d_discrete_posterior_sample");
 }
 
@@ -248,4 +340,51 @@ extern "C" int e3d_discrete_q_sample(const int32_t* x0_idx, const float* Qtb, co
     hipLaunchKernelGGL(discrete_q_sample_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, x0_idx, Qtb, u, mode, out_idx, L, C, n);
     return e3d_launch_status("e3d_discrete_q_sample");
+}
+
+// ---------------------------------------------------------------- keyed (seeded) entry points
+static int keyed_blocks(int64_t n) {
+    int64_t blocks = (n + 255) / 256;
+    return (int)(blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks));
+}
+
+extern "C" int e3d_keyed_ddpm_step_wrap(const float* x, const float* eps_hat, const float* coef_table, const int64_t* t_dev,
+                                        const int64_t* row_keys, uint64_t seed, int wrap, float* out, int64_t rows, int F,
+                                        void* stream) {
+    E3D_REQUIRE(x && eps_hat && coef_table && t_dev && row_keys && out && rows > 0, "keyed_ddpm_step_wrap: bad arguments");
+    E3D_REQUIRE(F > 0 && F % 4 == 0 && F / 4 <= 256, "keyed_ddpm_step_wrap: F must be a multiple of 4 in [4, 1024] (F=%d)", F);
+    E3D_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)eps_hat % 16) == 0 && ((uintptr_t)out % 16) == 0,
+                "keyed_ddpm_step_wrap: pointers must be 16B aligned");
+    const int64_t n4 = rows * (F / 4);
+    hipLaunchKernelGGL(keyed_ddpm_step_wrap_kernel, dim3(keyed_blocks(n4)), dim3(256), 0, (hipStream_t)stream, x, eps_hat,
+                       coef_table, t_dev, row_keys, seed, wrap, out, n4, F / 4);
+    return e3d_launch_status("e3d_keyed_ddpm_step_wrap");
+}
+
+extern "C" int e3d_keyed_discrete_posterior_sample(const int32_t* xt_idx, const float* logits, const float* Qsb,
+                                                   const float* Qtb, const int64_t* row_keys, uint64_t seed,
+                                                   const int64_t* s_dev, int32_t* out_idx, int B, int L, int C,
+                                                   void* stream) {
+    E3D_REQUIRE(xt_idx && logits && Qsb && Qtb && row_keys && s_dev && out_idx && B > 0 && L > 0,
+                "keyed_discrete_posterior: bad arguments");
+    E3D_REQUIRE(C >= 2 && C <= CMAX, "keyed_discrete_posterior: C must be in [2,%d] (C=%d)", CMAX, C);
+    hipLaunchKernelGGL(discrete_posterior_kernel<true>, dim3(B), dim3(256), 0, (hipStream_t)stream, xt_idx, logits, Qsb,
+                       Qtb, nullptr, 1, out_idx, nullptr, L, C, row_keys, seed, s_dev);
+    return e3d_launch_status("e3d_keyed_discrete_posterior_sample");
+}
+
+extern "C" int e3d_keyed_draws(const int64_t* row_keys, uint64_t seed, int stream_id, int t, int kind, int width,
+                               int wrap, float scale, void* out, int64_t rows, void* stream) {
+    E3D_REQUIRE(row_keys && out && rows > 0, "keyed_draws: bad arguments");
+    E3D_REQUIRE(stream_id >= 0 && stream_id <= 3 && t >= 0 && t <= 65535,
+                "keyed_draws: stream %d / step %d out of range", stream_id, t);
+    E3D_REQUIRE(kind >= 0 && kind <= 3, "keyed_draws: kind %d", kind);
+    E3D_REQUIRE(kind != 0 || (width > 0 && width % 4 == 0 && width / 4 <= 256 && ((uintptr_t)out % 16) == 0),
+                "keyed_draws: normals need F a multiple of 4 in [4, 1024] (F=%d) and a 16B aligned output", width);
+    E3D_REQUIRE(kind < 2 || (width >= 2 && width <= 1 << 24), "keyed_draws: class count %d", width);
+    const int nb = kind == 0 ? width / 4 : 1;
+    const int64_t n = rows * nb;
+    hipLaunchKernelGGL(keyed_draws_kernel, dim3(keyed_blocks(n)), dim3(256), 0, (hipStream_t)stream, row_keys, seed,
+                       stream_id, (uint32_t)t, kind, nb, width, wrap, scale, out, n);
+    return e3d_launch_status("e3d_keyed_draws");
 }

@@ -99,6 +99,10 @@ _SIGNATURES = {
     # attention over variable-length segments (ABI v5)
     "e3d_attn_varlen_fwd": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, _P, _P, _P, _P, _P, c_int, _P, c_int, _P,
                                     c_int64, c_int, c_int, c_int, c_int, _P]),
+    # keyed (seeded) sampling draws
+    "e3d_keyed_ddpm_step_wrap": (c_int, [_P, _P, _P, _P, _P, c_uint64, c_int, _P, c_int64, c_int, _P]),
+    "e3d_keyed_discrete_posterior_sample": (c_int, [_P, _P, _P, _P, _P, c_uint64, _P, _P, c_int, c_int, c_int, _P]),
+    "e3d_keyed_draws": (c_int, [_P, c_uint64, c_int, c_int, c_int, c_int, c_int, c_float, _P, c_int64, _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -1,0 +1,79 @@
+"""Keyed sampling streams: the row-key tables of seeded chains.
+
+A seeded chain draws every random number from Philox4x32-10 keyed by the seed, with the counter
+(item id, stream << 16 | step, position << 8 | block) -- DESIGN.md, "Keyed sampling streams"; csrc/e3d_philox.h.  The
+kernels find (item id, position) of a row in a key table, int64 [rows, 2], built here once per chain for the frame the
+chain runs in: the padded [B, L] frame, a trimmed frame (the same positions, fewer of them) or a ``packing.PackedLayout``
+(position = row - segment start; the zero tail gets ``SENTINEL`` and draws nothing).  The valid rows of one item carry
+the same keys in all three, so an item gets the same draws whatever its batch, order or frame.
+
+Item ids are the caller's (the module entry points use the global dataset index).  Two items with the same id and seed
+get the same draws: replicate samples of one pocket take one seed per replicate, or ids that encode (pocket, replicate).
+"""
+import torch
+
+SENTINEL = -1
+MAX_POSITION = 1 << 24          # c3 = position << 8 | block
+MAX_STEP = 65535                # c2 = stream << 16 | step
+
+# streams (counter word c2 = stream << 16 | step)
+STRUCT_XT, STRUCT_STEP, SEQ_XT, SEQ_U = 0, 1, 2, 3
+
+
+def check_seed(seed):
+    """The seed as a Python int in [0, 2^64) (the 64-bit Philox key)."""
+    if isinstance(seed, bool) or not isinstance(seed, int):
+        try:
+            seed = int(seed)
+        except (TypeError, ValueError):
+            raise TypeError(f"seed must be an integer, got {seed!r}") from None
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"seed must lie in [0, 2^64), got {seed}")
+    return seed
+
+
+def check_steps(T):
+    if T - 1 > MAX_STEP:
+        raise ValueError(f"keyed streams hold steps up to {MAX_STEP}; a chain of {T} steps does not fit")
+
+
+def item_ids(ids, B):
+    """Item ids as a list of B Python ints in [0, 2^64); ``None`` -> 0 .. B-1."""
+    if ids is None:
+        return list(range(B))
+    ids = [int(i) for i in (ids.tolist() if torch.is_tensor(ids) else ids)]
+    if len(ids) != B:
+        raise ValueError(f"{len(ids)} item ids for a batch of {B}")
+    if any(not 0 <= i < 1 << 64 for i in ids):
+        raise ValueError("item ids must lie in [0, 2^64)")
+    return ids
+
+
+def _as_int64(ids):
+    """[0, 2^64) -> the int64 of the same bit pattern (the kernels read the word as unsigned)."""
+    return torch.tensor([i - (1 << 64) if i >= 1 << 63 else i for i in ids], dtype=torch.int64)
+
+
+def padded_keys(ids, L, device):
+    """Key table of a [B, L] frame: row b * L + l = (ids[b], l).  A trimmed frame is the same with its shorter L."""
+    if L > MAX_POSITION:
+        raise ValueError(f"keyed streams hold positions below 2^24, got a frame of {L}")
+    B = len(ids)
+    keys = torch.empty((B, L, 2), dtype=torch.int64)
+    keys[:, :, 0] = _as_int64(ids)[:, None]
+    keys[:, :, 1] = torch.arange(L, dtype=torch.int64)[None]
+    return keys.reshape(B * L, 2).to(device)
+
+
+def packed_keys(layout, ids, device=None):
+    """Key table of a packed buffer: row start_s + l = (ids[s], l) for l < lengths[s]; the tail rows get SENTINEL."""
+    if len(ids) != layout.B:
+        raise ValueError(f"{len(ids)} item ids for a layout of {layout.B} segments")
+    if layout.max_len > MAX_POSITION:
+        raise ValueError("keyed streams hold positions below 2^24")
+    keys = torch.full((layout.rows, 2), SENTINEL, dtype=torch.int64)
+    sid = _as_int64(ids)
+    for s, (start, n) in enumerate(zip(layout.starts, layout.lengths)):
+        keys[start:start + n, 0] = sid[s]
+        keys[start:start + n, 1] = torch.arange(n, dtype=torch.int64)
+    return keys.to(layout.device if device is None else device)

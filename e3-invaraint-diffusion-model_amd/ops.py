@@ -6,7 +6,7 @@ import warnings
 
 import torch
 
-from . import hip
+from . import hip, keyed
 
 ACT_NONE, ACT_GELU, ACT_SILU = 0, 1, 2
 
@@ -700,3 +700,86 @@ def discrete_q_sample(x0_idx, qtb, u=None):
         hip.check(hip.lib().e3d_discrete_q_sample(_p(x0_idx), _p(qtb), _p(u), 0 if u is None else 1, _p(out),
                                                   B, L, C, _stream()), "e3d_discrete_q_sample")
     return out
+
+
+# ---------------------------------------------------------------------------------------------- keyed (seeded) draws
+# Row-key tables come from keyed.py: int64 [rows, 2] = (item id, position), position < 0 for rows of no item.
+
+def _chk_keys(row_keys, rows, name):
+    _chk(row_keys, name + ".row_keys", torch.int64)
+    if not (row_keys.is_contiguous() and row_keys.dim() == 2 and row_keys.shape == (rows, 2)):
+        raise ValueError(f"{name}: row_keys must be a contiguous [{rows}, 2] table, got {tuple(row_keys.shape)}")
+
+
+def keyed_ddpm_step_wrap(x, eps_hat, coef_table, t_dev, row_keys, seed, wrap=True, out=None):
+    """ddpm_step_wrap_table with the N(0,1) draw generated in the kernel from (seed, row key, stream 1, t_dev[0]):
+    x / eps_hat [.., F] with rows = x.numel() // F, F % 4 == 0.  No noise buffer, no host sync: graph-capturable."""
+    for n, t in (("x", x), ("eps_hat", eps_hat), ("coef_table", coef_table)):
+        _chk(t, "keyed_ddpm_step_wrap." + n)
+    _chk(t_dev, "keyed_ddpm_step_wrap.t_dev", torch.int64)
+    F = x.shape[-1]
+    if F % 4:
+        raise ValueError(f"keyed_ddpm_step_wrap: the feature count must be a multiple of 4, got {F}")
+    rows = x.numel() // F
+    _chk_keys(row_keys, rows, "keyed_ddpm_step_wrap")
+    assert x.is_contiguous() and eps_hat.is_contiguous() and coef_table.is_contiguous() and eps_hat.shape == x.shape
+    assert coef_table.dim() == 2 and coef_table.shape[1] == 4
+    if coef_table.shape[0] - 1 > 65535:
+        raise ValueError(f"keyed_ddpm_step_wrap: keyed streams hold steps up to 65535, the table has {coef_table.shape[0]}")
+    if out is None:
+        out = torch.empty_like(x)
+    with _timed("keyed_ddpm_step_wrap"):
+        hip.check(hip.lib().e3d_keyed_ddpm_step_wrap(_p(x), _p(eps_hat), _p(coef_table), _p(t_dev), _p(row_keys),
+                                                     keyed.check_seed(seed), int(wrap), _p(out), rows, F, _stream()),
+                  "e3d_keyed_ddpm_step_wrap")
+    return out
+
+
+def keyed_discrete_posterior_sample(xt_idx, logits, qsb, qtb, row_keys, seed, s_dev):
+    """discrete_posterior_sample (categorical draw) with the uniforms from (seed, row key, stream 3, s_dev[0]);
+    row_keys [B * L, 2]."""
+    _chk(xt_idx, "xt_idx", torch.int32); _chk(logits, "logits"); _chk(qsb, "qsb"); _chk(qtb, "qtb")
+    _chk(s_dev, "s_dev", torch.int64)
+    B, L, C = logits.shape
+    _chk_keys(row_keys, B * L, "keyed_discrete_posterior_sample")
+    assert xt_idx.is_contiguous() and logits.is_contiguous() and qsb.is_contiguous() and qtb.is_contiguous()
+    assert qsb.shape == (B, C, C) and qtb.shape == (B, C, C) and xt_idx.shape == (B, L)
+    out = torch.empty((B, L), device=logits.device, dtype=torch.int32)
+    with _timed("discrete_posterior"):
+        hip.check(hip.lib().e3d_keyed_discrete_posterior_sample(
+            _p(xt_idx), _p(logits), _p(qsb), _p(qtb), _p(row_keys), keyed.check_seed(seed), _p(s_dev), _p(out), B, L, C,
+            _stream()), "e3d_keyed_discrete_posterior_sample")
+    return out
+
+
+KEYED_NORMAL, KEYED_UNIFORM, KEYED_ONEHOT, KEYED_CLASS = 0, 1, 2, 3
+
+
+def keyed_draws(row_keys, seed, stream, t, kind, width=0, wrap=False, scale=1.0):
+    """Raw keyed draws of (stream, step t) for every row of ``row_keys`` (rows of no item: zeros).  ``kind``:
+    KEYED_NORMAL -> float [rows, width] (wrap: wrap_[-pi,pi)(scale * z)); KEYED_UNIFORM -> float [rows];
+    KEYED_ONEHOT -> float [rows, width] one-hot of a class in [0, width); KEYED_CLASS -> int32 [rows]."""
+    _chk(row_keys, "keyed_draws.row_keys", torch.int64)
+    rows = row_keys.shape[0]
+    _chk_keys(row_keys, rows, "keyed_draws")
+    if not 0 <= int(t) <= 65535:
+        raise ValueError(f"keyed_draws: step {t} outside [0, 65535]")
+    if kind == KEYED_NORMAL and width % 4:
+        raise ValueError(f"keyed_draws: the feature count must be a multiple of 4, got {width}")
+    shape, dtype = {KEYED_NORMAL: ((rows, width), torch.float32), KEYED_UNIFORM: ((rows,), torch.float32),
+                    KEYED_ONEHOT: ((rows, width), torch.float32), KEYED_CLASS: ((rows,), torch.int32)}[kind]
+    out = torch.empty(shape, device=row_keys.device, dtype=dtype)
+    if rows:
+        hip.check(hip.lib().e3d_keyed_draws(_p(row_keys), keyed.check_seed(seed), int(stream), int(t), int(kind), int(width),
+                                            int(wrap), float(scale), _p(out), rows, _stream()), "e3d_keyed_draws")
+    return out
+
+
+def keyed_initial_angles(row_keys, seed, F, scale=1.0):
+    """Keyed structure x_T: wrap_[-pi,pi)(scale * z), z the stream-0 normals, [rows, F]."""
+    return keyed_draws(row_keys, seed, keyed.STRUCT_XT, 0, KEYED_NORMAL, F, wrap=True, scale=scale)
+
+
+def keyed_initial_onehot(row_keys, seed, C):
+    """Keyed sequence x_T: one-hot of the stream-2 class of every row, float [rows, C]."""
+    return keyed_draws(row_keys, seed, keyed.SEQ_XT, 0, KEYED_ONEHOT, C)

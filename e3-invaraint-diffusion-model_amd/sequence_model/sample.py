@@ -19,7 +19,7 @@ import torch
 from torch.nn import functional as F
 from torch.utils.data import DataLoader
 
-from .. import ops, packing
+from .. import keyed, ops, packing
 from ..bert import BertConfig
 from .dataset import AA_VOCAB, LigandBindingSiteDataset
 from .model import PeptideDiff, onehot_to_index
@@ -34,6 +34,9 @@ OUTPUT_PATH = "./data/from_generated_angles/output.pkl"
 # Packed chains (denoise(pack=True)): the batch runs on its valid rows only; off by default, E3D_SAMPLE_PACK=1 turns it
 # on for ``run()``.
 PACK = os.environ.get("E3D_SAMPLE_PACK", "0") == "1"
+# Keyed draws (``run(seed=...)``): the initial one-hots and the posterior uniforms of a ligand are a function of
+# (seed, dataset index), whatever its batch, order or frame.  None (default): torch's generator, as before.
+SEED = int(os.environ["E3D_SAMPLE_SEED"], 0) if os.environ.get("E3D_SAMPLE_SEED") else None
 
 CONFIG = {
     "pocket_ext": 0,
@@ -99,6 +102,15 @@ def generate_discrete_noise(batch_size, length, num_classes=20, device=None):
     return F.one_hot(idx, num_classes).float()
 
 
+def keyed_discrete_noise(seed, item_ids, length, num_classes=20, device=None):
+    """Keyed x_T [B,L,C]: the one-hot of the stream-2 class of (seed, item_ids[b], l) -- generate_discrete_noise's
+    distribution, drawn per item instead of per batch."""
+    device = DEVICE if device is None else device
+    ids = keyed.item_ids(item_ids, len(item_ids))
+    keys = keyed.padded_keys(ids, length, device)
+    return ops.keyed_initial_onehot(keys, seed, num_classes).reshape(len(ids), length, num_classes)
+
+
 def compute_batched_over0_posterior_distribution(X_t, Q_t, Qsb, Qtb, batch):
     """[N,C,C] posterior table  (x_t Qt^T) * Qsb / (Qtb x_t)  (reference sample.py:120-139).
     API-compatibility helper in plain torch: the sampler below never materialises this tensor
@@ -110,16 +122,24 @@ def compute_batched_over0_posterior_distribution(X_t, Q_t, Qsb, Qtb, batch):
 
 
 def sample_p_zs_given_zt_discrete(t, s, noised_data, pred_noise, noise_schedule, transition, diverse,
-                                  is_last_step, u=None):
+                                  is_last_step, u=None, keyed_draw=None):
     """z_s ~ p(z_s | z_t) for every residue (reference sample.py:141-179).  ``diverse`` draws
     from the categorical (inverse CDF with uniforms ``u`` [B,L], default torch.rand on device),
-    otherwise argmax; the last step returns the raw logits, as the reference does."""
+    otherwise argmax; the last step returns the raw logits, as the reference does.
+    ``keyed_draw`` = (row keys [B*L, 2], seed, int64 step on the device): the uniforms are the keyed stream 3 of those
+    rows at that step, generated inside the posterior kernel (keyed.py); exclusive with ``u``."""
     if is_last_step:
         return pred_noise
     B, L, C = noised_data.shape
     dev = noised_data.device
     qtb = transition.get_Qt_bar(noise_schedule.get_alpha_bar(t_normalized=t), dev).contiguous()
     qsb = transition.get_Qt_bar(noise_schedule.get_alpha_bar(t_normalized=s), dev).contiguous()
+    if diverse and keyed_draw is not None:
+        if u is not None:
+            raise ValueError("sample_p_zs_given_zt_discrete: pass either uniforms or a keyed draw, not both")
+        idx = ops.keyed_discrete_posterior_sample(noised_data.argmax(dim=-1).to(torch.int32).contiguous(),
+                                                  pred_noise.contiguous().float(), qsb, qtb, *keyed_draw)
+        return F.one_hot(idx.long(), num_classes=C).float()
     if diverse and u is None:
         u = torch.rand(B, L, device=dev)
     idx = ops.discrete_posterior_sample(noised_data.argmax(dim=-1).to(torch.int32).contiguous(),
@@ -138,11 +158,16 @@ class GraphedDenoiseStep:
     150 launches per step): default for at most ``GRAPH_MAX_ROWS`` token rows, ``use_graph`` / E3D_SAMPLE_GRAPH override."""
 
     def __init__(self, model, x_like, ligand_angles, ligand_mask, receptor_seq, receptor_angles, receptor_mask, noise_schedule,
-                 transition, diverse, T, inject_u=False, layouts=None):
+                 transition, diverse, T, inject_u=False, layouts=None, row_keys=None, seed=None):
         """``layouts`` = (ligand, pocket) packing.PackedLayout: the step runs ``model.forward_packed`` on packed rows
         (``x_like`` [1, rows, C], packed angles and pocket inputs; the masks are not read).  The layouts' device tables
-        are fixed for the chain, so the capture holds them like any other argument."""
+        are fixed for the chain, so the capture holds them like any other argument.
+        ``row_keys`` + ``seed``: the uniforms are the keyed stream of those rows at the integer step ``self.s_idx``."""
         dev = x_like.device
+        if (row_keys is None) != (seed is None) or (seed is not None and inject_u):
+            raise ValueError("a keyed graph needs row_keys and a seed, and no injected uniforms")
+        self.s_idx = torch.zeros((1,), device=dev, dtype=torch.long)
+        self.keyed_draw = None if seed is None else (row_keys, keyed.check_seed(seed), self.s_idx)
         self.args = (ligand_angles, ligand_mask, receptor_seq, receptor_angles, receptor_mask)
         self.layouts = layouts
         self.model, self.schedule, self.transition, self.diverse, self.T = model, noise_schedule, transition, diverse, T
@@ -172,13 +197,14 @@ class GraphedDenoiseStep:
             ang, _, rseq, rang, _ = self.args
             logits = self.model.forward_packed(self.s, self.x, ang, rseq, rang, *self.layouts)[None]
         return sample_p_zs_given_zt_discrete((self.s + 1) / self.T, self.s / self.T, self.x, logits, self.schedule, self.transition,
-                                             self.diverse, is_last_step=False, u=self.u)
+                                             self.diverse, is_last_step=False, u=self.u, keyed_draw=self.keyed_draw)
 
     def step(self, s_int, x, u=None):
         """z_t -> z_s for the step index ``s_int`` (> 0); returns the graph's output buffer (overwritten by the next call)."""
         if (u is not None) != (self.u is not None):
             raise ValueError("this graph was captured %s injected uniforms" % ("with" if self.u is not None else "without"))
         self.s.fill_(float(s_int))
+        self.s_idx.fill_(s_int)
         if x is not self.x:
             self.x.copy_(x)
         if u is not None:
@@ -199,7 +225,8 @@ def _use_graph(x):
 
 @torch.no_grad()
 def denoise(batch, model: PeptideDiff, noise_schedule, transition, diverse, x_T=None, us=None,
-            generated_angles=None, timesteps=None, trim_padding=False, use_graph=None, pack=False):
+            generated_angles=None, timesteps=None, trim_padding=False, use_graph=None, pack=False, seed=None,
+            item_ids=None):
     """Full reverse chain over CONFIG["timesteps"] steps + recovery metrics (reference
     sample.py:181-229).  ``x_T`` / ``us`` inject the initial one-hot noise and the per-step
     uniforms (parity tests); ``generated_angles`` replaces the dataset's ligand angles
@@ -211,10 +238,25 @@ def denoise(batch, model: PeptideDiff, noise_schedule, transition, diverse, x_T=
     are gathered to the packed rows; the default initial noise is drawn in the padded frame as before, the default
     uniforms of ``diverse`` chains are drawn for the packed rows, i.e. from a different place in the random stream.
     Masks that are not prefix masks run the trimmed frame instead (with a warning); an item with ligand rows but an
-    empty pocket raises ``ValueError``."""
+    empty pocket raises ``ValueError``.
+
+    ``seed``: keyed draws (keyed.py, DESIGN.md "Keyed sampling streams"): x_T and the uniforms of item b are functions
+    of (seed, item_ids[b], step, position) alone, so they do not depend on the batch, its order, the frame (padded /
+    trimmed / packed) or eager / graph launches.  ``item_ids`` default to 0 .. B-1 (``run`` uses the dataset index).
+    Exclusive with ``x_T`` / ``us``."""
     T = CONFIG["timesteps"] if timesteps is None else timesteps
     B, max_len, C = batch["ligand_seq"].shape
     dev = next(model.parameters()).device
+    ids = None
+    if seed is not None:
+        if x_T is not None or us is not None:
+            raise ValueError("denoise: pass either injected x_T / us or a seed, not both")
+        seed = keyed.check_seed(seed)
+        keyed.check_steps(T)
+        ids = keyed.item_ids(item_ids, B)
+        x_T = keyed_discrete_noise(seed, ids, max_len, C, dev)
+    elif item_ids is not None:
+        raise ValueError("denoise: item_ids key the seeded draws; pass a seed with them")
     x = generate_discrete_noise(B, max_len, C, dev) if x_T is None else x_T.to(dev)
     ligand_seq = batch["ligand_seq"].to(dev)
     ligand_mask = batch["ligand_attn_mask"].to(dev)
@@ -230,8 +272,9 @@ def denoise(batch, model: PeptideDiff, noise_schedule, transition, diverse, x_T=
                           "trimmed frame instead")
             trim_padding = True
     if layouts is not None:
+        row_keys = None if seed is None else keyed.packed_keys(layouts[0], ids)
         x = _denoise_packed(model, layouts, x, ligand_angles, receptor_seq, receptor_angles, noise_schedule, transition,
-                            diverse, T, us, use_graph)
+                            diverse, T, us, use_graph, row_keys, seed)
     else:
         if trim_padding:
             # as structure_model/sample.py::p_sample_loop(trim_padding=True): padding cannot influence valid positions,
@@ -244,11 +287,13 @@ def denoise(batch, model: PeptideDiff, noise_schedule, transition, diverse, x_T=
             receptor_mask = receptor_mask[:, :Lr].contiguous()
             if us is not None:
                 us = [u[:, :Ll] if u is not None and u.dim() >= 2 else u for u in us]
+        row_keys = None if seed is None else keyed.padded_keys(ids, x.shape[1], dev)
         graphed = None
         if (_use_graph(x) if use_graph is None else use_graph) and T > 4:
             try:
                 graphed = GraphedDenoiseStep(model, x, ligand_angles.contiguous(), ligand_mask, receptor_seq, receptor_angles, receptor_mask,
-                                             noise_schedule, transition, diverse, T, inject_u=us is not None)
+                                             noise_schedule, transition, diverse, T, inject_u=us is not None,
+                                             row_keys=row_keys, seed=seed)
             except Exception as e:   # noqa: BLE001 -- any capture problem: eager launches are always correct
                 warnings.warn(f"HIP-graph capture of the sequence reverse step failed ({type(e).__name__}: {e}); using eager launches")
         for n, s_int in enumerate(reversed(range(T))):
@@ -260,7 +305,8 @@ def denoise(batch, model: PeptideDiff, noise_schedule, transition, diverse, x_T=
             t_array = s_array + 1
             logits = model.forward(s_array, x, ligand_angles, ligand_mask, receptor_seq, receptor_angles, receptor_mask)
             x = sample_p_zs_given_zt_discrete(t_array / T, s_array / T, x, logits, noise_schedule, transition,
-                                              diverse, is_last_step=s_int == 0, u=None if us is None else us[n])
+                                              diverse, is_last_step=s_int == 0, u=None if us is None else us[n],
+                                              keyed_draw=_keyed_draw(row_keys, seed, s_int, dev))
     pred_idx, true_idx = x.argmax(dim=-1).cpu(), ligand_seq.argmax(dim=-1).cpu()
     mask = ligand_mask.bool().cpu()
     ids, true_sequences, pred_sequences, recovery_rates = [], [], [], []
@@ -275,8 +321,13 @@ def denoise(batch, model: PeptideDiff, noise_schedule, transition, diverse, x_T=
     return ids, true_sequences, pred_sequences, recovery_rates
 
 
+def _keyed_draw(row_keys, seed, s_int, dev):
+    """The keyed_draw argument of one eager step (the step index goes to the device, as in the graph)."""
+    return None if seed is None else (row_keys, seed, torch.full((1,), s_int, device=dev, dtype=torch.long))
+
+
 def _denoise_packed(model, layouts, x, ligand_angles, receptor_seq, receptor_angles, noise_schedule, transition, diverse, T,
-                    us, use_graph):
+                    us, use_graph, row_keys=None, seed=None):
     """The chain of ``denoise`` on packed rows: state [1, rows, C] (the posterior kernel sees B = 1, L = rows with one
     Q pair: every item shares the step), returned as [B, L, C] with zeros at the padding positions."""
     lay, lay_r = layouts
@@ -290,7 +341,7 @@ def _denoise_packed(model, layouts, x, ligand_angles, receptor_seq, receptor_ang
     if (_use_graph(xp) if use_graph is None else use_graph) and T > 4:
         try:
             graphed = GraphedDenoiseStep(model, xp, ang, None, rseq, rang, None, noise_schedule, transition, diverse, T,
-                                         inject_u=us is not None, layouts=layouts)
+                                         inject_u=us is not None, layouts=layouts, row_keys=row_keys, seed=seed)
         except Exception as e:   # noqa: BLE001 -- any capture problem: eager launches are always correct
             warnings.warn(f"HIP-graph capture of the packed sequence reverse step failed ({type(e).__name__}: {e}); using "
                           "eager launches")
@@ -302,19 +353,25 @@ def _denoise_packed(model, layouts, x, ligand_angles, receptor_seq, receptor_ang
         s_array = torch.full((1, 1), float(s_int), device=dev)
         logits = model.forward_packed(s_array, xp, ang, rseq, rang, lay, lay_r)[None]
         xp = sample_p_zs_given_zt_discrete((s_array + 1) / T, s_array / T, xp, logits, noise_schedule, transition, diverse,
-                                           is_last_step=s_int == 0, u=None if us is None else us[n])
+                                           is_last_step=s_int == 0, u=None if us is None else us[n],
+                                           keyed_draw=_keyed_draw(row_keys, seed, s_int, dev))
     return lay.unpack(xp[0])
 
 
-def run(transition, diverse=True):
+def run(transition, diverse=True, seed=None):
+    """Sample every test ligand.  ``seed`` (default ``SEED``, E3D_SAMPLE_SEED): keyed draws by dataset index."""
     import pandas as pd
+    seed = SEED if seed is None else seed
     loader = get_dataloader(DATA_PATH)
     model = get_model(len(loader))
     schedule = PredefinedNoiseScheduleDiscrete(CONFIG["noise_schedule"], CONFIG["timesteps"]).to(DEVICE)
     cols = ([], [], [], [])
     for idx, batch in enumerate(loader):
         print(f"Generating Batch {idx}")
-        for acc, part in zip(cols, denoise(batch, model, schedule, transition, diverse, pack=PACK)):
+        n = batch["ligand_seq"].shape[0]
+        ids = None if seed is None else list(range(idx * CONFIG["batch_size"], idx * CONFIG["batch_size"] + n))
+        for acc, part in zip(cols, denoise(batch, model, schedule, transition, diverse, pack=PACK, seed=seed,
+                                           item_ids=ids)):
             acc.extend(part)
     res = pd.DataFrame(zip(*cols), columns=["structure_ids", "true_sequence", "predict_sequence", "recovery_rate"])
     res.to_pickle(OUTPUT_PATH)

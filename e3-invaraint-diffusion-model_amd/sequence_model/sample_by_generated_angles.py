@@ -55,7 +55,8 @@ def angles_from_trajectory(traj, ligand_mask):
 
 
 def denoise(batch, generated_angles, model, noise_schedule, transition, diverse, **kw):
-    """reference lines 196-243: sample.denoise with the ligand angles replaced."""
+    """reference lines 196-243: sample.denoise with the ligand angles replaced.  ``seed`` / ``item_ids`` (and every
+    other keyword of sample.denoise) pass through: a seeded joint run keys both stages by the same item ids."""
     return _denoise(batch, model, noise_schedule, transition, diverse, generated_angles=generated_angles, **kw)
 
 

@@ -23,7 +23,7 @@ import warnings
 import torch
 from torch import nn
 
-from .. import ops, packing
+from .. import keyed, ops, packing
 from ..bert import BertConfig
 from .dataset import LigandBindingSiteDataset, NoisedAnglesDataset
 from .model import ConditionalBertForDiffusion
@@ -42,6 +42,9 @@ ARITHMETIC = "f16x3"
 # Packed chains (p_sample_loop(pack=True)): the batch runs on its valid rows only; off by default, E3D_SAMPLE_PACK=1 turns
 # it on for ``sample()``.
 PACK = os.environ.get("E3D_SAMPLE_PACK", "0") == "1"
+# Keyed draws (``sample(seed=...)``): every random number of a pocket's chain is a function of (seed, dataset index), so
+# batch size, order, frame and launch mode do not change its sample.  None (default): torch's generator, as before.
+SEED = int(os.environ["E3D_SAMPLE_SEED"], 0) if os.environ.get("E3D_SAMPLE_SEED") else None
 
 CONFIG = {
     "pocket_ext": 0,
@@ -75,7 +78,8 @@ def _tables(betas):
 
 @torch.no_grad()
 def p_sample(model, ligand_mask, ligand_angle_noise, receptor_seq, receptor_mask, receptor_angle,
-             timestep, betas, noise=None, receptor_cache=None, out=None, wrap=False) -> torch.Tensor:
+             timestep, betas, noise=None, receptor_cache=None, out=None, wrap=False, seed=None,
+             item_ids=None) -> torch.Tensor:
     """One reverse step x_t -> x_{t-1} (reference sample.py:55-99).  Like the reference's
     p_sample the result is NOT wrapped unless ``wrap=True`` (p_sample_loop's sample.py:140-142
     fused into the same kernel).
@@ -83,13 +87,45 @@ def p_sample(model, ligand_mask, ligand_angle_noise, receptor_seq, receptor_mask
     ``timestep``: int64 [B] with one distinct value (asserted, as in the reference) or an int.
     ``betas``: the schedule betas [T] (any device) or a prebuilt CosineTables.
     ``noise``: optional injected N(0,1) draw (parity tests); default torch.randn_like on device.
+    ``seed``: draw the noise from the keyed stream of (seed, item_ids[b], position) instead (``item_ids`` default
+    0 .. B-1; see keyed.py); exclusive with ``noise``.
     """
+    keyed_step = None
+    if seed is not None:
+        if noise is not None:
+            raise ValueError("p_sample: pass either an injected noise or a seed, not both")
+        x = ligand_angle_noise
+        keyed_step = _keyed_step(seed, keyed.padded_keys(keyed.item_ids(item_ids, x.shape[0]), x.shape[1], x.device),
+                                 _tables(betas), x.device)
+    elif item_ids is not None:
+        raise ValueError("p_sample: item_ids key the seeded draws; pass a seed with them")
     return _reverse_step(model, ligand_mask, ligand_angle_noise, receptor_seq, receptor_mask,
-                         receptor_angle, timestep, betas, noise, receptor_cache, out, wrap=wrap)
+                         receptor_angle, timestep, betas, noise, receptor_cache, out, wrap=wrap, keyed_step=keyed_step)
+
+
+def _coef_table(tab, dev):
+    """[T,4] = (sqrt_recip_alpha, beta, sqrt_one_minus_alphas_cumprod, sigma): the table the device-step kernels read."""
+    return torch.stack([tab.sqrt_recip_alphas, tab.betas, tab.sqrt_one_minus_alphas_cumprod, tab.sigma],
+                       dim=1).float().contiguous().to(dev)
+
+
+def _keyed_step(seed, row_keys, tab, dev):
+    """What a keyed reverse step needs besides the state: (row keys, seed, coefficient table)."""
+    keyed.check_steps(tab.betas.shape[0])
+    return row_keys, keyed.check_seed(seed), _coef_table(tab, dev)
+
+
+def keyed_x_T(seed, item_ids, L, n_ft=8, scale=1.0, device=None):
+    """Keyed initial state [B, L, n_ft]: wrap_[-pi,pi)(scale * z) with z the stream-0 normals of (seed, item_ids[b], l)
+    -- NoisedAnglesDataset.sample_noise's distribution, drawn per item instead of per batch."""
+    device = DEVICE if device is None else device
+    ids = keyed.item_ids(item_ids, len(item_ids))
+    keys = keyed.padded_keys(ids, L, device)
+    return ops.keyed_initial_angles(keys, seed, n_ft, scale).reshape(len(ids), L, n_ft)
 
 
 def _reverse_step(model, ligand_mask, x_t, receptor_seq, receptor_mask, receptor_angle, timestep,
-                  betas, noise, receptor_cache, out, wrap, mod=None, layout=None):
+                  betas, noise, receptor_cache, out, wrap, mod=None, layout=None, keyed_step=None):
     tab = _tables(betas)
     if isinstance(timestep, int):
         t_index = timestep
@@ -108,6 +144,10 @@ def _reverse_step(model, ligand_mask, x_t, receptor_seq, receptor_mask, receptor
     beta = float(tab.betas[t_index])
     s1m = float(tab.sqrt_one_minus_alphas_cumprod[t_index])
     x_c = x_t.contiguous().float()
+    if keyed_step is not None:     # the draw happens in the kernel, at the device step index
+        row_keys, seed, coef = keyed_step
+        t_dev = timestep.to(device=x_c.device, dtype=torch.long).contiguous()
+        return ops.keyed_ddpm_step_wrap(x_c, eps_hat.contiguous(), coef, t_dev, row_keys, seed, wrap=wrap, out=out)
     if t_index == 0:
         noise, sigma = None, 0.0
     else:
@@ -123,6 +163,8 @@ class GraphedReverseStep:
     per step.  Everything that varies between steps lives on the device: the step index (``self.t``,
     also the row of the [T,4] coefficient table read by ``e3d_ddpm_step_wrap_table``), the state
     ``self.x`` and the noise draw.  Results are bit-identical to the eager path for the same noise.
+    A keyed step (``row_keys`` and ``seed``) generates its draw inside the update kernel from the step index: no noise
+    buffer, and bit-identical to the eager keyed step.
 
     Default for chains of at most GRAPH_MAX_ROWS token rows (up to ~16 pockets of 64 residues), ``use_graph=True`` /
     E3D_SAMPLE_GRAPH=1 forces it, =0 turns it off.  Measured on MI355X, one 64-residue pocket (tools/bench_single.py):
@@ -130,20 +172,24 @@ class GraphedReverseStep:
     busy with dependent kernels, the graph had nothing to remove.  Round 2, K-sliced small-M GEMMs of ~7 us per product
     (csrc/gemm_skinny.hip): eager launches are now host-bound at 2.4 ms per step, a replay takes 1.5 ms."""
 
-    def __init__(self, model, ligand_mask, cache, tab, x_like, wrap=True, draw=True, mod_table=None, layout=None):
+    def __init__(self, model, ligand_mask, cache, tab, x_like, wrap=True, draw=True, mod_table=None, layout=None,
+                 row_keys=None, seed=None):
         """``draw``: the graph draws its own N(0,1) noise each replay; False: ``step`` takes the draw (parity tests).
+        ``row_keys`` + ``seed`` (with ``draw``): the draw is the keyed stream of those rows (keyed.py).
         ``mod_table`` [T,6H]: row t = model.timestep_modulation(t), read on the device by the step index.
         ``layout``: the step runs on packed ligand rows (``x_like`` [rows,F]; a packed ``cache``); its segment and tile
         tables are device tensors fixed for the chain, so the capture holds them like any other argument."""
         dev = x_like.device
         self.model, self.mask, self.cache, self.wrap, self.mod_table = model, ligand_mask, cache, wrap, mod_table
         self.layout = layout
+        if (row_keys is None) != (seed is None) or (seed is not None and not draw):
+            raise ValueError("a keyed graph needs row_keys and a seed, and draws its own noise")
+        self.keyed = None if seed is None else (row_keys, keyed.check_seed(seed))
         self.x = torch.empty_like(x_like)
         self.out = torch.empty_like(x_like)
-        self.noise = torch.zeros_like(x_like)
+        self.noise = None if self.keyed is not None else torch.zeros_like(x_like)
         self.t = torch.zeros((x_like.shape[0],), device=dev, dtype=torch.long)
-        self.coef = torch.stack([tab.sqrt_recip_alphas, tab.betas, tab.sqrt_one_minus_alphas_cumprod, tab.sigma],
-                                dim=1).float().contiguous().to(dev)
+        self.coef = _coef_table(tab, dev)
         self.draw = draw
         self.x.copy_(x_like)
         side = torch.cuda.Stream(device=dev)
@@ -161,6 +207,10 @@ class GraphedReverseStep:
             eps_hat = self.model.decode(self.t, self.x, self.mask, self.cache, mod=mod)
         else:
             eps_hat = self.model.decode(self.t, self.x, self.mask, self.cache, mod=mod, layout=self.layout)
+        if self.keyed is not None:
+            ops.keyed_ddpm_step_wrap(self.x, eps_hat.contiguous(), self.coef, self.t, *self.keyed, wrap=self.wrap,
+                                     out=self.out)
+            return
         if self.draw:
             self.noise.normal_()
         ops.ddpm_step_wrap_table(self.x, eps_hat.contiguous(), self.noise, self.coef, self.t, wrap=self.wrap, out=self.out)
@@ -204,7 +254,7 @@ def trimmed_length(mask, multiple=32):
 def p_sample_loop(model: nn.Module, ligand_mask, ligand_angle_noise, receptor_seq, receptor_mask,
                   receptor_angle, total_timesteps: int, betas, disable_pbar: bool = False,
                   noises=None, return_device: bool = False, step: int = None, use_graph: bool = None,
-                  trim_padding: bool = False, pack: bool = False) -> torch.Tensor:
+                  trim_padding: bool = False, pack: bool = False, seed: int = None, item_ids=None) -> torch.Tensor:
     """Full reverse chain; returns [T/STEP, B, L, n_ft] (on the host like the reference,
     sample.py:101-144, unless ``return_device``).  ``noises`` [T/STEP,B,L,n_ft] injects the draws.
     ``use_graph``: replay one captured HIP graph per step (None: by size, E3D_SAMPLE_GRAPH=0/1 overrides -- see
@@ -216,17 +266,33 @@ def p_sample_loop(model: nn.Module, ligand_mask, ligand_angle_noise, receptor_se
     [T/STEP, B, L, n_ft] shape.  Injected ``noises`` (padded layout) are gathered to the packed rows; default draws are
     made for the packed rows, i.e. they come from a different place in the random stream than the padded chain's.
     Masks that are not prefix masks cannot be packed: the chain then runs the trimmed frame (with a warning).  An item
-    with ligand rows but an empty pocket raises ``ValueError``."""
+    with ligand rows but an empty pocket raises ``ValueError``.
+
+    ``seed``: keyed draws (keyed.py, DESIGN.md "Keyed sampling streams"): the noise of step i at position l of item b is
+    a function of (seed, item_ids[b], i, l) alone, generated inside the update kernel -- the same whatever the batch, its
+    order, the frame (padded / trimmed / packed) or eager / graph launches.  ``item_ids`` default to 0 .. B-1; pass
+    each pocket's own id (the entry point uses the dataset index).  Exclusive with ``noises``.  x_T stays the caller's
+    (``keyed_x_T`` draws a keyed one)."""
     step = STEP if step is None else step
     tab = _tables(betas)
     order = list(reversed(range(0, total_timesteps, step)))
     x = ligand_angle_noise.contiguous().float()
     full_traj = None
+    ids = None
+    if seed is not None:
+        if noises is not None:
+            raise ValueError("p_sample_loop: pass either injected noises or a seed, not both")
+        ids = keyed.item_ids(item_ids, x.shape[0])
+        seed = keyed.check_seed(seed)
+        keyed.check_steps(total_timesteps)
+    elif item_ids is not None:
+        raise ValueError("p_sample_loop: item_ids key the seeded draws; pass a seed with them")
     if pack:
         layouts = packing.layouts_or_none(ligand_mask, receptor_mask)
         if layouts is not None:
+            keyed_step = None if seed is None else _keyed_step(seed, keyed.packed_keys(layouts[0], ids), tab, x.device)
             return _p_sample_loop_packed(model, layouts, x, receptor_seq, receptor_angle, receptor_mask, total_timesteps,
-                                         tab, order, noises, return_device, use_graph)
+                                         tab, order, noises, return_device, use_graph, keyed_step)
         warnings.warn("pack=True: a padding mask is not a prefix mask, so the batch cannot be packed; running the "
                       "trimmed frame instead")
         trim_padding = True
@@ -244,6 +310,7 @@ def p_sample_loop(model: nn.Module, ligand_mask, ligand_angle_noise, receptor_se
             receptor_angle = receptor_angle[:, :Lr].contiguous()
             if noises is not None:
                 noises = noises[:, :, :Ll]
+    keyed_step = None if seed is None else _keyed_step(seed, keyed.padded_keys(ids, x.shape[1], x.device), tab, x.device)
     cache = model.encode_receptor(receptor_seq, receptor_angle, receptor_mask)
     traj = torch.empty((len(order),) + tuple(x.shape), device=x.device, dtype=torch.float32)
     # what depends on the timestep alone, for the whole chain at once: row t of the table = timestep_modulation(t)
@@ -254,7 +321,7 @@ def p_sample_loop(model: nn.Module, ligand_mask, ligand_angle_noise, receptor_se
     if (_use_graph(x) if use_graph is None else use_graph) and len(order) > 4:
         try:
             graphed = GraphedReverseStep(model, ligand_mask.contiguous().float(), cache, tab, x, draw=noises is None,
-                                         mod_table=mod_table)
+                                         mod_table=mod_table, **_graph_keys(keyed_step))
         except Exception as e:   # noqa: BLE001 -- any capture problem: eager launches are always correct
             warnings.warn(f"HIP-graph capture of the reverse step failed ({type(e).__name__}: {e}); using eager launches")
             graphed = None
@@ -264,15 +331,20 @@ def p_sample_loop(model: nn.Module, ligand_mask, ligand_angle_noise, receptor_se
             traj[n].copy_(x)
         else:
             x = _reverse_step(model, ligand_mask, x, None, None, None, i, tab,
-                              None if noises is None else noises[n], cache, traj[n], wrap=True, mod=mod_table[i:i + 1])
+                              None if noises is None else noises[n], cache, traj[n], wrap=True, mod=mod_table[i:i + 1],
+                              keyed_step=keyed_step)
     if full_traj is not None:
         full_traj[:, :, :traj.shape[2]] = traj
         traj = full_traj
     return traj if return_device else traj.cpu()
 
 
+def _graph_keys(keyed_step):
+    return {} if keyed_step is None else {"row_keys": keyed_step[0], "seed": keyed_step[1]}
+
+
 def _p_sample_loop_packed(model, layouts, x, receptor_seq, receptor_angle, receptor_mask, total_timesteps, tab, order,
-                          noises, return_device, use_graph):
+                          noises, return_device, use_graph, keyed_step=None):
     lay, lay_r = layouts
     cache = model.encode_receptor(receptor_seq, receptor_angle, receptor_mask, layout=lay_r)
     xp = lay.pack(x)                                                      # [rows, F], zero tail
@@ -285,7 +357,7 @@ def _p_sample_loop_packed(model, layouts, x, receptor_seq, receptor_angle, recep
     if (_use_graph(xp) if use_graph is None else use_graph) and len(order) > 4:
         try:
             graphed = GraphedReverseStep(model, None, cache, tab, xp, draw=noises is None, mod_table=mod_table,
-                                         layout=lay)
+                                         layout=lay, **_graph_keys(keyed_step))
         except Exception as e:   # noqa: BLE001 -- any capture problem: eager launches are always correct
             warnings.warn(f"HIP-graph capture of the packed reverse step failed ({type(e).__name__}: {e}); using eager "
                           "launches")
@@ -296,7 +368,7 @@ def _p_sample_loop_packed(model, layouts, x, receptor_seq, receptor_angle, recep
             traj[n].copy_(xp)
         else:
             xp = _reverse_step(model, None, xp, None, None, None, i, tab, None if noises_p is None else noises_p[n],
-                               cache, traj[n], wrap=True, mod=mod_table[i:i + 1], layout=lay)
+                               cache, traj[n], wrap=True, mod=mod_table[i:i + 1], layout=lay, keyed_step=keyed_step)
     traj = lay.unpack(traj, dim=1)                                        # [T/STEP, B, L, F], zeros at padding
     return traj if return_device else traj.cpu()
 
@@ -332,10 +404,15 @@ def load_model(dataset, model_path=None):
     return model.eval().to(DEVICE)
 
 
-def sample(model, test_angle_ds, all_batches: bool = False):
+def sample(model, test_angle_ds, all_batches: bool = False, seed: int = None):
     """Sample the test pockets in batches of CONFIG["batch_size"]; returns a list of
     [T, l_i, 8] arrays trimmed to each ligand's length.  Like the reference (sample.py:237) only
-    the first batch is generated unless ``all_batches``."""
+    the first batch is generated unless ``all_batches``.
+
+    ``seed`` (default ``SEED``, E3D_SAMPLE_SEED): keyed draws for x_T and the chain, keyed by the dataset index, so a
+    pocket's sample does not depend on the batch size, on its place in the batch, on packing or on an arithmetic
+    re-run of its batch."""
+    seed = SEED if seed is None else seed
     bs = CONFIG["batch_size"]
     items = [test_angle_ds[i] for i in range(len(test_angle_ds))]
 
@@ -349,7 +426,11 @@ def sample(model, test_angle_ds, all_batches: bool = False):
     for idx, lm in enumerate(ligand_mask):
         print(f"Generating Batch {idx}/{len(ligand_mask)}")
         lengths = lm.sum(dim=1).int()
-        x_T = test_angle_ds.sample_noise(torch.zeros((len(lengths), pad, feature_size)))
+        ids = list(range(idx * bs, idx * bs + len(lengths)))      # dataset indices of the batch
+        if seed is None:
+            x_T = test_angle_ds.sample_noise(torch.zeros((len(lengths), pad, feature_size)))
+        else:
+            x_T = keyed_x_T(seed, ids, pad, feature_size, test_angle_ds.angular_var_scale, DEVICE)
         def chain(arithmetic):
             with ops.arithmetic(arithmetic):
                 return p_sample_loop(
@@ -357,7 +438,7 @@ def sample(model, test_angle_ds, all_batches: bool = False):
                     receptor_seq=receptor_seq[idx].to(DEVICE), receptor_mask=receptor_mask[idx].to(DEVICE),
                     receptor_angle=receptor_angle[idx].to(DEVICE), total_timesteps=test_angle_ds.timesteps,
                     betas=test_angle_ds.alpha_beta_terms["betas"], trim_padding=True,   # sliced to l_i right below
-                    pack=PACK)
+                    pack=PACK, seed=seed, item_ids=None if seed is None else ids)
 
         sampled = chain(ARITHMETIC)
         if ops.GEMM_MODES.get(ARITHMETIC) == 19 and "E3D_GEMM_MODE" not in os.environ and not bool(torch.isfinite(sampled).all()):

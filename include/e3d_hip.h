@@ -245,6 +245,36 @@ int e3d_discrete_posterior_sample(const int32_t* xt_idx, const float* logits, co
 int e3d_discrete_q_sample(const int32_t* x0_idx, const float* Qtb, const float* u, int mode,
                           int32_t* out_idx, int B, int L, int C, void* stream);
 
+/* ------------------------------------------------------------------ keyed (seeded) sampling draws
+ * Every random number of a seeded chain is Philox4x32-10 of the counter (item id lo, item id hi, stream << 16 | step,
+ * position << 8 | block) under the key (seed lo, seed hi), mapped to fp32 from 24-bit fields ("Keyed
+ * sampling streams"; csrc/e3d_philox.h).  Streams: 0 structure x_T, 1 structure reverse-step noise, 2 sequence initial
+ * one-hot, 3 sequence posterior uniforms.  ``row_keys`` int64 [rows, 2] = (item id, position) per row; a negative
+ * position marks a row of no item (a packed buffer's tail), which draws nothing.  The caller guarantees positions
+ * < 2^24 and steps <= 65535.  Step indices are read from DEVICE memory (``t_dev`` / ``s_dev``, first element), so a
+ * captured graph replays them. */
+
+/* e3d_ddpm_step_wrap_table with the noise generated in-register: row r, features 4j .. 4j+3 take the normals of
+ * (seed, row_keys[r], stream 1, t_dev[0], block j).  x / eps_hat / out [rows, F], F % 4 == 0, F <= 1024.  Equals
+ * e3d_ddpm_step_wrap_table fed with those normals (zeros on rows of no item); sigma == 0 (t == 0) gives the mean. */
+int e3d_keyed_ddpm_step_wrap(const float* x, const float* eps_hat, const float* coef_table, const int64_t* t_dev,
+                             const int64_t* row_keys, uint64_t seed, int wrap, float* out, int64_t rows, int F,
+                             void* stream);
+
+/* e3d_discrete_posterior_sample in mode 1 with the uniform of row n = b * L + l drawn from stream 3 at step s_dev[0]
+ * with key row_keys[n] (padded [B, L] batches, or a packed buffer as B = 1, L = rows); rows of no item draw u = 0. */
+int e3d_keyed_discrete_posterior_sample(const int32_t* xt_idx, const float* logits, const float* Qsb,
+                                        const float* Qtb, const int64_t* row_keys, uint64_t seed,
+                                        const int64_t* s_dev, int32_t* out_idx, int B, int L, int C, void* stream);
+
+/* Raw keyed draws of one (stream_id, t) for every row of a key table; rows of no item give zeros.
+ *   kind 0: normals float [rows, width] (width % 4 == 0); wrap != 0: wrap_[-pi,pi)(scale * z) (stream 0: keyed x_T);
+ *   kind 1: uniforms float [rows] (word 0 of block 0);
+ *   kind 2: classes in [0, width) from word 0 of block 0, as a float one-hot [rows, width] (stream 2: keyed x_T);
+ *   kind 3: the same classes as int32 [rows]. */
+int e3d_keyed_draws(const int64_t* row_keys, uint64_t seed, int stream_id, int t, int kind, int width, int wrap,
+                    float scale, void* out, int64_t rows, void* stream);
+
 /* NeRF backbone builder, the step after structure sampling (structure_model/create_pdb.py:104-155,
  * 175-234): angles [B,L,8] fp32 in the dataset's column order
  * (phi psi omega dihedral_o tau CA:C:1N 1C:N:CA CA:C:O), lengths int32 [B] -> coords float64

@@ -24,7 +24,7 @@ from e3diff_amd.bert import BertConfig  # noqa: E402
 DEV = "cuda:0"
 
 
-def run(batch=128, seq_len=128, t_structure=1000, t_sequence=50, trim=False, device=DEV, pack=False):
+def run(batch=128, seq_len=128, t_structure=1000, t_sequence=50, trim=False, device=DEV, pack=False, seed=None):
     """One GPU's share of BASELINE config 5 (sequence_model/sample_by_generated_angles.py:196-278): structure chain ->
     hand-over on the device -> sequence chain.  Returns a dict (also the ``joint`` key of bench.py's line)."""
     B, L = batch, seq_len
@@ -48,6 +48,8 @@ def run(batch=128, seq_len=128, t_structure=1000, t_sequence=50, trim=False, dev
     dpk = {k: v.to(device) for k, v in pk.items() if torch.is_tensor(v)}
     tab = CosineTables(t_structure)
     x_T = modulo_with_wrapped_range(torch.randn(B, L, 8, device=device))
+    if seed is not None:
+        x_T = SS.keyed_x_T(seed, range(B), L, 8, device=device)
 
     def sync():
         torch.cuda.synchronize()
@@ -60,12 +62,13 @@ def run(batch=128, seq_len=128, t_structure=1000, t_sequence=50, trim=False, dev
     t0 = sync()
     traj = SS.p_sample_loop(smodel, dpk["ligand_attn_mask"], x_T, dpk["receptor_seq"], dpk["receptor_attn_mask"],
                             dpk["receptor_angles"], t_structure, tab, disable_pbar=True, return_device=True, step=1,
-                            trim_padding=trim, pack=pack)
+                            trim_padding=trim, pack=pack, seed=seed, item_ids=None if seed is None else range(B))
     t1 = sync()
     angles = QJ.angles_from_trajectory(traj, dpk["ligand_attn_mask"])
     schedule = PredefinedNoiseScheduleDiscrete("cosine", t_sequence).to(device)
     ids, true_s, pred_s, rec = QJ.denoise(pk, angles, qmodel, schedule, DiscreteUniformTransition(20), True, trim_padding=trim,
-                                          timesteps=t_sequence, pack=pack)
+                                          timesteps=t_sequence, pack=pack, seed=seed,
+                                          item_ids=None if seed is None else range(B))
     t2 = sync()
     assert len(pred_s) == B and bool(torch.isfinite(traj[-1]).all())
     mib = traj.numel() * 4 / 2 ** 20
@@ -85,8 +88,10 @@ def main():
     ap.add_argument("--t-sequence", type=int, default=50)
     ap.add_argument("--trim", action="store_true", help="trim_padding=True in both chains (frame of the longest ligand / pocket)")
     ap.add_argument("--pack", action="store_true", help="pack=True in both chains (the valid rows of every item back to back)")
+    ap.add_argument("--seed", type=int, default=None, help="keyed draws in both chains, items keyed 0 .. batch-1 "
+                    "(default: torch's generator)")
     a = ap.parse_args()
-    r = run(a.batch, a.seq_len, a.t_structure, a.t_sequence, a.trim, pack=a.pack)
+    r = run(a.batch, a.seq_len, a.t_structure, a.t_sequence, a.trim, pack=a.pack, seed=a.seed)
     print(f"joint sampling ({r['frames']}), {r['pockets']} pockets x L={r['seq_len']} on one GPU: structure {r['structure_steps']} steps "
           f"{r['structure_s']:.2f} s ({r['structure_pocket_steps_per_s']:.0f} pocket-steps/s, encoder cached), sequence "
           f"{r['sequence_steps']} steps {r['sequence_s']:.2f} s ({r['sequence_pocket_steps_per_s']:.0f} pocket-steps/s); total "

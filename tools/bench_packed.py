@@ -101,13 +101,14 @@ def sequence_leg(device, args, B_seq=128, L_seq=128, T_seq=50):
     Ll, Lr = trimmed_length(pk["ligand_attn_mask"]), trimmed_length(pk["receptor_attn_mask"])
     modes = {"padded": {}, "trimmed": {"trim_padding": True}, "packed": {"pack": True}}
     rate = {}
+    seeded = {} if args.seed is None else {"seed": args.seed, "item_ids": range(B_seq)}
     quiet = contextlib.redirect_stdout(io.StringIO())    # denoise prints the mean recovery rate
     with quiet:
         for name, kw in modes.items():
             denoise(pk, qmodel, sched, tr, True, timesteps=6, **kw)               # warm-up (first launches, capture)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            denoise(pk, qmodel, sched, tr, True, timesteps=T_seq, **kw)
+            denoise(pk, qmodel, sched, tr, True, timesteps=T_seq, **kw, **seeded)
             torch.cuda.synchronize()
             rate[name] = B_seq * T_seq / (time.perf_counter() - t0)
         torch.manual_seed(4)
@@ -131,6 +132,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--leg", choices=["packed", "trimmed"], default=None)
     ap.add_argument("--summarize", nargs=2, metavar=("PACKED_CSV", "TRIMMED_CSV"), default=None)
+    ap.add_argument("--seed", type=int, default=None, help="keyed draws in the timed chains, items keyed 0 .. B-1 "
+                    "(default: torch's generator)")
     args = ap.parse_args()
     if args.summarize:
         s = summarize(*args.summarize, args.steps)
@@ -180,9 +183,20 @@ def main():
         return None, lay.pack(x), cache, lay
 
     mod_table = model.timestep_modulation(torch.arange(1000, device=device)).contiguous()
+    from e3diff_amd import keyed
+
+    def frame_keys(kind):
+        """Key table of a frame's rows (--seed), or None."""
+        if args.seed is None:
+            return None
+        if kind == "packed":
+            return keyed.packed_keys(lay, list(range(B)))
+        return keyed.padded_keys(list(range(B)), L if kind == "padded" else Ll, device)
 
     def eager(kind, steps):
         mask, xa, cache, layout = frame(kind)
+        keys = frame_keys(kind)
+        ks = None if keys is None else S._keyed_step(args.seed, keys, tab, device)
         xb = torch.empty_like(xa)
         for k_steps in (args.warmup, steps):
             torch.cuda.synchronize()
@@ -190,7 +204,7 @@ def main():
             for j in range(k_steps):
                 i = 999 - j
                 y = S._reverse_step(model, mask, xa, None, None, None, i, tab, None, cache, xb, True,
-                                    mod=mod_table[i:i + 1], layout=layout)
+                                    mod=mod_table[i:i + 1], layout=layout, keyed_step=ks)
                 xa, xb = y, xa
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
@@ -198,8 +212,9 @@ def main():
 
     def graphed(kind, steps):
         mask, xa, cache, layout = frame(kind)
+        keys = frame_keys(kind)
         g = S.GraphedReverseStep(model, None if mask is None else mask.contiguous().float(), cache, tab, xa,
-                                 mod_table=mod_table, layout=layout)
+                                 mod_table=mod_table, layout=layout, row_keys=keys, seed=None if keys is None else args.seed)
         for k_steps in (args.warmup, steps):
             torch.cuda.synchronize()
             t0 = time.perf_counter()

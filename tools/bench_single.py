@@ -23,8 +23,9 @@ from e3diff_amd.bert import BertConfig  # noqa: E402
 DEV = "cuda:0"
 
 
-def run(seq_len=64, batch=1, steps=50, graph=None, chains=3):
-    """Best of ``chains`` full reverse chains; returns a dict (also the ``single_pocket`` key of bench.py's line)."""
+def run(seq_len=64, batch=1, steps=50, graph=None, chains=3, seed=None):
+    """Best of ``chains`` full reverse chains; returns a dict (also the ``single_pocket`` key of bench.py's line).
+    ``seed``: keyed draws (p_sample_loop(seed=...)): the noise is generated inside the update kernel."""
     from e3diff_amd.structure_model import sample as S
     from e3diff_amd.structure_model.model import ConditionalBertForDiffusionBase
     from e3diff_amd.structure_model.utils import CosineTables, modulo_with_wrapped_range
@@ -39,7 +40,7 @@ def run(seq_len=64, batch=1, steps=50, graph=None, chains=3):
     def chain():
         return S.p_sample_loop(model, pk["ligand_attn_mask"], x_T, pk["receptor_seq"], pk["receptor_attn_mask"],
                                pk["receptor_angles"], T, tab, disable_pbar=True, return_device=True, step=1,
-                               use_graph=None if graph is None else bool(graph))
+                               use_graph=None if graph is None else bool(graph), seed=seed)
 
     with pkg.ops.arithmetic(S.ARITHMETIC):
         chain()
@@ -54,7 +55,7 @@ def run(seq_len=64, batch=1, steps=50, graph=None, chains=3):
         mode = pkg.ops.GEMM_MODE
     assert bool(torch.isfinite(out).all())
     return {"batch": B, "seq_len": L, "timesteps": T, "arithmetic": mode, "graph_replay": "sampler default" if graph is None else bool(graph),
-            "ms_per_chain": best * 1e3, "ms_per_step": best / T * 1e3,
+            "seed": seed, "ms_per_chain": best * 1e3, "ms_per_step": best / T * 1e3,
             "note": "structure_model/sample.py p_sample_loop: encoder + cross K/V once per chain, 12-layer decoder + DDPM update per step"}
 
 
@@ -93,10 +94,11 @@ def main():
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--graph", type=int, default=None, choices=(0, 1), help="1: replay one captured HIP graph per step, 0: eager launches (default: the sampler's own choice)")
+    ap.add_argument("--seed", type=int, default=None, help="keyed draws with this seed (default: torch's generator)")
     a = ap.parse_args()
-    r = run(a.seq_len, a.batch, a.steps, a.graph)
+    r = run(a.seq_len, a.batch, a.steps, a.graph, seed=a.seed)
     print(f"single-pocket sampling B={r['batch']} L={r['seq_len']} T={r['timesteps']} ({r['arithmetic']}, skinny GEMM M<={pkg.ops.SKINNY_MAX_M}, "
-          f"graph={a.graph}): {r['ms_per_chain']:.1f} ms per chain = {r['ms_per_step']:.3f} ms per reverse step (encoder cached)", flush=True)
+          f"graph={a.graph}, seed={a.seed}): {r['ms_per_chain']:.1f} ms per chain = {r['ms_per_step']:.3f} ms per reverse step (encoder cached)", flush=True)
 
 
 if __name__ == "__main__":
