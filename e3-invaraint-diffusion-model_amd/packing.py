@@ -8,10 +8,20 @@ row kernel keeps the shapes it is tested on; the attention kernel writes zeros i
 
 Every op of the BERT stacks except attention is row-wise, so a packed forward runs the padded-frame executors on
 [rows, H] activations (B = 1, L = rows) with the attention calls replaced by the varlen kernel.  Inference only.
+
+A ``Frame`` is the choice both samplers make once per chain between the padded, the trimmed and the packed rows.
 """
+import os
+import warnings
+
 import torch
 
+from . import keyed
+
 TILE = 32
+# ligand rows up to which a sampling chain replays a captured graph by default (B=8 x L=64: 2.05 vs 2.16 ms eager;
+# B=16: GPU-bound, eager); E3D_SAMPLE_GRAPH=0/1 overrides
+GRAPH_MAX_ROWS = 512
 
 
 class NotPackable(Exception):
@@ -32,6 +42,16 @@ def prefix_lengths(mask):
     if m.shape[1] > 1 and not bool((m[:, :-1] >= m[:, 1:]).all()):
         raise NotPackable("padding mask is not a prefix mask: the batch cannot be packed")
     return [int(n) for n in lengths]
+
+
+def trimmed_length(mask, multiple=TILE):
+    """Smallest multiple of ``multiple`` that covers every valid position of a [B,L] 0/1 padding mask whose valid
+    positions are a prefix (the dataset layout, dataset.py:119-132); L itself if any row is not a prefix mask."""
+    try:
+        longest = max(prefix_lengths(mask), default=0)
+    except NotPackable:
+        return mask.shape[1]
+    return max(multiple, min(mask.shape[1], _ceil(longest, multiple)))
 
 
 class PackedLayout:
@@ -126,3 +146,79 @@ def layouts_or_none(ligand_mask, receptor_mask):
         return None
     check_cross(lig, rec)
     return lig, rec
+
+
+class Frame:
+    """The rows a sampling chain runs on, chosen once per chain from the batch's [B, L] ligand and pocket masks:
+
+    * padded (default): the dataset's [B, L] frame;
+    * trimmed (``trim``): the rows up to the longest ligand / pocket, rounded up to 32 (``trimmed_length``).  Padding
+      cannot influence valid positions (its keys carry the -10000 bias, whose softmax weight underflows to exactly
+      0.0f; every other op is row-wise), so a chain needs no other rows.  BioLiP ligands are 5-30 residues in a 64-256
+      row frame: the decoder then runs on 1/8 of the rows;
+    * packed (``pack``): every item's valid rows back to back (``layouts``: ligand and pocket ``PackedLayout``).  Masks
+      that are not prefix masks cannot be packed: the trimmed frame runs instead, with a warning.  An item with ligand
+      rows but an empty pocket raises ``ValueError``.
+
+    ``ligand`` / ``pocket`` move a padded-frame tensor into the frame, ``restore`` moves a ligand-side result back;
+    ``row_keys`` is the key table of the frame's ligand rows (keyed.py) and ``rows`` their count."""
+
+    def __init__(self, ligand_mask, receptor_mask, trim=False, pack=False):
+        self.B, self.L = ligand_mask.shape
+        self.layouts = layouts_or_none(ligand_mask, receptor_mask) if pack else None
+        if pack and self.layouts is None:
+            warnings.warn("pack=True: a padding mask is not a prefix mask, so the batch cannot be packed; running the "
+                          "trimmed frame instead")
+            trim = True
+        self.Ll, self.Lr = self.L, receptor_mask.shape[1]
+        if trim and self.layouts is None:
+            self.Ll, self.Lr = min(self.Ll, trimmed_length(ligand_mask)), min(self.Lr, trimmed_length(receptor_mask))
+        self.rows = self.B * self.Ll if self.layouts is None else self.layouts[0].rows
+
+    def _move(self, x, dim, n, side):
+        if self.layouts is not None:
+            return self.layouts[side].pack(x, dim)
+        return x if x.shape[dim + 1] == n else x.narrow(dim + 1, 0, n).contiguous()
+
+    def ligand(self, x, dim=0):
+        """x [.., B, L, ..] (B at ``dim``) on the ligand rows of the frame: x itself (padded), its first ``Ll`` rows
+        (trimmed, contiguous) or the packed rows [.., rows, ..]."""
+        return self._move(x, dim, self.Ll, 0)
+
+    def pocket(self, x, dim=0):
+        """``ligand`` for a pocket-side tensor (``Lr`` rows when trimmed)."""
+        return self._move(x, dim, self.Lr, 1)
+
+    def restore(self, y, dim=0):
+        """A ligand-side result in the frame -> [.., B, L, ..], with zeros at the rows the frame dropped."""
+        if self.layouts is not None:
+            return self.layouts[0].unpack(y, dim=dim)
+        if self.Ll == self.L:
+            return y
+        shape = list(y.shape)
+        shape[dim + 1] = self.L
+        out = y.new_zeros(shape)
+        out.narrow(dim + 1, 0, self.Ll).copy_(y)
+        return out
+
+    def row_keys(self, ids, device):
+        """Key table of the frame's ligand rows for the item ids ``ids``."""
+        if self.layouts is not None:
+            return keyed.packed_keys(self.layouts[0], ids, device)
+        return keyed.padded_keys(ids, self.Ll, device)
+
+
+def capture_graph(capture, rows, steps, use_graph=None, what="the reverse step"):
+    """The captured step ``capture()`` of a chain of ``steps`` steps on ``rows`` ligand rows, or None: eager launches.
+    ``use_graph`` None: replay for at most GRAPH_MAX_ROWS rows (E3D_SAMPLE_GRAPH=0/1 overrides); chains of at most 4
+    steps never replay.  A capture that fails warns and falls back to eager launches, which are always correct."""
+    if use_graph is None:
+        env = os.environ.get("E3D_SAMPLE_GRAPH")
+        use_graph = env == "1" if env in ("0", "1") else rows <= GRAPH_MAX_ROWS
+    if not use_graph or steps <= 4:
+        return None
+    try:
+        return capture()
+    except Exception as e:   # noqa: BLE001 -- any capture problem: eager launches are always correct
+        warnings.warn(f"HIP-graph capture of {what} failed ({type(e).__name__}: {e}); using eager launches")
+        return None

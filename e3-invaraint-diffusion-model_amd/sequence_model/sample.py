@@ -13,7 +13,6 @@ if __package__ in (None, ""):  # executed as a script from inside this directory
     __package__ = "e3diff_amd.sequence_model"
 
 import os
-import warnings
 
 import torch
 from torch.nn import functional as F
@@ -155,7 +154,8 @@ class GraphedDenoiseStep:
     schedule look-ups and the timestep embedding are computed from it inside the graph), the state ``self.x`` and the
     uniforms of the categorical draw (drawn inside the graph, or injected through ``self.u``).  The last step of a chain
     (which returns the raw logits) is not replayed.  Small chains are host-bound when launched kernel by kernel (about
-    150 launches per step): default for at most ``GRAPH_MAX_ROWS`` token rows, ``use_graph`` / E3D_SAMPLE_GRAPH override."""
+    150 launches per step): default for at most ``packing.GRAPH_MAX_ROWS`` token rows, ``use_graph`` /
+    E3D_SAMPLE_GRAPH override."""
 
     def __init__(self, model, x_like, ligand_angles, ligand_mask, receptor_seq, receptor_angles, receptor_mask, noise_schedule,
                  transition, diverse, T, inject_u=False, layouts=None, row_keys=None, seed=None):
@@ -213,16 +213,6 @@ class GraphedDenoiseStep:
         return self.out
 
 
-GRAPH_MAX_ROWS = 512      # token rows (B x L) up to which a chain replays a captured graph by default
-
-
-def _use_graph(x):
-    env = os.environ.get("E3D_SAMPLE_GRAPH")
-    if env in ("0", "1"):
-        return env == "1"
-    return x.shape[0] * x.shape[1] <= GRAPH_MAX_ROWS
-
-
 @torch.no_grad()
 def denoise(batch, model: PeptideDiff, noise_schedule, transition, diverse, x_T=None, us=None,
             generated_angles=None, timesteps=None, trim_padding=False, use_graph=None, pack=False, seed=None,
@@ -264,49 +254,39 @@ def denoise(batch, model: PeptideDiff, noise_schedule, transition, diverse, x_T=
     receptor_seq = batch["receptor_seq"].to(dev)
     receptor_angles = batch["receptor_angles"].to(dev)
     receptor_mask = batch["receptor_attn_mask"].to(dev)
-    layouts = None
-    if pack:
-        layouts = packing.layouts_or_none(ligand_mask, receptor_mask)
+    frame = packing.Frame(ligand_mask, receptor_mask, trim=trim_padding, pack=pack)
+    layouts = frame.layouts
+
+    def state(t):
+        """A ligand-side state tensor in the frame: packed rows are one item of ``rows`` rows, [1, rows, ..]."""
+        t = frame.ligand(t.float())
+        return t if layouts is None else t[None]
+
+    x = state(x)
+    if us is not None:
+        us = [state(u.to(dev)) if u is not None and u.dim() >= 2 else u for u in us]
+    ang = frame.ligand(ligand_angles.float()).contiguous()
+    rseq, rang = frame.pocket(receptor_seq.float()), frame.pocket(receptor_angles.float())
+    lmask, rmask = (None, None) if layouts is not None else (frame.ligand(ligand_mask), frame.pocket(receptor_mask))
+    row_keys = None if seed is None else frame.row_keys(ids, dev)
+    graphed = packing.capture_graph(
+        lambda: GraphedDenoiseStep(model, x, ang, lmask, rseq, rang, rmask, noise_schedule, transition, diverse, T,
+                                   inject_u=us is not None, layouts=layouts, row_keys=row_keys, seed=seed),
+        frame.rows, T, use_graph, "the sequence reverse step")
+    for n, s_int in enumerate(reversed(range(T))):
+        u = None if us is None else us[n]
+        if graphed is not None and s_int > 0:
+            x = graphed.step(s_int, x, u)
+            continue
+        s_array = torch.full((x.shape[0], 1), float(s_int), device=dev)     # [1, 1] packed: every item shares the step
         if layouts is None:
-            warnings.warn("pack=True: a padding mask is not a prefix mask, so the batch cannot be packed; running the "
-                          "trimmed frame instead")
-            trim_padding = True
-    if layouts is not None:
-        row_keys = None if seed is None else keyed.packed_keys(layouts[0], ids)
-        x = _denoise_packed(model, layouts, x, ligand_angles, receptor_seq, receptor_angles, noise_schedule, transition,
-                            diverse, T, us, use_graph, row_keys, seed)
-    else:
-        if trim_padding:
-            # as structure_model/sample.py::p_sample_loop(trim_padding=True): padding cannot influence valid positions,
-            # and only valid positions are read below, so the chain runs on the frame of the longest ligand / pocket
-            from ..structure_model.sample import trimmed_length
-            Ll, Lr = trimmed_length(ligand_mask), trimmed_length(receptor_mask)
-            x, ligand_seq, ligand_mask = x[:, :Ll].contiguous(), ligand_seq[:, :Ll], ligand_mask[:, :Ll].contiguous()
-            ligand_angles = ligand_angles[:, :Ll].contiguous()
-            receptor_seq, receptor_angles = receptor_seq[:, :Lr].contiguous(), receptor_angles[:, :Lr].contiguous()
-            receptor_mask = receptor_mask[:, :Lr].contiguous()
-            if us is not None:
-                us = [u[:, :Ll] if u is not None and u.dim() >= 2 else u for u in us]
-        row_keys = None if seed is None else keyed.padded_keys(ids, x.shape[1], dev)
-        graphed = None
-        if (_use_graph(x) if use_graph is None else use_graph) and T > 4:
-            try:
-                graphed = GraphedDenoiseStep(model, x, ligand_angles.contiguous(), ligand_mask, receptor_seq, receptor_angles, receptor_mask,
-                                             noise_schedule, transition, diverse, T, inject_u=us is not None,
-                                             row_keys=row_keys, seed=seed)
-            except Exception as e:   # noqa: BLE001 -- any capture problem: eager launches are always correct
-                warnings.warn(f"HIP-graph capture of the sequence reverse step failed ({type(e).__name__}: {e}); using eager launches")
-        for n, s_int in enumerate(reversed(range(T))):
-            if graphed is not None and s_int > 0:
-                u_n = None if us is None else us[n]
-                x = graphed.step(s_int, x, None if u_n is None else u_n.to(dev).float())
-                continue
-            s_array = s_int * torch.ones((B, 1), device=dev)
-            t_array = s_array + 1
-            logits = model.forward(s_array, x, ligand_angles, ligand_mask, receptor_seq, receptor_angles, receptor_mask)
-            x = sample_p_zs_given_zt_discrete(t_array / T, s_array / T, x, logits, noise_schedule, transition,
-                                              diverse, is_last_step=s_int == 0, u=None if us is None else us[n],
-                                              keyed_draw=_keyed_draw(row_keys, seed, s_int, dev))
+            logits = model.forward(s_array, x, ang, lmask, rseq, rang, rmask)
+        else:
+            logits = model.forward_packed(s_array, x, ang, rseq, rang, *layouts)[None]
+        x = sample_p_zs_given_zt_discrete((s_array + 1) / T, s_array / T, x, logits, noise_schedule, transition,
+                                          diverse, is_last_step=s_int == 0, u=u,
+                                          keyed_draw=_keyed_draw(row_keys, seed, s_int, dev))
+    x = frame.restore(x if layouts is None else x[0])
     pred_idx, true_idx = x.argmax(dim=-1).cpu(), ligand_seq.argmax(dim=-1).cpu()
     mask = ligand_mask.bool().cpu()
     ids, true_sequences, pred_sequences, recovery_rates = [], [], [], []
@@ -324,38 +304,6 @@ def denoise(batch, model: PeptideDiff, noise_schedule, transition, diverse, x_T=
 def _keyed_draw(row_keys, seed, s_int, dev):
     """The keyed_draw argument of one eager step (the step index goes to the device, as in the graph)."""
     return None if seed is None else (row_keys, seed, torch.full((1,), s_int, device=dev, dtype=torch.long))
-
-
-def _denoise_packed(model, layouts, x, ligand_angles, receptor_seq, receptor_angles, noise_schedule, transition, diverse, T,
-                    us, use_graph, row_keys=None, seed=None):
-    """The chain of ``denoise`` on packed rows: state [1, rows, C] (the posterior kernel sees B = 1, L = rows with one
-    Q pair: every item shares the step), returned as [B, L, C] with zeros at the padding positions."""
-    lay, lay_r = layouts
-    dev = x.device
-    xp = lay.pack(x.float())[None]
-    ang = lay.pack(ligand_angles.float())
-    rseq, rang = lay_r.pack(receptor_seq.float()), lay_r.pack(receptor_angles.float())
-    if us is not None:
-        us = [lay.pack(u.to(dev).float())[None] if u is not None and u.dim() >= 2 else u for u in us]
-    graphed = None
-    if (_use_graph(xp) if use_graph is None else use_graph) and T > 4:
-        try:
-            graphed = GraphedDenoiseStep(model, xp, ang, None, rseq, rang, None, noise_schedule, transition, diverse, T,
-                                         inject_u=us is not None, layouts=layouts, row_keys=row_keys, seed=seed)
-        except Exception as e:   # noqa: BLE001 -- any capture problem: eager launches are always correct
-            warnings.warn(f"HIP-graph capture of the packed sequence reverse step failed ({type(e).__name__}: {e}); using "
-                          "eager launches")
-    for n, s_int in enumerate(reversed(range(T))):
-        if graphed is not None and s_int > 0:
-            u_n = None if us is None else us[n]
-            xp = graphed.step(s_int, xp, u_n)
-            continue
-        s_array = torch.full((1, 1), float(s_int), device=dev)
-        logits = model.forward_packed(s_array, xp, ang, rseq, rang, lay, lay_r)[None]
-        xp = sample_p_zs_given_zt_discrete((s_array + 1) / T, s_array / T, xp, logits, noise_schedule, transition, diverse,
-                                           is_last_step=s_int == 0, u=None if us is None else us[n],
-                                           keyed_draw=_keyed_draw(row_keys, seed, s_int, dev))
-    return lay.unpack(xp[0])
 
 
 def run(transition, diverse=True, seed=None):

@@ -25,6 +25,7 @@ from torch import nn
 
 from .. import keyed, ops, packing
 from ..bert import BertConfig
+from ..packing import trimmed_length  # noqa: F401  (S.trimmed_length: bench.py and the tests read it here)
 from .dataset import LigandBindingSiteDataset, NoisedAnglesDataset
 from .model import ConditionalBertForDiffusion
 from .utils import CosineTables
@@ -136,10 +137,7 @@ def _reverse_step(model, ligand_mask, x_t, receptor_seq, receptor_mask, receptor
         t_index = int(t_unique.item())
     if receptor_cache is None:
         receptor_cache = model.encode_receptor(receptor_seq, receptor_angle, receptor_mask)
-    if layout is None:
-        eps_hat = model.decode(timestep, x_t, ligand_mask, receptor_cache, mod=mod)
-    else:
-        eps_hat = model.decode(timestep, x_t, ligand_mask, receptor_cache, mod=mod, layout=layout)
+    eps_hat = model.decode(timestep, x_t, ligand_mask, receptor_cache, mod=mod, layout=layout)
     sra = float(tab.sqrt_recip_alphas[t_index])
     beta = float(tab.betas[t_index])
     s1m = float(tab.sqrt_one_minus_alphas_cumprod[t_index])
@@ -156,8 +154,6 @@ def _reverse_step(model, ligand_mask, x_t, receptor_seq, receptor_mask, receptor
     return ops.ddpm_step_wrap(x_c, eps_hat.contiguous(), noise, sra, beta, s1m, sigma, wrap=wrap, out=out)
 
 
-
-
 class GraphedReverseStep:
     """One reverse step (decoder forward + DDPM update + wrap) captured once into a HIP graph and replayed
     per step.  Everything that varies between steps lives on the device: the step index (``self.t``,
@@ -166,11 +162,12 @@ class GraphedReverseStep:
     A keyed step (``row_keys`` and ``seed``) generates its draw inside the update kernel from the step index: no noise
     buffer, and bit-identical to the eager keyed step.
 
-    Default for chains of at most GRAPH_MAX_ROWS token rows (up to ~16 pockets of 64 residues), ``use_graph=True`` /
-    E3D_SAMPLE_GRAPH=1 forces it, =0 turns it off.  Measured on MI355X, one 64-residue pocket (tools/bench_single.py):
-    round 1, 6-workgroup tiled GEMMs of ~29 us each: 3.9 ms per replayed step against 3.8 ms eager -- the GPU was 100 %
-    busy with dependent kernels, the graph had nothing to remove.  Round 2, K-sliced small-M GEMMs of ~7 us per product
-    (csrc/gemm_skinny.hip): eager launches are now host-bound at 2.4 ms per step, a replay takes 1.5 ms."""
+    Default for chains of at most packing.GRAPH_MAX_ROWS token rows (up to ~16 pockets of 64 residues),
+    ``use_graph=True`` / E3D_SAMPLE_GRAPH=1 forces it, =0 turns it off.  Measured on MI355X, one 64-residue pocket
+    (tools/bench_single.py): round 1, 6-workgroup tiled GEMMs of ~29 us each: 3.9 ms per replayed step against 3.8 ms
+    eager -- the GPU was 100 % busy with dependent kernels, the graph had nothing to remove.  Round 2, K-sliced small-M
+    GEMMs of ~7 us per product (csrc/gemm_skinny.hip): eager launches are now host-bound at 2.4 ms per step, a replay
+    takes 1.5 ms."""
 
     def __init__(self, model, ligand_mask, cache, tab, x_like, wrap=True, draw=True, mod_table=None, layout=None,
                  row_keys=None, seed=None):
@@ -203,10 +200,7 @@ class GraphedReverseStep:
 
     def _body(self):
         mod = None if self.mod_table is None else self.mod_table.index_select(0, self.t[:1])
-        if self.layout is None:
-            eps_hat = self.model.decode(self.t, self.x, self.mask, self.cache, mod=mod)
-        else:
-            eps_hat = self.model.decode(self.t, self.x, self.mask, self.cache, mod=mod, layout=self.layout)
+        eps_hat = self.model.decode(self.t, self.x, self.mask, self.cache, mod=mod, layout=self.layout)
         if self.keyed is not None:
             ops.keyed_ddpm_step_wrap(self.x, eps_hat.contiguous(), self.coef, self.t, *self.keyed, wrap=self.wrap,
                                      out=self.out)
@@ -228,28 +222,6 @@ class GraphedReverseStep:
         return self.out
 
 
-GRAPH_MAX_ROWS = 512      # token rows (B x L) up to which a chain replays a captured graph by default (B=8 x L=64: 2.05 vs 2.16 ms eager; B=16: GPU-bound, eager)
-
-
-def _use_graph(x):
-    env = os.environ.get("E3D_SAMPLE_GRAPH")
-    if env in ("0", "1"):
-        return env == "1"
-    return x.shape[:-1].numel() <= GRAPH_MAX_ROWS    # (token rows: B x L, or the rows of a packed state)
-
-
-def trimmed_length(mask, multiple=32):
-    """Smallest multiple of ``multiple`` that covers every valid position of a [B,L] 0/1 padding mask whose valid
-    positions are a prefix (the dataset layout, dataset.py:119-132); L itself if any row is not a prefix mask."""
-    L = mask.shape[1]
-    lengths = mask.sum(dim=1)
-    prefix = (mask[:, :-1] >= mask[:, 1:]).all() if L > 1 else torch.tensor(True)
-    longest = int(lengths.max().item())
-    if not bool(prefix):
-        return L
-    return max(multiple, min(L, -(-longest // multiple) * multiple))
-
-
 @torch.no_grad()
 def p_sample_loop(model: nn.Module, ligand_mask, ligand_angle_noise, receptor_seq, receptor_mask,
                   receptor_angle, total_timesteps: int, betas, disable_pbar: bool = False,
@@ -259,6 +231,9 @@ def p_sample_loop(model: nn.Module, ligand_mask, ligand_angle_noise, receptor_se
     sample.py:101-144, unless ``return_device``).  ``noises`` [T/STEP,B,L,n_ft] injects the draws.
     ``use_graph``: replay one captured HIP graph per step (None: by size, E3D_SAMPLE_GRAPH=0/1 overrides -- see
     GraphedReverseStep); falls back to eager launches if the capture fails.
+
+    ``trim_padding=True``: the chain runs on the rows up to the longest ligand / pocket (packing.Frame); the rows it
+    drops come back as 0 (the reference's values there are never used: its sample.py:243 slices them off).
 
     ``pack=True``: the chain runs on the packed valid rows of the batch -- ligand and pocket (packing.PackedLayout,
     varlen attention) -- so its cost follows the residues the items have instead of the longest item.  Valid positions
@@ -277,7 +252,6 @@ def p_sample_loop(model: nn.Module, ligand_mask, ligand_angle_noise, receptor_se
     tab = _tables(betas)
     order = list(reversed(range(0, total_timesteps, step)))
     x = ligand_angle_noise.contiguous().float()
-    full_traj = None
     ids = None
     if seed is not None:
         if noises is not None:
@@ -287,89 +261,35 @@ def p_sample_loop(model: nn.Module, ligand_mask, ligand_angle_noise, receptor_se
         keyed.check_steps(total_timesteps)
     elif item_ids is not None:
         raise ValueError("p_sample_loop: item_ids key the seeded draws; pass a seed with them")
-    if pack:
-        layouts = packing.layouts_or_none(ligand_mask, receptor_mask)
-        if layouts is not None:
-            keyed_step = None if seed is None else _keyed_step(seed, keyed.packed_keys(layouts[0], ids), tab, x.device)
-            return _p_sample_loop_packed(model, layouts, x, receptor_seq, receptor_angle, receptor_mask, total_timesteps,
-                                         tab, order, noises, return_device, use_graph, keyed_step)
-        warnings.warn("pack=True: a padding mask is not a prefix mask, so the batch cannot be packed; running the "
-                      "trimmed frame instead")
-        trim_padding = True
-    if trim_padding:
-        # Padding positions cannot influence valid ones (their keys carry the -10000 bias, whose softmax weight
-        # underflows to exactly 0.0f; every other op is row-wise), so the chain only needs the rows up to the longest
-        # ligand / pocket of the batch, rounded up to the 32-row attention tile.  BioLiP ligands are 5-30 residues
-        # in a 64-256 row frame: the decoder then runs on 1/8 of the rows.  Valid positions are unchanged; trimmed
-        # positions come back as 0 (the reference's values there are never used: sample.py:243 slices them off).
-        Ll, Lr = trimmed_length(ligand_mask), trimmed_length(receptor_mask)
-        if Ll < x.shape[1] or Lr < receptor_mask.shape[1]:
-            full_traj = torch.zeros((len(order),) + tuple(x.shape), device=x.device, dtype=torch.float32)
-            x, ligand_mask = x[:, :Ll].contiguous(), ligand_mask[:, :Ll].contiguous()
-            receptor_seq, receptor_mask = receptor_seq[:, :Lr].contiguous(), receptor_mask[:, :Lr].contiguous()
-            receptor_angle = receptor_angle[:, :Lr].contiguous()
-            if noises is not None:
-                noises = noises[:, :, :Ll]
-    keyed_step = None if seed is None else _keyed_step(seed, keyed.padded_keys(ids, x.shape[1], x.device), tab, x.device)
-    cache = model.encode_receptor(receptor_seq, receptor_angle, receptor_mask)
+    frame = packing.Frame(ligand_mask, receptor_mask, trim=trim_padding, pack=pack)
+    layout, pocket_layout = frame.layouts or (None, None)
+    if pocket_layout is None:
+        cache = model.encode_receptor(frame.pocket(receptor_seq), frame.pocket(receptor_angle),
+                                      frame.pocket(receptor_mask))
+    else:   # packs the padded pocket itself
+        cache = model.encode_receptor(receptor_seq, receptor_angle, receptor_mask, layout=pocket_layout)
+    x = frame.ligand(x)
+    mask = None if layout is not None else frame.ligand(ligand_mask).contiguous().float()   # a packed decode reads none
+    if noises is not None:
+        noises = frame.ligand(noises.to(x.device).float(), dim=1)
+    row_keys = None if seed is None else frame.row_keys(ids, x.device)
+    keyed_step = None if seed is None else _keyed_step(seed, row_keys, tab, x.device)
     traj = torch.empty((len(order),) + tuple(x.shape), device=x.device, dtype=torch.float32)
     # what depends on the timestep alone, for the whole chain at once: row t of the table = timestep_modulation(t)
     mod_rows = model.timestep_modulation(torch.tensor(order, device=x.device, dtype=torch.long))
     mod_table = torch.zeros((total_timesteps, mod_rows.shape[1]), device=x.device, dtype=torch.float32)
     mod_table[order] = mod_rows
-    graphed = None
-    if (_use_graph(x) if use_graph is None else use_graph) and len(order) > 4:
-        try:
-            graphed = GraphedReverseStep(model, ligand_mask.contiguous().float(), cache, tab, x, draw=noises is None,
-                                         mod_table=mod_table, **_graph_keys(keyed_step))
-        except Exception as e:   # noqa: BLE001 -- any capture problem: eager launches are always correct
-            warnings.warn(f"HIP-graph capture of the reverse step failed ({type(e).__name__}: {e}); using eager launches")
-            graphed = None
+    graphed = packing.capture_graph(
+        lambda: GraphedReverseStep(model, mask, cache, tab, x, draw=noises is None, mod_table=mod_table, layout=layout,
+                                   row_keys=row_keys, seed=seed), frame.rows, len(order), use_graph)
     for n, i in enumerate(order):
         if graphed is not None:
-            x = graphed.step(i, graphed.out if n else x, None if noises is None else noises[n].contiguous())
+            x = graphed.step(i, graphed.out if n else x, None if noises is None else noises[n])
             traj[n].copy_(x)
         else:
-            x = _reverse_step(model, ligand_mask, x, None, None, None, i, tab,
-                              None if noises is None else noises[n], cache, traj[n], wrap=True, mod=mod_table[i:i + 1],
-                              keyed_step=keyed_step)
-    if full_traj is not None:
-        full_traj[:, :, :traj.shape[2]] = traj
-        traj = full_traj
-    return traj if return_device else traj.cpu()
-
-
-def _graph_keys(keyed_step):
-    return {} if keyed_step is None else {"row_keys": keyed_step[0], "seed": keyed_step[1]}
-
-
-def _p_sample_loop_packed(model, layouts, x, receptor_seq, receptor_angle, receptor_mask, total_timesteps, tab, order,
-                          noises, return_device, use_graph, keyed_step=None):
-    lay, lay_r = layouts
-    cache = model.encode_receptor(receptor_seq, receptor_angle, receptor_mask, layout=lay_r)
-    xp = lay.pack(x)                                                      # [rows, F], zero tail
-    noises_p = None if noises is None else lay.pack(noises.to(x.device).float(), dim=1)   # [T/STEP, rows, F]
-    traj = torch.empty((len(order),) + tuple(xp.shape), device=x.device, dtype=torch.float32)
-    mod_rows = model.timestep_modulation(torch.tensor(order, device=x.device, dtype=torch.long))
-    mod_table = torch.zeros((total_timesteps, mod_rows.shape[1]), device=x.device, dtype=torch.float32)
-    mod_table[order] = mod_rows
-    graphed = None
-    if (_use_graph(xp) if use_graph is None else use_graph) and len(order) > 4:
-        try:
-            graphed = GraphedReverseStep(model, None, cache, tab, xp, draw=noises is None, mod_table=mod_table,
-                                         layout=lay, **_graph_keys(keyed_step))
-        except Exception as e:   # noqa: BLE001 -- any capture problem: eager launches are always correct
-            warnings.warn(f"HIP-graph capture of the packed reverse step failed ({type(e).__name__}: {e}); using eager "
-                          "launches")
-            graphed = None
-    for n, i in enumerate(order):
-        if graphed is not None:
-            xp = graphed.step(i, graphed.out if n else xp, None if noises_p is None else noises_p[n])
-            traj[n].copy_(xp)
-        else:
-            xp = _reverse_step(model, None, xp, None, None, None, i, tab, None if noises_p is None else noises_p[n],
-                               cache, traj[n], wrap=True, mod=mod_table[i:i + 1], layout=lay, keyed_step=keyed_step)
-    traj = lay.unpack(traj, dim=1)                                        # [T/STEP, B, L, F], zeros at padding
+            x = _reverse_step(model, mask, x, None, None, None, i, tab, None if noises is None else noises[n], cache,
+                              traj[n], wrap=True, mod=mod_table[i:i + 1], layout=layout, keyed_step=keyed_step)
+    traj = frame.restore(traj, dim=1)                                     # [T/STEP, B, L, F], zeros outside the frame
     return traj if return_device else traj.cpu()
 
 

@@ -32,6 +32,7 @@ def adamw(params, lr, weight_decay):
 
 
 from . import autograd, ops, sharding
+from .packing import trimmed_length
 
 
 def clip_and_step(params, optim, max_norm, fold=None):
@@ -325,7 +326,6 @@ TRIM_TRAIN = os.environ.get("E3D_TRAIN_TRIM", "0") == "1"            # default o
 
 def trimmed_frame(batch, multiple=32):
     """(ligand rows, pocket rows) that cover every valid position of the batch, rounded up to the attention tile."""
-    from .structure_model.sample import trimmed_length
     return (trimmed_length(batch["ligand_attn_mask"], multiple), trimmed_length(batch["receptor_attn_mask"], multiple))
 
 

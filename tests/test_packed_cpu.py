@@ -106,3 +106,93 @@ def test_samplers_default_to_the_unpacked_frame(pkg):
     from e3diff_amd.structure_model import sample as S
     assert inspect.signature(S.p_sample_loop).parameters["pack"].default is False
     assert inspect.signature(Q.denoise).parameters["pack"].default is False
+
+
+def test_frames_move_in_restore_and_key_tables(pkg):
+    """packing.Frame, the frame of both samplers' chains: its rows, ligand / pocket tensors moved in (the [B, L] axes at
+    dim 0 or 1), results restored to the padded frame with zeros where the frame dropped rows, and its key table."""
+    P, K = pkg.packing, pkg.keyed
+    lig_len, rec_len, L, Lr = [7, 0, 30, 1], [40, 3, 33, 20], 96, 128
+    lig, rec = _mask(lig_len, L), _mask(rec_len, Lr)
+    ids = [5, 1 << 40, 2, 9]
+    x = torch.randn(4, L, 8) * lig[..., None]
+    noises = torch.randn(3, 4, L, 8)                     # [T, B, L, F], non-zero at padding
+    pocket = torch.randn(4, Lr, 8)
+    valid = lig.bool()[None, :, :, None].expand_as(noises)
+
+    padded = P.Frame(lig, rec)
+    assert padded.layouts is None and (padded.Ll, padded.Lr, padded.rows) == (L, Lr, 4 * L)
+    assert padded.ligand(noises, dim=1) is noises and padded.pocket(pocket) is pocket and padded.restore(x) is x
+    assert torch.equal(padded.row_keys(ids, "cpu"), K.padded_keys(ids, L, "cpu"))
+
+    trimmed = P.Frame(lig, rec, trim=True)
+    assert trimmed.layouts is None and (trimmed.Ll, trimmed.Lr, trimmed.rows) == (32, 64, 4 * 32)
+    t = trimmed.ligand(noises, dim=1)
+    assert t.shape == (3, 4, 32, 8) and t.is_contiguous() and torch.equal(t, noises[:, :, :32])
+    assert torch.equal(trimmed.pocket(pocket), pocket[:, :64])
+    back = trimmed.restore(t, dim=1)
+    assert back.shape == noises.shape and torch.equal(back[:, :, :32], t) and (back[:, :, 32:] == 0).all()
+    assert torch.equal(trimmed.restore(trimmed.ligand(x)), x)
+    assert torch.equal(trimmed.row_keys(ids, "cpu"), K.padded_keys(ids, 32, "cpu"))
+
+    packed = P.Frame(lig, rec, pack=True, trim=True)     # packing wins over trimming
+    lay, lay_r = packed.layouts
+    assert lay.lengths == lig_len and lay_r.lengths == rec_len and packed.rows == lay.rows == 64
+    p = packed.ligand(noises, dim=1)
+    assert p.shape == (3, 64, 8) and torch.equal(p, lay.pack(noises, dim=1))
+    assert torch.equal(packed.pocket(pocket), lay_r.pack(pocket))
+    back = packed.restore(p, dim=1)
+    assert back.shape == noises.shape and torch.equal(back[valid], noises[valid]) and (back[~valid] == 0).all()
+    assert torch.equal(packed.restore(packed.ligand(x)), x)
+    assert torch.equal(packed.row_keys(ids, "cpu"), K.packed_keys(lay, ids, "cpu"))
+
+
+def test_frame_falls_back_from_packed_to_trimmed(pkg):
+    P = pkg.packing
+    lig, rec = _mask([5, 9], 64), _mask([20, 40], 96)
+    holes = lig.clone()
+    holes[0, 40] = 1.0
+    assert P.trimmed_length(holes) == 64                # not a prefix mask: trimming keeps every row
+    with pytest.warns(UserWarning, match="cannot be packed"):
+        f = P.Frame(holes, rec, pack=True)
+    assert f.layouts is None and (f.Ll, f.Lr) == (64, 64)
+    rec_holes = rec.clone()
+    rec_holes[1, 90] = 1.0
+    with pytest.warns(UserWarning, match="cannot be packed"):
+        f = P.Frame(lig, rec_holes, pack=True)
+    assert f.layouts is None and (f.Ll, f.Lr) == (32, 96)
+    # an item with ligand rows and an empty pocket cannot be packed; the other frames run it
+    empty = _mask([20, 0], 96)
+    with pytest.raises(ValueError, match="empty pocket"):
+        P.Frame(lig, empty, pack=True)
+    assert P.Frame(lig, empty, trim=True).Lr == 32
+    # a frame shorter than one 32-row tile has nothing to trim
+    short = _mask([5, 3], 16)
+    assert P.trimmed_length(short) == 32 and P.Frame(short, short, trim=True).Ll == 16
+
+
+def test_graph_capture_default_override_and_fallback(pkg, monkeypatch):
+    P = pkg.packing
+    monkeypatch.delenv("E3D_SAMPLE_GRAPH", raising=False)
+    made = []
+
+    def capture():
+        made.append(1)
+        return "graph"
+
+    assert P.capture_graph(capture, P.GRAPH_MAX_ROWS, 5) == "graph"
+    assert P.capture_graph(capture, P.GRAPH_MAX_ROWS + 1, 5) is None
+    assert P.capture_graph(capture, 64, 4) is None                        # chains of <= 4 steps never replay
+    assert P.capture_graph(capture, 1 << 20, 5, use_graph=True) == "graph"
+    assert P.capture_graph(capture, 64, 5, use_graph=False) is None
+    monkeypatch.setenv("E3D_SAMPLE_GRAPH", "0")
+    assert P.capture_graph(capture, 64, 5) is None
+    monkeypatch.setenv("E3D_SAMPLE_GRAPH", "1")
+    assert P.capture_graph(capture, 1 << 20, 5) == "graph"
+    assert len(made) == 3
+
+    def broken():
+        raise RuntimeError("no capture here")
+
+    with pytest.warns(UserWarning, match="HIP-graph capture of the test step failed"):
+        assert P.capture_graph(broken, 64, 5, what="the test step") is None

@@ -59,6 +59,19 @@ def build(device):
     return model.eval().to(device), pkg
 
 
+def frames_of(lm, rm):
+    """The padded, trimmed and packed frames of a batch, as the samplers build them."""
+    from e3diff_amd import packing
+    return {"padded": packing.Frame(lm, rm), "trimmed": packing.Frame(lm, rm, trim=True),
+            "packed": packing.Frame(lm, rm, pack=True)}
+
+
+def rows_of(frames):
+    """Ligand and pocket rows of each frame."""
+    return {k: {"ligand": f.rows, "pocket": f.B * f.Lr if f.layouts is None else f.layouts[1].rows}
+            for k, f in frames.items()}
+
+
 def summarize(packed_csv, trimmed_csv, steps):
     def attn_rows(path):
         out = {}
@@ -82,12 +95,10 @@ def sequence_leg(device, args, B_seq=128, L_seq=128, T_seq=50):
     import io
     import torch
     from helpers import synthetic_pockets
-    from e3diff_amd import packing
     from e3diff_amd.bert import BertConfig
     from e3diff_amd.sequence_model.model import PeptideDiff
     from e3diff_amd.sequence_model.sample import denoise, generate_discrete_noise
     from e3diff_amd.sequence_model.utils import DiscreteUniformTransition, PredefinedNoiseScheduleDiscrete
-    from e3diff_amd.structure_model.sample import trimmed_length
     c = dict(hidden_size=H, num_attention_heads=NH, intermediate_size=INTER, num_hidden_layers=6,
              max_position_embeddings=L_seq, hidden_dropout_prob=0.1, attention_probs_dropout_prob=0.1)
     torch.manual_seed(0)
@@ -97,8 +108,7 @@ def sequence_leg(device, args, B_seq=128, L_seq=128, T_seq=50):
     pk = dict(synthetic_pockets(B_seq, L_seq, seed=0, with_ligand_seq=True), structure_ids=None)
     sched = PredefinedNoiseScheduleDiscrete("cosine", T_seq).to(device)
     tr = DiscreteUniformTransition(20)
-    lay, lay_r = packing.layouts_or_none(pk["ligand_attn_mask"], pk["receptor_attn_mask"])
-    Ll, Lr = trimmed_length(pk["ligand_attn_mask"]), trimmed_length(pk["receptor_attn_mask"])
+    frames = frames_of(pk["ligand_attn_mask"], pk["receptor_attn_mask"])
     modes = {"padded": {}, "trimmed": {"trim_padding": True}, "packed": {"pack": True}}
     rate = {}
     seeded = {} if args.seed is None else {"seed": args.seed, "item_ids": range(B_seq)}
@@ -119,9 +129,7 @@ def sequence_leg(device, args, B_seq=128, L_seq=128, T_seq=50):
     torch.cuda.empty_cache()
     return {"pockets": B_seq, "frame": L_seq, "steps": T_seq, "layers": 6, "pocket_steps_per_s": rate,
             "speedup_packed_over_trimmed": rate["packed"] / rate["trimmed"],
-            "rows": {"padded": {"ligand": B_seq * L_seq, "pocket": B_seq * L_seq},
-                     "trimmed": {"ligand": B_seq * Ll, "pocket": B_seq * Lr},
-                     "packed": {"ligand": lay.rows, "pocket": lay_r.rows}},
+            "rows": rows_of(frames),
             "argmax_T6_packed_vs_padded_identical_sequences": sum(a == b for a, b in zip(full[2], packed[2])) / B_seq,
             "argmax_T6_packed_vs_padded_identical_recovery": full[3] == packed[3]}
 
@@ -159,7 +167,6 @@ def main():
     torch.cuda.set_device(device)
     model, pkg = build(device)
     from helpers import synthetic_pockets
-    from e3diff_amd import packing
     from e3diff_amd.structure_model import sample as S
     from e3diff_amd.structure_model.utils import CosineTables, modulo_with_wrapped_range
 
@@ -168,30 +175,24 @@ def main():
     gen = torch.Generator(device=device).manual_seed(0)
     x = modulo_with_wrapped_range(torch.randn(B, L, 8, device=device, generator=gen)).contiguous()
     lm, rm = pk["ligand_attn_mask"], pk["receptor_attn_mask"]
-    Ll, Lr = S.trimmed_length(lm), S.trimmed_length(rm)
-    lay, lay_r = packing.layouts_or_none(lm, rm)
+    frames = frames_of(lm, rm)
+    lay = frames["packed"].layouts[0]
 
     def frame(kind):
-        """(mask, x, cache, layout) of one frame."""
-        if kind == "padded":
-            return lm, x, model.encode_receptor(pk["receptor_seq"], pk["receptor_angles"], rm), None
-        if kind == "trimmed":
-            cache = model.encode_receptor(pk["receptor_seq"][:, :Lr].contiguous(), pk["receptor_angles"][:, :Lr].contiguous(),
-                                          rm[:, :Lr].contiguous())
-            return lm[:, :Ll].contiguous(), x[:, :Ll].contiguous(), cache, None
-        cache = model.encode_receptor(pk["receptor_seq"], pk["receptor_angles"], rm, layout=lay_r)
-        return None, lay.pack(x), cache, lay
+        """(mask, x, cache, layout) of one frame, as p_sample_loop builds them."""
+        f = frames[kind]
+        layout, pocket_layout = f.layouts or (None, None)
+        if pocket_layout is None:
+            cache = model.encode_receptor(f.pocket(pk["receptor_seq"]), f.pocket(pk["receptor_angles"]), f.pocket(rm))
+        else:
+            cache = model.encode_receptor(pk["receptor_seq"], pk["receptor_angles"], rm, layout=pocket_layout)
+        return (None if layout is not None else f.ligand(lm)), f.ligand(x), cache, layout
 
     mod_table = model.timestep_modulation(torch.arange(1000, device=device)).contiguous()
-    from e3diff_amd import keyed
 
     def frame_keys(kind):
         """Key table of a frame's rows (--seed), or None."""
-        if args.seed is None:
-            return None
-        if kind == "packed":
-            return keyed.packed_keys(lay, list(range(B)))
-        return keyed.padded_keys(list(range(B)), L if kind == "padded" else Ll, device)
+        return None if args.seed is None else frames[kind].row_keys(list(range(B)), device)
 
     def eager(kind, steps):
         mask, xa, cache, layout = frame(kind)
@@ -232,8 +233,7 @@ def main():
         return
 
     out = {"metric": "packed_structure_reverse_step", "unit": "pocket-steps/s", "B": B, "frame": L,
-           "rows": {"padded": {"ligand": B * L, "pocket": B * L}, "trimmed": {"ligand": B * Ll, "pocket": B * Lr},
-                    "packed": {"ligand": lay.rows, "pocket": lay_r.rows}}}
+           "rows": rows_of(frames)}
     with torch.no_grad():
         out["eager"] = {k: eager(k, args.steps) for k in ("padded", "trimmed", "packed")}
         out["graph"] = {k: graphed(k, args.steps) for k in ("trimmed", "packed")}
@@ -243,11 +243,11 @@ def main():
         # the figure shows packing, not the x100 amplification of the schedule's last step (beta clipped to 0.9999),
         # which makes any two frames of a short T = 6 chain of this random-init model differ by ~0.3 rad.
         t = torch.full((B,), 500, device=device)
-        _, xt, cache_t, _ = frame("trimmed")
-        eps_t = model.decode(t, xt, lm[:, :Ll].contiguous(), cache_t)
+        mask_t, xt, cache_t, _ = frame("trimmed")
+        eps_t = frames["trimmed"].restore(model.decode(t, xt, mask_t, cache_t))
         _, xp, cache_p, _ = frame("packed")
-        eps_p = lay.unpack(model.decode(t, xp, None, cache_p, mod=model.timestep_modulation(t[:1]), layout=lay), L=Ll)
-        v = lm[:, :Ll].bool()
+        eps_p = lay.unpack(model.decode(t, xp, None, cache_p, mod=model.timestep_modulation(t[:1]), layout=lay))
+        v = lm.bool()
         out["parity_eps_rel_packed_vs_trimmed"] = ((eps_p - eps_t)[v].abs().max() / eps_t[v].abs().max()).item()
         noises = torch.randn(6, B, L, 8, device=device, generator=gen)
 
@@ -255,10 +255,9 @@ def main():
             mask, xa, cache, layout = frame(kind)
             for j in range(6):
                 i = 500 - j
-                nz = lay.pack(noises[j]) if layout is not None else noises[j][:, :xa.shape[1]].contiguous()
-                xa = S._reverse_step(model, mask, xa, None, None, None, i, tab, nz, cache, None, True,
-                                     mod=mod_table[i:i + 1], layout=layout)
-            return lay.unpack(xa, L=Ll) if layout is not None else xa
+                xa = S._reverse_step(model, mask, xa, None, None, None, i, tab, frames[kind].ligand(noises[j]), cache,
+                                     None, True, mod=mod_table[i:i + 1], layout=layout)
+            return frames[kind].restore(xa)
 
         d = modulo_with_wrapped_range((chain("packed") - chain("trimmed"))[v]).abs().max().item()
         out["parity_max_wrapped_diff_packed_vs_trimmed_6_steps_t500"] = d
