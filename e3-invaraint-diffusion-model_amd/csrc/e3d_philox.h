@@ -12,6 +12,12 @@
 #define E3D_STREAM_STRUCT_STEP 1    // structure reverse-step noise
 #define E3D_STREAM_SEQ_XT 2         // sequence initial one-hot classes
 #define E3D_STREAM_SEQ_U 3          // sequence posterior uniforms
+// training and validation draws: the step field is the epoch, E3D_EPOCH_VALIDATION for validation
+#define E3D_STREAM_TRAIN_STRUCT_T 4      // structure training timestep, class of T
+#define E3D_STREAM_TRAIN_STRUCT_NOISE 5  // structure forward noise, laid out as stream 1
+#define E3D_STREAM_TRAIN_SEQ_T 6         // sequence training timestep, class of T + 1
+#define E3D_STREAM_TRAIN_SEQ_U 7         // sequence forward-noising uniform
+#define E3D_EPOCH_VALIDATION 65535
 
 struct E3dU32x4 { uint32_t w[4]; };
 

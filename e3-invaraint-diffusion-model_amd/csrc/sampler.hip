@@ -18,6 +18,11 @@ __device__ __forceinline__ float wrap_pi(float v) {
     return r - pi_f;
 }
 
+// The step field of a training draw: the epoch word in device memory (a captured step replays it); 65535 = validation.
+__device__ __forceinline__ uint32_t keyed_epoch(const int64_t* __restrict__ epoch_dev) {
+    return (uint32_t)epoch_dev[0] & 0xFFFFu;
+}
+
 __global__ __launch_bounds__(256) void ddpm_step_wrap_kernel(
     const float* __restrict__ x, const float* __restrict__ eps_hat, const float* __restrict__ noise,
     float sra, float beta, float s1m, float sigma, const float* __restrict__ coef_table,
@@ -54,6 +59,11 @@ __global__ __launch_bounds__(256) void ddpm_step_wrap_kernel(
     }
 }
 
+// q(x_t | x_0) of one element: wrap(a_t x0 + s_t noise); shared by the buffer form and the keyed form
+__device__ __forceinline__ float q_sample_wrap_elem(float a, float s, float x0, float noise) {
+    return wrap_pi(a * x0 + s * noise);
+}
+
 __global__ __launch_bounds__(256) void q_sample_wrap_kernel(
     const float* __restrict__ x0, const float* __restrict__ noise, const int64_t* __restrict__ t,
     const float* __restrict__ sqrt_ab, const float* __restrict__ sqrt_1mab, float* __restrict__ out,
@@ -61,7 +71,7 @@ __global__ __launch_bounds__(256) void q_sample_wrap_kernel(
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const int64_t ti = t[i / per];
-        out[i] = wrap_pi(sqrt_ab[ti] * x0[i] + sqrt_1mab[ti] * noise[i]);
+        out[i] = q_sample_wrap_elem(sqrt_ab[ti], sqrt_1mab[ti], x0[i], noise[i]);
     }
 }
 
@@ -181,9 +191,12 @@ __global__ __launch_bounds__(256) void discrete_posterior_kernel(
     }
 }
 
+// KEYED (training draws): the uniform of row n = b * L + l is word 0 of stream 7 for (item_ids[b], epoch_dev[0], l).
+template <bool KEYED>
 __global__ __launch_bounds__(256) void discrete_q_sample_kernel(
     const int32_t* __restrict__ x0_idx, const float* __restrict__ Qtb, const float* __restrict__ u,
-    int mode, int32_t* __restrict__ out_idx, int L, int C, int64_t n_rows) {
+    int mode, int32_t* __restrict__ out_idx, int L, int C, int64_t n_rows, const int64_t* __restrict__ item_ids,
+    const int64_t* __restrict__ epoch_dev, uint64_t seed) {
     const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= n_rows) return;
     const int x0 = x0_idx[n];
@@ -196,7 +209,15 @@ __global__ __launch_bounds__(256) void discrete_q_sample_kernel(
         p[c] = c < C ? q[c * C + x0] : 0.f;  // (Qtb @ onehot)[c] = Qtb[c][x0]
         tot += p[c];
     }
-    out_idx[n] = pick_class(p, C, tot, mode, u ? u[n] : 0.f);
+    float un = 0.f;
+    if (KEYED) {
+        const int64_t b = n / L;
+        un = e3d_keyed_uniform(e3d_keyed_words(seed, (uint64_t)item_ids[b], E3D_STREAM_TRAIN_SEQ_U, keyed_epoch(epoch_dev),
+                                               (uint32_t)(n - b * L), 0).w[0]);
+    } else if (u) {
+        un = u[n];
+    }
+    out_idx[n] = pick_class(p, C, tot, mode, un);
 }
 
 // ---------------------------------------------------------------- keyed (seeded) draws
@@ -276,6 +297,46 @@ __global__ __launch_bounds__(256) void keyed_draws_kernel(
     }
 }
 
+// ---------------------------------------------------------------- keyed training draws
+// Frames are padded or trimmed [B, L]: row r is item r / L at position r % L; ids and the epoch live in device memory.
+// Timestep of item b: class of word 0 at position 0, block 0 (stream 4: C = T; stream 6: C = T + 1).
+__global__ __launch_bounds__(256) void keyed_timesteps_kernel(
+    const int64_t* __restrict__ item_ids, const int64_t* __restrict__ epoch_dev, uint64_t seed, int stream, int C,
+    int64_t* __restrict__ out, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    out[b] = e3d_keyed_class(e3d_keyed_words(seed, (uint64_t)item_ids[b], stream, keyed_epoch(epoch_dev), 0, 0).w[0], C);
+}
+
+// One thread per (row, block j of 4 features): noise = wrap(scale * z), z the stream-5 normals of (item, epoch,
+// position, j); x_t = q_sample_wrap_elem(a_t, s_t, x0, noise).  Timesteps are clamped to the tables' T rows.
+__global__ __launch_bounds__(256) void keyed_q_sample_wrap_kernel(
+    const float* __restrict__ x0, const int64_t* __restrict__ t, const float* __restrict__ sqrt_ab,
+    const float* __restrict__ sqrt_1mab, int T, float scale, const int64_t* __restrict__ item_ids,
+    const int64_t* __restrict__ epoch_dev, uint64_t seed, float* __restrict__ noise_out, float* __restrict__ xt_out,
+    int L, int nb, int64_t n4) {
+    const uint32_t epoch = keyed_epoch(epoch_dev);
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        const int64_t row = i / nb, b = row / L;
+        int64_t ti = t[b];
+        ti = ti < 0 ? 0 : (ti > T - 1 ? T - 1 : ti);
+        const float a = sqrt_ab[ti], s = sqrt_1mab[ti];
+        float z[4];
+        e3d_keyed_normal4(e3d_keyed_words(seed, (uint64_t)item_ids[b], E3D_STREAM_TRAIN_STRUCT_NOISE, epoch,
+                                          (uint32_t)(row - b * L), (uint32_t)(i - row * nb)), z);
+        const f32x4 xv = reinterpret_cast<const f32x4*>(x0)[i];
+        f32x4 nv, o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            nv[j] = wrap_pi(scale * z[j]);
+            o[j] = q_sample_wrap_elem(a, s, xv[j], nv[j]);
+        }
+        reinterpret_cast<f32x4*>(noise_out)[i] = nv;
+        reinterpret_cast<f32x4*>(xt_out)[i] = o;
+    }
+}
+
 }  // namespace
 
 extern "C" int e3d_ddpm_step_wrap(const float* x, const float* eps_hat, const float* noise,
@@ -337,8 +398,8 @@ extern "C" int e3d_discrete_q_sample(const int32_t* x0_idx, const float* Qtb, co
     E3D_REQUIRE(C >= 2 && C <= CMAX, "discrete_q_sample: C must be in [2,%d] (C=%d)", CMAX, C);
     E3D_REQUIRE(mode == 0 || (mode == 1 && u), "discrete_q_sample: mode 1 needs uniforms");
     const int64_t n = (int64_t)B * L;
-    hipLaunchKernelGGL(discrete_q_sample_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                       (hipStream_t)stream, x0_idx, Qtb, u, mode, out_idx, L, C, n);
+    hipLaunchKernelGGL(discrete_q_sample_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream, x0_idx, Qtb, u, mode, out_idx, L, C, n, nullptr, nullptr, 0ull);
     return e3d_launch_status("e3d_discrete_q_sample");
 }
 
@@ -387,4 +448,44 @@ extern "C" int e3d_keyed_draws(const int64_t* row_keys, uint64_t seed, int strea
     hipLaunchKernelGGL(keyed_draws_kernel, dim3(keyed_blocks(n)), dim3(256), 0, (hipStream_t)stream, row_keys, seed,
                        stream_id, (uint32_t)t, kind, nb, width, wrap, scale, out, n);
     return e3d_launch_status("e3d_keyed_draws");
+}
+
+// ---------------------------------------------------------------- keyed training draws (entry points)
+extern "C" int e3d_keyed_timesteps(const int64_t* item_ids, const int64_t* epoch_dev, uint64_t seed, int stream_id, int C,
+                                   int64_t* out, int B, void* stream) {
+    E3D_REQUIRE(item_ids && epoch_dev && out && B > 0, "keyed_timesteps: bad arguments");
+    E3D_REQUIRE(stream_id == E3D_STREAM_TRAIN_STRUCT_T || stream_id == E3D_STREAM_TRAIN_SEQ_T,
+                "keyed_timesteps: stream %d is not a timestep stream", stream_id);
+    E3D_REQUIRE(C >= 1 && C <= 1 << 24, "keyed_timesteps: class count %d", C);
+    hipLaunchKernelGGL(keyed_timesteps_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       item_ids, epoch_dev, seed, stream_id, C, out, B);
+    return e3d_launch_status("e3d_keyed_timesteps");
+}
+
+extern "C" int e3d_keyed_q_sample_wrap(const float* x0, const int64_t* t, const float* sqrt_ab, const float* sqrt_1mab,
+                                       int T, float scale, const int64_t* item_ids, const int64_t* epoch_dev,
+                                       uint64_t seed, float* noise_out, float* xt_out, int B, int L, int F,
+                                       void* stream) {
+    E3D_REQUIRE(x0 && t && sqrt_ab && sqrt_1mab && item_ids && epoch_dev && noise_out && xt_out && B > 0 && L > 0 && T > 0,
+                "keyed_q_sample_wrap: bad arguments");
+    E3D_REQUIRE(L <= 1 << 24, "keyed_q_sample_wrap: positions must stay below 2^24 (L=%d)", L);
+    E3D_REQUIRE(F > 0 && F % 4 == 0 && F / 4 <= 256, "keyed_q_sample_wrap: F must be a multiple of 4 in [4, 1024] (F=%d)", F);
+    E3D_REQUIRE(((uintptr_t)x0 % 16) == 0 && ((uintptr_t)noise_out % 16) == 0 && ((uintptr_t)xt_out % 16) == 0,
+                "keyed_q_sample_wrap: pointers must be 16B aligned");
+    const int64_t n4 = (int64_t)B * L * (F / 4);
+    hipLaunchKernelGGL(keyed_q_sample_wrap_kernel, dim3(keyed_blocks(n4)), dim3(256), 0, (hipStream_t)stream, x0, t, sqrt_ab,
+                       sqrt_1mab, T, scale, item_ids, epoch_dev, seed, noise_out, xt_out, L, F / 4, n4);
+    return e3d_launch_status("e3d_keyed_q_sample_wrap");
+}
+
+extern "C" int e3d_keyed_discrete_q_sample(const int32_t* x0_idx, const float* Qtb, const int64_t* item_ids,
+                                           const int64_t* epoch_dev, uint64_t seed, int32_t* out_idx, int B, int L, int C,
+                                           void* stream) {
+    E3D_REQUIRE(x0_idx && Qtb && item_ids && epoch_dev && out_idx && B > 0 && L > 0, "keyed_discrete_q_sample: bad arguments");
+    E3D_REQUIRE(L <= 1 << 24, "keyed_discrete_q_sample: positions must stay below 2^24 (L=%d)", L);
+    E3D_REQUIRE(C >= 2 && C <= CMAX, "keyed_discrete_q_sample: C must be in [2,%d] (C=%d)", CMAX, C);
+    const int64_t n = (int64_t)B * L;
+    hipLaunchKernelGGL(discrete_q_sample_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream, x0_idx, Qtb, nullptr, 1, out_idx, L, C, n, item_ids, epoch_dev, seed);
+    return e3d_launch_status("e3d_keyed_discrete_q_sample");
 }

@@ -103,6 +103,10 @@ _SIGNATURES = {
     "e3d_keyed_ddpm_step_wrap": (c_int, [_P, _P, _P, _P, _P, c_uint64, c_int, _P, c_int64, c_int, _P]),
     "e3d_keyed_discrete_posterior_sample": (c_int, [_P, _P, _P, _P, _P, c_uint64, _P, _P, c_int, c_int, c_int, _P]),
     "e3d_keyed_draws": (c_int, [_P, c_uint64, c_int, c_int, c_int, c_int, c_int, c_float, _P, c_int64, _P]),
+    # keyed training and validation draws (ids and epoch read from device memory)
+    "e3d_keyed_timesteps": (c_int, [_P, _P, c_uint64, c_int, c_int, _P, c_int, _P]),
+    "e3d_keyed_q_sample_wrap": (c_int, [_P, _P, _P, _P, c_int, c_float, _P, _P, c_uint64, _P, _P, c_int, c_int, c_int, _P]),
+    "e3d_keyed_discrete_q_sample": (c_int, [_P, _P, _P, _P, c_uint64, _P, c_int, c_int, c_int, _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -7,6 +7,10 @@ chain runs in: the padded [B, L] frame, a trimmed frame (the same positions, few
 (position = row - segment start; the zero tail gets ``SENTINEL`` and draws nothing).  The valid rows of one item carry
 the same keys in all three, so an item gets the same draws whatever its batch, order or frame.
 
+Training and validation draws (streams 4-7, ``training.fit(seed=)``) put the epoch in the step field -- VALIDATION_EPOCH for
+validation -- and need no key table: their frames are padded or trimmed, so the kernels take the batch's item ids and the
+epoch from device memory (``epoch_word``), where a captured training step finds the current ones at every replay.
+
 Item ids are the caller's (the module entry points use the global dataset index).  Two items with the same id and seed
 get the same draws: replicate samples of one pocket take one seed per replicate, or ids that encode (pocket, replicate).
 """
@@ -18,6 +22,10 @@ MAX_STEP = 65535                # c2 = stream << 16 | step
 
 # streams (counter word c2 = stream << 16 | step)
 STRUCT_XT, STRUCT_STEP, SEQ_XT, SEQ_U = 0, 1, 2, 3
+# training and validation draws: the step field is the epoch (0 .. MAX_EPOCH), VALIDATION_EPOCH for validation
+TRAIN_STRUCT_T, TRAIN_STRUCT_NOISE, TRAIN_SEQ_T, TRAIN_SEQ_U = 4, 5, 6, 7
+VALIDATION_EPOCH = 65535
+MAX_EPOCH = VALIDATION_EPOCH - 1
 
 
 def check_seed(seed):
@@ -35,6 +43,47 @@ def check_seed(seed):
 def check_steps(T):
     if T - 1 > MAX_STEP:
         raise ValueError(f"keyed streams hold steps up to {MAX_STEP}; a chain of {T} steps does not fit")
+
+
+def check_epoch(epoch):
+    """A training epoch as a Python int in [0, MAX_EPOCH]; the value after it is the validation draw's."""
+    epoch = int(epoch)
+    if not 0 <= epoch <= MAX_EPOCH:
+        raise ValueError(f"keyed training streams hold epochs 0 .. {MAX_EPOCH} ({VALIDATION_EPOCH} is the validation "
+                         f"draw), got {epoch}")
+    return epoch
+
+
+def epoch_word(device, epoch=0):
+    """The int64 scalar in device memory that the training-draw kernels read their epoch from."""
+    return torch.full((1,), check_epoch(epoch), dtype=torch.int64, device=device)
+
+
+def set_epoch(word, epoch):
+    """Fill an epoch word in place (a captured step keeps reading the same memory); ``None``: the validation value."""
+    word.fill_(VALIDATION_EPOCH if epoch is None else check_epoch(epoch))
+    return word
+
+
+def device_item_ids(ids, B, device):
+    """Item ids as the int64 [B] device tensor the training-draw kernels read (ids >= 2^63 as the int64 of the same
+    bits).  An int64 tensor -- a batch's ``item_id`` -- is taken as it is."""
+    if torch.is_tensor(ids) and ids.dtype == torch.int64:
+        if ids.numel() != B:
+            raise ValueError(f"{ids.numel()} item ids for a batch of {B}")
+        return ids.reshape(B).to(device).contiguous()
+    return _as_int64(item_ids(ids, B)).to(device)
+
+
+def batch_item_ids(batch, B):
+    """The ``item_id`` entry of a batch as the int64 [B] tensor the training-draw kernels read."""
+    ids = batch.get("item_id")
+    if ids is None:
+        raise ValueError("seeded training draws are keyed by the batch's 'item_id' (int64 [B], the index in the split's "
+                         "dataset) and this batch has none: wrap the dataset in training.ItemIdDataset")
+    if not torch.is_tensor(ids) or ids.dtype != torch.int64 or ids.numel() != B:
+        raise ValueError(f"batch['item_id'] must be an int64 tensor of {B} ids")
+    return ids.reshape(B).contiguous()
 
 
 def item_ids(ids, B):

@@ -783,3 +783,69 @@ def keyed_initial_angles(row_keys, seed, F, scale=1.0):
 def keyed_initial_onehot(row_keys, seed, C):
     """Keyed sequence x_T: one-hot of the stream-2 class of every row, float [rows, C]."""
     return keyed_draws(row_keys, seed, keyed.SEQ_XT, 0, KEYED_ONEHOT, C)
+
+
+# ------------------------------------------------------------------------------- keyed training and validation draws
+# ``item_ids`` int64 [B] and ``epoch`` (an int64 scalar tensor, keyed.epoch_word) are read on the device by the kernels:
+# a captured training step replays them with the static batch's ids and whatever the epoch word holds.
+
+def _chk_ids_epoch(item_ids, epoch, B, name):
+    _chk(item_ids, name + ".item_ids", torch.int64)
+    _chk(epoch, name + ".epoch", torch.int64)
+    if not (item_ids.is_contiguous() and item_ids.shape == (B,)):
+        raise ValueError(f"{name}: item_ids must be a contiguous int64 [{B}], got {tuple(item_ids.shape)}")
+    if epoch.numel() != 1:
+        raise ValueError(f"{name}: the epoch is one int64 on the device, got {tuple(epoch.shape)}")
+
+
+def keyed_timesteps(item_ids, epoch, seed, stream, C):
+    """int64 [B] timesteps in [0, C): stream keyed.TRAIN_STRUCT_T (C = T) or keyed.TRAIN_SEQ_T (C = T + 1)."""
+    if stream not in (keyed.TRAIN_STRUCT_T, keyed.TRAIN_SEQ_T):
+        raise ValueError(f"keyed_timesteps: stream {stream} is not a timestep stream")
+    if not 1 <= int(C) <= 1 << 24:
+        raise ValueError(f"keyed_timesteps: class count {C}")
+    B = item_ids.shape[0]
+    _chk_ids_epoch(item_ids, epoch, B, "keyed_timesteps")
+    out = torch.empty((B,), device=item_ids.device, dtype=torch.int64)
+    with _timed("keyed_timesteps"):
+        hip.check(hip.lib().e3d_keyed_timesteps(_p(item_ids), _p(epoch), keyed.check_seed(seed), int(stream), int(C),
+                                                _p(out), B, _stream()), "e3d_keyed_timesteps")
+    return out
+
+
+def keyed_q_sample_wrap(x0, t, sqrt_ab, sqrt_1mab, scale, item_ids, epoch, seed):
+    """(known_noise, x_t) of q_sample_wrap with the noise wrap(scale * z) drawn in the kernel from stream 5:
+    x0 [B, L, F], F % 4 == 0; t int64 [B] on the device."""
+    for n, tt in (("x0", x0), ("sqrt_ab", sqrt_ab), ("sqrt_1mab", sqrt_1mab)):
+        _chk(tt, "keyed_q_sample_wrap." + n)
+    _chk(t, "keyed_q_sample_wrap.t", torch.int64)
+    if x0.dim() != 3 or x0.shape[-1] % 4:
+        raise ValueError(f"keyed_q_sample_wrap: x0 must be [B, L, F] with F a multiple of 4, got {tuple(x0.shape)}")
+    B, L, F = x0.shape
+    if L > keyed.MAX_POSITION:
+        raise ValueError(f"keyed streams hold positions below 2^24, got a frame of {L}")
+    _chk_ids_epoch(item_ids, epoch, B, "keyed_q_sample_wrap")
+    assert x0.is_contiguous() and t.is_contiguous() and t.shape == (B,)
+    assert sqrt_ab.is_contiguous() and sqrt_1mab.is_contiguous() and sqrt_ab.shape == sqrt_1mab.shape and sqrt_ab.dim() == 1
+    noise, x_t = torch.empty_like(x0), torch.empty_like(x0)
+    with _timed("keyed_q_sample_wrap"):
+        hip.check(hip.lib().e3d_keyed_q_sample_wrap(_p(x0), _p(t), _p(sqrt_ab), _p(sqrt_1mab), sqrt_ab.shape[0], float(scale),
+                                                    _p(item_ids), _p(epoch), keyed.check_seed(seed), _p(noise), _p(x_t),
+                                                    B, L, F, _stream()), "e3d_keyed_q_sample_wrap")
+    return noise, x_t
+
+
+def keyed_discrete_q_sample(x0_idx, qtb, item_ids, epoch, seed):
+    """discrete_q_sample (categorical draw) with the uniform of (b, l) from stream 7 of (item_ids[b], epoch, l)."""
+    _chk(x0_idx, "x0_idx", torch.int32); _chk(qtb, "qtb")
+    B, L = x0_idx.shape
+    C = qtb.shape[-1]
+    if L > keyed.MAX_POSITION:
+        raise ValueError(f"keyed streams hold positions below 2^24, got a frame of {L}")
+    _chk_ids_epoch(item_ids, epoch, B, "keyed_discrete_q_sample")
+    assert x0_idx.is_contiguous() and qtb.is_contiguous() and qtb.shape == (B, C, C)
+    out = torch.empty((B, L), device=qtb.device, dtype=torch.int32)
+    with _timed("discrete_q_sample"):
+        hip.check(hip.lib().e3d_keyed_discrete_q_sample(_p(x0_idx), _p(qtb), _p(item_ids), _p(epoch), keyed.check_seed(seed),
+                                                        _p(out), B, L, C, _stream()), "e3d_keyed_discrete_q_sample")
+    return out

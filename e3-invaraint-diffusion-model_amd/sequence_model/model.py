@@ -14,7 +14,7 @@ import torch
 from torch import nn
 from torch.nn import functional as F
 
-from .. import bert, ops
+from .. import bert, keyed, ops
 from ..blocks import (BertEmbeddings, GaussianFourierProjection, Predictor, SELayer, flat2d,
                       require_gpu)
 from ..training import adamw
@@ -130,16 +130,39 @@ class PeptideDiff(ConditionalBertForDiffusionBase):
         self.lr, self.l2_lambda, self.lr_scheduler = learning_rate, l2_lambda, lr_scheduler
         self.max_epochs, self.steps_per_epoch = max_epochs, steps_per_epoch
         self.valid_epoch_losses, self.train_epoch_losses = [], []
+        self.keyed_draws = None
 
-    def apply_aa_noise(self, ligand_seq, t_int, u=None):
+    def use_keyed_draws(self, seed, epoch=None):
+        """Seeded training / validation draws ("Keyed sampling streams"): with a seed, ``training_step`` and
+        ``validation_step`` take an item's timestep and forward-noising uniforms from the keyed streams 6 / 7 of
+        (seed, batch["item_id"], epoch, position) instead of torch's generator, so they no longer depend on the item's
+        batch, row or frame.  ``epoch``: the int64 word in device memory the kernels read the epoch from
+        (``keyed.epoch_word``; ``keyed.set_epoch`` fills it, also between replays of a captured step); default: a
+        word of this model's own at epoch 0.  ``seed=None`` switches back to torch's generator.  Returns the word."""
+        if seed is None:
+            self.keyed_draws = None
+            return None
+        if epoch is None:
+            epoch = keyed.epoch_word(next(self.parameters()).device)
+        self.keyed_draws = (keyed.check_seed(seed), epoch)
+        return epoch
+
+    def apply_aa_noise(self, ligand_seq, t_int, u=None, keyed_draw=None):
         """x_t ~ Cat(Qtb[b] @ onehot(x_0)) per residue; all-zero (padding) rows -> class 0
         (reference model.py:291-311).  One HIP launch over all B*L rows instead of the reference's
-        per-row Python multinomial loop; ``u`` injects the uniforms (default torch.rand on device)."""
+        per-row Python multinomial loop; ``u`` injects the uniforms (default torch.rand on device).
+        ``keyed_draw`` = (item ids int64 [B], epoch word, seed), all but the seed on the device: the uniforms are the
+        keyed stream 7 of those items, generated inside the kernel; exclusive with ``u``."""
         require_gpu(ligand_seq)
         B, L, C = ligand_seq.shape
         t_float = t_int / self.timesteps
         alpha_t_bar = self.discrete_noise_schedule.get_alpha_bar(t_normalized=t_float)
         qtb = self.aa_transition_model.get_Qt_bar(alpha_t_bar, device=ligand_seq.device).contiguous()
+        if keyed_draw is not None:
+            if u is not None:
+                raise ValueError("apply_aa_noise: pass either uniforms or a keyed draw, not both")
+            idx = ops.keyed_discrete_q_sample(onehot_to_index(ligand_seq).contiguous(), qtb, *keyed_draw)
+            return F.one_hot(idx.long(), num_classes=C).float()
         if u is None:
             u = torch.rand(B, L, device=ligand_seq.device)
         idx = ops.discrete_q_sample(onehot_to_index(ligand_seq).contiguous(), qtb, u.contiguous().float())
@@ -187,6 +210,12 @@ class PeptideDiff(ConditionalBertForDiffusionBase):
 
     def _draw_and_score(self, batch):
         B = batch["ligand_seq"].shape[0]
+        if self.keyed_draws is not None:     # two launches that read ids and epoch on the device: part of a captured step
+            seed, epoch = self.keyed_draws
+            ids = keyed.batch_item_ids(batch, B)
+            t_int = ops.keyed_timesteps(ids, epoch, seed, keyed.TRAIN_SEQ_T, self.timesteps + 1).reshape(B, 1).float()
+            noised = self.apply_aa_noise(batch["ligand_seq"], t_int, keyed_draw=(ids, epoch, seed))
+            return self.get_loss(batch, t_int / self.timesteps, noised)
         t_int = torch.randint(0, self.timesteps + 1, size=(B, 1), device=batch["ligand_seq"].device).float()
         noised = self.apply_aa_noise(batch["ligand_seq"], t_int)
         return self.get_loss(batch, t_int / self.timesteps, noised)

@@ -28,6 +28,8 @@ MODEL_PATH = ""
 DATA_FILE = "./data/biolip.pt"
 GPU_ID = [0]
 NUM_THREAD = 16
+# keyed training and validation draws (training.fit(seed=)); unset: torch's generator, as the reference
+SEED = int(os.environ["E3D_TRAIN_SEED"], 0) if os.environ.get("E3D_TRAIN_SEED") else None
 
 CONFIG = {
     "pocket_ext": 4,
@@ -54,11 +56,15 @@ CONFIG = {
 }
 
 
-def get_dataloader(file_path, records=None):
+def get_dataloader(file_path, records=None, seed=None):
+    """``seed`` (default ``SEED``, E3D_TRAIN_SEED): items carry their ``item_id``, the key of a seeded ``fit``'s draws."""
+    seed = SEED if seed is None else seed
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     out = []
     for split, shuffle in (("train", True), ("validation", False)):
         ds = LigandBindingSiteDataset(file_path, split, CONFIG["max_seq_len"], CONFIG["pocket_ext"], records=records)
+        if seed is not None:
+            ds = training.ItemIdDataset(ds)
         sampler = DistributedSampler(ds, num_replicas=world, rank=rank, shuffle=shuffle) if world > 1 else None
         out.append(DataLoader(dataset=ds, batch_size=CONFIG["batch_size"], shuffle=shuffle and sampler is None,
                               sampler=sampler, num_workers=NUM_THREAD))
@@ -75,7 +81,7 @@ def build_configs():
     return BertConfig(**common), BertConfig(**common, is_decoder=True, add_cross_attention=True)
 
 
-def train_model(encoder_config, decoder_config, train_dataloader, val_dataloader, max_steps=None):
+def train_model(encoder_config, decoder_config, train_dataloader, val_dataloader, max_steps=None, seed=None):
     model = PeptideDiff(
         encoder_config=encoder_config, decoder_config=decoder_config,
         feature_names=LigandBindingSiteDataset.feature_names, max_epochs=CONFIG["max_epochs"],
@@ -89,7 +95,8 @@ def train_model(encoder_config, decoder_config, train_dataloader, val_dataloader
     print("Start training")
     history = training.fit(model, train_dataloader, val_dataloader, min_epochs=CONFIG["min_epochs"],
                            max_epochs=CONFIG["max_epochs"], gradient_clip=CONFIG["gradient_clip"], device=device,
-                           checkpoint_path="./best_val_model.pt", checkpoint_mode="max", max_steps=max_steps)
+                           checkpoint_path="./best_val_model.pt", checkpoint_mode="max", max_steps=max_steps,
+                           seed=SEED if seed is None else seed)
     return history, model
 
 

@@ -164,13 +164,33 @@ class NoisedAnglesDataset(Dataset):
         return item
 
 
-def noise_batch_on_device(ligand_angles, tables: CosineTables, timestep=None, noise=None):
+def noise_batch_on_device(ligand_angles, tables: CosineTables, timestep=None, noise=None, *, scale=1.0, seed=None,
+                          item_ids=None, epoch=None):
     """Batched q(x_t | x_0) on the GPU (HIP ``e3d_q_sample_wrap``): the device-side equivalent of
     NoisedAnglesDataset.__getitem__ for a whole [B,L,8] batch.  Returns dict(timestep [B,1],
-    known_noise, noised_ligand_angle)."""
-    from .. import ops
+    known_noise, noised_ligand_angle).
+
+    ``seed``: keyed draws (keyed.py, DESIGN.md "Keyed sampling streams"): the timestep of item b is the stream-4 class of
+    (seed, item_ids[b], epoch) and its noise wrap(``scale`` * z) with z the stream-5 normals of (.., position, block),
+    whatever the batch, the row or the frame; exclusive with ``timestep`` / ``noise``.  ``item_ids``: ints or an int64
+    tensor (a batch's ``item_id``; default 0 .. B-1); ``epoch``: a training epoch 0 .. 65534 (default 0) or the int64
+    word on the device that holds it (``keyed.epoch_word``; ``keyed.set_epoch(word, None)`` = validation)."""
+    from .. import keyed, ops
     B = ligand_angles.shape[0]
     dev = ligand_angles.device
+    if seed is not None:
+        if timestep is not None or noise is not None:
+            raise ValueError("noise_batch_on_device: pass either a seed or injected timesteps / noise, not both")
+        seed = keyed.check_seed(seed)
+        if not torch.is_tensor(epoch):
+            epoch = keyed.epoch_word(dev, 0 if epoch is None else epoch)
+        ids = keyed.device_item_ids(item_ids, B, dev)
+        t = ops.keyed_timesteps(ids, epoch, seed, keyed.TRAIN_STRUCT_T, tables.timesteps)
+        noise, x_t = ops.keyed_q_sample_wrap(ligand_angles.contiguous().float(), t, tables.sqrt_alphas_cumprod.to(dev),
+                                             tables.sqrt_one_minus_alphas_cumprod.to(dev), scale, ids, epoch, seed)
+        return {"timestep": t.reshape(B, 1), "known_noise": noise, "noised_ligand_angle": x_t}
+    if item_ids is not None or epoch is not None or scale != 1.0:
+        raise ValueError("noise_batch_on_device: item_ids, epoch and scale belong to seeded draws: pass a seed")
     if timestep is None:
         timestep = torch.randint(0, tables.timesteps, (B, 1), device=dev)
     if noise is None:

@@ -27,6 +27,8 @@ MODEL_PATH = ""          # where the final state_dict is written
 DATA_FILE = "./data/biolip.pt"
 GPU_ID = [0]
 NUM_THREAD = 16
+# keyed training and validation draws (training.fit(seed=)); unset: torch's generators, as the reference
+SEED = int(os.environ["E3D_TRAIN_SEED"], 0) if os.environ.get("E3D_TRAIN_SEED") else None
 
 CONFIG = {
     "pocket_ext": 4,
@@ -58,14 +60,19 @@ def _loader(ds, shuffle, world, rank):
                       sampler=sampler, num_workers=NUM_THREAD)
 
 
-def get_dataloader(file_path, records=None):
+def get_dataloader(file_path, records=None, seed=None):
     """(train, validation) loaders of noised items; per-rank shards under torchrun (Lightning's
-    DDP semantics: ``batch_size`` is per process)."""
+    DDP semantics: ``batch_size`` is per process).  ``seed`` (default ``SEED``, E3D_TRAIN_SEED): items carry their
+    ``item_id`` and skip the CPU noising, which a seeded ``fit`` replaces on the device."""
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
+    seed = SEED if seed is None else seed
     out = []
     for split, shuffle in (("train", True), ("validation", False)):
         ds = LigandBindingSiteDataset(file_path, split, CONFIG["max_seq_len"], CONFIG["pocket_ext"], records=records)
-        out.append(_loader(NoisedAnglesDataset(ds, timesteps=CONFIG["timesteps"]), shuffle, world, rank))
+        ds = NoisedAnglesDataset(ds, timesteps=CONFIG["timesteps"])
+        if seed is not None:
+            ds = training.ItemIdDataset(ds, skip_noising=True)
+        out.append(_loader(ds, shuffle, world, rank))
     return tuple(out)
 
 
@@ -79,7 +86,7 @@ def build_configs():
     return BertConfig(**common), BertConfig(**common, is_decoder=True, add_cross_attention=True)
 
 
-def train_model(encoder_config, decoder_config, train_dataloader, val_dataloader, max_steps=None):
+def train_model(encoder_config, decoder_config, train_dataloader, val_dataloader, max_steps=None, seed=None):
     model = ConditionalBertForDiffusion(
         encoder_config=encoder_config, decoder_config=decoder_config,
         feature_names=train_dataloader.dataset.feature_names, epochs=CONFIG["max_epochs"],
@@ -93,7 +100,8 @@ def train_model(encoder_config, decoder_config, train_dataloader, val_dataloader
     print("Start training")
     history = training.fit(model, train_dataloader, val_dataloader, min_epochs=CONFIG["min_epochs"],
                            max_epochs=CONFIG["max_epochs"], gradient_clip=CONFIG["gradient_clip"], device=device,
-                           checkpoint_path="./best_val_model.pt", checkpoint_mode="max", max_steps=max_steps)
+                           checkpoint_path="./best_val_model.pt", checkpoint_mode="max", max_steps=max_steps,
+                           seed=SEED if seed is None else seed)
     return history, model
 
 

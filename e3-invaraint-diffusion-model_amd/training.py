@@ -5,6 +5,7 @@ validation every epoch, best-checkpoint bookkeeping with the reference's ``mode=
 and -- new relative to the single-GPU reference -- data-parallel gradient averaging over RCCL when
 launched with one process per GPU (``torchrun``).
 """
+import contextlib
 import math
 import os
 import time
@@ -31,7 +32,7 @@ def adamw(params, lr, weight_decay):
         return torch.optim.AdamW(params, lr=lr, weight_decay=weight_decay)
 
 
-from . import autograd, ops, sharding
+from . import autograd, keyed, ops, sharding
 from .packing import trimmed_length
 
 
@@ -338,7 +339,8 @@ def trim_batch(batch, frame=None, multiple=32):
     0.0f; every other op is row-wise) and receives exactly zero gradient in the backward pass (the losses are means over
     valid positions), so loss and parameter gradients of the trimmed batch are those of the padded one up to the order of
     the fp32 sums (tests/test_training_gpu.py::test_trimmed_*).  What changes: draws made per frame position inside the
-    step (dropout, PeptideDiff.apply_aa_noise) come from a different place of the random stream."""
+    step (dropout, PeptideDiff.apply_aa_noise) come from a different place of the random stream -- unless the noising draws
+    are keyed (``fit(seed=)``): those follow the item and its positions, not the frame."""
     Ll, Lr = frame if frame is not None else trimmed_frame(batch, multiple)
     out = dict(batch)
     for keys, n in ((LIGAND_FRAME_KEYS, Ll), (RECEPTOR_FRAME_KEYS, Lr)):
@@ -351,6 +353,95 @@ def trim_batch(batch, frame=None, multiple=32):
 
 def move_batch(batch, device):
     return {k: (v.to(device, non_blocking=True) if torch.is_tensor(v) else v) for k, v in batch.items()}
+
+
+class ItemIdDataset(torch.utils.data.Dataset):
+    """A dataset's items plus ``item_id`` (int64 scalar: the index in this dataset), the key of the seeded training and
+    validation draws (``fit(seed=)``; DESIGN.md, "Keyed sampling streams").  The default collate turns it into the
+    batch's int64 [B]; every other entry is the wrapped dataset's, untouched, and its attributes (``feature_names``,
+    ``tables``, ...) are reachable through the wrapper.
+
+    ``skip_noising`` (a ``NoisedAnglesDataset`` inside): serve the un-noised item and zeros for ``timestep``,
+    ``known_noise`` and ``noised_ligand_angle`` -- a seeded ``fit`` replaces the three on the device, so the CPU draws
+    would be thrown away."""
+
+    def __init__(self, dset, skip_noising=False):
+        super().__init__()
+        if skip_noising and not hasattr(dset, "dset"):
+            raise ValueError("skip_noising needs a dataset that wraps the un-noised one (NoisedAnglesDataset)")
+        self.dset, self.skip_noising = dset, skip_noising
+
+    def __getattr__(self, name):
+        if name == "dset":                       # (not set yet: unpickling in a DataLoader worker)
+            raise AttributeError(name)
+        return getattr(self.dset, name)
+
+    def __len__(self):
+        return len(self.dset)
+
+    def __getitem__(self, index):
+        if self.skip_noising:
+            item = dict(self.dset.dset[index])
+            angles = item["ligand_angles"]
+            item.update(timestep=torch.zeros(1, dtype=torch.int64), known_noise=torch.zeros_like(angles),
+                        noised_ligand_angle=torch.zeros_like(angles))
+        else:
+            item = dict(self.dset[index])
+        if "item_id" in item:
+            raise ValueError("the wrapped dataset's items already carry an 'item_id'")
+        item["item_id"] = torch.tensor(index, dtype=torch.int64)
+        return item
+
+
+class _KeyedDraws:
+    """What a seeded ``fit`` holds: the seed, the epoch word in device memory, and -- for a model whose batches arrive
+    noised (structure model) -- the schedule tables to noise them again on the device from streams 4 / 5."""
+
+    def __init__(self, model, seed, device, max_epochs, loader, noise_tables, noise_scale):
+        self.seed = keyed.check_seed(seed)
+        keyed.check_epoch(max(0, max_epochs - 1))
+        self.word = keyed.epoch_word(device)
+        self.model = model if hasattr(model, "use_keyed_draws") else None    # draws inside the step (sequence model)
+        self.tables = self.scale = None
+        if self.model is None:
+            ds = getattr(loader, "dataset", None)
+            tables = noise_tables if noise_tables is not None else getattr(ds, "tables", None)
+            if tables is None:
+                raise ValueError("a seeded fit noises the batches on the device and needs the schedule tables: "
+                                 "a loader over a NoisedAnglesDataset (inside training.ItemIdDataset), or noise_tables=")
+            self.scale = float(noise_scale if noise_scale is not None else getattr(ds, "angular_var_scale", 1.0))
+            keyed.check_steps(tables.timesteps)
+            self.tables = _DeviceTables(tables, device)
+
+    def __enter__(self):
+        if self.model is not None:
+            self.model.use_keyed_draws(self.seed, self.word)
+        return self
+
+    def __exit__(self, *exc):
+        if self.model is not None:
+            self.model.use_keyed_draws(None)
+
+    def set_epoch(self, epoch):
+        keyed.set_epoch(self.word, epoch)
+
+    def batch(self, batch):
+        """The batch as the step takes it (on the device already)."""
+        ids = keyed.batch_item_ids(batch, batch["ligand_angles"].shape[0])
+        if self.tables is None:
+            return batch
+        from .structure_model.dataset import noise_batch_on_device
+        return dict(batch, **noise_batch_on_device(batch["ligand_angles"], self.tables, scale=self.scale, seed=self.seed,
+                                                   item_ids=ids, epoch=self.word))
+
+
+class _DeviceTables:
+    """The two forward-noising tables of a ``CosineTables`` on the device, copied once."""
+
+    def __init__(self, tables, device):
+        self.timesteps = tables.timesteps
+        self.sqrt_alphas_cumprod = tables.sqrt_alphas_cumprod.to(device)
+        self.sqrt_one_minus_alphas_cumprod = tables.sqrt_one_minus_alphas_cumprod.to(device)
 
 
 class BestCheckpoint:
@@ -382,9 +473,16 @@ DEFER_WEIGHT_GRADS = os.environ.get("E3D_DEFER_WGRAD", "1") == "1"   # autograd.
 
 def fit(model, train_loader, val_loader=None, *, max_epochs, min_epochs=0, gradient_clip=1.0, device="cuda:0",
         log_every_n_steps=30, checkpoint_path="./best_val_model.pt", checkpoint_mode="max", max_steps=None,
-        log=print, trim_padding=None):
+        log=print, trim_padding=None, seed=None, noise_tables=None, noise_scale=None):
     """Returns a history dict.  ``model`` provides training_step / validation_step /
     configure_optimizers (the reference's LightningModule surface).
+    ``seed`` (default None: torch's generators, as ever): keyed training and validation draws ("Keyed sampling
+    streams").  An item's timestep and noise are then functions of (seed, batch["item_id"], epoch, position) alone --
+    not of the batch, the row, the frame, the DataLoader workers or the world size -- and validation draws do not depend on
+    the epoch, so ``val_loss`` is a function of the weights.  Batches must carry ``item_id`` (``ItemIdDataset``).  A
+    model with ``use_keyed_draws`` (sequence model) draws inside its step; any other gets ``timestep`` / ``known_noise`` /
+    ``noised_ligand_angle`` replaced on the device before the step, with the tables of the loader's dataset
+    (``NoisedAnglesDataset.tables`` / ``.angular_var_scale``) or ``noise_tables`` / ``noise_scale``.
     ``trim_padding`` (None: E3D_TRAIN_TRIM, default off = the reference's padded frames): run every training and
     validation step on the frame of the batch's longest ligand / pocket (``trim_batch``; under a process group the frame
     is the maximum over the ranks, agreed on the host, so that every rank replays the same kind of step)."""
@@ -392,13 +490,24 @@ def fit(model, train_loader, val_loader=None, *, max_epochs, min_epochs=0, gradi
         return _fit(model, train_loader, val_loader, max_epochs=max_epochs, min_epochs=min_epochs, gradient_clip=gradient_clip,
                     device=device, log_every_n_steps=log_every_n_steps, checkpoint_path=checkpoint_path,
                     checkpoint_mode=checkpoint_mode, max_steps=max_steps, log=log,
-                    trim_padding=TRIM_TRAIN if trim_padding is None else bool(trim_padding))
+                    trim_padding=TRIM_TRAIN if trim_padding is None else bool(trim_padding), seed=seed,
+                    noise_tables=noise_tables, noise_scale=noise_scale)
 
 
 def _fit(model, train_loader, val_loader, *, max_epochs, min_epochs, gradient_clip, device, log_every_n_steps, checkpoint_path,
-         checkpoint_mode, max_steps, log, trim_padding=False):
+         checkpoint_mode, max_steps, log, trim_padding=False, seed=None, noise_tables=None, noise_scale=None):
     rank, world, _ = sharding.init_distributed()
     model.to(device)
+    draws = None if seed is None else _KeyedDraws(model, seed, device, max_epochs, train_loader, noise_tables, noise_scale)
+    with draws if draws is not None else contextlib.nullcontext():
+        return _fit_epochs(model, train_loader, val_loader, rank, world, draws, max_epochs=max_epochs,
+                           gradient_clip=gradient_clip, device=device, log_every_n_steps=log_every_n_steps,
+                           checkpoint_path=checkpoint_path, checkpoint_mode=checkpoint_mode, max_steps=max_steps, log=log,
+                           trim_padding=trim_padding)
+
+
+def _fit_epochs(model, train_loader, val_loader, rank, world, draws, *, max_epochs, gradient_clip, device, log_every_n_steps,
+                checkpoint_path, checkpoint_mode, max_steps, log, trim_padding):
     sharding.broadcast_parameters(model, src=0)
     conf = model.configure_optimizers()
     optim = conf["optimizer"]
@@ -421,11 +530,15 @@ def _fit(model, train_loader, val_loader, *, max_epochs, min_epochs, gradient_cl
         model.train()
         if hasattr(getattr(train_loader, "sampler", None), "set_epoch"):
             train_loader.sampler.set_epoch(epoch)
+        if draws is not None:
+            draws.set_epoch(epoch)
         losses = []
         for batch_idx, batch in enumerate(train_loader):
             if trim_padding:                         # (on the loader's host tensors: no device round trip)
                 batch = trim_batch(batch, sharding.max_over_ranks_host(trimmed_frame(batch)) if world > 1 else None)
             batch = move_batch(batch, device)
+            if draws is not None:
+                batch = draws.batch(batch)
             if stepper is not None:
                 loss = stepper.step(batch, batch_idx)
                 if sched is not None and sched.get("interval") == "step":
@@ -470,12 +583,19 @@ def _fit(model, train_loader, val_loader, *, max_epochs, min_epochs, gradient_cl
         if val_loader is not None:
             model.eval()
             vals = []
+            if draws is not None:
+                draws.set_epoch(None)                # the validation value: the same draws after every epoch
             with torch.no_grad():
                 for batch_idx, batch in enumerate(val_loader):
                     if trim_padding:
                         batch = trim_batch(batch)
-                    out = model.validation_step(move_batch(batch, device), batch_idx)
+                    batch = move_batch(batch, device)
+                    if draws is not None:
+                        batch = draws.batch(batch)
+                    out = model.validation_step(batch, batch_idx)
                     vals.append(float(out["val_loss"] if isinstance(out, dict) else out))
+            if draws is not None:
+                draws.set_epoch(epoch)
             val = sum(vals) / max(1, len(vals)) if vals else math.nan
             if world > 1:
                 val = sharding.mean_over_ranks(val)

@@ -275,6 +275,33 @@ int e3d_keyed_discrete_posterior_sample(const int32_t* xt_idx, const float* logi
 int e3d_keyed_draws(const int64_t* row_keys, uint64_t seed, int stream_id, int t, int kind, int width, int wrap,
                     float scale, void* out, int64_t rows, void* stream);
 
+/* ------------------------------------------------------------------ keyed training and validation draws
+ * The same generator and counter layout with the EPOCH in the step field (training epochs 0 .. 65534; 65535 is the
+ * validation value) and streams 4 structure timestep, 5 structure forward noise, 6 sequence timestep, 7 sequence
+ * forward-noising uniform.  Frames are padded or trimmed [B, L]: row r is item r / L at position r % L.  ``item_ids``
+ * int64 [B] and ``epoch_dev`` (int64, first element) are read from DEVICE memory by the kernels, so a captured
+ * training step replays them with whatever the static batch and the epoch word hold.  Nothing is allocated or read
+ * back. */
+
+/* out[b] = class in [0, C) of word 0 of (seed, item_ids[b], stream_id, epoch, position 0, block 0); stream_id 4
+ * (C = T) or 6 (C = T + 1). */
+int e3d_keyed_timesteps(const int64_t* item_ids, const int64_t* epoch_dev, uint64_t seed, int stream_id, int C,
+                        int64_t* out, int B, void* stream);
+
+/* Structure forward noising with the noise drawn in-register from stream 5:
+ *   noise_out = wrap(scale * z),  xt_out = wrap(sqrt_ab[t[b]] * x0 + sqrt_1mab[t[b]] * noise_out)
+ * (the arithmetic of e3d_q_sample_wrap), z the normals of (position l, block j -> features 4j .. 4j+3).  x0 and both
+ * outputs [B, L, F], F % 4 == 0, F <= 1024; t int64 [B] on the device, clamped to the T rows of the two tables. */
+int e3d_keyed_q_sample_wrap(const float* x0, const int64_t* t, const float* sqrt_ab, const float* sqrt_1mab, int T,
+                            float scale, const int64_t* item_ids, const int64_t* epoch_dev, uint64_t seed,
+                            float* noise_out, float* xt_out, int B, int L, int F, void* stream);
+
+/* e3d_discrete_q_sample in mode 1 with the uniform of row b * L + l taken from stream 7 (word 0 of block 0 at
+ * position l) instead of a buffer; x0 index < 0 (padding row) -> class 0. */
+int e3d_keyed_discrete_q_sample(const int32_t* x0_idx, const float* Qtb, const int64_t* item_ids,
+                                const int64_t* epoch_dev, uint64_t seed, int32_t* out_idx, int B, int L, int C,
+                                void* stream);
+
 /* NeRF backbone builder, the step after structure sampling (structure_model/create_pdb.py:104-155,
  * 175-234): angles [B,L,8] fp32 in the dataset's column order
  * (phi psi omega dihedral_o tau CA:C:1N 1C:N:CA CA:C:O), lengths int32 [B] -> coords float64
