@@ -30,8 +30,8 @@ def gemm_general(a, a_kmajor, b, b_kmajor, M, N, K, bias=None, act=ops.ACT_NONE,
 class deferred_weight_grads:
     """``with deferred_weight_grads() as q: loss.backward()`` -- inside the block the backward of every linear layer
     computes only its input gradient and QUEUES its weight / bias gradient (the (dz, x) pair stays alive); leaving the
-    block (or ``q.flush()``) computes all queued gradients, the layers of one shape together in one launch
-    (``e3d_gemm_wgrad_grouped_f32_split``: whole reductions over the tokens instead of split-K slices meeting through
+    block (or ``q.flush()``) computes all queued gradients, the layers of one token count together in one launch
+    (``e3d_gemm_wgrad_ragged_f32_split``: whole reductions over the tokens instead of split-K slices meeting through
     atomics -- 82 -> 250 TFLOP/s on a 768x768 weight at 4096 tokens -- with the bias column sums riding along), and
     writes them straight into ``param.grad`` (added to an existing gradient, like autograd's accumulation).
     Nothing reaches autograd's own accumulation for these parameters, so post-accumulate-grad hooks do not fire for
@@ -174,31 +174,26 @@ class deferred_weight_grads:
                     if last_slice[id(p)] == si:
                         self.on_param(p)
 
-    # One launch for layers of different shapes / strides (e3d_gemm_wgrad_ragged_f32_split); 0: one launch per
-    # (shape, stride) group as in round 2 (A/B runs)
-    RAGGED = os.environ.get("E3D_WGRAD_RAGGED", "1") == "1"
-
-    def _flush_ragged(self, items, M, terms, touched):
-        """All queued layers of one token count, 64 per launch, whatever their shapes and row strides."""
+    def _flush_ragged(self, items, M, terms):
+        """All queued layers of one token count, 64 per launch, whatever their shapes and row strides
+        (e3d_gemm_wgrad_ragged_f32_split).  Returns the items in the order their gradients were enqueued."""
         import ctypes
         lib = hip.lib()
         tiles = sum((-(-it[0].shape[1] // 256)) * (-(-it[1].shape[1] // 128)) for it in items)
         if tiles < self.MIN_TILES:
-            for dz, x, w, b in items:
-                self._single(dz, x, w, b, dz.shape[1], x.shape[1], M)
-                touched[id(w)] = w
-                if b is not None:
-                    touched[id(b)] = b
-            return
-        mixed = [it for it in items if it[3] is not None and (it[2].grad is None) != (it[3].grad is None)]
-        for dz, x, w, b in mixed:     # one accumulate bit per problem covers weight and bias: these take the per-layer path
+            # too few output tiles even together: whole reductions would leave most of the chip idle -- the per-layer
+            # split-K launch is the better kernel for these
+            single = items
+        else:
+            # a layer whose weight already holds a gradient while its bias does not (or the reverse: a bias shared with a
+            # layer outside the queue, a gradient set by hand) cannot ride in a grouped launch -- one accumulate bit per
+            # problem covers both outputs -- so it takes the per-layer path
+            single = [it for it in items if it[3] is not None and (it[2].grad is None) != (it[3].grad is None)]
+        for dz, x, w, b in single:
             self._single(dz, x, w, b, dz.shape[1], x.shape[1], M)
-            touched[id(w)] = w
-            touched[id(b)] = b
-        if mixed:
-            items = [it for it in items if not any(it is m for m in mixed)]
-        for lo in range(0, len(items), 64):
-            chunk = items[lo:lo + 64]
+        grouped = [it for it in items if not any(it is s for s in single)] if single else items
+        for lo in range(0, len(grouped), 64):
+            chunk = grouped[lo:lo + 64]
             n = len(chunk)
             a_dz, a_x, a_dw, a_db = ((ctypes.c_void_p * n)() for _ in range(4))
             a_n, a_k = (ctypes.c_int * n)(), (ctypes.c_int * n)()
@@ -209,87 +204,32 @@ class deferred_weight_grads:
                 a_dz[i], a_x[i], a_dw[i] = dz.data_ptr(), x.data_ptr(), gw.data_ptr()
                 if b is not None:
                     gb, acc_b = self._grad_buffer(b)
-                    assert acc_b == acc_w
+                    assert acc_b == acc_w      # (mixed layers were taken out above)
                     a_db[i] = gb.data_ptr()
                 a_n[i], a_k[i], a_ldz[i], a_ldx[i] = dz.shape[1], x.shape[1], dz.stride(0), x.stride(0)
                 bits |= int(acc_w) << i
-                touched[id(w)] = w
-                if b is not None:
-                    touched[id(b)] = b
             hip.check(lib.e3d_gemm_wgrad_ragged_f32_split(a_dz, a_x, a_dw, a_db, a_n, a_k, a_ldz, a_ldx, bits, n, M, terms,
                                                           _stream()), "e3d_gemm_wgrad_ragged_f32_split")
+        return single + grouped
 
     def _flush_slice(self, pending):
-        import ctypes
+        """Computes the queued gradients; returns ``{id(param): param}`` of what it wrote."""
         terms = ops.GEMM_MODES[ops.GEMM_MODE] or 6
-        lib = hip.lib()
-        if self.RAGGED:
-            # a weight used more than once in the forward pass: its later uses go to later rounds (a launch must not hold
-            # two problems with the same output), each adding to what the earlier rounds wrote
-            rounds, seen, touched = [], {}, {}
-            for item in pending:
-                r = seen.get(id(item[2]), 0)
-                seen[id(item[2])] = r + 1
-                while len(rounds) <= r:
-                    rounds.append({})
-                rounds[r].setdefault(item[0].shape[0], []).append(item)       # by token count
-            for by_m in rounds:
-                for M, items in by_m.items():
-                    self._flush_ragged(items, M, terms, touched)
-            return touched
-        # a weight used more than once in the forward pass: its later uses go to later rounds (a launch must not
-        # hold two problems with the same output), each adding to what the earlier rounds wrote
-        rounds, seen = [], {}
+        # a weight used more than once in the forward pass: its later uses go to later rounds (a launch must not hold
+        # two problems with the same output), each adding to what the earlier rounds wrote
+        rounds, seen, touched = [], {}, {}
         for item in pending:
             r = seen.get(id(item[2]), 0)
             seen[id(item[2])] = r + 1
             while len(rounds) <= r:
                 rounds.append({})
-            dz, x = item[0], item[1]
-            key = (dz.shape[1], x.shape[1], dz.shape[0], dz.stride(0), x.stride(0), item[3] is not None)
-            rounds[r].setdefault(key, []).append(item)
-        touched = {}
-        for groups in rounds:
-            for (N, K, M, ldz, ldx, has_bias), items in groups.items():
-                if len(items) * (-(-N // 256)) * (-(-K // 128)) < self.MIN_TILES:
-                    # too few output tiles even together (a shape only one or two layers have): whole reductions would
-                    # leave most of the chip idle -- the per-layer split-K launch is the better kernel for these
-                    for dz, x, w, b in items:
-                        self._single(dz, x, w, b, N, K, M)
-                        touched[id(w)] = w
-                        if has_bias:
-                            touched[id(b)] = b
-                    continue
-                # a layer whose weight already holds a gradient while its bias does not (or the reverse: a bias shared
-                # with a layer outside the queue, a gradient set by hand) cannot ride in a grouped launch -- one
-                # accumulate bit per problem covers both outputs -- so it takes the per-layer path
-                mixed = [it for it in items if has_bias and (it[2].grad is None) != (it[3].grad is None)]
-                for dz, x, w, b in mixed:
-                    self._single(dz, x, w, b, N, K, M)
+            rounds[r].setdefault(item[0].shape[0], []).append(item)       # by token count
+        for by_m in rounds:
+            for M, items in by_m.items():
+                for _, _, w, b in self._flush_ragged(items, M, terms):
                     touched[id(w)] = w
-                    touched[id(b)] = b
-                if mixed:
-                    items = [it for it in items if not any(it is m for m in mixed)]
-                for lo in range(0, len(items), 64):
-                    chunk = items[lo:lo + 64]
-                    n = len(chunk)
-                    arr = lambda: (ctypes.c_void_p * n)()   # noqa: E731
-                    a_dz, a_x, a_dw, a_db, bits = arr(), arr(), arr(), arr(), 0
-                    for i, (dz, x, w, b) in enumerate(chunk):
-                        gw, acc_w = self._grad_buffer(w)
-                        a_dz[i], a_x[i], a_dw[i] = dz.data_ptr(), x.data_ptr(), gw.data_ptr()
-                        if has_bias:
-                            gb, acc_b = self._grad_buffer(b)
-                            assert acc_b == acc_w      # (mixed layers were taken out above)
-                            a_db[i] = gb.data_ptr()
-                        bits |= int(acc_w) << i
-                    hip.check(lib.e3d_gemm_wgrad_grouped_f32_split(a_dz, a_x, a_dw, a_db if has_bias else None, bits, n, ldz,
-                                                                   ldx, N, K, M, terms, _stream()),
-                              "e3d_gemm_wgrad_grouped_f32_split")
-                    for _, _, w, b in chunk:
-                        touched[id(w)] = w
-                        if has_bias:
-                            touched[id(b)] = b
+                    if b is not None:
+                        touched[id(b)] = b
         return touched
 
 

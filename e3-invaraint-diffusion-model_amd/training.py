@@ -12,6 +12,9 @@ import time
 
 import torch
 
+from . import autograd, keyed, ops, sharding
+from .packing import trimmed_length
+
 
 def adamw(params, lr, weight_decay):
     """torch.optim.AdamW as the reference builds it (structure_model/model.py:361-366).  With every parameter on the GPU
@@ -30,10 +33,6 @@ def adamw(params, lr, weight_decay):
             torch.optim.AdamW(params, lr=lr, weight_decay=weight_decay)
     except (TypeError, RuntimeError):
         return torch.optim.AdamW(params, lr=lr, weight_decay=weight_decay)
-
-
-from . import autograd, keyed, ops, sharding
-from .packing import trimmed_length
 
 
 def clip_and_step(params, optim, max_norm, fold=None):
@@ -66,7 +65,61 @@ def clip_and_step(params, optim, max_norm, fold=None):
     return norm
 
 
-class GraphedStep:
+# single-process training replays the step from a HIP graph (GraphedStep); 0: eager steps
+GRAPH_TRAIN = os.environ.get("E3D_TRAIN_GRAPH", "1") == "1"
+DEFER_WEIGHT_GRADS = os.environ.get("E3D_DEFER_WGRAD", "1") == "1"   # autograd.deferred_weight_grads in the step
+
+
+def backward(loss, averager=None):
+    """``loss.backward()`` as the training step runs it: the weight gradients of all linear layers are computed together
+    when the block ends (grouped launches, written into .grad, i.e. into the all-reduce buckets of an active ``averager``,
+    which learns of them through ``mark_ready``); E3D_DEFER_WGRAD=0: layer by layer inside backward."""
+    if not DEFER_WEIGHT_GRADS:
+        loss.backward()
+        return
+    active = averager is not None and averager._active()
+    with autograd.deferred_weight_grads(on_param=averager.mark_ready if active else None):
+        loss.backward()
+
+
+def train_step(model, optim, params, clip, batch, batch_idx=0, averager=None):
+    """THE training step, eagerly, on the current stream (CPU parameters and any optimizer included); returns the loss."""
+    loss = model.training_step(batch, batch_idx)
+    optim.zero_grad(set_to_none=True)
+    if averager is not None:
+        averager.prepare()                       # grads as views of the all-reduce buckets (no-op for one process)
+    backward(loss, averager)
+    if averager is not None:
+        averager.average()                       # RCCL all-reduce (no-op for one process)
+    clip_and_step(params, optim, clip)           # global-norm clip of the averaged grads, then AdamW
+    return loss
+
+
+class EagerStep:
+    """The stepper of a run that replays nothing (CPU parameters, another optimizer than ClipAdamW, E3D_TRAIN_GRAPH=0):
+    every step is ``train_step`` on the caller's stream.  The graph steppers below extend it and share its ``step``."""
+
+    graph = None                                     # nothing captured
+
+    def __init__(self, model, optim, params, gradient_clip, averager=None):
+        self.model, self.optim, self.params, self.clip, self.averager = model, optim, params, gradient_clip, averager
+
+    def _replayed(self, batch):
+        """The loss of the step if a captured graph ran it, None if it has yet to run (eagerly)."""
+        return None
+
+    def _eager(self, batch, batch_idx):
+        loss = train_step(self.model, self.optim, self.params, self.clip, batch, batch_idx, self.averager)
+        ops.invalidate_weight_caches()               # belt and braces beside the global optimizer hook (ops.py)
+        return loss.detach()
+
+    def step(self, batch, batch_idx=0):
+        """Returns the loss (a device tensor; for a replayed step it is overwritten by the next replay of its graph)."""
+        loss = self._replayed(batch)
+        return self._eager(batch, batch_idx) if loss is None else loss
+
+
+class GraphedStep(EagerStep):
     """One training step -- ``training_step`` + backward with deferred weight gradients + gradient-norm clip + AdamW -- as
     a HIP graph: captured once per batch signature (tensor names, shapes, dtypes) after ``warmup`` eager steps, then
     replayed.  The eager step of the structure model needs ~25 ms of Python and launch calls for ~1 350 kernels that keep
@@ -83,15 +136,17 @@ class GraphedStep:
     shared.  Single process; the data-parallel step is ``GraphedDDPStep`` (two segments around the collectives)."""
 
     MAX_GRAPHS = 8
+    REPLAY_ON_SIDE_STREAM = False                    # replays run on the caller's current stream, eager steps on self.stream
+    CAPTURE_FAILED = "training step could not be captured in a HIP graph"
 
     def __init__(self, model, optim, params, gradient_clip, warmup=2):
         from .optim import ClipAdamW
         if not isinstance(optim, ClipAdamW):
             raise TypeError("GraphedStep needs optim.ClipAdamW (device-side learning rate and step counts)")
-        self.model, self.optim, self.params, self.clip = model, optim, params, gradient_clip
+        super().__init__(model, optim, params, gradient_clip)
         self.warmup, self.seen = warmup, {}
-        self.graphs = {}                             # signature -> the captured step (graph, static batch, loss tensor)
-        self.graph = self.key = self.static = self.loss = None   # ... and the one used last
+        self.graphs = {}                             # signature -> the captured step (graph segments, static batch, loss, grads)
+        self.segments = self.key = self.static = self.loss = None   # ... and the one used last
         self.failed = None
         optim.use_device_scalars(True)
         self.epoch = ops.dropout_epoch(params[0].device)
@@ -101,24 +156,30 @@ class GraphedStep:
         # garbage gradients a few hundred replays in: tools/lab/train_soak.py)
         self.stream = torch.cuda.Stream(device=params[0].device)
 
-    def _body(self, batch, batch_idx=0):
-        loss = self.model.training_step(batch, batch_idx)
-        self.optim.zero_grad(set_to_none=True)
-        if DEFER_WEIGHT_GRADS:
-            with autograd.deferred_weight_grads():
-                loss.backward()
-        else:
-            loss.backward()
-        clip_and_step(self.params, self.optim, self.clip)
-        return loss
+    @property
+    def graph(self):
+        """The first segment of the captured step used last; None until something is captured."""
+        return self.segments[0] if self.segments else None
 
     @staticmethod
     def _signature(batch):
         return tuple((k, tuple(v.shape), v.dtype) for k, v in sorted(batch.items()) if torch.is_tensor(v))
 
+    def _record(self, static):
+        """Capture the step on ``static``: (graph segments, loss tensor)."""
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=self.stream):
+            loss = train_step(self.model, self.optim, self.params, self.clip, static)
+            self.epoch.add_(1)
+        return (graph,), loss
+
+    def _between_segments(self):
+        """What a replay runs between two segments (here there is one)."""
+
     def _capture(self, batch):
+        """Records (does not execute) the step of this batch's signature; returns its ``graphs`` entry."""
         dev = self.params[0].device
-        self.static = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in batch.items()}
+        static = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in batch.items()}
         import gc
         gc.collect()                                 # autograd graphs of earlier steps (and their AccumulateGrad nodes) gone
         autograd.forget_transposes({id(p) for p in self.model.parameters()})   # nothing of another model in this graph
@@ -126,21 +187,18 @@ class GraphedStep:
         self.optim.zero_grad(set_to_none=True)       # the gradients of the replayed step live in the graph's pool
         self.optim.sync_lr()
         self.optim.new_capture_staging()             # (an earlier graph keeps re-reading ITS gradient addresses from its own)
-        graph = torch.cuda.CUDAGraph()
         quiet = getattr(torch.autograd.graph, "set_warn_on_accumulate_grad_stream_mismatch", None)
         if quiet is not None:      # AccumulateGrad nodes of the eager steps meet the capture stream once: expected here
             quiet(False)
         try:
-            with torch.cuda.graph(graph, stream=self.stream):
-                loss = self._body(self.static)
-                self.epoch.add_(1)
+            segments, loss = self._record(static)
         finally:
             if quiet is not None:
                 quiet(True)
-        self.graph, self.loss = graph, loss
         self.optim.note_replayed_step(-1)            # capture ran step()'s host bookkeeping without executing anything
         self.tab = self.optim._e3d_tab               # the optimizer tables (parameter / moment pointers) the graph baked
         self.ptrs = [p.data_ptr() for p in self.params]
+        return dict(graphs=segments, static=static, loss=loss, grads=[p.grad for p in self.params])
 
     def _stale(self):
         """The graph carries raw pointers: parameters that moved (``module.to()``) or optimizer state that was replaced
@@ -151,11 +209,6 @@ class GraphedStep:
         return (self.failed is None and key not in self.graphs and len(self.graphs) < self.MAX_GRAPHS
                 and self.seen.get(key, 0) >= self.warmup)
 
-    def _remember(self, key):
-        self.graphs[key] = dict(graph=self.graph, graph2=getattr(self, "graph2", None), static=self.static, loss=self.loss,
-                                grads=[p.grad for p in self.params])
-        self.key = key
-
     def _select(self, key):
         """Make the captured step of this signature the current one; False if there is none."""
         e = self.graphs.get(key)
@@ -164,51 +217,61 @@ class GraphedStep:
         if self.params[0].grad is not e["grads"][0]:   # ``p.grad`` shows the gradients of the step that ran last
             for p, g in zip(self.params, e["grads"]):
                 p.grad = g
-        self.graph, self.static, self.loss, self.key = e["graph"], e["static"], e["loss"], key
-        if e["graph2"] is not None:
-            self.graph2 = e["graph2"]
+        self.segments, self.static, self.loss, self.key = e["graphs"], e["static"], e["loss"], key
         return True
 
     def _drop_graphs(self):
         self.graphs, self.seen = {}, {}
-        self.graph = self.key = self.static = self.loss = None
-        if hasattr(self, "graph2"):
-            self.graph2 = None
+        self.segments = self.key = self.static = self.loss = None
 
-    def step(self, batch, batch_idx=0):
-        """Returns the loss (a device tensor; for a replayed step it is overwritten by the next replay of its graph)."""
+    def _on_stream(self, fn, *args):
+        """``fn(*args)`` (returns the loss) on ``self.stream``, ordered after and before the caller's current stream."""
+        cur = torch.cuda.current_stream(self.stream.device)
+        self.stream.wait_stream(cur)
+        with torch.cuda.stream(self.stream):
+            loss = fn(*args)
+        cur.wait_stream(self.stream)
+        loss.record_stream(cur)
+        return loss
+
+    def _replay(self, batch):
+        for k, v in batch.items():
+            if torch.is_tensor(v):
+                self.static[k].copy_(v, non_blocking=True)
+        self.optim.sync_lr()
+        for i, graph in enumerate(self.segments):
+            if i:
+                self._between_segments()
+            graph.replay()
+        self.optim.note_replayed_step()
+        ops.invalidate_weight_caches()
+        return self.loss
+
+    def _replayed(self, batch):
         key = self._signature(batch)
         if self.graphs and self._stale():
             self._drop_graphs()
         if self._may_capture(key):
             try:
-                self._capture(batch)                # (records, does not execute: this batch runs as the first replay below)
-                self._remember(key)
+                self.graphs[key] = self._capture(batch)    # (this batch runs as the first replay below)
             except Exception as e:                  # noqa: BLE001 -- any capture failure: stay eager, say so once
                 self.failed = e
                 self._drop_graphs()
                 import traceback
                 import warnings
-                warnings.warn(f"training step could not be captured in a HIP graph, staying eager: {e!r}\n"
-                              + "".join(traceback.format_exc(limit=-6)))
-        if self._select(key):
-            for k, v in batch.items():
-                if torch.is_tensor(v):
-                    self.static[k].copy_(v, non_blocking=True)
-            self.optim.sync_lr()
-            self.graph.replay()
-            self.optim.note_replayed_step()
-            ops.invalidate_weight_caches()
-            return self.loss
-        self.seen[key] = self.seen.get(key, 0) + 1
-        cur = torch.cuda.current_stream(self.stream.device)
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
-            loss = self._body(batch, batch_idx).detach()
-            self.epoch.add_(1)
-        cur.wait_stream(self.stream)
-        loss.record_stream(cur)
+                warnings.warn(f"{self.CAPTURE_FAILED}, staying eager: {e!r}\n" + "".join(traceback.format_exc(limit=-6)))
+        if not self._select(key):
+            self.seen[key] = self.seen.get(key, 0) + 1
+            return None
+        return self._on_stream(self._replay, batch) if self.REPLAY_ON_SIDE_STREAM else self._replay(batch)
+
+    def _eager_body(self, batch, batch_idx):
+        loss = train_step(self.model, self.optim, self.params, self.clip, batch, batch_idx, self.averager).detach()
+        self.epoch.add_(1)
         return loss
+
+    def _eager(self, batch, batch_idx):
+        return self._on_stream(self._eager_body, batch, batch_idx)
 
 
 class GraphedDDPStep(GraphedStep):
@@ -220,102 +283,44 @@ class GraphedDDPStep(GraphedStep):
     the same step; ``E3D_TRAIN_GRAPH=0`` keeps that eager path for every step.  The buckets travel AFTER the backward segment
     (the eager path overlaps them with it): ~1-2 ms for the sequence model's 289 MB on eight GPUs against a ~20-ms step."""
 
+    REPLAY_ON_SIDE_STREAM = True                     # replay and eager alike inside self.stream
+    CAPTURE_FAILED = "data-parallel training step could not be captured in HIP graphs"
+
     def __init__(self, model, optim, params, gradient_clip, averager, warmup=2):
         super().__init__(model, optim, params, gradient_clip, warmup)
-        self.avg = averager
-        self.graph2 = None
+        self.averager = averager
         self.world = torch.distributed.get_world_size()
 
-    def _eager(self, batch, batch_idx=0):
-        loss = self.model.training_step(batch, batch_idx)
-        self.optim.zero_grad(set_to_none=True)
-        self.avg.prepare()
-        if DEFER_WEIGHT_GRADS:
-            with autograd.deferred_weight_grads(on_param=self.avg.mark_ready):
-                loss.backward()
-        else:
-            loss.backward()
-        self.avg.average()
-        clip_and_step(self.params, self.optim, self.clip)
-        return loss
-
-    def _body(self, batch, batch_idx=0):
-        return self._eager(batch, batch_idx)
-
-    def _capture(self, batch):
-        dev = self.params[0].device
-        self.static = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in batch.items()}
-        import gc
-        gc.collect()
-        autograd.forget_transposes({id(p) for p in self.model.parameters()})
-        torch.cuda.synchronize(dev)
-        self.optim.zero_grad(set_to_none=True)
-        self.optim.sync_lr()
-        self.optim.new_capture_staging()
-        avg = self.avg
+    def _record(self, static):
+        avg = self.averager
         g1, g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        quiet = getattr(torch.autograd.graph, "set_warn_on_accumulate_grad_stream_mismatch", None)
-        if quiet is not None:
-            quiet(False)
-        try:
-            with torch.cuda.graph(g1, stream=self.stream):
-                loss = self.model.training_step(self.static, 0)
-                avg.bind(collect_only=True)          # gradients = zeroed views of the flat buckets; hooks only take notes
-                if DEFER_WEIGHT_GRADS:
-                    with autograd.deferred_weight_grads(on_param=avg.mark_ready):
-                        loss.backward()
-                else:
-                    loss.backward()
-                self.epoch.add_(1)
-            avg.finish_collect()                      # never-used parameters: grad None, as in every eager step
-            with torch.cuda.graph(g2, stream=self.stream, pool=g1.pool()):
-                for flat in avg.flats():
-                    flat.div_(self.world)
-                clip_and_step(self.params, self.optim, self.clip)
-        finally:
-            if quiet is not None:
-                quiet(True)
-        self.graph, self.graph2, self.loss = g1, g2, loss
-        self.optim.note_replayed_step(-1)
-        self.tab = self.optim._e3d_tab
-        self.ptrs = [p.data_ptr() for p in self.params]
+        with torch.cuda.graph(g1, stream=self.stream):
+            loss = self.model.training_step(static, 0)
+            avg.bind(collect_only=True)          # gradients = zeroed views of the flat buckets; hooks only take notes
+            backward(loss, avg)
+            self.epoch.add_(1)
+        avg.finish_collect()                      # never-used parameters: grad None, as in every eager step
+        with torch.cuda.graph(g2, stream=self.stream, pool=g1.pool()):
+            for flat in avg.flats():
+                flat.div_(self.world)
+            clip_and_step(self.params, self.optim, self.clip)
+        return (g1, g2), loss
 
-    def step(self, batch, batch_idx=0):
-        key = self._signature(batch)
-        if self.graphs and self._stale():
-            self._drop_graphs()
-        if self._may_capture(key):
-            try:
-                self._capture(batch)
-                self._remember(key)
-            except Exception as e:                  # noqa: BLE001 -- any capture failure: stay eager, say so once
-                self.failed = e
-                self._drop_graphs()
-                import traceback
-                import warnings
-                warnings.warn(f"data-parallel training step could not be captured in HIP graphs, staying eager: {e!r}\n"
-                              + "".join(traceback.format_exc(limit=-6)))
-        cur = torch.cuda.current_stream(self.stream.device)
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
-            if self._select(key):
-                for k, v in batch.items():
-                    if torch.is_tensor(v):
-                        self.static[k].copy_(v, non_blocking=True)
-                self.optim.sync_lr()
-                self.graph.replay()
-                self.avg.all_reduce_flats()          # the only eager launches of the step
-                self.graph2.replay()
-                self.optim.note_replayed_step()
-                ops.invalidate_weight_caches()
-                loss = self.loss
-            else:
-                self.seen[key] = self.seen.get(key, 0) + 1
-                loss = self._eager(batch, batch_idx).detach()
-                self.epoch.add_(1)
-        cur.wait_stream(self.stream)
-        loss.record_stream(cur)
-        return loss
+    def _between_segments(self):
+        self.averager.all_reduce_flats()             # the only eager launches of the step
+
+
+def make_stepper(model, optim, params, gradient_clip, averager=None, graph=None):
+    """The stepper a run gets: the step replayed from HIP graphs where that is possible (GPU parameters under ClipAdamW;
+    ``graph`` None: E3D_TRAIN_GRAPH) -- ``GraphedStep`` for one process, ``GraphedDDPStep`` under an active averager whose
+    hooks are in place -- and ``EagerStep`` everywhere else."""
+    from .optim import ClipAdamW
+    if (GRAPH_TRAIN if graph is None else graph) and params and params[0].is_cuda and isinstance(optim, ClipAdamW):
+        if averager is None or not averager._active():
+            return GraphedStep(model, optim, params, gradient_clip)
+        if averager._hooked:
+            return GraphedDDPStep(model, optim, params, gradient_clip, averager)
+    return EagerStep(model, optim, params, gradient_clip, averager)
 
 
 # the tensors of a dataset.py batch that are laid out [B, L, ...] over the ligand / the pocket frame
@@ -466,9 +471,15 @@ class BestCheckpoint:
 # E3D_TRAIN_ARITHMETIC=bf16 (opt-in): the reference's own training precision -- plain bf16 products in every GEMM (forward,
 # input and weight gradients), bf16x3 in the attention kernels; ~1e-2-grade gradients instead of ~1e-4-grade.
 TRAIN_ARITHMETIC = os.environ.get("E3D_TRAIN_ARITHMETIC", "bf16x3")
-# single-process training replays the step from a HIP graph (GraphedStep); 0: eager steps
-GRAPH_TRAIN = os.environ.get("E3D_TRAIN_GRAPH", "1") == "1"
-DEFER_WEIGHT_GRADS = os.environ.get("E3D_DEFER_WGRAD", "1") == "1"   # autograd.deferred_weight_grads in the step
+
+
+def _step_batch(batch, device, draws, trim, frame=None):
+    """A loader's batch as a step takes it: trimmed (on the loader's host tensors: no device round trip; ``frame``: rows
+    agreed on elsewhere), moved to the device, its keyed draws made."""
+    if trim:
+        batch = trim_batch(batch, frame)
+    batch = move_batch(batch, device)
+    return batch if draws is None else draws.batch(batch)
 
 
 def fit(model, train_loader, val_loader=None, *, max_epochs, min_epochs=0, gradient_clip=1.0, device="cuda:0",
@@ -486,62 +497,36 @@ def fit(model, train_loader, val_loader=None, *, max_epochs, min_epochs=0, gradi
     ``trim_padding`` (None: E3D_TRAIN_TRIM, default off = the reference's padded frames): run every training and
     validation step on the frame of the batch's longest ligand / pocket (``trim_batch``; under a process group the frame
     is the maximum over the ranks, agreed on the host, so that every rank replays the same kind of step)."""
-    with ops.arithmetic(TRAIN_ARITHMETIC):
-        return _fit(model, train_loader, val_loader, max_epochs=max_epochs, min_epochs=min_epochs, gradient_clip=gradient_clip,
-                    device=device, log_every_n_steps=log_every_n_steps, checkpoint_path=checkpoint_path,
-                    checkpoint_mode=checkpoint_mode, max_steps=max_steps, log=log,
-                    trim_padding=TRIM_TRAIN if trim_padding is None else bool(trim_padding), seed=seed,
-                    noise_tables=noise_tables, noise_scale=noise_scale)
-
-
-def _fit(model, train_loader, val_loader, *, max_epochs, min_epochs, gradient_clip, device, log_every_n_steps, checkpoint_path,
-         checkpoint_mode, max_steps, log, trim_padding=False, seed=None, noise_tables=None, noise_scale=None):
-    rank, world, _ = sharding.init_distributed()
-    model.to(device)
-    draws = None if seed is None else _KeyedDraws(model, seed, device, max_epochs, train_loader, noise_tables, noise_scale)
-    with draws if draws is not None else contextlib.nullcontext():
-        return _fit_epochs(model, train_loader, val_loader, rank, world, draws, max_epochs=max_epochs,
-                           gradient_clip=gradient_clip, device=device, log_every_n_steps=log_every_n_steps,
-                           checkpoint_path=checkpoint_path, checkpoint_mode=checkpoint_mode, max_steps=max_steps, log=log,
-                           trim_padding=trim_padding)
-
-
-def _fit_epochs(model, train_loader, val_loader, rank, world, draws, *, max_epochs, gradient_clip, device, log_every_n_steps,
-                checkpoint_path, checkpoint_mode, max_steps, log, trim_padding):
-    sharding.broadcast_parameters(model, src=0)
-    conf = model.configure_optimizers()
-    optim = conf["optimizer"]
-    sched = conf.get("lr_scheduler")
-    averager = sharding.GradientAverager(model.parameters())
-    ckpt = BestCheckpoint(checkpoint_path, checkpoint_mode)
-    history = {"train_loss": [], "val_loss": [], "steps": 0, "seconds": 0.0}
-    params = [p for p in model.parameters() if p.requires_grad]
-    stepper = None
-    if GRAPH_TRAIN and params and params[0].is_cuda:
-        from .optim import ClipAdamW
-        if isinstance(optim, ClipAdamW):
-            if world == 1 and not averager._active():
-                stepper = GraphedStep(model, optim, params, gradient_clip)
-            elif averager._active() and averager._hooked:
-                stepper = GraphedDDPStep(model, optim, params, gradient_clip, averager)
-    t0 = time.perf_counter()
-    step = 0
-    for epoch in range(max_epochs):
-        model.train()
-        if hasattr(getattr(train_loader, "sampler", None), "set_epoch"):
-            train_loader.sampler.set_epoch(epoch)
-        if draws is not None:
-            draws.set_epoch(epoch)
-        losses = []
-        for batch_idx, batch in enumerate(train_loader):
-            if trim_padding:                         # (on the loader's host tensors: no device round trip)
-                batch = trim_batch(batch, sharding.max_over_ranks_host(trimmed_frame(batch)) if world > 1 else None)
-            batch = move_batch(batch, device)
+    trim = TRIM_TRAIN if trim_padding is None else bool(trim_padding)
+    with contextlib.ExitStack() as whole_run:
+        whole_run.enter_context(ops.arithmetic(TRAIN_ARITHMETIC))
+        rank, world, _ = sharding.init_distributed()
+        model.to(device)
+        draws = None
+        if seed is not None:
+            draws = whole_run.enter_context(
+                _KeyedDraws(model, seed, device, max_epochs, train_loader, noise_tables, noise_scale))
+        sharding.broadcast_parameters(model, src=0)
+        conf = model.configure_optimizers()
+        optim = conf["optimizer"]
+        sched = conf.get("lr_scheduler") or {}
+        params = [p for p in model.parameters() if p.requires_grad]
+        stepper = make_stepper(model, optim, params, gradient_clip, sharding.GradientAverager(model.parameters()))
+        ckpt = BestCheckpoint(checkpoint_path, checkpoint_mode)
+        history = {"train_loss": [], "val_loss": [], "steps": 0, "seconds": 0.0}
+        t0 = time.perf_counter()
+        step = 0
+        for epoch in range(max_epochs):
+            model.train()
+            if hasattr(getattr(train_loader, "sampler", None), "set_epoch"):
+                train_loader.sampler.set_epoch(epoch)
             if draws is not None:
-                batch = draws.batch(batch)
-            if stepper is not None:
-                loss = stepper.step(batch, batch_idx)
-                if sched is not None and sched.get("interval") == "step":
+                draws.set_epoch(epoch)
+            losses = []
+            for batch_idx, batch in enumerate(train_loader):
+                frame = sharding.max_over_ranks_host(trimmed_frame(batch)) if trim and world > 1 else None
+                loss = stepper.step(_step_batch(batch, device, draws, trim, frame), batch_idx)
+                if sched.get("interval") == "step":
                     sched["scheduler"].step()
                 losses.append(loss.detach().clone())     # (a replayed step's loss tensor is overwritten by the next replay)
                 step += 1
@@ -549,63 +534,36 @@ def _fit_epochs(model, train_loader, val_loader, rank, world, draws, *, max_epoc
                     log(f"epoch {epoch} step {step} train_loss {float(losses[-1]):.5f}")
                 if max_steps is not None and step >= max_steps:
                     break
-                continue
-            loss = model.training_step(batch, batch_idx)
-            optim.zero_grad(set_to_none=True)
-            averager.prepare()                       # grads as views of the all-reduce buckets (no-op for one process)
-            # the weight gradients of all linear layers are computed together when the block ends (grouped launches,
-            # written into .grad, i.e. into the all-reduce buckets); E3D_DEFER_WGRAD=0: layer by layer inside backward
-            if DEFER_WEIGHT_GRADS:
-                with autograd.deferred_weight_grads(on_param=averager.mark_ready if averager._active() else None):
-                    loss.backward()
-            else:
-                loss.backward()
-            averager.average()                       # RCCL all-reduce (no-op for one process)
-            clip_and_step(params, optim, gradient_clip)   # global-norm clip of the averaged grads, then AdamW
-            ops.invalidate_weight_caches()           # belt and braces beside the global optimizer hook (ops.py)
-            if sched is not None and sched.get("interval") == "step":
+            if sched.get("interval") == "epoch":
                 sched["scheduler"].step()
-            losses.append(loss.detach())
-            step += 1
-            if rank == 0 and log_every_n_steps and step % log_every_n_steps == 0:
-                log(f"epoch {epoch} step {step} train_loss {float(losses[-1]):.5f}")
+            # the per-step losses stay on the device until here: a float() per step would make the host wait for every step
+            # (Lightning reads the loss for its progress bar every step; the values of the logged steps are the same)
+            losses = torch.stack(losses).double().cpu().tolist() if losses else []
+            mean_train = sum(losses) / max(1, len(losses))
+            history["train_loss"].append(mean_train)
+            if rank == 0:
+                log(f"Traning Loss:{mean_train}")
+            if val_loader is not None:
+                model.eval()
+                vals = []
+                if draws is not None:
+                    draws.set_epoch(None)                # the validation value: the same draws after every epoch
+                with torch.no_grad():
+                    for batch_idx, batch in enumerate(val_loader):
+                        out = model.validation_step(_step_batch(batch, device, draws, trim), batch_idx)
+                        vals.append(float(out["val_loss"] if isinstance(out, dict) else out))
+                if draws is not None:
+                    draws.set_epoch(epoch)
+                val = sum(vals) / max(1, len(vals)) if vals else math.nan
+                if world > 1:
+                    val = sharding.mean_over_ranks(val)
+                history["val_loss"].append(val)
+                if rank == 0:
+                    log(f"Validation Loss:{val}")
+                if not math.isnan(val):
+                    ckpt.update(model, val, rank)
             if max_steps is not None and step >= max_steps:
                 break
-        if sched is not None and sched.get("interval") == "epoch":
-            sched["scheduler"].step()
-        # the per-step losses stay on the device until here: a float() per step would make the host wait for every step
-        # (Lightning reads the loss for its progress bar every step; the values of the logged steps are the same)
-        losses = torch.stack(losses).double().cpu().tolist() if losses else []
-        mean_train = sum(losses) / max(1, len(losses))
-        history["train_loss"].append(mean_train)
-        if rank == 0:
-            log(f"Traning Loss:{mean_train}")
-        if val_loader is not None:
-            model.eval()
-            vals = []
-            if draws is not None:
-                draws.set_epoch(None)                # the validation value: the same draws after every epoch
-            with torch.no_grad():
-                for batch_idx, batch in enumerate(val_loader):
-                    if trim_padding:
-                        batch = trim_batch(batch)
-                    batch = move_batch(batch, device)
-                    if draws is not None:
-                        batch = draws.batch(batch)
-                    out = model.validation_step(batch, batch_idx)
-                    vals.append(float(out["val_loss"] if isinstance(out, dict) else out))
-            if draws is not None:
-                draws.set_epoch(epoch)
-            val = sum(vals) / max(1, len(vals)) if vals else math.nan
-            if world > 1:
-                val = sharding.mean_over_ranks(val)
-            history["val_loss"].append(val)
-            if rank == 0:
-                log(f"Validation Loss:{val}")
-            if not math.isnan(val):
-                ckpt.update(model, val, rank)
-        if max_steps is not None and step >= max_steps:
-            break
-    history["steps"] = step
-    history["seconds"] = time.perf_counter() - t0
-    return history
+        history["steps"] = step
+        history["seconds"] = time.perf_counter() - t0
+        return history

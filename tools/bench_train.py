@@ -81,17 +81,11 @@ def run(model_name="structure", batch=None, seq_len=128, steps=8, dropout=0.0, w
         sharding.broadcast_parameters(model, src=0)
         averager = sharding.GradientAverager(model.parameters())
 
-    # as training.fit does for a single process: the step replayed from a HIP graph (training.GraphedStep) after two eager
-    # steps; ``graph=False`` / E3D_TRAIN_GRAPH=0: eager
-    graph = (pkg.training.GRAPH_TRAIN if graph is None else graph) and isinstance(optim, pkg.optim.ClipAdamW)
-    stepper = None
-    if graph and not ddp:
-        stepper = pkg.training.GraphedStep(model, optim, params, 1.0)
-    elif graph and ddp and averager._active() and averager._hooked:
-        # as training.fit does under a process group: forward + backward and clip + AdamW as two graph segments around the
-        # eager all-reduce of the gradient buckets (training.GraphedDDPStep)
-        stepper = pkg.training.GraphedDDPStep(model, optim, params, 1.0, averager)
-    warmup = max(warmup, 4) if stepper is not None else warmup
+    # the stepper training.fit would use (a single process: the step replayed from a HIP graph after two eager steps; under
+    # a process group: two graph segments around the eager all-reduce); ``graph=False`` / E3D_TRAIN_GRAPH=0: eager
+    stepper = pkg.training.make_stepper(model, optim, params, 1.0, averager, graph=graph)
+    if isinstance(stepper, pkg.training.GraphedStep):
+        warmup = max(warmup, 4)
 
     def step():
         if epoch is not None:
@@ -103,22 +97,7 @@ def run(model_name="structure", batch=None, seq_len=128, steps=8, dropout=0.0, w
             batch_ = dict(pk, **noise_batch_on_device(pk["ligand_angles"], tab))
         else:
             batch_ = pk
-        if stepper is not None:
-            return stepper.step(batch_)
-        loss = model.training_step(batch_)
-        optim.zero_grad(set_to_none=True)
-        if averager is not None:
-            averager.prepare()
-        if pkg.training.DEFER_WEIGHT_GRADS:        # as training.fit does: weight gradients grouped at the end of backward
-            on_param = averager.mark_ready if (averager is not None and averager._active()) else None
-            with pkg.autograd.deferred_weight_grads(on_param=on_param):
-                loss.backward()
-        else:
-            loss.backward()
-        if averager is not None:
-            averager.average()
-        pkg.training.clip_and_step(params, optim, 1.0)      # as training.fit does
-        return loss
+        return stepper.step(batch_)
 
     with pkg.ops.arithmetic(arithmetic or pkg.training.TRAIN_ARITHMETIC):   # bf16x3 unless E3D_GEMM_MODE says otherwise
         mode = pkg.ops.GEMM_MODE
@@ -154,7 +133,7 @@ def run(model_name="structure", batch=None, seq_len=128, steps=8, dropout=0.0, w
         dist.all_gather(ws, w)
         assert all(float(t) == float(ws[0]) for t in ws), "ranks diverged"
     return {"model": model_name, **({"train_seed": train_seed} if train_seed is not None else {}), "batch": B, "seq_len": L, "frame": list(frame), "layers": layers, "params_M": sum(p.numel() for p in params) / 1e6,
-            "arithmetic": mode, "dropout": dropout, "graph_replay": bool(stepper is not None and stepper.graph is not None),
+            "arithmetic": mode, "dropout": dropout, "graph_replay": stepper.graph is not None,
             "ms_per_step": dt * 1e3, "samples_per_s": B / dt, "host_enqueue_ms": host_ms,
             **({"ranks": dist.get_world_size(), "global_batch": B * dist.get_world_size(),
                 "global_samples_per_s": B * dist.get_world_size() / dt, "backend": dist.get_backend(),

@@ -49,7 +49,7 @@ def audited(batch):
     torch.cuda.synchronize()
     before = default_pool_blocks()
     torch.cuda.memory._record_memory_history(enabled="all", context="all", stacks="python", max_entries=200000)
-    orig_capture(batch)
+    entry = orig_capture(batch)
     snap = torch.cuda.memory._snapshot()
     torch.cuda.memory._record_memory_history(enabled=None)
     default_segs = [(sg["address"], sg["address"] + sg["total_size"]) for sg in snap["segments"] if tuple(sg.get("segment_pool_id", (0, 0))) == (0, 0)]
@@ -81,6 +81,7 @@ def audited(batch):
     print("   still referenced from Python:", len(owners), "of", len(new), list(owners.values())[:12])
     sizes = sorted(new.values(), reverse=True)[:12]
     print("   largest:", sizes)
+    return entry
 
 
 stepper._capture = audited

@@ -13,7 +13,7 @@ import __graft_entry__  # noqa: E402
 
 pkg = __graft_entry__.load_package()
 import test_training_gpu as T  # noqa: E402
-from e3diff_amd import autograd, ops, training  # noqa: E402
+from e3diff_amd import ops, training  # noqa: E402
 
 batches = [b for i, b in enumerate(T._structure_batches(10)) if i != 4]
 res = []
@@ -28,12 +28,7 @@ for graphed in (True, False, True, True):
             if graphed:
                 losses.append(float(stepper.step(batch)))
             else:
-                loss = model.training_step(batch)
-                optim.zero_grad(set_to_none=True)
-                with autograd.deferred_weight_grads():
-                    loss.backward()
-                training.clip_and_step(params, optim, 1.0)
-                losses.append(float(loss))
+                losses.append(float(training.train_step(model, optim, params, 1.0, batch).detach()))
     res.append((graphed, losses, [p.detach().clone() for p in params]))
     del model, optim, stepper
 ref = res[1]

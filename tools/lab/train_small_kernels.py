@@ -24,11 +24,7 @@ pk = {k: v.to(DEV) for k, v in synthetic_pockets(B, L, seed=0).items() if torch.
 tab = CosineTables(1000)
 
 def step():
-    loss = model.training_step(dict(pk, **noise_batch_on_device(pk["ligand_angles"], tab)))
-    optim.zero_grad(set_to_none=True)
-    with pkg.autograd.deferred_weight_grads():
-        loss.backward()
-    pkg.training.clip_and_step(params, optim, 1.0)
+    pkg.training.train_step(model, optim, params, 1.0, dict(pk, **noise_batch_on_device(pk["ligand_angles"], tab)))
 
 with pkg.ops.arithmetic("bf16x3"):
     for _ in range(2):
