@@ -259,7 +259,7 @@ def act_bwd(dh, z, act):
 
 
 def layernorm_bwd(dy, s, gamma, eps, want_affine_grads=True, drop=None):
-    """``drop`` = (p, seed) of a dropout folded into the forward (ops.residual_layernorm(..., drop=)): returns
+    """``drop`` = (p, seed) or (p, site, row_keys) of a dropout folded into the forward (ops.residual_layernorm(..., drop=)): returns
     (ds, dg, db, ds_dropped) -- ds_dropped = dropout(ds, p, seed), the gradient of the dropped-out input."""
     M, H = s.shape
     ds = torch.empty_like(s)
@@ -271,6 +271,11 @@ def layernorm_bwd(dy, s, gamma, eps, want_affine_grads=True, drop=None):
         n_ws = hip.lib().e3d_layernorm_bwd_workspace_floats(M, H)
         ws = torch.empty((n_ws,), device=s.device, dtype=torch.float32)
     dsd = torch.empty_like(s) if drop is not None else None
+    if drop is not None and len(drop) == 3:      # keyed decisions: (p, site, row_keys)
+        p, site, keys = ops._keyed_drop(drop, M, "layernorm_bwd")
+        hip.check(hip.lib().e3d_layernorm_bwd_ws_keyed(_p(dy), _p(s), _p(gamma), eps, _p(ds), _p(dsd), _p(dg), _p(db), M, H, p,
+                                                       site, keys, _p(ws), n_ws, _stream()), "e3d_layernorm_bwd_ws_keyed")
+        return ds, dg, db, dsd
     p, seed = (float(drop[0]), int(drop[1])) if drop is not None else (0.0, 0)
     hip.check(hip.lib().e3d_layernorm_bwd_ws(_p(dy), _p(s), _p(gamma), eps, _p(ds), _p(dsd), _p(dg), _p(db), M, H, p, seed,
                                              _p(ws), n_ws, _stream()), "e3d_layernorm_bwd_ws")
@@ -451,10 +456,10 @@ class _Attention(torch.autograd.Function):
         return q_src, kv_src[:, :H], kv_src[:, H:]
 
     @staticmethod
-    def forward(ctx, q_src, kv_src, dist_emb, key_mask, B, nh, Lq, Lk, max_pos, drop_p=0.0, bounds=None):
+    def forward(ctx, q_src, kv_src, dist_emb, key_mask, B, nh, Lq, Lk, max_pos, drop_p=0.0, bounds=None, row_keys=None):
         H = nh * 64
         q, k, v = _Attention._views(q_src, kv_src, H)
-        drop = (float(drop_p), ops.next_dropout_seed()) if drop_p > 0 else (0.0, 0)
+        drop = ops.site_drop(drop_p, row_keys) if drop_p > 0 else (0.0, 0)
         out, lse = ops.attention(q, k, v, B, nh, Lq, Lk, key_mask=key_mask, dist_emb=dist_emb, max_pos=max_pos,
                                  want_lse=True, drop=drop, bounds=bounds)
         ctx.save_for_backward(q_src, kv_src, dist_emb, key_mask, out, lse)
@@ -479,27 +484,31 @@ class _Attention(torch.autograd.Function):
         lib = hip.lib()
         ws = torch.empty((lib.e3d_relkey_attn_bwd_workspace_floats(B, nh, Lq, Lk, int(dist_emb is not None)),),
                          device=q.device, dtype=torch.float32)
-        with ops._timed("attn_bwd", (B, nh, Lq, Lk)):
-            hip.check(lib.e3d_relkey_attn_bwd_ex(
-                _p(q), Lq * q.stride(0), q.stride(0), _p(k), Lk * k.stride(0), k.stride(0), _p(v), Lk * v.stride(0),
+        args = (_p(q), Lq * q.stride(0), q.stride(0), _p(k), Lk * k.stride(0), k.stride(0), _p(v), Lk * v.stride(0),
                 v.stride(0), _p(dist_emb), max_pos, _p(key_mask), _p(out), _p(lse), _p(dout),
                 _p(dq), Lq * dq.stride(0), dq.stride(0), _p(dk), Lk * dk.stride(0), dk.stride(0),
-                _p(dv), Lk * dv.stride(0), dv.stride(0), _p(dE), _p(ws), B, nh, Lq, Lk, ctx.terms, ctx.drop[0], ctx.drop[1],
-                _stream()), "e3d_relkey_attn_bwd_ex")
-        return dq_src, dkv_src, dE, None, None, None, None, None, None, None, None
+                _p(dv), Lk * dv.stride(0), dv.stride(0), _p(dE), _p(ws), B, nh, Lq, Lk, ctx.terms)
+        with ops._timed("attn_bwd", (B, nh, Lq, Lk)):
+            if len(ctx.drop) == 3:               # keyed decisions: (p, site, row_keys) of the forward
+                hip.check(lib.e3d_relkey_attn_bwd_ex_keyed(*args, *ops._keyed_drop(ctx.drop, B * Lq, "attention backward", nh),
+                                                           _stream()), "e3d_relkey_attn_bwd_ex_keyed")
+            else:
+                hip.check(lib.e3d_relkey_attn_bwd_ex(*args, ctx.drop[0], ctx.drop[1], _stream()), "e3d_relkey_attn_bwd_ex")
+        return dq_src, dkv_src, dE, None, None, None, None, None, None, None, None, None
 
 
 class _Dropout(torch.autograd.Function):
     """y = x * keep / (1 - p'); the gradient passes through the same decisions (regenerated from the seed)."""
 
     @staticmethod
-    def forward(ctx, x, p):
-        ctx.p, ctx.seed = float(p), ops.next_dropout_seed()
-        return ops.dropout(x.contiguous(), ctx.p, ctx.seed)
+    def forward(ctx, x, p, row_keys=None):
+        ctx.p, ctx.seed = ops.site_drop(p, row_keys)[:2]      # keyed decisions: the "seed" is the site
+        ctx.row_keys = row_keys
+        return ops.dropout(x.contiguous(), ctx.p, ctx.seed, row_keys=row_keys)
 
     @staticmethod
     def backward(ctx, dy):
-        return ops.dropout(dy.contiguous(), ctx.p, ctx.seed), None
+        return ops.dropout(dy.contiguous(), ctx.p, ctx.seed, row_keys=ctx.row_keys), None, None
 
 
 class _ResidualLayerNorm(torch.autograd.Function):
@@ -507,8 +516,8 @@ class _ResidualLayerNorm(torch.autograd.Function):
     BertSelfOutput / BertOutput into the LayerNorm kernels (no [M, H] dropout pass in either direction)."""
 
     @staticmethod
-    def forward(ctx, x, residual, gamma, beta, eps, p_drop=0.0):
-        ctx.drop = (float(p_drop), ops.next_dropout_seed()) if p_drop and p_drop > 0 else None
+    def forward(ctx, x, residual, gamma, beta, eps, p_drop=0.0, row_keys=None):
+        ctx.drop = ops.site_drop(p_drop, row_keys) if p_drop and p_drop > 0 else None
         out, s = ops.residual_layernorm(x, residual, gamma, beta, eps, want_s=True, drop=ctx.drop)
         ctx.save_for_backward(s, gamma)
         ctx.eps, ctx.has_res = eps, residual is not None
@@ -519,9 +528,9 @@ class _ResidualLayerNorm(torch.autograd.Function):
         s, gamma = ctx.saved_tensors
         if ctx.drop is not None:
             ds, dg, db, dsd = layernorm_bwd(dy.contiguous(), s, gamma, ctx.eps, drop=ctx.drop)
-            return dsd, (ds if ctx.has_res else None), dg, db, None, None
+            return dsd, (ds if ctx.has_res else None), dg, db, None, None, None
         ds, dg, db = layernorm_bwd(dy.contiguous(), s, gamma, ctx.eps)
-        return ds, (ds if ctx.has_res else None), dg, db, None, None
+        return ds, (ds if ctx.has_res else None), dg, db, None, None, None
 
 
 class _AdaLNGate(torch.autograd.Function):
@@ -604,48 +613,50 @@ class functional:
         return out
 
     @staticmethod
-    def attention(q_src, kv_src, B, nh, Lq, Lk, key_mask=None, dist_emb=None, max_pos=0, drop_p=0.0):
+    def attention(q_src, kv_src, B, nh, Lq, Lk, key_mask=None, dist_emb=None, max_pos=0, drop_p=0.0, row_keys=None):
         """q_src = packed qkv [B*L,3H] (kv_src None, self-attention) or q [B*Lq,H] with packed kv [B*Lk,2H].
-        ``drop_p`` > 0 (training): dropout on the attention probabilities."""
+        ``drop_p`` > 0 (training): dropout on the attention probabilities.  ``row_keys`` (inside ``ops.keyed_dropout``, here
+        and in ``dropout`` / ``residual_layernorm``): the key table of the site's rows -- here the [B, Lq] query frame."""
         # element bounds left by the projections (functional.linear(..., absmax=)): they let the kernels skip all-padding
         # key tiles when that is provably exact; absent (direct callers) = full sweep
         q_abs = getattr(q_src, "_e3d_absmax", None)
         k_abs = q_abs if kv_src is None else getattr(kv_src, "_e3d_absmax", None)
         bounds = (q_abs, k_abs) if q_abs is not None and k_abs is not None else None
         if _needs_grad(q_src, kv_src, dist_emb):
-            return _Attention.apply(q_src, kv_src, dist_emb, key_mask, B, nh, Lq, Lk, max_pos, drop_p, bounds)
+            return _Attention.apply(q_src, kv_src, dist_emb, key_mask, B, nh, Lq, Lk, max_pos, drop_p, bounds, row_keys)
         q, k, v = _Attention._views(q_src, kv_src, nh * 64)
-        drop = (float(drop_p), ops.next_dropout_seed()) if drop_p > 0 else None
+        drop = ops.site_drop(drop_p, row_keys) if drop_p > 0 else None
         return ops.attention(q, k, v, B, nh, Lq, Lk, key_mask=key_mask, dist_emb=dist_emb, max_pos=max_pos, drop=drop,
                              bounds=bounds)
 
     @staticmethod
-    def dropout(x, p, training=True):
+    def dropout(x, p, training=True, row_keys=None):
         """nn.Dropout(p) of the reference: identity unless ``training`` and p > 0."""
         if not training or not p:
             return x
         if _needs_grad(x):
-            return _Dropout.apply(x, p)
-        return ops.dropout(x.contiguous(), p, ops.next_dropout_seed())
+            return _Dropout.apply(x, p, row_keys)
+        p, seed = ops.site_drop(p, row_keys)[:2]
+        return ops.dropout(x.contiguous(), p, seed, row_keys=row_keys)
 
     @staticmethod
-    def residual_layernorm(x, residual, gamma, beta, eps, p_drop=0.0):
+    def residual_layernorm(x, residual, gamma, beta, eps, p_drop=0.0, row_keys=None):
         """LayerNorm(dropout(x, p_drop) + residual)."""
         if _needs_grad(x, residual, gamma, beta):
-            return _ResidualLayerNorm.apply(x, residual, gamma, beta, eps, p_drop)
-        drop = (float(p_drop), ops.next_dropout_seed()) if p_drop and p_drop > 0 else None
+            return _ResidualLayerNorm.apply(x, residual, gamma, beta, eps, p_drop, row_keys)
+        drop = ops.site_drop(p_drop, row_keys) if p_drop and p_drop > 0 else None
         return ops.residual_layernorm(x, residual, gamma, beta, eps, drop=drop)
 
     @staticmethod
-    def linear_residual_layernorm(x, weight, bias, residual, gamma, beta, eps, p_drop=0.0):
+    def linear_residual_layernorm(x, weight, bias, residual, gamma, beta, eps, p_drop=0.0, row_keys=None):
         """BertSelfOutput / BertOutput: LayerNorm(dropout(x W^T + b) + residual).  Inference at small M takes the
         fused skinny-GEMM finish (ops.linear_residual_layernorm); training and every other shape the three ops."""
         if not p_drop and not _needs_grad(x, weight, bias, residual, gamma, beta):
             return ops.linear_residual_layernorm(x, weight, bias, residual, gamma, beta, eps)
         fn = functional
         if FUSE_HIDDEN_DROPOUT:
-            return fn.residual_layernorm(fn.linear(x, weight, bias), residual, gamma, beta, eps, p_drop)
-        return fn.residual_layernorm(fn.dropout(fn.linear(x, weight, bias), p_drop), residual, gamma, beta, eps)
+            return fn.residual_layernorm(fn.linear(x, weight, bias), residual, gamma, beta, eps, p_drop, row_keys)
+        return fn.residual_layernorm(fn.dropout(fn.linear(x, weight, bias), p_drop, row_keys=row_keys), residual, gamma, beta, eps)
 
     @staticmethod
     def adaln_gate(x, y, mod, branch, rows_per_cond):

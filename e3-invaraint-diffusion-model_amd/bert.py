@@ -211,9 +211,15 @@ def dropout_rates(module):
 
 
 # ----------------------------------------------------------------------------- executors
-def _attention_output(att, ctx, x, p_hidden=0.0):
+def _attention_output(att, ctx, x, p_hidden=0.0, row_keys=None):
     return F.linear_residual_layernorm(ctx, att.output.dense.weight, att.output.dense.bias, x, att.output.LayerNorm.weight,
-                                       att.output.LayerNorm.bias, att.eps, p_hidden)
+                                       att.output.LayerNorm.bias, att.eps, p_hidden, row_keys)
+
+
+def drop_keys(drop):
+    """The row-key table of a ``drop`` value -- (hidden rate, attention rate) or, in a seeded step with keyed dropout,
+    (hidden rate, attention rate, key table of the rows being processed: ``ops.KeyedDropout.row_keys``) -- or None."""
+    return drop[2] if len(drop) > 2 else None
 
 
 def run_self_attention(att, x, mask, B, L, drop=(0.0, 0.0), layout=None):
@@ -232,8 +238,8 @@ def run_self_attention(att, x, mask, B, L, drop=(0.0, 0.0), layout=None):
         return _attention_output(att, ctx, x)
     ctx = F.attention(qkv, None, B, att.num_heads, L, L, key_mask=mask,
                       dist_emb=sa.distance_embedding.weight if relkey else None,
-                      max_pos=sa.max_position_embeddings, drop_p=drop[1])
-    return _attention_output(att, ctx, x, drop[0])
+                      max_pos=sa.max_position_embeddings, drop_p=drop[1], row_keys=drop_keys(drop))
+    return _attention_output(att, ctx, x, drop[0], drop_keys(drop))
 
 
 def project_cross_kv(att, enc):
@@ -252,14 +258,15 @@ def run_cross_attention(att, x, kv, enc_mask, B, Lq, Lk, drop=(0.0, 0.0), layout
         H = att.num_heads * 64
         ctx = ops.attention_varlen(q, kv[:, :H], kv[:, H:], layout, enc_layout, att.num_heads)
         return _attention_output(att, ctx, x)
-    ctx = F.attention(q, kv, B, att.num_heads, Lq, Lk, key_mask=enc_mask, drop_p=drop[1])
-    return _attention_output(att, ctx, x, drop[0])
+    ctx = F.attention(q, kv, B, att.num_heads, Lq, Lk, key_mask=enc_mask, drop_p=drop[1], row_keys=drop_keys(drop))
+    return _attention_output(att, ctx, x, drop[0], drop_keys(drop))
 
 
 def run_layer(layer, x, mask, B, L, cross_kv=None, enc_mask=None, Lk=None, drop=(0.0, 0.0), layout=None,
               enc_layout=None):
-    """``drop`` = (hidden, attention-probability) dropout rates of this call (training only).  ``layout`` /
-    ``enc_layout``: packed rows (run_self_attention, run_cross_attention)."""
+    """``drop`` = (hidden, attention-probability) dropout rates of this call (training only), plus -- keyed dropout -- the
+    key table of the rows of x (the query rows of both attentions).  ``layout`` / ``enc_layout``: packed rows
+    (run_self_attention, run_cross_attention)."""
     x = run_self_attention(layer.attention, x, mask, B, L, drop, layout=layout)
     if hasattr(layer, "crossattention"):
         if cross_kv is None:
@@ -268,16 +275,21 @@ def run_layer(layer, x, mask, B, L, cross_kv=None, enc_mask=None, Lk=None, drop=
                                 enc_layout=enc_layout)
     inter = F.linear(x, layer.intermediate.dense.weight, layer.intermediate.dense.bias, ops.ACT_GELU)
     return F.linear_residual_layernorm(inter, layer.output.dense.weight, layer.output.dense.bias, x,
-                                       layer.output.LayerNorm.weight, layer.output.LayerNorm.bias, layer.eps, drop[0])
+                                       layer.output.LayerNorm.weight, layer.output.LayerNorm.bias, layer.eps, drop[0],
+                                       drop_keys(drop))
 
 
-def run_encoder(encoder, x, mask, B, L, enc=None, enc_mask=None, Lk=None, cross_kv=None, layout=None, enc_layout=None):
+def run_encoder(encoder, x, mask, B, L, enc=None, enc_mask=None, Lk=None, cross_kv=None, layout=None, enc_layout=None,
+                row_keys=None):
     """BertEncoder(...).last_hidden_state on flat activations.  ``cross_kv`` (list, one per
     layer) short-cuts the per-layer K/V projection of ``enc``.  ``layout`` / ``enc_layout`` (packing.PackedLayout,
-    inference): x (and enc) hold packed rows; the masks, B, L and Lk are then not read."""
+    inference): x (and enc) hold packed rows; the masks, B, L and Lk are then not read.  ``row_keys`` (keyed dropout):
+    the key table of the rows of x."""
     drop = dropout_rates(encoder)
     if layout is not None and drop != (0.0, 0.0):
         raise RuntimeError("packed layouts are inference-only: put the model in eval mode")
+    if row_keys is not None:
+        drop = drop + (row_keys,)
     for i, layer in enumerate(encoder.layer):
         kv = None
         if hasattr(layer, "crossattention"):

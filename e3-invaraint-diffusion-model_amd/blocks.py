@@ -6,7 +6,9 @@ import math
 import torch
 from torch import nn
 
-from . import bert, ops
+import contextlib
+
+from . import bert, keyed, ops
 from .autograd import functional as F
 
 
@@ -33,12 +35,13 @@ class SELayer(nn.Module):
         m0, m2 = self.adaLN_modulation[0], self.adaLN_modulation[2]
         return F.linear(F.linear(c, m0.weight, m0.bias, ops.ACT_SILU), m2.weight, m2.bias)
 
-    def run(self, x, c, mask, B, L, mod=None, layout=None):
+    def run(self, x, c, mask, B, L, mod=None, layout=None, row_keys=None):
         """x [B*L,H]; c [B*L,H] (per token) or [B,H] (one conditioning row per item).  ``mod``: the rows
         ``modulation(c)`` would give, computed by the caller ([B*L,6H], [B,6H], or ONE row [1,6H] shared by every
         item: samplers precompute it per timestep) -- ``c`` is then not read.  ``layout`` (packing.PackedLayout,
         inference): x holds packed rows [layout.rows, H] (pass B = 1, L = layout.rows) and the conditioning is per
-        token ([rows,H]) or ONE row shared by every item (a sampler's single timestep); ``mask`` is not read."""
+        token ([rows,H]) or ONE row shared by every item (a sampler's single timestep); ``mask`` is not read.
+        ``row_keys`` (keyed dropout, training): the key table of the rows of x."""
         if mod is None:
             mod = self.modulation(c)
         if layout is not None:
@@ -48,10 +51,12 @@ class SELayer(nn.Module):
         rows_per_cond = x.shape[0] // mod.shape[0]
         assert rows_per_cond in (1, L, B * L) and rows_per_cond * mod.shape[0] == x.shape[0], (x.shape, mod.shape)
         drop = bert.dropout_rates(self.attn)   # (hidden, attention) rates in training, zeros in eval
+        if row_keys is not None:
+            drop = drop + (row_keys,)
         att = bert.run_self_attention(self.attn, x, mask, B, L, drop, layout=layout)
         x = F.adaln_gate(x, att, mod, 0, rows_per_cond)
-        h = F.dropout(F.linear(x, self.mlp[0].weight, self.mlp[0].bias, ops.ACT_GELU), self.mlp[2].p, self.training)
-        h = F.dropout(F.linear(h, self.mlp[3].weight, self.mlp[3].bias), self.mlp[4].p, self.training)
+        h = F.dropout(F.linear(x, self.mlp[0].weight, self.mlp[0].bias, ops.ACT_GELU), self.mlp[2].p, self.training, row_keys)
+        h = F.dropout(F.linear(h, self.mlp[3].weight, self.mlp[3].bias), self.mlp[4].p, self.training, row_keys)
         return F.adaln_gate(x, h, mod, 1, rows_per_cond)
 
 
@@ -84,13 +89,14 @@ class BertEmbeddings(nn.Module):
         self.LayerNorm = nn.LayerNorm(bert_config.hidden_size, eps=bert_config.layer_norm_eps)
         self.dropout = nn.Dropout(bert_config.hidden_dropout_prob)
 
-    def run(self, x2d, post_add=None, rows_per_add=1):
+    def run(self, x2d, post_add=None, rows_per_add=1, row_keys=None):
         """``post_add`` [M / rows_per_add, H] is what the caller adds to the embedding afterwards (the sequence
-        model's timestep term): fused into the kernel, except in training with dropout, which sits between."""
+        model's timestep term): fused into the kernel, except in training with dropout, which sits between.
+        ``row_keys`` (keyed dropout, training): the key table of the rows of x2d."""
         if self.training and self.dropout.p > 0:
             e = F.embed_layernorm(x2d, self.linear.weight, self.linear.bias, self.LayerNorm.weight,
                                   self.LayerNorm.bias, self.LayerNorm.eps, None, 1)
-            e = F.dropout(e, self.dropout.p)
+            e = F.dropout(e, self.dropout.p, row_keys=row_keys)
             if post_add is not None:
                 e = (e.view(-1, rows_per_add, e.shape[1]) + post_add[:, None, :]).view_as(e)
             return e
@@ -113,6 +119,44 @@ class Predictor(nn.Module):
         h = F.linear(x, self.dense1.weight, self.dense1.bias, ops.ACT_GELU)
         h = F.residual_layernorm(h, None, self.layer_norm.weight, self.layer_norm.bias, self.layer_norm.eps)
         return F.head_linear(h, self.dense2.weight, self.dense2.bias)
+
+
+class KeyedDropoutSwitch:
+    """Keyed dropout for a training wrapper ("Keyed sampling streams"): with a seed, every dropout decision of
+    ``training_step`` is a function of (seed, batch["item_id"], epoch, dropout site, position, head, column or key) --
+    not of the batch, the row, the frame, the launch mode or the steps run before."""
+
+    keyed_dropout = None
+
+    def use_keyed_dropout(self, seed, epoch=None):
+        """``seed=None`` switches back to torch-seeded dropout.  ``epoch``: the int64 word in device memory the row keys
+        take the epoch from (``keyed.epoch_word`` / ``keyed.set_epoch``; a seeded ``training.fit`` shares the word of its
+        keyed draws); default: a word of this model's own at epoch 0.  Returns the word."""
+        if seed is None:
+            self.keyed_dropout = None
+            return None
+        if epoch is None:
+            epoch = keyed.epoch_word(next(self.parameters()).device)
+        self.keyed_dropout = (keyed.check_seed(seed), epoch)
+        return epoch
+
+    def keyed_dropout_step(self, batch):
+        """The context ``training_step`` runs in: ``ops.keyed_dropout`` over this batch's item ids -- its site counter
+        starts at 0, so every step numbers its dropout calls alike -- when the switch is on and dropout acts at all."""
+        cfgs = (self.encoder_config, self.decoder_config)
+        acts = self.training and any(getattr(c, "hidden_dropout_prob", 0.0) > 0 or getattr(c, "attention_probs_dropout_prob", 0.0) > 0
+                                     for c in cfgs)
+        if self.keyed_dropout is None or not acts:
+            return contextlib.nullcontext()
+        seed, epoch = self.keyed_dropout
+        return ops.keyed_dropout(seed, epoch, keyed.batch_item_ids(batch, batch["ligand_attn_mask"].shape[0]))
+
+
+def drop_row_keys(stream, L):
+    """Inside ``ops.keyed_dropout``: the row-key table of the batch's [B, L] frame on ``stream`` (keyed.DROP_LIGAND /
+    keyed.DROP_POCKET), built once per step and frame; else None."""
+    kd = ops.keyed_dropout_state()
+    return None if kd is None else kd.row_keys(stream, L)
 
 
 def flat2d(x):

@@ -89,6 +89,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(
     const int q0 = qt * 32;
     const int lq = min(q0 + qi, Lq - 1);
     const bool q_ok = q0 + qi < Lq;
+    uint64_t drop_row = 0;   // dropout: this query row's part of the hash input (its key, when the decisions are keyed)
+    if (DROP) drop_row = e3d_drop_attn_row(drop, b, h, nh, Lq, Lk, lq);
     const int HD = nh * D;
     f32x4 qf[8], dof[8];
     load_frag8(qf, q + b * q_bs + (int64_t)lq * q_rs + h * D, half);
@@ -178,7 +180,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 float m[4];
-                e3d_drop_mult4(drop, e3d_attn_drop_idx4(bh, Lq, Lk, q0 + qi, r0 + 8 * g + 4 * half), m);
+                e3d_drop_mult4_row(drop, drop_row, (uint32_t)((r0 >> 2) + 2 * g + half), m);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     ds[4 * g + j] = s[4 * g + j] * (ds[4 * g + j] * m[j] - delta) * 0.125f;
@@ -345,16 +347,15 @@ extern "C" int64_t e3d_relkey_attn_bwd_workspace_floats(int B, int nh, int Lq, i
     return (2 * pm > head ? 2 * pm : head) + part + (relkey ? e3d_attn_bwd_coop_de_floats(Lq, Lk) + (int64_t)B * nh * q_tiles : 0);
 }
 
-extern "C" int e3d_relkey_attn_bwd_ex(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs,
-                                      int64_t k_rs, const float* v, int64_t v_bs, int64_t v_rs, const float* dist_emb,
-                                      int P, const float* key_mask, const float* out, const float* lse,
-                                      const float* dout, float* dq, int64_t dq_bs, int64_t dq_rs, float* dk,
-                                      int64_t dk_bs, int64_t dk_rs, float* dv, int64_t dv_bs, int64_t dv_rs,
-                                      float* d_dist_emb, float* workspace, int B, int nh, int Lq, int Lk, int terms,
-                                      float drop_p, uint64_t drop_seed, void* stream) {
+// the body of e3d_relkey_attn_bwd_ex and of its keyed form: ``drop`` = the decisions of drop_p
+static int attn_bwd_dispatch(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs, int64_t k_rs,
+                             const float* v, int64_t v_bs, int64_t v_rs, const float* dist_emb, int P, const float* key_mask,
+                             const float* out, const float* lse, const float* dout, float* dq, int64_t dq_bs, int64_t dq_rs,
+                             float* dk, int64_t dk_bs, int64_t dk_rs, float* dv, int64_t dv_bs, int64_t dv_rs,
+                             float* d_dist_emb, float* workspace, int B, int nh, int Lq, int Lk, int terms, float drop_p,
+                             const E3dDrop drop, void* stream) {
     E3D_REQUIRE(terms == 0 || terms == 3 || terms == 6, "attn_bwd: terms must be 0 (fp32 MFMA), 3 or 6 (got %d)", terms);
     E3D_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "attn_bwd: drop_p=%g outside [0, 1)", (double)drop_p);
-    const E3dDrop drop = e3d_drop_make(drop_p, drop_seed);
     E3D_REQUIRE(q && k && v && out && lse && dout && dq && dk && dv && workspace, "attn_bwd: null pointer");
     E3D_REQUIRE(B > 0 && nh > 0 && Lq > 0 && Lk > 0, "attn_bwd: bad shape");
     E3D_REQUIRE(q_rs % 4 == 0 && k_rs % 4 == 0 && v_rs % 4 == 0 && dq_rs % 4 == 0 && dk_rs % 4 == 0 && dv_rs % 4 == 0 &&
@@ -422,6 +423,33 @@ extern "C" int e3d_relkey_attn_bwd_ex(const float* q, int64_t q_bs, int64_t q_rs
     return 0;
 }
 
+extern "C" int e3d_relkey_attn_bwd_ex(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs,
+                                      int64_t k_rs, const float* v, int64_t v_bs, int64_t v_rs, const float* dist_emb,
+                                      int P, const float* key_mask, const float* out, const float* lse,
+                                      const float* dout, float* dq, int64_t dq_bs, int64_t dq_rs, float* dk,
+                                      int64_t dk_bs, int64_t dk_rs, float* dv, int64_t dv_bs, int64_t dv_rs,
+                                      float* d_dist_emb, float* workspace, int B, int nh, int Lq, int Lk, int terms,
+                                      float drop_p, uint64_t drop_seed, void* stream) {
+    return attn_bwd_dispatch(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, dist_emb, P, key_mask, out, lse, dout, dq, dq_bs,
+                             dq_rs, dk, dk_bs, dk_rs, dv, dv_bs, dv_rs, d_dist_emb, workspace, B, nh, Lq, Lk, terms, drop_p,
+                             e3d_drop_make(drop_p, drop_seed), stream);
+}
+
+// As e3d_relkey_attn_bwd_ex with the keyed decisions of e3d_relkey_attn_fwd_split_ex_keyed (same p, site and row keys)
+extern "C" int e3d_relkey_attn_bwd_ex_keyed(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs,
+                                            int64_t k_rs, const float* v, int64_t v_bs, int64_t v_rs, const float* dist_emb,
+                                            int P, const float* key_mask, const float* out, const float* lse,
+                                            const float* dout, float* dq, int64_t dq_bs, int64_t dq_rs, float* dk,
+                                            int64_t dk_bs, int64_t dk_rs, float* dv, int64_t dv_bs, int64_t dv_rs,
+                                            float* d_dist_emb, float* workspace, int B, int nh, int Lq, int Lk, int terms,
+                                            float drop_p, uint32_t site, const uint64_t* row_keys, void* stream) {
+    E3D_REQUIRE(row_keys && drop_p > 0.f, "attn_bwd (keyed): row keys and drop_p > 0 required");
+    E3D_REQUIRE(site < E3D_DROP_MAX_SITE && nh < E3D_DROP_MAX_HEADS, "attn_bwd (keyed): site %u / %d heads out of range", site, nh);
+    return attn_bwd_dispatch(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, dist_emb, P, key_mask, out, lse, dout, dq, dq_bs,
+                             dq_rs, dk, dk_bs, dk_rs, dv, dv_bs, dv_rs, d_dist_emb, workspace, B, nh, Lq, Lk, terms, drop_p,
+                             e3d_drop_make_keyed(drop_p, site, row_keys), stream);
+}
+
 extern "C" int e3d_relkey_attn_bwd(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs,
                                    int64_t k_rs, const float* v, int64_t v_bs, int64_t v_rs, const float* dist_emb, int P,
                                    const float* key_mask, const float* out, const float* lse, const float* dout,
@@ -443,4 +471,16 @@ extern "C" int e3d_relkey_attn_bwd_drop(const float* q, int64_t q_bs, int64_t q_
     return e3d_relkey_attn_bwd_ex(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, dist_emb, P, key_mask, out, lse, dout, dq,
                                   dq_bs, dq_rs, dk, dk_bs, dk_rs, dv, dv_bs, dv_rs, d_dist_emb, workspace, B, nh, Lq, Lk, 0,
                                   drop_p, drop_seed, stream);
+}
+
+extern "C" int e3d_relkey_attn_bwd_drop_keyed(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs,
+                                              int64_t k_rs, const float* v, int64_t v_bs, int64_t v_rs, const float* dist_emb,
+                                              int P, const float* key_mask, const float* out, const float* lse,
+                                              const float* dout, float* dq, int64_t dq_bs, int64_t dq_rs, float* dk,
+                                              int64_t dk_bs, int64_t dk_rs, float* dv, int64_t dv_bs, int64_t dv_rs,
+                                              float* d_dist_emb, float* workspace, int B, int nh, int Lq, int Lk, float drop_p,
+                                              uint32_t site, const uint64_t* row_keys, void* stream) {
+    return e3d_relkey_attn_bwd_ex_keyed(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, dist_emb, P, key_mask, out, lse, dout, dq,
+                                        dq_bs, dq_rs, dk, dk_bs, dk_rs, dv, dv_bs, dv_rs, d_dist_emb, workspace, B, nh, Lq, Lk,
+                                        0, drop_p, site, row_keys, stream);
 }

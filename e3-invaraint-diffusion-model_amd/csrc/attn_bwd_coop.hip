@@ -43,6 +43,7 @@ constexpr int ROWS_F = 3 * MAX_TILES * 32 + 32;    // lse2, delta, key bias (+ 3
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr float S_SCALE = 0.125f * LOG2E;
 constexpr size_t LDS_BYTES = 2 * IMG_B + (ROWS_F + 4 * WAVE_F) * sizeof(float);
+constexpr size_t DROP_ROWS_B = MAX_TILES * 32 * sizeof(uint64_t);   // dropout: + the query rows' hash terms, after everything else
 
 #ifdef BWD_STAMPS   // lab builds only (tools/lab/attn_bwd_stamps.py): s_memrealtime (100 MHz) stamps per workgroup and wave
 __device__ long long bwd_stamps[2][512][4][8];
@@ -248,6 +249,8 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_coop_kernel(
     const int l31 = lane & 31, half = lane >> 5;
     int* q_live = reinterpret_cast<int*>(kbias + MAX_TILES * 32);   // [q tile] != 0: some dO row of the tile is not all zeros
     float* scratch = kbias + MAX_TILES * 32 + 32 + wid * WAVE_F;
+    // dropout: a query row's part of the hash input (e3d_drop_attn_row: its key, when the decisions are keyed), one per row
+    uint64_t* drop_rows = reinterpret_cast<uint64_t*>(smem_raw + LDS_BYTES);
     const int bh = xcd_remap(blockIdx.x, gridDim.x), h = bh % nh, b = bh / nh;
     const int PHASE = blockIdx.y;
     const int q_tiles = (Lq + 31) >> 5, k_tiles = (Lk + 31) >> 5;
@@ -287,9 +290,11 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_coop_kernel(
         }
     }
     float lse_in = 0.f, mask_in = 1.f;
+    uint64_t drop_row_in = 0;
     if (tid < MAX_TILES * 32) {
         if (tid < Lq) lse_in = lse[((int64_t)b * nh + h) * Lq + tid];
         if (tid < Lk && key_mask) mask_in = key_mask[(int64_t)b * Lk + tid];
+        if (DROP) drop_row_in = e3d_drop_attn_row(drop, b, h, nh, Lq, Lk, min(tid, Lq - 1));
     }
     // Dead query tiles (round 4).  A query row whose dO is ALL ZEROS contributes exact zeros to everything this kernel sums
     // (dP = dO V^T = 0, delta = 0, so dS = P (dP - delta) = 0; dV += dO^T P gets 0) and its own dQ row is 0: in training that is
@@ -333,6 +338,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_coop_kernel(
     if (tid < MAX_TILES * 32) {
         lse2[tid] = lse_in * LOG2E;
         kbias[tid] = (tid < Lk && key_mask) ? (1.0f - mask_in) * (-10000.0f * LOG2E) : 0.f;
+        if (DROP) drop_rows[tid] = drop_row_in;
     }
     __syncthreads();
     BSTAMP(2);
@@ -395,7 +401,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_coop_kernel(
                     float mult = 1.0f;
                     if (DROP) {   // one hash per 4 consecutive keys of a query row: this lane's key is element key & 3
                         float m4[4];
-                        e3d_drop_mult4(drop, e3d_attn_drop_idx4(bh, Lq, Lk, min(qg, Lq - 1), min(key, Lk - 1) & ~3), m4);
+                        e3d_drop_mult4_row(drop, drop_rows[qg], (uint32_t)(min(key, Lk - 1) >> 2), m4);   // (qg < 32 MAX_TILES)
                         const int e = key & 3;
                         mult = e == 0 ? m4[0] : (e == 1 ? m4[1] : (e == 2 ? m4[2] : m4[3]));
                     }
@@ -439,6 +445,8 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_coop_kernel(
         load_row_split(qf, qb + (int64_t)min(qrow, Lq - 1) * q_rs, half);
         load_row_split(dof, dob + (int64_t)min(qrow, Lq - 1) * HD, half);
         const float lse_q = lse2[min(qrow, MAX_TILES * 32 - 1)], delta_q = delta[min(qrow, MAX_TILES * 32 - 1)];
+        uint64_t drop_row = 0;
+        if (DROP) drop_row = drop_rows[min(qrow, MAX_TILES * 32 - 1)];
         float* ring = scratch;                     // T^T window: 64 x RB_LD (rows = window offset, cols = query)
         float* X = scratch + 64 * RB_LD;           // dS^T tile: 32 x X_LD
         f32x16 dq0 = zero16(), dq1 = zero16(), elo0 = zero16(), elo1 = zero16(), ehi0 = zero16(), ehi1 = zero16();
@@ -506,7 +514,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_coop_kernel(
             for (int g = 0; g < 4; ++g) {
                 const f32x4 b4 = *reinterpret_cast<const f32x4*>(kbias + r0 + 8 * g + 4 * half);
                 float m4[4] = {1.f, 1.f, 1.f, 1.f};
-                if (DROP) e3d_drop_mult4(drop, e3d_attn_drop_idx4(bh, Lq, Lk, min(qrow, Lq - 1), r0 + 8 * g + 4 * half), m4);
+                if (DROP) e3d_drop_mult4_row(drop, drop_row, (uint32_t)(kt * 8 + 2 * g + half), m4);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int r = 4 * g + j;
@@ -714,8 +722,9 @@ int e3d_attn_bwd_coop_launch(const float* q, int64_t q_bs, int64_t q_rs, const f
     static std::atomic<uint64_t> ok[4];
 #define E3D_BWD_COOP(RK, DR)                                                                                               \
     do {                                                                                                                   \
-        e3d_allow_lds(ok[2 * RK + DR], attn_bwd_coop_kernel<RK, DR>, LDS_BYTES);                                           \
-        hipLaunchKernelGGL((attn_bwd_coop_kernel<RK, DR>), dim3(B * nh, 2), dim3(256), LDS_BYTES, s, q, q_bs, q_rs, k, k_bs, \
+        constexpr size_t lds = LDS_BYTES + (DR ? DROP_ROWS_B : 0);                                                         \
+        e3d_allow_lds(ok[2 * RK + DR], attn_bwd_coop_kernel<RK, DR>, lds);                                                 \
+        hipLaunchKernelGGL((attn_bwd_coop_kernel<RK, DR>), dim3(B * nh, 2), dim3(256), lds, s, q, q_bs, q_rs, k, k_bs,      \
                            k_rs, v, v_bs, v_rs, e_row, e_tr, P, key_mask, dout, out, lse, dq, dq_bs, dq_rs, dk, dk_bs,      \
                            dk_rs, dv, dv_bs, dv_rs, part, unit_live, nh, Lq, Lk, drop);                                    \
     } while (0)

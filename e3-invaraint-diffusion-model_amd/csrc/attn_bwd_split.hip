@@ -135,6 +135,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_split_kernel(
     const int q0 = qt * 32;
     const int lq = min(q0 + qi, Lq - 1);
     const bool q_ok = q0 + qi < Lq;
+    uint64_t drop_row = 0;   // dropout: this query row's part of the hash input (its key, when the decisions are keyed)
+    if (DROP) drop_row = e3d_drop_attn_row(drop, b, h, nh, Lq, Lk, lq);
     const int HD = nh * D;
     Frag qf[4], dof[4];
     load_row_split(qf, q + b * q_bs + (int64_t)lq * q_rs + h * D, half);
@@ -226,7 +228,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_split_kernel(
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 float m[4];
-                e3d_drop_mult4(drop, e3d_attn_drop_idx4(bh, Lq, Lk, q0 + qi, r0 + 8 * g + 4 * half), m);
+                e3d_drop_mult4_row(drop, drop_row, (uint32_t)((r0 >> 2) + 2 * g + half), m);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     ds[4 * g + j] = s[4 * g + j] * (ds[4 * g + j] * m[j] - delta) * 0.125f;

@@ -208,6 +208,8 @@ __global__ __launch_bounds__(W * 64, 2) void attn_coop_kernel(
             qraw[2 * kb + 1] = *reinterpret_cast<const f32x4*>(qrow + 16 * kb + 4);
         }
     }
+    uint64_t drop_row = 0;   // dropout: this query row's part of the hash input (its key, when the decisions are keyed)
+    if (DROP) drop_row = e3d_drop_attn_row(drop, b, h, nh, Lq, Lk, min(q0 + qi, Lq - 1));
     // key-mask values of keys 64 c + lane, c < 4 (Lk <= 256: every configuration of the reference); unconditional
     // loads from a valid address (no branch around a load), longer rows finish with the loop below
     const bool scan_mask = mb && skip_padded_tiles && e3d_mask_skip_is_exact(bnd);   // (block-uniform)
@@ -450,7 +452,7 @@ __global__ __launch_bounds__(W * 64, 2) void attn_coop_kernel(
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 float m[4];
-                e3d_drop_mult4(drop, e3d_attn_drop_idx4(bh, Lq, Lk, min(q0 + qi, Lq - 1), kt * 32 + 8 * g + 4 * half), m);
+                e3d_drop_mult4_row(drop, drop_row, (uint32_t)(kt * 8 + 2 * g + half), m);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) s[4 * g + j] *= m[j];
             }

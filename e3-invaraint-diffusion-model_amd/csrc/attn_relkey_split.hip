@@ -35,6 +35,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_split_kernel(
 
     const int q0 = qt * 32;
     const int lq = min(q0 + qi, Lq - 1);
+    uint64_t drop_row = 0;   // dropout: this query row's part of the hash input (its key, when the decisions are keyed)
+    if (DROP) drop_row = e3d_drop_attn_row(drop, b, h, nh, Lq, Lk, lq);
     bf16x8 qf[4][NS];
     load_row_split<NS>(qf, q + b * q_bs + (int64_t)lq * q_rs + h * D, half);
 
@@ -140,7 +142,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_split_kernel(
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 float m[4];
-                e3d_drop_mult4(drop, e3d_attn_drop_idx4(bh, Lq, Lk, q0 + qi, r0 + 8 * g + 4 * half), m);
+                e3d_drop_mult4_row(drop, drop_row, (uint32_t)((r0 >> 2) + 2 * g + half), m);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) s[4 * g + j] *= m[j];
             }
@@ -211,12 +213,12 @@ extern "C" int e3d_attn_skip_padded_tiles(int enable) {
     return prev;
 }
 
-extern "C" int e3d_relkey_attn_fwd_split_ex(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs,
-                                            int64_t k_rs, const float* v, int64_t v_bs, int64_t v_rs,
-                                            const float* dist_emb, int P, const float* key_mask, float* out,
-                                            float* lse, int B, int nh, int Lq, int Lk, int terms, float drop_p,
-                                            uint64_t drop_seed, void* e_scratch, int e_scratch_ready, const float* q_absmax,
-                                            const float* k_absmax, float* e_absmax, void* stream) {
+// the body of e3d_relkey_attn_fwd_split_ex and of its keyed form: ``d`` = the decisions of drop_p
+static int attn_fwd_dispatch(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs, int64_t k_rs,
+                             const float* v, int64_t v_bs, int64_t v_rs, const float* dist_emb, int P, const float* key_mask,
+                             float* out, float* lse, int B, int nh, int Lq, int Lk, int terms, float drop_p, const E3dDrop d,
+                             void* e_scratch, int e_scratch_ready, const float* q_absmax, const float* k_absmax,
+                             float* e_absmax, void* stream) {
     const E3dBounds bnd{q_absmax, k_absmax, dist_emb ? e_absmax : nullptr};
     E3D_REQUIRE(!dist_emb || !q_absmax || e_absmax, "attn_split: rel-key attention with element bounds needs e_absmax too");
     E3D_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "attn_split: drop_p=%g outside [0, 1)", (double)drop_p);
@@ -248,7 +250,6 @@ extern "C" int e3d_relkey_attn_fwd_split_ex(const float* q, int64_t q_bs, int64_
         coop = e ? atoi(e) : 1;
     }
     const bool dropping = drop_p > 0.f;
-    const E3dDrop d = e3d_drop_make(drop_p, drop_seed);
     // two-wave groups (q_tiles % 4 != 0) measured slower than the per-wave kernel: too little sharing per barrier
     // the cooperative kernel reads the distance table as fragment-order bf16 planes from a CALLER-provided scratch
     // (e3d_attn_scratch_bytes); without one the per-wave kernel below serves the call -- the library never allocates.
@@ -274,6 +275,32 @@ extern "C" int e3d_relkey_attn_fwd_split_ex(const float* q, int64_t q_bs, int64_
     return launch<3>(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, dist_emb, P, key_mask, out, lse, B, nh, Lq, Lk, bnd, s);
 }
 
+extern "C" int e3d_relkey_attn_fwd_split_ex(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs,
+                                            int64_t k_rs, const float* v, int64_t v_bs, int64_t v_rs,
+                                            const float* dist_emb, int P, const float* key_mask, float* out,
+                                            float* lse, int B, int nh, int Lq, int Lk, int terms, float drop_p,
+                                            uint64_t drop_seed, void* e_scratch, int e_scratch_ready, const float* q_absmax,
+                                            const float* k_absmax, float* e_absmax, void* stream) {
+    return attn_fwd_dispatch(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, dist_emb, P, key_mask, out, lse, B, nh, Lq, Lk, terms,
+                             drop_p, e3d_drop_make(drop_p, drop_seed), e_scratch, e_scratch_ready, q_absmax, k_absmax, e_absmax,
+                             stream);
+}
+
+// As e3d_relkey_attn_fwd_split_ex with keyed dropout decisions (drop_p > 0): ``row_keys`` uint64 [B * Lq], the table of the
+// QUERY frame (e3d_keyed_drop_row_keys); ``site`` < 2^24, nh < 2^16
+extern "C" int e3d_relkey_attn_fwd_split_ex_keyed(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs,
+                                                  int64_t k_rs, const float* v, int64_t v_bs, int64_t v_rs,
+                                                  const float* dist_emb, int P, const float* key_mask, float* out,
+                                                  float* lse, int B, int nh, int Lq, int Lk, int terms, float drop_p,
+                                                  uint32_t site, const uint64_t* row_keys, void* e_scratch, int e_scratch_ready,
+                                                  const float* q_absmax, const float* k_absmax, float* e_absmax, void* stream) {
+    E3D_REQUIRE(row_keys && drop_p > 0.f, "attn_split (keyed): row keys and drop_p > 0 required");
+    E3D_REQUIRE(site < E3D_DROP_MAX_SITE && nh < E3D_DROP_MAX_HEADS, "attn_split (keyed): site %u / %d heads out of range", site, nh);
+    return attn_fwd_dispatch(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, dist_emb, P, key_mask, out, lse, B, nh, Lq, Lk, terms,
+                             drop_p, e3d_drop_make_keyed(drop_p, site, row_keys), e_scratch, e_scratch_ready, q_absmax, k_absmax,
+                             e_absmax, stream);
+}
+
 extern "C" int e3d_relkey_attn_fwd_split(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs,
                                          int64_t k_rs, const float* v, int64_t v_bs, int64_t v_rs,
                                          const float* dist_emb, int P, const float* key_mask, float* out, float* lse,
@@ -289,4 +316,14 @@ extern "C" int e3d_relkey_attn_fwd_split_drop(const float* q, int64_t q_bs, int6
                                               uint64_t drop_seed, void* stream) {
     return e3d_relkey_attn_fwd_split_ex(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, dist_emb, P, key_mask, out, lse, B,
                                         nh, Lq, Lk, terms, drop_p, drop_seed, nullptr, 0, nullptr, nullptr, nullptr, stream);
+}
+
+extern "C" int e3d_relkey_attn_fwd_split_drop_keyed(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs,
+                                                    int64_t k_rs, const float* v, int64_t v_bs, int64_t v_rs,
+                                                    const float* dist_emb, int P, const float* key_mask, float* out,
+                                                    float* lse, int B, int nh, int Lq, int Lk, int terms, float drop_p,
+                                                    uint32_t site, const uint64_t* row_keys, void* stream) {
+    return e3d_relkey_attn_fwd_split_ex_keyed(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, dist_emb, P, key_mask, out, lse, B,
+                                              nh, Lq, Lk, terms, drop_p, site, row_keys, nullptr, 0, nullptr, nullptr, nullptr,
+                                              stream);
 }

@@ -187,6 +187,12 @@ struct E3dDrop {
     uint32_t thr;
     float scale;
     const uint64_t* epoch;   // device word added to the seed inside the kernel (may be null): see e3d_dropout_set_epoch_ptr
+    // Keyed decisions ("Keyed sampling streams"; e3d_keyed_drop_row_keys): one 64-bit key per frame row, the
+    // Philox words of (seed, item id, stream 8 / 9, epoch, position).  When set, a row's key takes the place of ``seed``,
+    // the group index is site << 40 | head << 24 | (column or key position) >> 2 -- nothing of the frame or the batch --
+    // and no epoch word is added.  Null: the decisions of (seed, element index) above, bit for bit.
+    const uint64_t* row_keys;
+    uint64_t site;           // keyed: site << 40, the ordinal of the dropout call within the step
 };
 // The word registered for the calling thread's current device (capi.hip), or null.  A captured HIP graph bakes the
 // ``seed`` argument of every dropout launch; a training step replayed from a graph advances this word instead, so every
@@ -200,12 +206,46 @@ static inline E3dDrop e3d_drop_make(float p, uint64_t seed) {
     d.epoch = e3d_dropout_epoch_ptr();
     d.thr = (uint32_t)t;
     d.scale = 65536.0f / (float)(65536 - t);
+    d.row_keys = nullptr;
+    d.site = 0;
+    return d;
+}
+#define E3D_DROP_MAX_SITE (1u << 24)
+#define E3D_DROP_MAX_HEADS (1 << 16)
+static inline E3dDrop e3d_drop_make_keyed(float p, uint32_t site, const uint64_t* row_keys) {   // site < E3D_DROP_MAX_SITE
+    E3dDrop d = e3d_drop_make(p, 0);
+    d.epoch = nullptr;
+    d.row_keys = row_keys;
+    d.site = (uint64_t)site << 40;
     return d;
 }
 __device__ __forceinline__ E3dDrop e3d_drop_resolve(E3dDrop d) {   // once, at kernel entry
     if (d.epoch) d.seed += *d.epoch * 0xD1342543DE82EF95ull;
     d.epoch = nullptr;
     return d;
+}
+// The hash input of a group is (row term) + (group within the row): the row term -- e3d_drop_hidden_row /
+// e3d_drop_attn_row, everything that does not change along a row, the row's key included -- is formed once per row,
+// outside the column / key sweep, and the sweep adds the group (e3d_drop_mult4_row).
+__device__ __forceinline__ void e3d_drop_mult4_row(const E3dDrop d, uint64_t row_term, uint32_t group, float (&m)[4]) {
+    uint64_t z = row_term + group;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) m[j] = ((uint32_t)(z >> (16 * j)) & 0xFFFFu) >= d.thr ? d.scale : 0.f;
+}
+// row ``row`` of an [M, H] hidden-state tensor, H4 = H / 4 groups per row; group = column >> 2
+__device__ __forceinline__ uint64_t e3d_drop_hidden_row(const E3dDrop d, int64_t row, int H4) {
+    if (d.row_keys) return d.row_keys[row] * 0x9E3779B97F4A7C15ull + 0x9E3779B97F4A7C15ull + d.site;
+    return (uint64_t)row * (uint64_t)H4 + d.seed * 0x9E3779B97F4A7C15ull + 0x9E3779B97F4A7C15ull;
+}
+// query row q < Lq of P[b, h, q, key]; group = key position >> 2.  Keyed: the key of the QUERY's frame row b * Lq + q.
+__device__ __forceinline__ uint64_t e3d_drop_attn_row(const E3dDrop d, int b, int h, int nh, int Lq, int Lk, int q) {
+    if (d.row_keys)
+        return d.row_keys[(int64_t)b * Lq + q] * 0x9E3779B97F4A7C15ull + 0x9E3779B97F4A7C15ull + (d.site | (uint64_t)h << 24);
+    return ((uint64_t)(b * nh + h) * Lq + q) * (uint64_t)((Lk + 3) >> 2) + d.seed * 0x9E3779B97F4A7C15ull +
+           0x9E3779B97F4A7C15ull;
 }
 __device__ __forceinline__ void e3d_drop_mult4(const E3dDrop d, uint64_t idx4, float (&m)[4]) {
     uint64_t z = idx4 + d.seed * 0x9E3779B97F4A7C15ull + 0x9E3779B97F4A7C15ull;
@@ -214,10 +254,6 @@ __device__ __forceinline__ void e3d_drop_mult4(const E3dDrop d, uint64_t idx4, f
     z ^= z >> 31;
 #pragma unroll
     for (int j = 0; j < 4; ++j) m[j] = ((uint32_t)(z >> (16 * j)) & 0xFFFFu) >= d.thr ? d.scale : 0.f;
-}
-// attention probabilities P[b, h, q, key]: group index of keys key0 .. key0+3 (key0 % 4 == 0)
-__device__ __forceinline__ uint64_t e3d_attn_drop_idx4(int bh, int Lq, int Lk, int q, int key0) {
-    return ((uint64_t)bh * Lq + q) * (uint64_t)((Lk + 3) >> 2) + (uint64_t)(key0 >> 2);
 }
 
 int e3d_attn_fill_planes(const float* dist_emb, int P, int Lk, void* scratch, int f16, float* e_absmax, hipStream_t s);

@@ -18,6 +18,10 @@
 #define E3D_STREAM_TRAIN_SEQ_T 6         // sequence training timestep, class of T + 1
 #define E3D_STREAM_TRAIN_SEQ_U 7         // sequence forward-noising uniform
 #define E3D_EPOCH_VALIDATION 65535
+// dropout decisions of a seeded training step: a row's key = words 0, 1 of (seed, item, stream, epoch, position, block 0).
+// Streams 8 and 9 yield keys, not draws: E3D_STREAM_* above stays the list of the streams that draws are mapped from.
+#define E3D_DROP_STREAM_LIGAND 8         // dropout on ligand rows (attention rows: the query's)
+#define E3D_DROP_STREAM_POCKET 9         // dropout on pocket (receptor) rows
 
 struct E3dU32x4 { uint32_t w[4]; };
 

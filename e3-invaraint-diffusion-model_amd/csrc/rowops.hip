@@ -42,7 +42,9 @@ __device__ __forceinline__ void row_normalize(f32x4 (&r)[V], float eps) {
 // DROP: x is the output of a dense layer that nn.Dropout follows (BertSelfOutput / BertOutput in training mode): the
 // multipliers of e3d_dropout_f32 for the same (p, seed) -- element index = row * H + column -- are applied as x is read,
 // instead of by a pass of their own over the [M, H] tensor
-template <int V, bool DROP = false>
+// KEYED (with DROP): the decisions take the row's key from drop.row_keys (e3d_common.h) -- an instantiation of its own, so
+// that the unkeyed one keeps the code it had
+template <int V, bool DROP = false, bool KEYED = false>
 __global__ __launch_bounds__(256) void residual_layernorm_kernel(
     const float* __restrict__ x, const float* __restrict__ res, const float* __restrict__ gamma,
     const float* __restrict__ beta, float eps, float* __restrict__ s_out, float* __restrict__ out, int M, E3dDrop drop_in = E3dDrop{}) {
@@ -54,10 +56,12 @@ __global__ __launch_bounds__(256) void residual_layernorm_kernel(
     row_load<V>(r, x + (int64_t)row * H, lane);
     if (DROP) {
         const E3dDrop drop = e3d_drop_resolve(drop_in);
+        const uint64_t key_term = KEYED ? e3d_drop_hidden_row(drop, row, H / 4) : 0;
 #pragma unroll
         for (int i = 0; i < V; ++i) {
             float m[4];
-            e3d_drop_mult4(drop, (uint64_t)row * (H / 4) + 64 * i + lane, m);
+            if (KEYED) e3d_drop_mult4_row(drop, key_term, 64 * i + lane, m);
+            else e3d_drop_mult4(drop, (uint64_t)row * (H / 4) + 64 * i + lane, m);
 #pragma unroll
             for (int j = 0; j < 4; ++j) r[i][j] *= m[j];
         }
@@ -274,6 +278,20 @@ extern "C" int e3d_residual_layernorm_drop_fwd(const float* x, const float* resi
     DISPATCH_V(H, hipLaunchKernelGGL((residual_layernorm_kernel<V, true>), grid, block, 0, (hipStream_t)stream, x, residual, gamma,
                                      beta, eps, s_out, out, M, d));
     return e3d_launch_status("e3d_residual_layernorm_drop_fwd");
+}
+
+// As e3d_residual_layernorm_drop_fwd with keyed decisions: ``row_keys`` uint64 [M] (e3d_keyed_drop_row_keys), ``site`` < 2^24
+extern "C" int e3d_residual_layernorm_drop_fwd_keyed(const float* x, const float* residual, const float* gamma, const float* beta,
+                                                     float eps, float* s_out, float* out, int M, int H, float drop_p, uint32_t site,
+                                                     const uint64_t* row_keys, void* stream) {
+    E3D_REQUIRE(x && gamma && beta && out && row_keys && M > 0, "residual_layernorm_drop_keyed: bad arguments");
+    E3D_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "residual_layernorm_drop_keyed: p = %f", (double)drop_p);
+    E3D_REQUIRE(site < E3D_DROP_MAX_SITE, "residual_layernorm_drop_keyed: site %u does not fit 24 bits", site);
+    const dim3 grid((M + 3) / 4), block(256);
+    const E3dDrop d = e3d_drop_make_keyed(drop_p, site, row_keys);
+    DISPATCH_V(H, hipLaunchKernelGGL((residual_layernorm_kernel<V, true, true>), grid, block, 0, (hipStream_t)stream, x, residual,
+                                     gamma, beta, eps, s_out, out, M, d));
+    return e3d_launch_status("e3d_residual_layernorm_drop_fwd_keyed");
 }
 
 extern "C" int e3d_adaln_gate_fwd(const float* x, const float* y, const float* mod, int branch,

@@ -70,7 +70,9 @@ __device__ __forceinline__ void ln_input_grad(f32x4 (&g)[V], const f32x4 (&xhat)
 // summed over the block in LDS and added once per block (float atomics: order-dependent last bits).
 // DROP: the LayerNorm's first input was dropout(x) (e3d_residual_layernorm_drop_fwd): besides ds (the gradient of the
 // pre-norm sum = of the residual) the kernel writes ds * multipliers (the gradient of x) to ``dsd``
-template <int V, bool DROP = false>
+// KEYED (with DROP): the decisions take the row's key from drop.row_keys (e3d_common.h) -- an instantiation of its own, so
+// that the unkeyed one keeps the code it had
+template <int V, bool DROP = false, bool KEYED = false>
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restrict__ dy,
                                                             const float* __restrict__ s,
                                                             const float* __restrict__ gamma, float eps,
@@ -82,10 +84,12 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
     const E3dDrop drop = DROP ? e3d_drop_resolve(drop_in) : drop_in;
     auto store_dropped = [&](const f32x4 (&g)[V], int row) {
         f32x4 d[V];
+        const uint64_t key_term = KEYED ? e3d_drop_hidden_row(drop, row, H / 4) : 0;
 #pragma unroll
         for (int i = 0; i < V; ++i) {
             float m[4];
-            e3d_drop_mult4(drop, (uint64_t)row * (H / 4) + 64 * i + lane, m);
+            if (KEYED) e3d_drop_mult4_row(drop, key_term, 64 * i + lane, m);
+            else e3d_drop_mult4(drop, (uint64_t)row * (H / 4) + 64 * i + lane, m);
 #pragma unroll
             for (int j = 0; j < 4; ++j) d[i][j] = g[i][j] * m[j];
         }
@@ -557,9 +561,9 @@ extern "C" int64_t e3d_layernorm_bwd_workspace_floats(int M, int H) { return (M 
 
 // As e3d_layernorm_bwd / e3d_layernorm_bwd_drop (ds_dropped == NULL: no dropout), with the parameter gradients summed through
 // ``workspace`` (e3d_layernorm_bwd_workspace_floats(M, H) floats) instead of atomics on a zeroed output: deterministic.
-extern "C" int e3d_layernorm_bwd_ws(const float* dy, const float* s, const float* gamma, float eps, float* ds, float* ds_dropped,
-                                    float* dgamma, float* dbeta, int M, int H, float drop_p, uint64_t drop_seed, float* workspace,
-                                    int64_t workspace_floats, void* stream) {
+static int layernorm_bwd_ws_launch(const float* dy, const float* s, const float* gamma, float eps, float* ds, float* ds_dropped,
+                                   float* dgamma, float* dbeta, int M, int H, float drop_p, E3dDrop d, float* workspace,
+                                   int64_t workspace_floats, void* stream) {
     E3D_REQUIRE(dy && s && ds && M > 0, "layernorm_bwd_ws: bad arguments");
     E3D_REQUIRE(drop_p >= 0.f && drop_p < 1.f && (ds_dropped || drop_p == 0.f), "layernorm_bwd_ws: p = %f", (double)drop_p);
     const bool affine = dgamma || dbeta;
@@ -568,8 +572,10 @@ extern "C" int e3d_layernorm_bwd_ws(const float* dy, const float* s, const float
                 "layernorm_bwd_ws: workspace of %lld floats, %lld needed", (long long)workspace_floats, (long long)blocks * 2 * H);
     float* part = affine ? workspace : nullptr;
     hipStream_t st = (hipStream_t)stream;
-    if (ds_dropped) {
-        const E3dDrop d = e3d_drop_make(drop_p, drop_seed);
+    if (ds_dropped && d.row_keys) {
+        DISPATCH_V(H, hipLaunchKernelGGL((layernorm_bwd_kernel<V, true, true>), dim3(blocks), dim3(256), 0, st, dy, s, gamma, eps,
+                                         ds, dgamma, dbeta, M, ds_dropped, d, part));
+    } else if (ds_dropped) {
         DISPATCH_V(H, hipLaunchKernelGGL((layernorm_bwd_kernel<V, true>), dim3(blocks), dim3(256), 0, st, dy, s, gamma, eps, ds,
                                          dgamma, dbeta, M, ds_dropped, d, part));
     } else {
@@ -581,8 +587,25 @@ extern "C" int e3d_layernorm_bwd_ws(const float* dy, const float* s, const float
     return e3d_launch_status("e3d_layernorm_bwd_ws");
 }
 
-extern "C" int e3d_layernorm_bwd_drop(const float* dy, const float* s, const float* gamma, float eps, float* ds, float* ds_dropped,
-                                      float* dgamma, float* dbeta, int M, int H, float drop_p, uint64_t drop_seed, void* stream) {
+extern "C" int e3d_layernorm_bwd_ws(const float* dy, const float* s, const float* gamma, float eps, float* ds, float* ds_dropped,
+                                    float* dgamma, float* dbeta, int M, int H, float drop_p, uint64_t drop_seed, float* workspace,
+                                    int64_t workspace_floats, void* stream) {
+    return layernorm_bwd_ws_launch(dy, s, gamma, eps, ds, ds_dropped, dgamma, dbeta, M, H, drop_p, e3d_drop_make(drop_p, drop_seed),
+                                   workspace, workspace_floats, stream);
+}
+
+// As e3d_layernorm_bwd_ws with the keyed decisions of e3d_residual_layernorm_drop_fwd_keyed (ds_dropped required)
+extern "C" int e3d_layernorm_bwd_ws_keyed(const float* dy, const float* s, const float* gamma, float eps, float* ds,
+                                          float* ds_dropped, float* dgamma, float* dbeta, int M, int H, float drop_p, uint32_t site,
+                                          const uint64_t* row_keys, float* workspace, int64_t workspace_floats, void* stream) {
+    E3D_REQUIRE(ds_dropped && row_keys, "layernorm_bwd_ws_keyed: bad arguments");
+    E3D_REQUIRE(site < E3D_DROP_MAX_SITE, "layernorm_bwd_ws_keyed: site %u does not fit 24 bits", site);
+    return layernorm_bwd_ws_launch(dy, s, gamma, eps, ds, ds_dropped, dgamma, dbeta, M, H, drop_p,
+                                   e3d_drop_make_keyed(drop_p, site, row_keys), workspace, workspace_floats, stream);
+}
+
+static int layernorm_bwd_drop_launch(const float* dy, const float* s, const float* gamma, float eps, float* ds, float* ds_dropped,
+                                     float* dgamma, float* dbeta, int M, int H, float drop_p, const E3dDrop d, void* stream) {
     E3D_REQUIRE(dy && s && ds && ds_dropped && M > 0, "layernorm_bwd_drop: bad arguments");
     E3D_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "layernorm_bwd_drop: p = %f", (double)drop_p);
     hipError_t e = hipSuccess;
@@ -594,10 +617,28 @@ extern "C" int e3d_layernorm_bwd_drop(const float* dy, const float* s, const flo
     }
     E3D_REQUIRE(e == hipSuccess, "layernorm_bwd_drop: zero-fill failed: %s", hipGetErrorString(e));
     const int blocks = (M + 15) / 16 < 512 ? (M + 15) / 16 : 512;
-    const E3dDrop d = e3d_drop_make(drop_p, drop_seed);
-    DISPATCH_V(H, hipLaunchKernelGGL((layernorm_bwd_kernel<V, true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, dy, s, gamma,
-                                     eps, ds, dgamma, dbeta, M, ds_dropped, d));
+    if (d.row_keys) {
+        DISPATCH_V(H, hipLaunchKernelGGL((layernorm_bwd_kernel<V, true, true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, dy, s,
+                                         gamma, eps, ds, dgamma, dbeta, M, ds_dropped, d));
+    } else {
+        DISPATCH_V(H, hipLaunchKernelGGL((layernorm_bwd_kernel<V, true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, dy, s, gamma,
+                                         eps, ds, dgamma, dbeta, M, ds_dropped, d));
+    }
     return e3d_launch_status("e3d_layernorm_bwd_drop");
+}
+
+extern "C" int e3d_layernorm_bwd_drop(const float* dy, const float* s, const float* gamma, float eps, float* ds, float* ds_dropped,
+                                      float* dgamma, float* dbeta, int M, int H, float drop_p, uint64_t drop_seed, void* stream) {
+    return layernorm_bwd_drop_launch(dy, s, gamma, eps, ds, ds_dropped, dgamma, dbeta, M, H, drop_p, e3d_drop_make(drop_p, drop_seed),
+                                     stream);
+}
+
+extern "C" int e3d_layernorm_bwd_drop_keyed(const float* dy, const float* s, const float* gamma, float eps, float* ds,
+                                            float* ds_dropped, float* dgamma, float* dbeta, int M, int H, float drop_p, uint32_t site,
+                                            const uint64_t* row_keys, void* stream) {
+    E3D_REQUIRE(row_keys && site < E3D_DROP_MAX_SITE, "layernorm_bwd_drop_keyed: row keys and a site below 2^24 required");
+    return layernorm_bwd_drop_launch(dy, s, gamma, eps, ds, ds_dropped, dgamma, dbeta, M, H, drop_p,
+                                     e3d_drop_make_keyed(drop_p, site, row_keys), stream);
 }
 
 extern "C" int e3d_adaln_gate_bwd(const float* dout, const float* y, const float* mod, int branch,

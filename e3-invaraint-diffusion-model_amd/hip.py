@@ -6,7 +6,7 @@ The library is the product's only compute path: there is no CPU or eager-PyTorch
 """
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_int64, c_uint64, c_void_p
+from ctypes import c_char_p, c_float, c_int, c_int64, c_uint32, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("E3D_HIP_LIB", os.path.join(_HERE, "libe3d_hip.so"))   # override: kernel experiments
@@ -107,6 +107,26 @@ _SIGNATURES = {
     "e3d_keyed_timesteps": (c_int, [_P, _P, c_uint64, c_int, c_int, _P, c_int, _P]),
     "e3d_keyed_q_sample_wrap": (c_int, [_P, _P, _P, _P, c_int, c_float, _P, _P, c_uint64, _P, _P, c_int, c_int, c_int, _P]),
     "e3d_keyed_discrete_q_sample": (c_int, [_P, _P, _P, _P, c_uint64, _P, c_int, c_int, c_int, _P]),
+    # keyed dropout decisions: (drop_p, site, row_keys) in the place of (drop_p, drop_seed)
+    "e3d_keyed_drop_row_keys": (c_int, [_P, c_int, c_int, _P, c_uint64, c_int, _P, _P]),
+    "e3d_dropout_f32_keyed": (c_int, [_P, c_float, c_uint32, _P, _P, c_int, c_int, _P]),
+    "e3d_keyed_attn_dropout_mask": (c_int, [c_int, c_int, c_int, c_int, c_float, c_uint32, _P, _P, _P]),
+    "e3d_residual_layernorm_drop_fwd_keyed": (c_int, [_P, _P, _P, _P, c_float, _P, _P, c_int, c_int, c_float, c_uint32, _P, _P]),
+    "e3d_layernorm_bwd_drop_keyed": (c_int, [_P, _P, _P, c_float, _P, _P, _P, _P, c_int, c_int, c_float, c_uint32, _P, _P]),
+    "e3d_layernorm_bwd_ws_keyed": (c_int, [_P, _P, _P, c_float, _P, _P, _P, _P, c_int, c_int, c_float, c_uint32, _P, _P, c_int64,
+                                           _P]),
+    "e3d_relkey_attn_fwd_split_drop_keyed": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int64, c_int64,
+                                                     _P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float,
+                                                     c_uint32, _P, _P]),
+    "e3d_relkey_attn_fwd_split_ex_keyed": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int64, c_int64,
+                                                   _P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float,
+                                                   c_uint32, _P, _P, c_int, _P, _P, _P, _P]),
+    "e3d_relkey_attn_bwd_drop_keyed": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int, _P,
+                                               _P, _P, _P, _P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int64, c_int64,
+                                               _P, _P, c_int, c_int, c_int, c_int, c_float, c_uint32, _P, _P]),
+    "e3d_relkey_attn_bwd_ex_keyed": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int, _P,
+                                             _P, _P, _P, _P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int64, c_int64,
+                                             _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, c_uint32, _P, _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

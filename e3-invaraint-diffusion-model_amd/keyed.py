@@ -10,6 +10,8 @@ the same keys in all three, so an item gets the same draws whatever its batch, o
 Training and validation draws (streams 4-7, ``training.fit(seed=)``) put the epoch in the step field -- VALIDATION_EPOCH for
 validation -- and need no key table: their frames are padded or trimmed, so the kernels take the batch's item ids and the
 epoch from device memory (``epoch_word``), where a captured training step finds the current ones at every replay.
+Dropout decisions of a seeded step (streams 8 / 9) are keyed the same way: one 64-bit key per frame row, built inside the
+step from the ids and the epoch word (``ops.keyed_drop_row_keys``), seeds the generator of that row's decisions.
 
 Item ids are the caller's (the module entry points use the global dataset index).  Two items with the same id and seed
 get the same draws: replicate samples of one pocket take one seed per replicate, or ids that encode (pocket, replicate).
@@ -26,6 +28,9 @@ STRUCT_XT, STRUCT_STEP, SEQ_XT, SEQ_U = 0, 1, 2, 3
 TRAIN_STRUCT_T, TRAIN_STRUCT_NOISE, TRAIN_SEQ_T, TRAIN_SEQ_U = 4, 5, 6, 7
 VALIDATION_EPOCH = 65535
 MAX_EPOCH = VALIDATION_EPOCH - 1
+# dropout decisions of a seeded training step: a frame row's 64-bit key is w0 | w1 << 32 of (seed, item id, stream, epoch,
+# position, block 0); an item's ligand position l and pocket position l must not share decisions, hence two streams
+DROP_LIGAND, DROP_POCKET = 8, 9
 
 
 def check_seed(seed):

@@ -1,5 +1,6 @@
 """Tensor-level wrappers over the C-ABI: allocate outputs with torch (device memory + stream
 plumbing only) and enqueue the HIP kernels on torch's current stream."""
+import contextlib
 import math
 import os
 import warnings
@@ -362,19 +363,128 @@ def dropout_epoch(device):
     return t
 
 
+MAX_DROPOUT_SITES = 1 << 24     # group index = site << 40 | head << 24 | group (include/e3d_hip.h)
+MAX_DROPOUT_HEADS = 1 << 16
+
+
+class KeyedDropout:
+    """The keyed dropout decisions of ONE seeded training step ("Keyed sampling streams"): the seed, the epoch
+    word and the batch's item ids (both in device memory, where a captured step finds the current ones at every replay),
+    the row-key tables built from them -- one launch per (stream, frame length), inside the step -- and the site counter:
+    the ordinal of the dropout call within the step, which starts at 0 for every step and is the same on every frame,
+    because the model makes the same calls in the same order."""
+
+    def __init__(self, seed, epoch_word, ids):
+        self.seed, self.epoch, self.ids = keyed.check_seed(seed), epoch_word, ids
+        self.site = 0
+        self._tables = {}
+
+    def next_site(self):
+        site = self.site
+        if site >= MAX_DROPOUT_SITES:
+            raise ValueError(f"keyed dropout holds {MAX_DROPOUT_SITES} sites per step")
+        self.site = site + 1
+        return site
+
+    def row_keys(self, stream, L):
+        """uint64 keys of the rows of this batch's [B, L] frame on ``stream`` (keyed.DROP_LIGAND / DROP_POCKET), as int64."""
+        t = self._tables.get((stream, L))
+        if t is None:
+            t = self._tables[(stream, L)] = keyed_drop_row_keys(self.ids, L, self.epoch, self.seed, stream)
+        return t
+
+
+_KEYED_DROPOUT = None
+
+
+def keyed_dropout_state():
+    """The ``KeyedDropout`` of the step being built, or None (torch-seeded dropout)."""
+    return _KEYED_DROPOUT
+
+
+@contextlib.contextmanager
+def keyed_dropout(seed, epoch_word, ids):
+    """Inside: dropout sites take keyed decisions -- ``next_dropout_seed`` hands out site ordinals (from 0) and makes no
+    torch generator call; every site must be given the key table of its rows."""
+    global _KEYED_DROPOUT
+    prev, _KEYED_DROPOUT = _KEYED_DROPOUT, KeyedDropout(seed, epoch_word, ids)
+    try:
+        yield _KEYED_DROPOUT
+    finally:
+        _KEYED_DROPOUT = prev
+
+
 def next_dropout_seed():
     """A fresh 63-bit seed for one dropout site call, drawn from torch's global CPU generator
-    (so ``torch.manual_seed`` makes training runs repeatable)."""
+    (so ``torch.manual_seed`` makes training runs repeatable).  Inside ``keyed_dropout``: the site's ordinal."""
+    if _KEYED_DROPOUT is not None:
+        return _KEYED_DROPOUT.next_site()
     return int(torch.randint(0, 2 ** 62, (), dtype=torch.int64))
 
 
-def dropout(x, p, seed, out=None):
+def site_drop(p, row_keys=None):
+    """The ``drop`` value of one dropout site call: (p, seed) from torch's generator, or -- inside ``keyed_dropout`` --
+    (p, site, row_keys) with the key table of the rows the site works on (attention: the query rows)."""
+    if _KEYED_DROPOUT is None:
+        if row_keys is not None:
+            raise RuntimeError("row keys given to a dropout site outside ops.keyed_dropout")
+        return float(p), next_dropout_seed()
+    if row_keys is None:
+        raise RuntimeError("a dropout site inside ops.keyed_dropout needs the key table of its rows")
+    return float(p), next_dropout_seed(), row_keys
+
+
+def _keyed_drop(drop, rows, what, heads=1):
+    """(p, site, row-key pointer) of a keyed ``drop`` = (p, site, row_keys), checked against the site's rows."""
+    p, site, row_keys = drop
+    if not 0 <= int(site) < MAX_DROPOUT_SITES:
+        raise ValueError(f"{what}: dropout site {site} outside [0, 2^24)")
+    if heads >= MAX_DROPOUT_HEADS:
+        raise ValueError(f"{what}: keyed dropout holds fewer than 2^16 heads, got {heads}")
+    if row_keys.dtype != torch.int64 or not row_keys.is_cuda or not row_keys.is_contiguous() or row_keys.numel() != rows:
+        raise ValueError(f"{what}: row keys must be a contiguous int64 device tensor of {rows} keys")
+    return float(p), int(site), _p(row_keys)
+
+
+def keyed_drop_row_keys(ids, L, epoch_word, seed, stream):
+    """Row keys of a [B, L] frame for keyed dropout: key[b * L + l] = w0 | w1 << 32 of the Philox words of
+    (seed, ids[b], stream, epoch, l) -- int64 [B * L] holding the uint64 bits.  ``ids`` int64 [B] and ``epoch_word`` are
+    read on the device."""
+    if stream not in (keyed.DROP_LIGAND, keyed.DROP_POCKET):
+        raise ValueError(f"dropout row keys live on streams {keyed.DROP_LIGAND} / {keyed.DROP_POCKET}, got {stream}")
+    if L > keyed.MAX_POSITION:
+        raise ValueError(f"keyed streams hold positions below 2^24, got a frame of {L}")
+    B = ids.numel()
+    assert ids.dtype == torch.int64 and ids.is_cuda and ids.is_contiguous() and epoch_word.dtype == torch.int64 and epoch_word.is_cuda
+    out = torch.empty((B * L,), device=ids.device, dtype=torch.int64)
+    hip.check(hip.lib().e3d_keyed_drop_row_keys(_p(ids), B, L, _p(epoch_word), keyed.check_seed(seed), int(stream), _p(out),
+                                                _stream()), "e3d_keyed_drop_row_keys")
+    return out
+
+
+def dropout(x, p, seed, out=None, row_keys=None):
     """out = x * keep / (1 - p'): the counter-based dropout of include/e3d_hip.h.  The backward pass is the
-    same call on the gradient with the same (p, seed)."""
+    same call on the gradient with the same (p, seed).  ``row_keys`` (keyed decisions): x is [rows, H] with one key per
+    row and ``seed`` is the site."""
     _chk(x, "dropout.x")
     assert x.is_contiguous()
     out = torch.empty_like(x) if out is None else out
+    if row_keys is not None:
+        H = x.shape[-1]
+        M = x.numel() // H
+        p, site, keys = _keyed_drop((p, seed, row_keys), M, "dropout")
+        hip.check(hip.lib().e3d_dropout_f32_keyed(_p(x), p, site, keys, _p(out), M, H, _stream()), "e3d_dropout_f32_keyed")
+        return out
     hip.check(hip.lib().e3d_dropout_f32(_p(x), float(p), int(seed), _p(out), x.numel(), _stream()), "e3d_dropout_f32")
+    return out
+
+
+def keyed_attn_dropout_mask(B, nh, Lq, Lk, p, site, row_keys):
+    """Test aid: multipliers applied to the attention probabilities by ``attention(..., drop=(p, site, row_keys))``."""
+    out = torch.empty((B, nh, Lq, Lk), device=row_keys.device, dtype=torch.float32)
+    p, site, keys = _keyed_drop((p, site, row_keys), B * Lq, "keyed_attn_dropout_mask", nh)
+    hip.check(hip.lib().e3d_keyed_attn_dropout_mask(B, nh, Lq, Lk, p, site, keys, _p(out), _stream()),
+              "e3d_keyed_attn_dropout_mask")
     return out
 
 
@@ -390,7 +500,8 @@ def attention(q, k, v, B, nh, Lq, Lk, key_mask=None, dist_emb=None, max_pos=0, w
               bounds=None):
     """q [B*Lq, >=nh*64] / k, v [B*Lk, ...] row-strided 2-D views (e.g. slices of a fused QKV
     buffer).  Returns ctx [B*Lq, nh*64] (and lse [B,nh,Lq]).  ``drop`` = (p, seed): dropout on the
-    normalised probabilities (training); the exact-fp32 mode then runs its fp32-grade bf16x6 twin.
+    normalised probabilities (training); the exact-fp32 mode then runs its fp32-grade bf16x6 twin.  ``drop`` =
+    (p, site, row_keys): keyed decisions, row_keys the table of the [B, Lq] query frame.
     ``bounds`` = (q_absmax, k_absmax): 1-element device tensors bounding |element| of the Q rows and of ALL K rows
     (``gemm(..., absmax=)``); with them the split kernels skip all-padding key tiles when that is provably exact,
     without them every call sweeps all keys."""
@@ -450,6 +561,12 @@ def attention(q, k, v, B, nh, Lq, Lk, key_mask=None, dist_emb=None, max_pos=0, w
             p, seed = (float(drop[0]), int(drop[1])) if dropping else (0.0, 0)
             if q_abs is None or k_abs is None or (dist_emb is not None and e_abs is None):
                 q_abs = k_abs = e_abs = None
+            if dropping and len(drop) == 3:
+                p, site, keys = _keyed_drop(drop, B * Lq, "attention", nh)
+                hip.check(hip.lib().e3d_relkey_attn_fwd_split_ex_keyed(*args, terms or 6, p, site, keys, _p(scratch), ready,
+                                                                       _p(q_abs), _p(k_abs), _p(e_abs), _stream()),
+                          "e3d_relkey_attn_fwd_split_ex_keyed")
+                return (out, lse) if want_lse else out
             hip.check(hip.lib().e3d_relkey_attn_fwd_split_ex(*args, terms or 6, p, seed, _p(scratch), ready, _p(q_abs),
                                                              _p(k_abs), _p(e_abs), _stream()),
                       "e3d_relkey_attn_fwd_split_ex")
@@ -495,7 +612,7 @@ def attention_varlen(q, k, v, q_layout, k_layout, nh, dist_emb=None, max_pos=0, 
 
 def residual_layernorm(x, residual, gamma, beta, eps, want_s=False, drop=None):
     """LayerNorm(x + residual); ``drop`` = (p, seed): LayerNorm(dropout(x) + residual) with the multipliers of
-    ``dropout(x, p, seed)`` applied inside the kernel."""
+    ``dropout(x, p, seed)`` applied inside the kernel; (p, site, row_keys): keyed decisions, one key per row of x."""
     for n, t in (("x", x), ("residual", residual), ("gamma", gamma), ("beta", beta)):
         _chk(t, "residual_layernorm." + n)
     assert x.is_contiguous() and (residual is None or residual.is_contiguous())
@@ -503,7 +620,12 @@ def residual_layernorm(x, residual, gamma, beta, eps, want_s=False, drop=None):
     out = torch.empty_like(x)
     s = torch.empty_like(x) if want_s else None
     with _timed("residual_layernorm", (M, H)):
-        if drop is not None and drop[0] > 0:
+        if drop is not None and drop[0] > 0 and len(drop) == 3:
+            p, site, keys = _keyed_drop(drop, M, "residual_layernorm")
+            hip.check(hip.lib().e3d_residual_layernorm_drop_fwd_keyed(_p(x), _p(residual), _p(gamma), _p(beta), eps, _p(s), _p(out),
+                                                                      M, H, p, site, keys, _stream()),
+                      "e3d_residual_layernorm_drop_fwd_keyed")
+        elif drop is not None and drop[0] > 0:
             hip.check(hip.lib().e3d_residual_layernorm_drop_fwd(_p(x), _p(residual), _p(gamma), _p(beta), eps, _p(s), _p(out), M, H,
                                                                 float(drop[0]), int(drop[1]), _stream()),
                       "e3d_residual_layernorm_drop_fwd")

@@ -15,8 +15,8 @@ from torch import nn
 from torch.nn import functional as F
 
 from .. import bert, keyed, ops
-from ..blocks import (BertEmbeddings, GaussianFourierProjection, Predictor, SELayer, flat2d,
-                      require_gpu)
+from ..blocks import (BertEmbeddings, GaussianFourierProjection, KeyedDropoutSwitch, Predictor, SELayer, drop_row_keys,
+                      flat2d, require_gpu)
 from ..training import adamw
 from .utils import BlosumTransition, PredefinedNoiseScheduleDiscrete, elbo_loss
 
@@ -72,14 +72,16 @@ class ConditionalBertForDiffusionBase(nn.Module):
         lig_mask = ligand_attention_masks.contiguous().float()
         rec_mask = receptor_attention_masks.contiguous().float()
         temb = self.timestep_projector(timestep.squeeze(dim=-1)).contiguous()            # [B,H]
-        lig_seq = self.ligand_seq_embedding.run(flat2d(noised_ligand_seq))
-        lig_ang = self.ligand_angle_embedding.run(flat2d(ligand_angle), post_add=temb, rows_per_add=L)
-        lig = self.ligand_feature_emb.run(lig_seq, lig_ang, lig_mask, B, L)
-        rec_seq = self.receptor_seq_embedding.run(flat2d(receptor_seq))
-        rec_ang = self.receptor_angle_embedding.run(flat2d(receptor_angle), post_add=temb, rows_per_add=Lr)
-        rec = self.ligand_feature_emb.run(rec_seq, rec_ang, rec_mask, B, Lr)
-        x = bert.run_encoder(self.decoder, lig, lig_mask, B, L, enc=rec, enc_mask=rec_mask, Lk=Lr)
-        x = self.decoder_normalize.run(x, temb, lig_mask, B, L)
+        # keyed dropout: the key tables of the ligand rows and of the pocket rows
+        lk, rk = drop_row_keys(keyed.DROP_LIGAND, L), drop_row_keys(keyed.DROP_POCKET, Lr)
+        lig_seq = self.ligand_seq_embedding.run(flat2d(noised_ligand_seq), row_keys=lk)
+        lig_ang = self.ligand_angle_embedding.run(flat2d(ligand_angle), post_add=temb, rows_per_add=L, row_keys=lk)
+        lig = self.ligand_feature_emb.run(lig_seq, lig_ang, lig_mask, B, L, row_keys=lk)
+        rec_seq = self.receptor_seq_embedding.run(flat2d(receptor_seq), row_keys=rk)
+        rec_ang = self.receptor_angle_embedding.run(flat2d(receptor_angle), post_add=temb, rows_per_add=Lr, row_keys=rk)
+        rec = self.ligand_feature_emb.run(rec_seq, rec_ang, rec_mask, B, Lr, row_keys=rk)
+        x = bert.run_encoder(self.decoder, lig, lig_mask, B, L, enc=rec, enc_mask=rec_mask, Lk=Lr, row_keys=lk)
+        x = self.decoder_normalize.run(x, temb, lig_mask, B, L, row_keys=lk)
         return self.amino_acid_predictor.run(x).view(B, L, -1)
 
 
@@ -113,7 +115,7 @@ def onehot_to_index(onehot: torch.Tensor) -> torch.Tensor:
     return torch.where(onehot.sum(dim=-1) != 0, idx, torch.full_like(idx, -1))
 
 
-class PeptideDiff(ConditionalBertForDiffusionBase):
+class PeptideDiff(KeyedDropoutSwitch, ConditionalBertForDiffusionBase):
     """Training wrapper (reference model.py:256-450 minus Lightning logging): discrete forward
     noising, losses, optimizer recipe."""
 
@@ -221,7 +223,8 @@ class PeptideDiff(ConditionalBertForDiffusionBase):
         return self.get_loss(batch, t_int / self.timesteps, noised)
 
     def training_step(self, batch, batch_idx=0):
-        return self._draw_and_score(batch)[0]
+        with self.keyed_dropout_step(batch):
+            return self._draw_and_score(batch)[0]
 
     @torch.no_grad()
     def validation_step(self, batch, batch_idx=0):

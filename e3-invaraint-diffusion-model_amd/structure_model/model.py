@@ -9,9 +9,9 @@ from typing import List
 import torch
 from torch import nn
 
-from .. import bert, ops
-from ..blocks import (BertEmbeddings, GaussianFourierProjection, Predictor, SELayer, flat2d,
-                      require_gpu)
+from .. import bert, keyed, ops
+from ..blocks import (BertEmbeddings, GaussianFourierProjection, KeyedDropoutSwitch, Predictor, SELayer, drop_row_keys,
+                      flat2d, require_gpu)
 from ..training import adamw
 import os
 
@@ -64,10 +64,11 @@ class ConditionalBertForDiffusionBase(nn.Module):
             kv = [bert.project_cross_kv(layer.crossattention, x) for layer in self.decoder.layer] if project_cross_kv else None
             return ReceptorCache(x, kv, None, B, L, layout=layout)
         mask = receptor_attention_masks.contiguous().float()
-        ang = self.receptor_angle_emb.run(flat2d(receptor_angles))
-        seq = self.receptor_seq_emb.run(flat2d(receptor_seq))
-        x = self.receptor_emb.run(ang, seq, mask, B, L)
-        x = bert.run_encoder(self.encoder, x, mask, B, L)
+        rk = drop_row_keys(keyed.DROP_POCKET, L)     # keyed dropout: the key table of the pocket rows
+        ang = self.receptor_angle_emb.run(flat2d(receptor_angles), row_keys=rk)
+        seq = self.receptor_seq_emb.run(flat2d(receptor_seq), row_keys=rk)
+        x = self.receptor_emb.run(ang, seq, mask, B, L, row_keys=rk)
+        x = bert.run_encoder(self.encoder, x, mask, B, L, row_keys=rk)
         kv = None
         if project_cross_kv:
             kv = [bert.project_cross_kv(layer.crossattention, x) for layer in self.decoder.layer]
@@ -92,12 +93,13 @@ class ConditionalBertForDiffusionBase(nn.Module):
         require_gpu(timestep, noised_ligand_angles, ligand_attention_masks)
         B, L = noised_ligand_angles.shape[:2]
         mask = ligand_attention_masks.contiguous().float()
-        x = self.ligand_angle_emb.run(flat2d(noised_ligand_angles))
+        lk = drop_row_keys(keyed.DROP_LIGAND, L)     # keyed dropout: the key table of the ligand rows
+        x = self.ligand_angle_emb.run(flat2d(noised_ligand_angles), row_keys=lk)
         if mod is None:
             mod = self.timestep_modulation(timestep.squeeze(dim=-1))             # [B,6H]
-        x = self.timestep_emb.run(x, None, mask, B, L, mod=mod)
+        x = self.timestep_emb.run(x, None, mask, B, L, mod=mod, row_keys=lk)
         x = bert.run_encoder(self.decoder, x, mask, B, L, enc=receptor.encoder_states,
-                             enc_mask=receptor.mask, Lk=receptor.L, cross_kv=receptor.cross_kv)
+                             enc_mask=receptor.mask, Lk=receptor.L, cross_kv=receptor.cross_kv, row_keys=lk)
         return self.angles_predictor.run(x).view(B, L, -1)
 
     def _decode_packed(self, timestep, x_packed, receptor, mod, layout):
@@ -126,7 +128,7 @@ class ConditionalBertForDiffusionBase(nn.Module):
         return self.decode(timestep, noised_ligand_angles, ligand_attention_masks, rec)
 
 
-class ConditionalBertForDiffusion(ConditionalBertForDiffusionBase):
+class ConditionalBertForDiffusion(KeyedDropoutSwitch, ConditionalBertForDiffusionBase):
     """Training wrapper (reference model.py:233-403 minus the Lightning logging hooks):
     per-feature wrapped-angle loss terms and the AdamW / LinearWarmup optimizer recipe."""
     diheral_loss_func = radian_l1_loss
@@ -194,7 +196,8 @@ class ConditionalBertForDiffusion(ConditionalBertForDiffusionBase):
         return torch.stack(terms)
 
     def training_step(self, batch, batch_idx=0):
-        return torch.mean(self._get_loss_terms(batch))
+        with self.keyed_dropout_step(batch):
+            return torch.mean(self._get_loss_terms(batch))
 
     @torch.no_grad()
     def validation_step(self, batch, batch_idx=0):

@@ -127,7 +127,8 @@ class GraphedStep(EagerStep):
 
     What makes the step replayable: no device-to-host synchronisation inside it (the losses are masked means, not index
     lists); the learning rate and the AdamW step counts live in device memory (``ClipAdamW.use_device_scalars``); dropout
-    decisions take a device-side epoch word on top of their baked seeds (``ops.dropout_epoch``), advanced inside the graph;
+    decisions take a device-side epoch word on top of their baked seeds (``ops.dropout_epoch``), advanced inside the graph
+    -- or, keyed (a seeded ``fit``), are regenerated from the static batch's item ids and the epoch word at every replay;
     derived-weight caches (W^T, distance-table planes) are refreshed by launches inside the captured backward / forward.
     One graph per batch signature, up to ``MAX_GRAPHS`` of them (frames trimmed to the batch's longest ligand / pocket come
     in a handful of shapes: ``trim_batch``); a signature seen fewer than ``warmup`` times, or beyond that number, runs
@@ -328,6 +329,7 @@ def make_stepper(model, optim, params, gradient_clip, averager=None, graph=None)
 LIGAND_FRAME_KEYS = ("ligand_angles", "ligand_attn_mask", "ligand_seq", "known_noise", "noised_ligand_angle")
 RECEPTOR_FRAME_KEYS = ("receptor_angles", "receptor_attn_mask", "receptor_seq")
 TRIM_TRAIN = os.environ.get("E3D_TRAIN_TRIM", "0") == "1"            # default of fit(trim_padding=None)
+KEYED_DROPOUT = os.environ.get("E3D_TRAIN_KEYED_DROPOUT", "1") == "1"   # default of fit(seed=, keyed_dropout=None)
 
 
 def trimmed_frame(batch, multiple=32):
@@ -344,8 +346,9 @@ def trim_batch(batch, frame=None, multiple=32):
     0.0f; every other op is row-wise) and receives exactly zero gradient in the backward pass (the losses are means over
     valid positions), so loss and parameter gradients of the trimmed batch are those of the padded one up to the order of
     the fp32 sums (tests/test_training_gpu.py::test_trimmed_*).  What changes: draws made per frame position inside the
-    step (dropout, PeptideDiff.apply_aa_noise) come from a different place of the random stream -- unless the noising draws
-    are keyed (``fit(seed=)``): those follow the item and its positions, not the frame."""
+    step (dropout, PeptideDiff.apply_aa_noise) come from a different place of the random stream -- unless they are keyed
+    (``fit(seed=)``): the noising draws and the dropout decisions of a seeded run follow the item and its positions, not
+    the frame (tests/test_keyed_dropout_gpu.py)."""
     Ll, Lr = frame if frame is not None else trimmed_frame(batch, multiple)
     out = dict(batch)
     for keys, n in ((LIGAND_FRAME_KEYS, Ll), (RECEPTOR_FRAME_KEYS, Lr)):
@@ -400,13 +403,16 @@ class ItemIdDataset(torch.utils.data.Dataset):
 
 class _KeyedDraws:
     """What a seeded ``fit`` holds: the seed, the epoch word in device memory, and -- for a model whose batches arrive
-    noised (structure model) -- the schedule tables to noise them again on the device from streams 4 / 5."""
+    noised (structure model) -- the schedule tables to noise them again on the device from streams 4 / 5.  For the run it
+    also switches the model's dropout to keyed decisions (streams 8 / 9) unless ``keyed_dropout`` is off."""
 
-    def __init__(self, model, seed, device, max_epochs, loader, noise_tables, noise_scale):
+    def __init__(self, model, seed, device, max_epochs, loader, noise_tables, noise_scale, keyed_dropout=True):
         self.seed = keyed.check_seed(seed)
         keyed.check_epoch(max(0, max_epochs - 1))
         self.word = keyed.epoch_word(device)
         self.model = model if hasattr(model, "use_keyed_draws") else None    # draws inside the step (sequence model)
+        # dropout decisions keyed by the same seed, ids and epoch word (both models: blocks.KeyedDropoutSwitch)
+        self.dropout_model = model if keyed_dropout and hasattr(model, "use_keyed_dropout") else None
         self.tables = self.scale = None
         if self.model is None:
             ds = getattr(loader, "dataset", None)
@@ -421,11 +427,15 @@ class _KeyedDraws:
     def __enter__(self):
         if self.model is not None:
             self.model.use_keyed_draws(self.seed, self.word)
+        if self.dropout_model is not None:
+            self.dropout_model.use_keyed_dropout(self.seed, self.word)
         return self
 
     def __exit__(self, *exc):
         if self.model is not None:
             self.model.use_keyed_draws(None)
+        if self.dropout_model is not None:
+            self.dropout_model.use_keyed_dropout(None)
 
     def set_epoch(self, epoch):
         keyed.set_epoch(self.word, epoch)
@@ -484,7 +494,7 @@ def _step_batch(batch, device, draws, trim, frame=None):
 
 def fit(model, train_loader, val_loader=None, *, max_epochs, min_epochs=0, gradient_clip=1.0, device="cuda:0",
         log_every_n_steps=30, checkpoint_path="./best_val_model.pt", checkpoint_mode="max", max_steps=None,
-        log=print, trim_padding=None, seed=None, noise_tables=None, noise_scale=None):
+        log=print, trim_padding=None, seed=None, noise_tables=None, noise_scale=None, keyed_dropout=None):
     """Returns a history dict.  ``model`` provides training_step / validation_step /
     configure_optimizers (the reference's LightningModule surface).
     ``seed`` (default None: torch's generators, as ever): keyed training and validation draws ("Keyed sampling
@@ -494,6 +504,10 @@ def fit(model, train_loader, val_loader=None, *, max_epochs, min_epochs=0, gradi
     model with ``use_keyed_draws`` (sequence model) draws inside its step; any other gets ``timestep`` / ``known_noise`` /
     ``noised_ligand_angle`` replaced on the device before the step, with the tables of the loader's dataset
     (``NoisedAnglesDataset.tables`` / ``.angular_var_scale``) or ``noise_tables`` / ``noise_scale``.
+    ``keyed_dropout`` (None: E3D_TRAIN_KEYED_DROPOUT, default on): under a seed, the dropout decisions of every training step
+    are keyed as well -- functions of (seed, item id, epoch, dropout site, position, head, column or key) -- so a seeded
+    run with dropout > 0 is reproducible whatever the batch, frame, launch mode or point of resumption; False keeps
+    torch-seeded dropout under the seed.  Without a seed it has no effect.
     ``trim_padding`` (None: E3D_TRAIN_TRIM, default off = the reference's padded frames): run every training and
     validation step on the frame of the batch's longest ligand / pocket (``trim_batch``; under a process group the frame
     is the maximum over the ranks, agreed on the host, so that every rank replays the same kind of step)."""
@@ -504,8 +518,9 @@ def fit(model, train_loader, val_loader=None, *, max_epochs, min_epochs=0, gradi
         model.to(device)
         draws = None
         if seed is not None:
+            keyed_drop = KEYED_DROPOUT if keyed_dropout is None else bool(keyed_dropout)
             draws = whole_run.enter_context(
-                _KeyedDraws(model, seed, device, max_epochs, train_loader, noise_tables, noise_scale))
+                _KeyedDraws(model, seed, device, max_epochs, train_loader, noise_tables, noise_scale, keyed_drop))
         sharding.broadcast_parameters(model, src=0)
         conf = model.configure_optimizers()
         optim = conf["optimizer"]

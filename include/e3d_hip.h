@@ -545,6 +545,55 @@ int e3d_adamw_step(float* const* params, const float* const* grads, float* const
                    const float* norm_and_clip, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                    void* stream);
 
+/* ---- keyed dropout decisions (seeded training; additions to ABI v5)
+ * With a seed, every dropout decision of a training step is a pure function of (seed, item id, epoch, site, position, head,
+ * column or key) -- not of the batch, the row, the frame or the number of steps run before.
+ *   e3d_keyed_drop_row_keys: one 64-bit key per row of a [B, L] frame, out[b * L + l] = w0 | w1 << 32 of
+ *     Philox4x32-10(seed; ids[b]; stream << 16 | epoch; l << 8): stream 8 = ligand rows, 9 = pocket rows; ids int64 [B] and the
+ *     epoch word are read from DEVICE memory, so a captured step replays the launch with the current ones.
+ *   the _keyed entry points: their (drop_p, drop_seed) counterparts with (drop_p, site, row_keys) instead.  A row's key takes
+ *     the place of the seed of the generator above, the group index is site << 40 | head << 24 | group with group = column >> 2
+ *     (hidden states; head = 0) or key position >> 2 (attention probabilities; the row is the QUERY's, row_keys is the table of
+ *     the [B, Lq] query frame), and the device word of e3d_dropout_set_epoch_ptr is NOT added.  site < 2^24 is the ordinal of the
+ *     dropout call within the step; nh < 2^16.  e3d_dropout_f32_keyed takes the tensor as [M, H] rows, H % 4 == 0.  */
+int e3d_keyed_drop_row_keys(const int64_t* ids, int B, int L, const int64_t* epoch_word, uint64_t seed, int stream,
+                            uint64_t* out, void* st);
+int e3d_dropout_f32_keyed(const float* x, float p, uint32_t site, const uint64_t* row_keys, float* out, int M, int H,
+                          void* stream);
+int e3d_keyed_attn_dropout_mask(int B, int nh, int Lq, int Lk, float p, uint32_t site, const uint64_t* row_keys, float* out,
+                                void* stream);
+int e3d_residual_layernorm_drop_fwd_keyed(const float* x, const float* residual, const float* gamma, const float* beta, float eps,
+                                          float* s_out, float* out, int M, int H, float drop_p, uint32_t site,
+                                          const uint64_t* row_keys, void* stream);
+int e3d_layernorm_bwd_drop_keyed(const float* dy, const float* s, const float* gamma, float eps, float* ds, float* ds_dropped,
+                                 float* dgamma, float* dbeta, int M, int H, float drop_p, uint32_t site, const uint64_t* row_keys,
+                                 void* stream);
+int e3d_layernorm_bwd_ws_keyed(const float* dy, const float* s, const float* gamma, float eps, float* ds, float* ds_dropped,
+                               float* dgamma, float* dbeta, int M, int H, float drop_p, uint32_t site, const uint64_t* row_keys,
+                               float* workspace, int64_t workspace_floats, void* stream);
+int e3d_relkey_attn_fwd_split_drop_keyed(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs,
+                                         int64_t k_rs, const float* v, int64_t v_bs, int64_t v_rs, const float* dist_emb,
+                                         int P, const float* key_mask, float* out, float* lse, int B, int nh, int Lq, int Lk,
+                                         int terms, float drop_p, uint32_t site, const uint64_t* row_keys, void* stream);
+int e3d_relkey_attn_fwd_split_ex_keyed(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs,
+                                       int64_t k_rs, const float* v, int64_t v_bs, int64_t v_rs, const float* dist_emb,
+                                       int P, const float* key_mask, float* out, float* lse, int B, int nh, int Lq, int Lk,
+                                       int terms, float drop_p, uint32_t site, const uint64_t* row_keys, void* e_scratch,
+                                       int e_scratch_ready, const float* q_absmax, const float* k_absmax, float* e_absmax,
+                                       void* stream);
+int e3d_relkey_attn_bwd_drop_keyed(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs, int64_t k_rs,
+                                   const float* v, int64_t v_bs, int64_t v_rs, const float* dist_emb, int P,
+                                   const float* key_mask, const float* out, const float* lse, const float* dout, float* dq,
+                                   int64_t dq_bs, int64_t dq_rs, float* dk, int64_t dk_bs, int64_t dk_rs, float* dv,
+                                   int64_t dv_bs, int64_t dv_rs, float* d_dist_emb, float* workspace, int B, int nh, int Lq,
+                                   int Lk, float drop_p, uint32_t site, const uint64_t* row_keys, void* stream);
+int e3d_relkey_attn_bwd_ex_keyed(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs, int64_t k_rs,
+                                 const float* v, int64_t v_bs, int64_t v_rs, const float* dist_emb, int P,
+                                 const float* key_mask, const float* out, const float* lse, const float* dout, float* dq,
+                                 int64_t dq_bs, int64_t dq_rs, float* dk, int64_t dk_bs, int64_t dk_rs, float* dv,
+                                 int64_t dv_bs, int64_t dv_rs, float* d_dist_emb, float* workspace, int B, int nh, int Lq,
+                                 int Lk, int terms, float drop_p, uint32_t site, const uint64_t* row_keys, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

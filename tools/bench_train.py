@@ -31,7 +31,7 @@ def run(model_name="structure", batch=None, seq_len=128, steps=8, dropout=0.0, w
     per-rank batch 64; ``trim``: the same batch on the frame of its longest ligand / pocket, ``training.trim_batch``)
     ``train_seed``: keyed training draws as ``training.fit(seed=)`` makes them, items keyed 0 .. B-1, the epoch word
     advanced every step -- the structure batch noised from streams 4 / 5 before the step, the sequence model drawing from
-    streams 6 / 7 inside it.
+    streams 6 / 7 inside it, dropout decisions (``dropout`` > 0) keyed from streams 8 / 9.
     -- weights broadcast from rank 0, gradients as views of the all-reduce buckets, the buckets sent
     (RCCL; gloo in rehearsals) while the deferred weight-gradient launches of the later layers still run; timed between
     barriers, max over ranks by the caller."""
@@ -67,6 +67,7 @@ def run(model_name="structure", batch=None, seq_len=128, steps=8, dropout=0.0, w
         epoch = keyed.epoch_word(DEV)
         if model_name == "sequence":
             model.use_keyed_draws(train_seed, epoch)
+        model.use_keyed_dropout(train_seed, epoch)      # as a seeded fit: with --dropout > 0 the step's decisions are keyed too
     frame = (L, L)
     if trim:
         frame = pkg.training.trimmed_frame(pk)
