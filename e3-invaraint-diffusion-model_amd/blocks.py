@@ -7,9 +7,63 @@ import torch
 from torch import nn
 
 import contextlib
+import os
 
 from . import bert, keyed, ops
 from .autograd import functional as F
+
+# SELayer conditioning on one-hot rows (the pocket's residue types): modulation rows from a table of the distinct rows
+# (``onehot_modulation``).  0 = always the dense [M, 6H] launches (A/B runs, tests).
+ADALN_TABLE = os.environ.get("E3D_ADALN_TABLE", "1") == "1"
+TABLE_ROWS = 256     # the canonical inputs are padded to one row block of the GEMM kernels
+_CANONICAL_ROWS = {}
+
+
+class IndexedModulation:
+    """What ``onehot_modulation`` hands ``SELayer.run`` in the place of ``mod``: row r's modulation is ``table[idx[r]]``
+    where idx[r] >= 0, ``mod[r]`` elsewhere (``mod`` holds rows only when the device found such a row and raised
+    ``other_rows``, a one-int device word)."""
+
+    def __init__(self, idx, table, mod, other_rows):
+        self.idx, self.table, self.mod, self.other_rows = idx, table, mod, other_rows
+        self.shape = mod.shape
+
+
+def _canonical_rows(F_in, device):
+    """[TABLE_ROWS, F]: the F one-hot rows, then zero rows (row F: the padding row of a pocket)."""
+    key = (F_in, device)
+    t = _CANONICAL_ROWS.get(key)
+    if t is None:
+        t = torch.zeros(TABLE_ROWS, F_in, device=device, dtype=torch.float32)
+        t[:F_in] = torch.eye(F_in, device=device, dtype=torch.float32)
+        _CANONICAL_ROWS[key] = t
+    return t
+
+
+def onehot_modulation(layer, emb, x2d):
+    """``layer.modulation(emb.run(x2d))`` for per-token features x2d [M, F] that are one-hot or all-zero rows (a pocket's
+    residue types: dataset._one_hot / _pad): such input has F + 1 distinct rows, so the embedding and both modulation GEMMs
+    run on a table of those rows -- in the kernel form of the M-row launch, so a table row equals the row that launch would
+    have written bit for bit -- and the gates look their row up.  The M-row launches stay in the sequence behind a device
+    flag that a classification pass over x2d raises for any other row (soft labels, NaN): they then run as ever and such
+    rows read their own modulation; with one-hot input they return at once.  No host synchronisation.
+    Inference only; returns None where the path does not apply (the caller then runs the dense one)."""
+    m0, m2 = layer.adaLN_modulation[0], layer.adaLN_modulation[2]
+    M, F_in = x2d.shape
+    H = m0.weight.shape[0]
+    params = (emb.linear.weight, emb.linear.bias, emb.LayerNorm.weight, emb.LayerNorm.bias, m0.weight, m0.bias, m2.weight, m2.bias)
+    if (not ADALN_TABLE or F_in >= TABLE_ROWS or F_in > 32 or not ops.gemm_is_tiled(M)
+            or (emb.training and emb.dropout.p > 0)
+            or (torch.is_grad_enabled() and any(t.requires_grad for t in params + (x2d,)))):
+        return None
+    ln = emb.LayerNorm
+    idx, other_rows = ops.classify_onehot_rows(x2d)
+    # (the embedding's two kernel forms, few rows and many, run the same arithmetic in the same order: no form to ask for)
+    e = ops.embed_layernorm(_canonical_rows(F_in, x2d.device), emb.linear.weight, emb.linear.bias, ln.weight, ln.bias, ln.eps)
+    table = ops.gemm(ops.gemm(e, m0.weight, m0.bias, ops.ACT_SILU, plan_m=M), m2.weight, m2.bias, plan_m=M)
+    c = ops.embed_layernorm(x2d, emb.linear.weight, emb.linear.bias, ln.weight, ln.bias, ln.eps, run_if=other_rows)
+    mod = ops.gemm(ops.gemm(c, m0.weight, m0.bias, ops.ACT_SILU, run_if=other_rows), m2.weight, m2.bias, run_if=other_rows)
+    return IndexedModulation(idx, table, mod, other_rows)
 
 
 class SELayer(nn.Module):
@@ -38,7 +92,7 @@ class SELayer(nn.Module):
     def run(self, x, c, mask, B, L, mod=None, layout=None, row_keys=None):
         """x [B*L,H]; c [B*L,H] (per token) or [B,H] (one conditioning row per item).  ``mod``: the rows
         ``modulation(c)`` would give, computed by the caller ([B*L,6H], [B,6H], or ONE row [1,6H] shared by every
-        item: samplers precompute it per timestep) -- ``c`` is then not read.  ``layout`` (packing.PackedLayout,
+        item: samplers precompute it per timestep), or an ``IndexedModulation`` (per token) -- ``c`` is then not read.  ``layout`` (packing.PackedLayout,
         inference): x holds packed rows [layout.rows, H] (pass B = 1, L = layout.rows) and the conditioning is per
         token ([rows,H]) or ONE row shared by every item (a sampler's single timestep); ``mask`` is not read.
         ``row_keys`` (keyed dropout, training): the key table of the rows of x."""
@@ -54,10 +108,15 @@ class SELayer(nn.Module):
         if row_keys is not None:
             drop = drop + (row_keys,)
         att = bert.run_self_attention(self.attn, x, mask, B, L, drop, layout=layout)
-        x = F.adaln_gate(x, att, mod, 0, rows_per_cond)
+        if isinstance(mod, IndexedModulation):
+            assert rows_per_cond == 1
+            gate = lambda a, y, branch: ops.adaln_gate_indexed(a, y, mod.idx, mod.table, mod.mod, branch)   # noqa: E731
+        else:
+            gate = lambda a, y, branch: F.adaln_gate(a, y, mod, branch, rows_per_cond)   # noqa: E731
+        x = gate(x, att, 0)
         h = F.dropout(F.linear(x, self.mlp[0].weight, self.mlp[0].bias, ops.ACT_GELU), self.mlp[2].p, self.training, row_keys)
         h = F.dropout(F.linear(h, self.mlp[3].weight, self.mlp[3].bias), self.mlp[4].p, self.training, row_keys)
-        return F.adaln_gate(x, h, mod, 1, rows_per_cond)
+        return gate(x, h, 1)
 
 
 class GaussianFourierProjection(nn.Module):

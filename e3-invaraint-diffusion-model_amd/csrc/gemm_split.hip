@@ -50,7 +50,10 @@ __device__ __forceinline__ f32x16 mma16(const f16x8 a, const f16x8 b, const f32x
 // what the forward epilogues do besides bias + activation: ``absmax`` (may be null) is raised to the largest |out|
 // (e3d_common.h), ``scale`` multiplies the accumulator before the bias -- the inverse of the power of two a caller
 // scaled the weight by so that its fp16 terms sit in the normal range (include/e3d_hip.h, out_scale)
-struct Epi { float* absmax; float scale; };
+// ``plan_m`` > 0: choose the kernel form as a launch of plan_m rows would (a tile's result does not depend on which other
+// row blocks the launch has, so rows computed apart equal the rows of the larger launch bit for bit).  ``run_if`` (device
+// word, may be null): every workgroup reads it first and returns when it is zero (e3d_gemm_bias_act_f32_split_gated).
+struct Epi { float* absmax; float scale; int plan_m = 0; const int* run_if = nullptr; };
 
 constexpr int BN = 128, BK = 32;
 #ifdef GEMM_STAMPS   // lab builds only (tools/lab/gemm_stamps.py): s_memtime stamps of waves 0 and 4 of ONE workgroup of the general kernel
@@ -559,7 +562,9 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_split_kernel(const float* _
                                                          const float* __restrict__ bias,
                                                          float* __restrict__ out, int64_t ldc, int M,
                                                          int N, int K_total, int tiles_m, int tiles_n,
-                                                         int k_chunk, float* __restrict__ absmax, float out_scale) {
+                                                         int k_chunk, float* __restrict__ absmax, float out_scale,
+                                                         const int* __restrict__ run_if) {
+    if (run_if && *run_if == 0) return;   // uniform: before any barrier
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     gemm_split_body<NS, ACT, A_KMAJ, B_KMAJ, WM, WN, E, TN, TR>(smem_raw, A, lda, Bm, ldb, bias, out, ldc, M, N, K_total, tiles_m,
                                                         tiles_n, k_chunk, xcd_remap(blockIdx.x, tiles_m * tiles_n),
@@ -666,8 +671,10 @@ __global__ __launch_bounds__(WR * WC * 64, 2) void gemm_split256_kernel(const fl
                                                                         const float* __restrict__ bias,
                                                                         float* __restrict__ out, int64_t ldc,
                                                                         int M, int N, int K, int tiles_m,
-                                                                        int tiles_n, float* __restrict__ absmax, float out_scale) {
+                                                                        int tiles_n, float* __restrict__ absmax, float out_scale,
+                                                                        const int* __restrict__ run_if) {
     static_assert(!PIPE || NBUF == 2, "PIPE needs two LDS buffers");
+    if (run_if && *run_if == 0) return;   // uniform: before any barrier
     STAMP_K(0);   // kernel entry
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     constexpr int NT = WR * WC * 64, TM = WR * 128, TN = WC * 64;
@@ -873,7 +880,9 @@ __global__ __launch_bounds__(512, 2) void gemm_split256p_kernel(const float* __r
                                                                  const float* __restrict__ W,
                                                                  const float* __restrict__ bias,
                                                                  float* __restrict__ out, int64_t ldc, int N, int K,
-                                                                 int tiles_m, int tiles_n, float* __restrict__ absmax, float out_scale) {
+                                                                 int tiles_m, int tiles_n, float* __restrict__ absmax, float out_scale,
+                                                                 const int* __restrict__ run_if) {
+    if (run_if && *run_if == 0) return;   // uniform: before any load, LDS write or barrier
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     constexpr int NS = 2, T_BYTES = BT * ROW64, BUF_BYTES = 2 * NS * T_BYTES;
     constexpr int NI = 8;   // float4 items per thread and k-tile: 0..3 from A, 4..7 from W
@@ -1018,7 +1027,7 @@ int launch256p(const float* A, int64_t lda, const float* W, const float* bias, f
     const int total = tiles_m * tiles_n;
     e3d_allow_lds(lds_ok, gemm_split256p_kernel<ACT, E>, lds);
     hipLaunchKernelGGL((gemm_split256p_kernel<ACT, E>), dim3(total < n_cu ? total : n_cu), dim3(512), lds, s, A, lda, W, bias, out,
-                       ldc, N, K, tiles_m, tiles_n, epi.absmax, epi.scale);
+                       ldc, N, K, tiles_m, tiles_n, epi.absmax, epi.scale, epi.run_if);
     return e3d_launch_status("e3d_gemm_f32_split (persistent 256x256)");
 }
 
@@ -1035,7 +1044,7 @@ int launch256(const float* A, int64_t lda, const float* W, const float* bias, fl
     static std::atomic<uint64_t> lds_ok{0};
     e3d_allow_lds(lds_ok, gemm_split256_kernel<NS, ACT, WR, WC, NBUF, PIPE, E>, lds);
     hipLaunchKernelGGL((gemm_split256_kernel<NS, ACT, WR, WC, NBUF, PIPE, E>), dim3(tiles_m * tiles_n), dim3(WR * WC * 64), lds, s,
-                       A, lda, W, bias, out, ldc, M, N, K, tiles_m, tiles_n, epi.absmax, epi.scale);
+                       A, lda, W, bias, out, ldc, M, N, K, tiles_m, tiles_n, epi.absmax, epi.scale, epi.run_if);
     return e3d_launch_status("e3d_gemm_f32_split (128x64 wave tiles)");
 }
 
@@ -1060,25 +1069,26 @@ int launch(const float* A, int64_t lda, const float* B, int64_t ldb, const float
         const char* e = getenv("E3D_GEMM_TILE");
         g_tile_pref = e ? atoi(e) : 4;
     }
+    const int Mp = epi.plan_m > 0 ? epi.plan_m : M;   // the row count the form is chosen for
     if constexpr (!A_KMAJ && !B_KMAJ) {
         if constexpr (NS == 2) {
             // the persistent kernel from 160 tiles upwards -- and from 96 when the output is at least 6 tiles wide (N >= 1536):
             // there the 128x128 form needs 1.5+ rounds of 256 CUs (M = 4096, N = 1536: 384 tiles), one 256x256 tile per CU
             // is faster (structure training step 32.0 -> 31.1 ms); narrow outputs with 96-159 tiles (M = 8192, N = 768)
             // measured 6 % slower on it (sequence step 25.0 -> 26.6 ms) and stay on the 128x128 form
-            const int64_t n_tiles = (int64_t)(M / BT) * (N / BT);
-            if (N % BT == 0 && M % BT == 0 && ldb == K && g_tile_pref >= 4 && K >= 2 * BK && lda < (1 << 22) &&
+            const int64_t n_tiles = (int64_t)(Mp / BT) * (N / BT);
+            if (N % BT == 0 && M % BT == 0 && Mp % BT == 0 && ldb == K && g_tile_pref >= 4 && K >= 2 * BK && lda < (1 << 22) &&
                 (g_tile_pref >= 5 || n_tiles >= p_min() || (n_tiles >= 96 && N >= 6 * BT && !getenv("E3D_GEMM_P_MIN"))))
                 return launch256p<ACT, E>(A, lda, B, bias, out, ldc, M, N, K, epi, s);
-            if (N % BT == 0 && ldb == K && g_tile_pref >= 3 && (int64_t)((M + BT - 1) / BT) * (N / BT) >= 256)
+            if (N % BT == 0 && ldb == K && g_tile_pref >= 3 && (int64_t)((Mp + BT - 1) / BT) * (N / BT) >= 256)
                 return launch256<NS, ACT, 2, 4, 2, true, E>(A, lda, B, bias, out, ldc, M, N, K, epi, s);
         }
         if constexpr (NS == 1) {   // single-product form: the interleaved-staging 256x256 kernel from 160 tiles upwards
-            if (N % BT == 0 && ldb == K && g_tile_pref >= 3 && (int64_t)((M + BT - 1) / BT) * (N / BT) >= 160)
+            if (N % BT == 0 && ldb == K && g_tile_pref >= 3 && (int64_t)((Mp + BT - 1) / BT) * (N / BT) >= 160)
                 return launch256<NS, ACT, 2, 4, 2, true, E>(A, lda, B, bias, out, ldc, M, N, K, epi, s);
         }
         if (N % BT == 0 && ldb == K && g_tile_pref >= 1 &&
-            (int64_t)((M + BT - 1) / BT) * (N / BT) >= 256)   // enough 256x256 tiles to fill the 256 CUs
+            (int64_t)((Mp + BT - 1) / BT) * (N / BT) >= 256)   // enough 256x256 tiles to fill the 256 CUs
             return launch256<NS, ACT, 2, 4, (NS <= 2 ? 2 : 1), false, E>(A, lda, B, bias, out, ldc, M, N, K, epi, s);
     }
     // general kernel, three tile forms: 1 = 256x128 (8 waves, one workgroup per CU: 96 KB of LDS), 2 = 128x128 (4 waves,
@@ -1091,7 +1101,7 @@ int launch(const float* A, int64_t lda, const float* B, int64_t ldb, const float
     }
     int form = g_general_form;
     if (form != 1 && form != 2 && form != 3 && form != 4) {
-        const int64_t g256 = (int64_t)((M + 255) / 256) * ((N + 127) / 128), g128 = (int64_t)((M + 127) / 128) * ((N + 127) / 128);
+        const int64_t g256 = (int64_t)((Mp + 255) / 256) * ((N + 127) / 128), g128 = (int64_t)((Mp + 127) / 128) * ((N + 127) / 128);
         const int64_t cus = e3d_cu_count();
         if (NS == 3) form = g256 < 128 && !A_KMAJ && !B_KMAJ ? 2 : 1;       // 3-term kernels: as measured in round 1
         else if (A_KMAJ && B_KMAJ) form = 1;                                // weight gradients (split-K over one resident round): +4 %
@@ -1104,7 +1114,7 @@ int launch(const float* A, int64_t lda, const float* B, int64_t ldb, const float
         // tiles on four waves, up to three workgroups per CU with barriers of their own -- 18.8 against 22.4 us at M = 1024, N = K =
         // 768, 19.6 against 22.8 at N = 1024, 19.7 against 23.0 at M = 2048 (profiles/r04_gemm_mid_m_ab.log); in the step:
         // profiles/r04_gemm_form4_small_m_in_step.log.  (At M = 4096 and above the same form changed nothing in the step: below.)
-        if (NS == 2 && !A_KMAJ && !B_KMAJ && M <= 2048 && N <= 1024) form = 4;
+        if (NS == 2 && !A_KMAJ && !B_KMAJ && Mp <= 2048 && N <= 1024) form = 4;
     }
     // form 4 (round 4, selectable only: E3D_GEMM_FORM=4 / e3d_gemm_general_select(4)): 128x64 tiles on FOUR waves -- 48 KB of LDS,
     // so up to three workgroups share a CU with barriers of their own.  Standalone (hot operands, tools/lab/gemm_forms_ab.py) a
@@ -1177,7 +1187,7 @@ int launch_general(const float* A, int64_t lda, const float* B, int64_t ldb, con
     }
     hipLaunchKernelGGL((gemm_split_kernel<NS, ACT, A_KMAJ, B_KMAJ, WM, WN, E, TN, TR>), dim3(tiles_m * tiles_n, splits),
                        dim3(WM * WN * 64), lds, s, A, lda, B, ldb, bias, out, ldc, M, N, K, tiles_m, tiles_n, k_chunk,
-                       splits > 1 ? nullptr : epi.absmax, epi.scale);
+                       splits > 1 ? nullptr : epi.absmax, epi.scale, epi.run_if);
     return e3d_launch_status("e3d_gemm_f32_split");
 }
 
@@ -1237,8 +1247,10 @@ extern "C" int e3d_gemm_general_select(int form) {
 
 static int gemm_split_general(const float* A, int64_t lda, int a_kmajor, const float* B, int64_t ldb, int b_kmajor,
                               const float* bias, float* out, int64_t ldc, int M, int N, int K, int act, int terms,
-                              float* absmax, float out_scale, void* stream) {
-    const Epi epi{absmax, out_scale};
+                              float* absmax, float out_scale, void* stream, int plan_m = 0, const int* run_if = nullptr) {
+    const Epi epi{absmax, out_scale, plan_m, run_if};
+    E3D_REQUIRE(plan_m >= 0 && (!(a_kmajor || b_kmajor) || (plan_m == 0 && !run_if)),
+                "gemm_split: plan_m / run_if exist for the forward (K-contiguous) layout (plan_m=%d)", plan_m);
     E3D_REQUIRE(out_scale == 1.0f || !(a_kmajor && b_kmajor), "gemm_split: out_scale is not available for the split-K layout");
     E3D_REQUIRE(A && B && out, "gemm_split: null pointer");
     E3D_REQUIRE(M > 0 && N > 0 && K > 0, "gemm_split: bad shape M=%d N=%d K=%d", M, N, K);
@@ -1379,4 +1391,12 @@ extern "C" int e3d_gemm_bias_act_f32_split_ex(const float* A, int64_t lda, const
                                               float out_scale, void* stream) {
     E3D_REQUIRE(N % BN == 0, "gemm_split: need N%%128==0 (N=%d)", N);
     return gemm_split_general(A, lda, 0, W, (int64_t)K, 0, bias, out, ldc, M, N, K, act, terms, out_absmax, out_scale, stream);
+}
+
+extern "C" int e3d_gemm_bias_act_f32_split_gated(const float* A, int64_t lda, const float* W, const float* bias, float* out,
+                                                 int64_t ldc, int M, int N, int K, int act, int terms, float* out_absmax,
+                                                 float out_scale, int plan_m, const int* run_if, void* stream) {
+    E3D_REQUIRE(N % BN == 0, "gemm_split: need N%%128==0 (N=%d)", N);
+    return gemm_split_general(A, lda, 0, W, (int64_t)K, 0, bias, out, ldc, M, N, K, act, terms, out_absmax, out_scale, stream,
+                              plan_m, run_if);
 }

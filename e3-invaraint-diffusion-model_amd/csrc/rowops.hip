@@ -104,13 +104,67 @@ __global__ __launch_bounds__(256) void adaln_gate_kernel(const float* __restrict
     row_store<V>(r, out + (int64_t)row * H, lane);
 }
 
+// adaln_gate_kernel with the modulation row looked up: row r takes its chunks from table[idx[r]] when idx[r] names a table
+// row, from mod[r] otherwise (rows_per_cond = 1).  Same arithmetic per row; the table (a few rows of 6H floats) stays in L2.
+template <int V>
+__global__ __launch_bounds__(256) void adaln_gate_indexed_kernel(const float* __restrict__ x, const float* __restrict__ y,
+                                                                 const int* __restrict__ idx, const float* __restrict__ table,
+                                                                 int table_rows, const float* __restrict__ mod, int branch,
+                                                                 float* __restrict__ out, int M) {
+    constexpr int H = 256 * V;
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    f32x4 r[V], xr[V], sh[V], sc[V], ga[V];
+    row_load<V>(r, y + (int64_t)row * H, lane);
+    row_normalize<V>(r, 1e-5f);
+    const int t = idx[row];
+    const float* mrow = ((unsigned)t < (unsigned)table_rows ? table + (int64_t)t * 6 * H : mod + (int64_t)row * 6 * H) +
+                        (int64_t)branch * 3 * H;
+    row_load<V>(sh, mrow, lane);
+    row_load<V>(sc, mrow + H, lane);
+    row_load<V>(ga, mrow + 2 * H, lane);
+    row_load<V>(xr, x + (int64_t)row * H, lane);
+#pragma unroll
+    for (int i = 0; i < V; ++i) r[i] = xr[i] + ga[i] * (r[i] * (1.0f + sc[i]) + sh[i]);
+    row_store<V>(r, out + (int64_t)row * H, lane);
+}
+
+// One-hot rows: idx[row] = k when the row is exactly 1.0f at k and (+/-)0.0f elsewhere, F when it is all zero, -1 for
+// anything else (NaN included); *flag is raised when any row got -1.  One thread per row; VEC: 16-byte loads (F % 4 == 0).
+template <bool VEC>
+__global__ __launch_bounds__(256) void classify_onehot_kernel(const float* __restrict__ x, int F, int* __restrict__ idx,
+                                                              int* __restrict__ flag, int M) {
+    const int row = blockIdx.x * 256 + threadIdx.x;
+    if (row >= M) return;
+    const float* xr = x + (int64_t)row * F;
+    int nonzero = 0, ones = 0, pos = 0;
+    auto see = [&](float v, int f) {
+        nonzero += !(v == 0.0f);   // NaN counts
+        if (v == 1.0f) { ++ones; pos = f; }
+    };
+    if (VEC) {
+        for (int f0 = 0; f0 < F; f0 += 4) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(xr + f0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) see(v[j], f0 + j);
+        }
+    } else {
+        for (int f = 0; f < F; ++f) see(xr[f], f);
+    }
+    const int k = nonzero == 0 ? F : (nonzero == 1 && ones == 1 ? pos : -1);
+    idx[row] = k;
+    if (k < 0) atomicOr(flag, 1);
+}
+
 template <int V>
 __global__ __launch_bounds__(256) void embed_layernorm_kernel(
     const float* __restrict__ x, int F, const float* __restrict__ W, const float* __restrict__ bias,
     const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
     const float* __restrict__ post_add, int rows_per_add, float* __restrict__ z_out,
-    float* __restrict__ out, int M) {
+    float* __restrict__ out, int M, const int* __restrict__ run_if) {
     constexpr int H = 256 * V;
+    if (run_if && *run_if == 0) return;   // uniform: before the LDS staging and its barrier
     // W^T [F][H] lives in LDS for the whole workgroup (W is [H][F]: reading it per row straight from
     // global memory is a stride-F gather); each wave then walks rows wave, wave + n_waves, ...
     extern __shared__ __attribute__((aligned(16))) float wt[];
@@ -177,11 +231,11 @@ __global__ __launch_bounds__(256) void embed_layernorm_rows_kernel(
     const float* __restrict__ x, int F, const float* __restrict__ W, const float* __restrict__ bias,
     const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
     const float* __restrict__ post_add, int rows_per_add, float* __restrict__ z_out,
-    float* __restrict__ out, int M) {
+    float* __restrict__ out, int M, const int* __restrict__ run_if) {
     constexpr int H = 256 * V;
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= M) return;
+    if (row >= M || (run_if && *run_if == 0)) return;
     const float* xr = x + (int64_t)row * F;
     f32x4 r[V], g[V], b[V];
     row_load<V>(r, bias, lane);
@@ -305,17 +359,18 @@ extern "C" int e3d_adaln_gate_fwd(const float* x, const float* y, const float* m
     return e3d_launch_status("e3d_adaln_gate_fwd");
 }
 
-extern "C" int e3d_embed_layernorm_fwd(const float* x, int F, const float* W, const float* b,
-                                       const float* gamma, const float* beta, float eps,
-                                       const float* post_add, int rows_per_add, float* z_out,
-                                       float* out, int M, int H, void* stream) {
+// ``run_if`` (device word, may be null): every workgroup returns at once when it is zero
+extern "C" int e3d_embed_layernorm_fwd_ex(const float* x, int F, const float* W, const float* b,
+                                          const float* gamma, const float* beta, float eps,
+                                          const float* post_add, int rows_per_add, float* z_out,
+                                          float* out, int M, int H, const int* run_if, void* stream) {
     E3D_REQUIRE(x && W && b && gamma && beta && out && M > 0, "embed_layernorm: bad arguments");
     E3D_REQUIRE(F >= 1 && F <= 32, "embed_layernorm: F must be in [1,32] (F=%d)", F);
     E3D_REQUIRE(!post_add || rows_per_add >= 1, "embed_layernorm: rows_per_add=%d", rows_per_add);
     if (M <= 512) {   // few rows: one wave per row, no staging
         const dim3 grid((M + 3) / 4), block(256);
         DISPATCH_V(H, hipLaunchKernelGGL(embed_layernorm_rows_kernel<V>, grid, block, 0, (hipStream_t)stream, x, F, W, b,
-                                         gamma, beta, eps, post_add, rows_per_add, z_out, out, M));
+                                         gamma, beta, eps, post_add, rows_per_add, z_out, out, M, run_if));
         return e3d_launch_status("e3d_embed_layernorm_fwd");
     }
     // every workgroup re-stages W^T (F*H*4 bytes of LDS): each one amortises it over >= 32 rows, and a launch that does not
@@ -331,9 +386,37 @@ extern "C" int e3d_embed_layernorm_fwd(const float* x, int F, const float* W, co
         static std::atomic<uint64_t> lds_ok{0};
         e3d_allow_lds(lds_ok, embed_layernorm_kernel<V>, 32 * (size_t)H * sizeof(float));
         hipLaunchKernelGGL(embed_layernorm_kernel<V>, grid, block, lds, (hipStream_t)stream, x, F, W, b, gamma, beta,
-                           eps, post_add, rows_per_add, z_out, out, M);
+                           eps, post_add, rows_per_add, z_out, out, M, run_if);
     });
     return e3d_launch_status("e3d_embed_layernorm_fwd");
+}
+
+extern "C" int e3d_embed_layernorm_fwd(const float* x, int F, const float* W, const float* b,
+                                       const float* gamma, const float* beta, float eps,
+                                       const float* post_add, int rows_per_add, float* z_out,
+                                       float* out, int M, int H, void* stream) {
+    return e3d_embed_layernorm_fwd_ex(x, F, W, b, gamma, beta, eps, post_add, rows_per_add, z_out, out, M, H, nullptr, stream);
+}
+
+extern "C" int e3d_classify_onehot_rows(const float* x, int F, int* idx, int* flag, int M, void* stream) {
+    E3D_REQUIRE(x && idx && flag && M > 0, "classify_onehot_rows: bad arguments");
+    E3D_REQUIRE(F >= 1 && F <= 32, "classify_onehot_rows: F must be in [1,32] (F=%d)", F);
+    const dim3 grid((M + 255) / 256), block(256);
+    if (F % 4 == 0 && ((uintptr_t)x % 16) == 0)
+        hipLaunchKernelGGL(classify_onehot_kernel<true>, grid, block, 0, (hipStream_t)stream, x, F, idx, flag, M);
+    else
+        hipLaunchKernelGGL(classify_onehot_kernel<false>, grid, block, 0, (hipStream_t)stream, x, F, idx, flag, M);
+    return e3d_launch_status("e3d_classify_onehot_rows");
+}
+
+extern "C" int e3d_adaln_gate_indexed_fwd(const float* x, const float* y, const int* idx, const float* table, int table_rows,
+                                          const float* mod, int branch, float* out, int M, int H, void* stream) {
+    E3D_REQUIRE(x && y && idx && table && mod && out && M > 0 && table_rows > 0, "adaln_gate_indexed: bad arguments");
+    E3D_REQUIRE(branch == 0 || branch == 1, "adaln_gate_indexed: branch=%d", branch);
+    const dim3 grid((M + 3) / 4), block(256);
+    DISPATCH_V(H, hipLaunchKernelGGL(adaln_gate_indexed_kernel<V>, grid, block, 0, (hipStream_t)stream, x, y, idx, table,
+                                     table_rows, mod, branch, out, M));
+    return e3d_launch_status("e3d_adaln_gate_indexed_fwd");
 }
 
 extern "C" int e3d_head_linear_fwd(const float* x, const float* W, const float* b, float* out,

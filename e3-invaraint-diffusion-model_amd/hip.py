@@ -19,6 +19,8 @@ _SIGNATURES = {
     "e3d_gemm_bias_act_f32": (c_int, [_P, c_int64, _P, _P, _P, c_int64, c_int, c_int, c_int, c_int, _P]),
     "e3d_gemm_bias_act_f32_split": (c_int, [_P, c_int64, _P, _P, _P, c_int64, c_int, c_int, c_int, c_int, c_int, _P]),
     "e3d_gemm_bias_act_f32_split_ex": (c_int, [_P, c_int64, _P, _P, _P, c_int64, c_int, c_int, c_int, c_int, c_int, _P, c_float, _P]),
+    "e3d_gemm_bias_act_f32_split_gated": (c_int, [_P, c_int64, _P, _P, _P, c_int64, c_int, c_int, c_int, c_int, c_int, _P, c_float,
+                                                  c_int, _P, _P]),
     "e3d_absmax_f32": (c_int, [_P, c_int64, _P, _P]),
     "e3d_relkey_attn_fwd": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int64, c_int64,
                                     _P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
@@ -39,6 +41,9 @@ _SIGNATURES = {
     "e3d_residual_layernorm_fwd": (c_int, [_P, _P, _P, _P, c_float, _P, _P, c_int, c_int, _P]),
     "e3d_adaln_gate_fwd": (c_int, [_P, _P, _P, c_int, c_int, _P, c_int, c_int, _P]),
     "e3d_embed_layernorm_fwd": (c_int, [_P, c_int, _P, _P, _P, _P, c_float, _P, c_int, _P, _P, c_int, c_int, _P]),
+    "e3d_adaln_gate_indexed_fwd": (c_int, [_P, _P, _P, _P, c_int, _P, c_int, _P, c_int, c_int, _P]),
+    "e3d_classify_onehot_rows": (c_int, [_P, c_int, _P, _P, c_int, _P]),
+    "e3d_embed_layernorm_fwd_ex": (c_int, [_P, c_int, _P, _P, _P, _P, c_float, _P, c_int, _P, _P, c_int, c_int, _P, _P]),
     "e3d_nerf_backbone": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
     # training (backward) side
     "e3d_gemm_f32_split_general": (c_int, [_P, c_int64, c_int, _P, c_int64, c_int, _P, _P, c_int64, c_int, c_int,

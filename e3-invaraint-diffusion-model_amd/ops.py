@@ -270,14 +270,24 @@ def _skinny_ok(terms, M, N, K, a):
             and -(-M // 32) * (N // 32) <= SKINNY_MAX_TILES)
 
 
-def gemm(a, weight, bias=None, act=ACT_NONE, out=None, mode=None, absmax=None, prescale=True):
+def gemm_is_tiled(M, mode=None):
+    """Whether ``gemm`` sends a launch of M rows to the tiled split kernels (gemm_split.hip): the only ones that take
+    ``plan_m`` / ``run_if``.  (Conservative below the skinny bound: the tile count is not looked at.)"""
+    terms = GEMM_MODES[GEMM_MODE if mode is None else mode]
+    return terms != 0 and not (terms in (3, 19) and M <= min(SKINNY_MAX_M, SKINNY_GEMM_MAX_M))
+
+
+def gemm(a, weight, bias=None, act=ACT_NONE, out=None, mode=None, absmax=None, prescale=True, plan_m=None, run_if=None):
     """out[M,N] = act(a[M,K] @ weight[N,K]^T + bias).  ``a`` may be a row-strided 2-D view; its start and row stride must
     stay 16-byte aligned (the kernels load float4s): a view that starts off alignment (``x[:, 1:1+K]``) raises a
     RuntimeError naming the alignment, nothing is copied.  ``absmax`` (1-element
     device tensor, act = none): raised to the largest |out| by the kernel's epilogue (split arithmetics; the exact-f32
     kernels have no use for it -- their attention twin never skips key tiles).  ``prescale`` (f16x3 only): run the
     product on the cached power-of-two-scaled copy of the weight (``f16_weight``); False for weights that change every
-    step (the training forward)."""
+    step (the training forward).  ``plan_m`` / ``run_if`` (tiled split kernels only -- ``gemm_is_tiled(plan_m)``; include/e3d_hip.h,
+    e3d_gemm_bias_act_f32_split_gated): the kernel form a launch of plan_m rows would take, so that these rows equal the rows of
+    that launch bit for bit; a one-int device word that, when zero, turns the launch into an empty dispatch (``out`` is
+    then not written)."""
     _chk(a, "gemm.a"); _chk(weight, "gemm.weight"); _chk(bias, "gemm.bias")
     assert a.dim() == 2 and a.stride(1) == 1 and weight.is_contiguous()
     M, K = a.shape
@@ -293,6 +303,17 @@ def gemm(a, weight, bias=None, act=ACT_NONE, out=None, mode=None, absmax=None, p
     scale = 1.0
     if terms == 19 and prescale:
         weight, scale = f16_weight(weight)
+    if plan_m is not None or run_if is not None:
+        _chk(run_if, "gemm.run_if", torch.int32)
+        plan_m = M if plan_m is None else plan_m
+        if not gemm_is_tiled(plan_m, mode):
+            raise ValueError(f"gemm: plan_m / run_if exist on the tiled split kernels only (plan_m={plan_m}, mode={mode or GEMM_MODE})")
+        # (a launch that may be skipped is kept out of the "gemm" records: their time is set against their flops)
+        with _timed("gemm" if run_if is None else "gemm_gated", (M, N, K, act)):
+            hip.check(hip.lib().e3d_gemm_bias_act_f32_split_gated(
+                _p(a), a.stride(0), _p(weight), _p(bias), _p(out), out.stride(0), M, N, K, act, terms, _p(absmax), scale,
+                plan_m, _p(run_if), _stream()), "e3d_gemm_bias_act_f32_split_gated")
+        return out
     with _timed("gemm", (M, N, K, act)):
         if _skinny_ok(terms, M, N, K, a) and out.stride(0) % 4 == 0 and M <= min(SKINNY_MAX_M, SKINNY_GEMM_MAX_M):
             ws = _skinny_workspace(a.device, M, N, K)
@@ -724,7 +745,39 @@ def adaln_gate(x, y, mod, branch, rows_per_cond):
     return out
 
 
-def embed_layernorm(x, weight, bias, gamma, beta, eps, post_add=None, rows_per_add=1, want_z=False):
+def adaln_gate_indexed(x, y, idx, table, mod, branch):
+    """``adaln_gate`` (rows_per_cond = 1) with row r's modulation taken from ``table[idx[r]]`` ([rows, 6H]) where idx[r]
+    names a table row, from ``mod[r]`` ([M, 6H]) elsewhere."""
+    for n, t in (("x", x), ("y", y), ("table", table), ("mod", mod)):
+        _chk(t, "adaln_gate_indexed." + n)
+    _chk(idx, "adaln_gate_indexed.idx", torch.int32)
+    assert x.is_contiguous() and y.is_contiguous() and mod.is_contiguous() and table.is_contiguous() and idx.is_contiguous()
+    M, H = x.shape
+    assert y.shape == x.shape and mod.shape == (M, 6 * H) and table.shape[1] == 6 * H and idx.shape == (M,), (mod.shape, table.shape, idx.shape)
+    out = torch.empty_like(x)
+    with _timed("adaln_gate", (M, H)):
+        hip.check(hip.lib().e3d_adaln_gate_indexed_fwd(_p(x), _p(y), _p(idx), _p(table), table.shape[0], _p(mod), branch,
+                                                       _p(out), M, H, _stream()), "e3d_adaln_gate_indexed_fwd")
+    return out
+
+
+def classify_onehot_rows(x, flag=None):
+    """(idx int32 [M], flag int32 [1]) of x [M, F <= 32]: idx[m] = k for a row that is exactly 1.0 at k and zero elsewhere,
+    F for an all-zero row, -1 for any other row (NaN included); ``flag`` (zeroed here when not given) is raised when any row
+    got -1.  No host synchronisation."""
+    _chk(x, "classify_onehot_rows.x")
+    assert x.dim() == 2 and x.is_contiguous()
+    M, F = x.shape
+    if flag is None:
+        flag = torch.zeros(1, device=x.device, dtype=torch.int32)
+    _chk(flag, "classify_onehot_rows.flag", torch.int32)
+    idx = torch.empty(M, device=x.device, dtype=torch.int32)
+    with _timed("classify_onehot", (M, F)):
+        hip.check(hip.lib().e3d_classify_onehot_rows(_p(x), F, _p(idx), _p(flag), M, _stream()), "e3d_classify_onehot_rows")
+    return idx, flag
+
+
+def embed_layernorm(x, weight, bias, gamma, beta, eps, post_add=None, rows_per_add=1, want_z=False, run_if=None):
     for n, t in (("x", x), ("weight", weight), ("bias", bias), ("gamma", gamma), ("beta", beta),
                  ("post_add", post_add)):
         _chk(t, "embed_layernorm." + n)
@@ -736,10 +789,11 @@ def embed_layernorm(x, weight, bias, gamma, beta, eps, post_add=None, rows_per_a
         assert post_add.is_contiguous() and post_add.shape == (M // rows_per_add, H)
     out = torch.empty((M, H), device=x.device, dtype=torch.float32)
     z = torch.empty_like(out) if want_z else None
-    with _timed("embed_layernorm", (M, H)):
-        hip.check(hip.lib().e3d_embed_layernorm_fwd(_p(x), F, _p(weight), _p(bias), _p(gamma), _p(beta), eps,
-                                                    _p(post_add), rows_per_add, _p(z), _p(out), M, H, _stream()),
-                  "e3d_embed_layernorm_fwd")
+    _chk(run_if, "embed_layernorm.run_if", torch.int32)
+    with _timed("embed_layernorm", (M, H)):   # run_if: as in ``gemm``
+        hip.check(hip.lib().e3d_embed_layernorm_fwd_ex(_p(x), F, _p(weight), _p(bias), _p(gamma), _p(beta), eps,
+                                                       _p(post_add), rows_per_add, _p(z), _p(out), M, H, _p(run_if),
+                                                       _stream()), "e3d_embed_layernorm_fwd_ex")
     return (out, z) if want_z else out
 
 

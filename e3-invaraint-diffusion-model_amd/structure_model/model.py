@@ -11,7 +11,7 @@ from torch import nn
 
 from .. import bert, keyed, ops
 from ..blocks import (BertEmbeddings, GaussianFourierProjection, KeyedDropoutSwitch, Predictor, SELayer, drop_row_keys,
-                      flat2d, require_gpu)
+                      flat2d, onehot_modulation, require_gpu)
 from ..training import adamw
 import os
 
@@ -58,16 +58,20 @@ class ConditionalBertForDiffusionBase(nn.Module):
         ops.reset_absmax(receptor_angles.device)   # |Q|, |K| bounds of the attention calls: fresh per batch / chain
         if layout is not None:
             ang = self.receptor_angle_emb.run(flat2d(layout.pack(receptor_angles)))
-            seq = self.receptor_seq_emb.run(flat2d(layout.pack(receptor_seq)))
-            x = self.receptor_emb.run(ang, seq, None, 1, layout.rows, layout=layout)
+            seq2d = flat2d(layout.pack(receptor_seq))
+            mod = onehot_modulation(self.receptor_emb, self.receptor_seq_emb, seq2d)   # residue types: one-hot rows
+            seq = self.receptor_seq_emb.run(seq2d) if mod is None else None
+            x = self.receptor_emb.run(ang, seq, None, 1, layout.rows, mod=mod, layout=layout)
             x = bert.run_encoder(self.encoder, x, None, 1, layout.rows, layout=layout)
             kv = [bert.project_cross_kv(layer.crossattention, x) for layer in self.decoder.layer] if project_cross_kv else None
             return ReceptorCache(x, kv, None, B, L, layout=layout)
         mask = receptor_attention_masks.contiguous().float()
         rk = drop_row_keys(keyed.DROP_POCKET, L)     # keyed dropout: the key table of the pocket rows
         ang = self.receptor_angle_emb.run(flat2d(receptor_angles), row_keys=rk)
-        seq = self.receptor_seq_emb.run(flat2d(receptor_seq), row_keys=rk)
-        x = self.receptor_emb.run(ang, seq, mask, B, L, row_keys=rk)
+        seq2d = flat2d(receptor_seq)
+        mod = onehot_modulation(self.receptor_emb, self.receptor_seq_emb, seq2d)   # residue types: one-hot rows (inference)
+        seq = self.receptor_seq_emb.run(seq2d, row_keys=rk) if mod is None else None
+        x = self.receptor_emb.run(ang, seq, mask, B, L, mod=mod, row_keys=rk)
         x = bert.run_encoder(self.encoder, x, mask, B, L, row_keys=rk)
         kv = None
         if project_cross_kv:

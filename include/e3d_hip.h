@@ -76,6 +76,16 @@ int e3d_gemm_bias_act_f32_split(const float* A, int64_t lda, const float* W, con
 int e3d_gemm_bias_act_f32_split_ex(const float* A, int64_t lda, const float* W, const float* bias, float* out,
                                    int64_t ldc, int M, int N, int K, int act, int terms, float* out_absmax,
                                    float out_scale, void* stream);
+/* The _ex entry point with two more arguments, for launches whose rows may already be known from a table
+ * (SELayer conditioning on one-hot residue rows, blocks.onehot_modulation):
+ * ``plan_m`` > 0: the kernel form is chosen as for a launch of plan_m rows (0: by M, as the _ex entry point does).  A
+ *   tile's result does not depend on which other row blocks the launch has, so a few rows computed apart with
+ *   plan_m = M_dense equal the same rows of the M_dense-row launch bit for bit.
+ * ``run_if`` (device, one int, may be NULL): every workgroup reads the word first and returns when it is zero -- the
+ *   launch then costs an empty dispatch and ``out`` is not written. */
+int e3d_gemm_bias_act_f32_split_gated(const float* A, int64_t lda, const float* W, const float* bias, float* out,
+                                      int64_t ldc, int M, int N, int K, int act, int terms, float* out_absmax,
+                                      float out_scale, int plan_m, const int* run_if, void* stream);
 /* target = max(target, max_i |x[i]|), same conventions (distance-embedding tables, test aids). */
 int e3d_absmax_f32(const float* x, int64_t n, float* target, void* stream);
 
@@ -192,6 +202,16 @@ int e3d_residual_layernorm_fwd(const float* x, const float* residual, const floa
 int e3d_adaln_gate_fwd(const float* x, const float* y, const float* mod, int branch,
                        int rows_per_cond, float* out, int M, int H, void* stream);
 
+/* The gate with the modulation row looked up: row m takes (shift, scale, gate) from table[idx[m]] ([table_rows, 6H]) when
+ * 0 <= idx[m] < table_rows, from mod[m] ([M, 6H], rows_per_cond = 1) otherwise.  Arithmetic per row as above. */
+int e3d_adaln_gate_indexed_fwd(const float* x, const float* y, const int* idx, const float* table, int table_rows,
+                               const float* mod, int branch, float* out, int M, int H, void* stream);
+
+/* Rows of one-hot features (a residue type per pocket row, or a padding row of zeros): idx[m] = k when row m of x [M,F]
+ * is exactly 1.0f at position k and +0.0f / -0.0f elsewhere, F when every element is zero, -1 otherwise (NaN included).
+ * *flag (device, one int, zeroed by the caller) is set non-zero when any row got -1.  F <= 32. */
+int e3d_classify_onehot_rows(const float* x, int F, int* idx, int* flag, int M, void* stream);
+
 /* BertEmbeddings (structure_model/model.py:111-118, eval):
  *   out[M,H] = LayerNorm_eps(x[M,F] @ W[H,F]^T + b) * gamma + beta (+ post_add[m / rows_per_add])
  * post_add ([M / rows_per_add, H], may be NULL) is the timestep embedding the sequence model
@@ -201,6 +221,11 @@ int e3d_embed_layernorm_fwd(const float* x, int F, const float* W, const float* 
                             const float* gamma, const float* beta, float eps,
                             const float* post_add, int rows_per_add, float* z_out, float* out,
                             int M, int H, void* stream);
+/* ... with ``run_if`` of e3d_gemm_bias_act_f32_split_gated. */
+int e3d_embed_layernorm_fwd_ex(const float* x, int F, const float* W, const float* b,
+                               const float* gamma, const float* beta, float eps,
+                               const float* post_add, int rows_per_add, float* z_out, float* out,
+                               int M, int H, const int* run_if, void* stream);
 
 /* predictor.dense2 (structure_model/model.py:153): out[M,Nout] = x[M,H] @ W[Nout,H]^T + b,
  * Nout <= 32 (8 angles / 20 amino-acid logits). */
