@@ -2,7 +2,8 @@
 as written by the reference's offline preprocessing (clean_data/data_preprocessing.py:838-893).
 This module validates that schema and generates synthetic BioLiP-shaped files for benchmarks/tests
 (SURVEY.md section 8(f) rank 4).  The preprocessing itself (BioLiP meta TSV + PDB/CIF -> DSSP
-features) needs BioLiP downloads, Biopython and a DSSP binary and is out of scope.
+features) needs BioLiP downloads, Biopython and a DSSP binary; featurize.py builds records from PDB
+files with everything the models read (no DSSP features).
 
 Schema of one record (receptor residues first, then ligand residues; N = both):
     structure_ids        dict(pdb_id, receptor_chain, ligand_chain)

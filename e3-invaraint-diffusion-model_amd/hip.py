@@ -132,6 +132,9 @@ _SIGNATURES = {
     "e3d_relkey_attn_bwd_ex_keyed": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int, _P,
                                              _P, _P, _P, _P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int64, c_int64,
                                              _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, c_uint32, _P, _P]),
+    # featurization of PDB coordinates (featurize.py)
+    "e3d_backbone_angles": (c_int, [_P, _P, _P, _P, c_int, c_float, _P]),
+    "e3d_contact_residues": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -619,6 +619,32 @@ int e3d_relkey_attn_bwd_ex_keyed(const float* q, int64_t q_bs, int64_t q_rs, con
                                  int64_t dv_bs, int64_t dv_rs, float* d_dist_emb, float* workspace, int B, int nh, int Lq,
                                  int Lk, int terms, float drop_p, uint32_t site, const uint64_t* row_keys, void* stream);
 
+/* ---- featurization of PDB coordinates (featurize.py; additions to ABI v5)
+ * The inverse direction of e3d_nerf_backbone, and the pocket definition, for records built from PDB files.
+ *   backbone angles: coords [R,4,3] fp32 (N, CA, C, O per residue row, many chains back to back), seg int32 [R] (the chain
+ *     of a row) -> angles [R,8] fp32 radians in the STORED column order of a biolip.pt (omega, phi, psi, dihedral_o, theta1 N:CA:C,
+ *     theta2 CA:C:1N, theta3 1C:N:CA, theta_o CA:C:O; clean_data/data_preprocessing.py:688-731) and status int32 [R].  A row
+ *     is interior when seg[r-1] == seg[r] == seg[r+1]; every other row gets zeros and status bit 0, and no row of another
+ *     chain or outside [0, R) is read.  float64 algebra from the float32 coordinates, atan2 forms (dihedral =
+ *     atan2((n1 x n2) . v2 / |v2|, n1 . n2), angle = atan2(|u x w|, u . w)), one rounding to float32; the dihedral's sign is
+ *     the reference's sign((n1 x n2) . v2).  KNOWN DIFFERENCE: at exact planarity the reference returns 0 (its arccos is
+ *     multiplied by np.sign(0)); this kernel returns +-pi for a trans arrangement.
+ *     status bit 1: a zero-length bond or a zero plane normal (the reference raises / gives NaN): zeros are written.
+ *     status bit 2: C-1 - N or C - N+1 longer than max_peptide_bond (a chain break); the angles are still written, as the
+ *     reference computes across breaks.
+ *   contact residues: hit[row] = 1 when any atom of receptor residue row lies within cutoff (same unit as the coordinates)
+ *     of any ligand atom of the SAME complex, else 0, for all complexes in one launch.  rec_xyz [n_rec_atoms,3] and lig_xyz
+ *     [n_lig_atoms,3] fp32 hold the atoms of complex c at rec_off[c] .. rec_off[c+1]-1 and lig_off[c] .. lig_off[c+1]-1
+ *     (int32 [n_complexes+1], on the device); rec_row int32 [n_rec_atoms] is the residue row of a receptor atom, hit int32
+ *     [n_rows].  n_lig_atoms == 0 (lig_xyz may be null) gives all zeros.  The cutoff is the caller's choice: BioLiP's own
+ *     binding-site rule (van-der-Waals radii) is not reproduced.
+ * Both validate before any launch: null pointers, R > 0, max_peptide_bond > 0, counts, cutoff > 0. */
+int e3d_backbone_angles(const float* coords, const int32_t* seg, float* angles, int32_t* status, int R,
+                        float max_peptide_bond, void* stream);
+int e3d_contact_residues(const float* rec_xyz, const int32_t* rec_row, const int32_t* rec_off, const float* lig_xyz,
+                         const int32_t* lig_off, int32_t* hit, int n_complexes, int n_rec_atoms, int n_lig_atoms, int n_rows,
+                         float cutoff, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
