@@ -175,9 +175,12 @@ def test_keyed_attention_dropout_forward_and_backward(pkg, hip, B, nh, Lq, Lk, P
                                         mult.double())
         ref2d = ref.permute(0, 2, 1, 3).reshape(B * Lq, H)
         ref2d.backward(go.double())
-        figures = [("out", out, ref2d), ("dq", qd.grad, qr.grad)]
+        figures = [("out", out, ref2d)]
         if cross:
-            figures.append(("dkv", kvd.grad, kvr.grad))
+            figures += [("dq", qd.grad, qr.grad), ("dk", kvd.grad[:, :H], kvr.grad[:, :H]), ("dv", kvd.grad[:, H:], kvr.grad[:, H:])]
+        else:
+            figures += [(name, qd.grad[:, part], qr.grad[:, part])
+                        for part, name in ((slice(0, H), "dq"), (slice(H, 2 * H), "dk"), (slice(2 * H, 3 * H), "dv"))]
         if E is not None:
             figures.append(("dE", Ed.grad, Er.grad))
         for name, a, b in figures:
