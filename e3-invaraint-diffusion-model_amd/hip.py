@@ -135,6 +135,8 @@ _SIGNATURES = {
     # featurization of PDB coordinates (featurize.py)
     "e3d_backbone_angles": (c_int, [_P, _P, _P, _P, c_int, c_float, _P]),
     "e3d_contact_residues": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P]),
+    # rigid superposition of structure pairs (evaluate.py)
+    "e3d_superpose_pairs": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

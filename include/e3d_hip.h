@@ -645,6 +645,30 @@ int e3d_contact_residues(const float* rec_xyz, const int32_t* rec_row, const int
                          const int32_t* lig_off, int32_t* hit, int n_complexes, int n_rec_atoms, int n_lig_atoms, int n_rows,
                          float cutoff, void* stream);
 
+/* ---- rigid superposition of structure pairs (evaluate.py; an addition to ABI v5)
+ * Scores sampled backbones: for each pair p the proper rotation R (det R = +1, never a reflection) and translation t that
+ * minimise msd = (1/n) sum_i | R a_i + t - b_i |^2 over the n atoms a_i of structure mob[p] (the mobile one) and b_i of
+ * structure ref[p] (the reference one), and that minimum.  CONVENTION: x' = R x + t maps the mobile structure onto the
+ * reference one; rot is row-major.
+ *   xyz fp64 [n_atoms,3]: all structures back to back; off int32 [n_structs+1]: structure s holds atoms off[s] .. off[s+1]-1
+ *   (off[0] = 0); mob, ref int32 [n_pairs]; msd fp64 [n_pairs]; rot fp64 [n_pairs,9] and trans fp64 [n_pairs,3] may be null
+ *   TOGETHER (msd is the same, bit for bit); status int32 [n_pairs].  All on the device.
+ *   status 0: ok.  n = 1 gives msd 0 and R = identity; a collinear or planar set gives one of its minimisers.
+ *   status 1: the two structures differ in atom count.       status 2: both are empty.
+ *   status 3: mob[p] or ref[p] outside [0, n_structs), or an offset of theirs outside [0, n_atoms] or descending; nothing is
+ *             read through such an index or offset.
+ *   status 4: a non-finite coordinate (or coordinates whose float64 sums overflow).
+ *   Every status but 0 writes NaN to msd, rot and trans of its pair and leaves the other pairs alone.
+ * Arithmetic: float64 throughout.  Two passes (centroids, then the centred cross-covariance S and G = sum |a - abar|^2 +
+ * sum |b - bbar|^2; no raw moments), the largest eigenpair of Horn's symmetric 4x4 matrix of S by cyclic Jacobi with a fixed
+ * maximum of sweeps (a NaN ends in NaN, no loop waits for convergence alone), msd = max(0, (G - 2 lambda) / n).  Take the
+ * square root on the caller's side: on near-identical structures msd is good to ~32 eps64 G / n, which is ~1e-6 Angstrom
+ * of RMSD.  One 64-lane wave per pair, one launch for all pairs.
+ * Validates before any launch: xyz, off, mob, ref, msd, status non-null; rot and trans both null or both set; n_structs,
+ * n_atoms, n_pairs > 0. */
+int e3d_superpose_pairs(const double* xyz, const int32_t* off, const int32_t* mob, const int32_t* ref, double* msd,
+                        double* rot, double* trans, int32_t* status, int n_structs, int n_atoms, int n_pairs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
