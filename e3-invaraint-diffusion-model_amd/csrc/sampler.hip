@@ -1,5 +1,5 @@
-// Diffusion-process kernels: DDPM ancestral update + angular wrap, forward noising, and the
-// discrete (BLOSUM / uniform transition) posterior + categorical draw.  All HBM-bound.
+// Diffusion-process kernels: DDPM ancestral update + angular wrap, the strided (DDIM / respaced) update t -> s < t,
+// forward noising, and the discrete (BLOSUM / uniform transition) posterior + categorical draw.  All HBM-bound.
 // The keyed forms (seeded chains) generate their draws in-register from (seed, row key, step): e3d_philox.h.
 #include "e3d_common.h"
 #include "e3d_philox.h"
@@ -57,6 +57,62 @@ __global__ __launch_bounds__(256) void ddpm_step_wrap_kernel(
         if (noise) mean = mean + sigma * noise[t];
         out[t] = wrap ? wrap_pi(mean) : mean;
     }
+}
+
+// ---------------------------------------------------------------- strided (DDIM / respaced-ancestral) update
+// The schedule-consistent jump from t to its successor s < t (Song et al. 2021, eqs. 12 and 16) in the x0 form -- the
+// wrap of the x0 estimate is nonlinear, so the update cannot be collapsed into one linear expression:
+//   x0 = (x - s1m e) rsa;  wrap_x0: x0 = wrap_pi(x0);  mean = a_s x0 + c_dir e;  out = mean (+ sigma z);  wrap: wrap_pi(out)
+// Row t of the [T,8] table (structure_model/utils.py, StridedTables) = (s1m, rsa, a_s, c_dir, sigma, 0, 0, 0).  The
+// multiply-adds are written as fmaf, so both kernels (and the tail) round alike whatever the compiler contracts.
+struct StridedCoef { float s1m, rsa, a_s, c_dir, sigma; };
+
+__device__ __forceinline__ StridedCoef strided_row(const float* __restrict__ coef_table, int64_t t) {
+    const float* r = coef_table + 8 * t;
+    return StridedCoef{r[0], r[1], r[2], r[3], r[4]};
+}
+
+__device__ __forceinline__ float strided_elem(const StridedCoef c, float x, float e, float z, bool noisy, int wrap,
+                                              int wrap_x0) {
+    float x0 = fmaf(-c.s1m, e, x) * c.rsa;
+    if (wrap_x0) x0 = wrap_pi(x0);
+    float v = fmaf(c.a_s, x0, c.c_dir * e);
+    if (noisy) v = fmaf(c.sigma, z, v);
+    return wrap ? wrap_pi(v) : v;
+}
+
+// A step index outside [0, T): no table row is read, every output is NaN (a wrong index must not pass for a sample)
+__device__ __forceinline__ void strided_fill_nan(float* __restrict__ out, int64_t n4, int64_t n) {
+    const float q = __builtin_nanf("");
+    const f32x4 qv = {q, q, q, q};
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x, first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (int64_t i = first; i < n4; i += stride) reinterpret_cast<f32x4*>(out)[i] = qv;
+    if (n4 * 4 + first < n) out[n4 * 4 + first] = q;
+}
+
+// ``out`` may be ``x``: every element is read before it is written, by the thread that writes it.
+__global__ __launch_bounds__(256) void strided_step_wrap_kernel(
+    const float* x, const float* __restrict__ eps_hat, const float* __restrict__ noise,
+    const float* __restrict__ coef_table, const int64_t* __restrict__ t_dev, int T, int wrap, int wrap_x0, float* out,
+    int64_t n4, int64_t n) {
+    const int64_t t = t_dev[0];
+    if (t < 0 || t >= T) { strided_fill_nan(out, n4, n); return; }
+    const StridedCoef c = strided_row(coef_table, t);
+    const bool noisy = noise != nullptr && c.sigma != 0.f;   // sigma == 0 (eta = 0, or the last step): nothing is read through noise
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        const f32x4 xv = reinterpret_cast<const f32x4*>(x)[i];
+        const f32x4 ev = reinterpret_cast<const f32x4*>(eps_hat)[i];
+        f32x4 nv = {0.f, 0.f, 0.f, 0.f};
+        if (noisy) nv = reinterpret_cast<const f32x4*>(noise)[i];
+        f32x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = strided_elem(c, xv[j], ev[j], nv[j], noisy, wrap, wrap_x0);
+        reinterpret_cast<f32x4*>(out)[i] = o;
+    }
+    // tail (n % 4)
+    const int64_t r = n4 * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < n) out[r] = strided_elem(c, x[r], eps_hat[r], noisy ? noise[r] : 0.f, noisy, wrap, wrap_x0);
 }
 
 // q(x_t | x_0) of one element: wrap(a_t x0 + s_t noise); shared by the buffer form and the keyed form
@@ -262,6 +318,35 @@ __global__ __launch_bounds__(256) void keyed_ddpm_step_wrap_kernel(
     }
 }
 
+// strided_step_wrap_kernel with the noise generated from stream 1 at step t_dev[0] -- the ancestral keyed kernel's
+// stream, so a pocket's draw at timestep t is the same under either update.  Same arithmetic per element: the result
+// equals the unkeyed form fed with these normals (rows of no item: no noise term; sigma == 0: no Philox call).
+__global__ __launch_bounds__(256) void keyed_strided_step_wrap_kernel(
+    const float* x, const float* __restrict__ eps_hat, const float* __restrict__ coef_table,
+    const int64_t* __restrict__ t_dev, int T, const int64_t* __restrict__ row_keys, uint64_t seed, int wrap, int wrap_x0,
+    float* out, int64_t n4, int nb) {
+    const int64_t t = t_dev[0];
+    if (t < 0 || t >= T) { strided_fill_nan(out, n4, n4 * 4); return; }
+    const StridedCoef c = strided_row(coef_table, t);
+    const bool noisy = c.sigma != 0.f;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        const f32x4 xv = reinterpret_cast<const f32x4*>(x)[i];
+        const f32x4 ev = reinterpret_cast<const f32x4*>(eps_hat)[i];
+        const int64_t row = i / nb;
+        uint64_t item;
+        uint32_t pos;
+        const bool has = noisy && keyed_row(row_keys, row, item, pos);
+        float nv[4] = {0.f, 0.f, 0.f, 0.f};
+        if (has) e3d_keyed_normal4(e3d_keyed_words(seed, item, E3D_STREAM_STRUCT_STEP, (uint32_t)t, pos,
+                                                   (uint32_t)(i - row * nb)), nv);
+        f32x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = strided_elem(c, xv[j], ev[j], nv[j], has, wrap, wrap_x0);
+        reinterpret_cast<f32x4*>(out)[i] = o;
+    }
+}
+
 // Raw keyed draws of one (stream, step) over a key table (rows of no item: zeros):
 //   kind 0: wrap ? wrap_pi(scale * z) : z, z the normals  -> float [rows, 4 nb]   (wrap + stream 0: keyed x_T)
 //   kind 1: uniforms from word 0 of block 0                -> float [rows]
@@ -368,6 +453,20 @@ extern "C" int e3d_ddpm_step_wrap_table(const float* x, const float* eps_hat, co
     return e3d_launch_status("e3d_ddpm_step_wrap_table");
 }
 
+extern "C" int e3d_strided_step_wrap(const float* x, const float* eps_hat, const float* noise, const float* coef_table,
+                                     const int64_t* t_dev, int T, int wrap, int wrap_x0, float* out, int64_t n,
+                                     void* stream) {
+    E3D_REQUIRE(x && eps_hat && coef_table && t_dev && out && n > 0 && T > 0, "strided_step_wrap: bad arguments");
+    E3D_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)eps_hat % 16) == 0 && ((uintptr_t)out % 16) == 0 &&
+                    ((uintptr_t)noise % 16) == 0, "strided_step_wrap: pointers must be 16B aligned");
+    const int64_t n4 = n / 4;
+    int64_t blocks = (n4 + 255) / 256;
+    blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
+    hipLaunchKernelGGL(strided_step_wrap_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, eps_hat, noise,
+                       coef_table, t_dev, T, wrap, wrap_x0, out, n4, n);
+    return e3d_launch_status("e3d_strided_step_wrap");
+}
+
 extern "C" int e3d_q_sample_wrap(const float* x0, const float* noise, const int64_t* t,
                                  const float* sqrt_ab, const float* sqrt_1mab, float* out, int B,
                                  int64_t per, void* stream) {
@@ -420,6 +519,21 @@ extern "C" int e3d_keyed_ddpm_step_wrap(const float* x, const float* eps_hat, co
     hipLaunchKernelGGL(keyed_ddpm_step_wrap_kernel, dim3(keyed_blocks(n4)), dim3(256), 0, (hipStream_t)stream, x, eps_hat,
                        coef_table, t_dev, row_keys, seed, wrap, out, n4, F / 4);
     return e3d_launch_status("e3d_keyed_ddpm_step_wrap");
+}
+
+extern "C" int e3d_keyed_strided_step_wrap(const float* x, const float* eps_hat, const float* coef_table,
+                                           const int64_t* t_dev, int T, const int64_t* row_keys, uint64_t seed, int wrap,
+                                           int wrap_x0, float* out, int64_t rows, int F, void* stream) {
+    E3D_REQUIRE(x && eps_hat && coef_table && t_dev && row_keys && out && rows > 0 && T > 0,
+                "keyed_strided_step_wrap: bad arguments");
+    E3D_REQUIRE(F > 0 && F % 4 == 0 && F / 4 <= 256, "keyed_strided_step_wrap: F must be a multiple of 4 in [4, 1024] (F=%d)", F);
+    E3D_REQUIRE(T <= 65536, "keyed_strided_step_wrap: keyed streams hold steps up to 65535 (T=%d)", T);
+    E3D_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)eps_hat % 16) == 0 && ((uintptr_t)out % 16) == 0,
+                "keyed_strided_step_wrap: pointers must be 16B aligned");
+    const int64_t n4 = rows * (F / 4);
+    hipLaunchKernelGGL(keyed_strided_step_wrap_kernel, dim3(keyed_blocks(n4)), dim3(256), 0, (hipStream_t)stream, x, eps_hat,
+                       coef_table, t_dev, T, row_keys, seed, wrap, wrap_x0, out, n4, F / 4);
+    return e3d_launch_status("e3d_keyed_strided_step_wrap");
 }
 
 extern "C" int e3d_keyed_discrete_posterior_sample(const int32_t* xt_idx, const float* logits, const float* Qsb,

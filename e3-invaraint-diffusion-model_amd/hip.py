@@ -108,6 +108,9 @@ _SIGNATURES = {
     "e3d_keyed_ddpm_step_wrap": (c_int, [_P, _P, _P, _P, _P, c_uint64, c_int, _P, c_int64, c_int, _P]),
     "e3d_keyed_discrete_posterior_sample": (c_int, [_P, _P, _P, _P, _P, c_uint64, _P, _P, c_int, c_int, c_int, _P]),
     "e3d_keyed_draws": (c_int, [_P, c_uint64, c_int, c_int, c_int, c_int, c_int, c_float, _P, c_int64, _P]),
+    # strided (DDIM / respaced) structure update: [T,8] coefficient table, step index on the device
+    "e3d_strided_step_wrap": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P, c_int64, _P]),
+    "e3d_keyed_strided_step_wrap": (c_int, [_P, _P, _P, _P, c_int, _P, c_uint64, c_int, c_int, _P, c_int64, c_int, _P]),
     # keyed training and validation draws (ids and epoch read from device memory)
     "e3d_keyed_timesteps": (c_int, [_P, _P, c_uint64, c_int, c_int, _P, c_int, _P]),
     "e3d_keyed_q_sample_wrap": (c_int, [_P, _P, _P, _P, c_int, c_float, _P, _P, c_uint64, _P, _P, c_int, c_int, c_int, _P]),

@@ -838,6 +838,25 @@ def ddpm_step_wrap_table(x, eps_hat, noise, coef_table, t_dev, wrap=True, out=No
     return out
 
 
+def strided_step_wrap(x, eps_hat, noise, coef_table, t_dev, wrap=True, wrap_x0=False, out=None):
+    """The strided (DDIM / respaced) update t -> successor(t): x0 form with the coefficients in row ``t_dev[0]`` of
+    ``coef_table`` [T,8] (structure_model.utils.StridedTables.coef).  ``noise`` None: no noise term; a row with
+    sigma == 0 reads nothing through ``noise``.  ``wrap_x0``: wrap the x0 estimate to [-pi, pi).  ``out`` may be ``x``."""
+    for n, t in (("x", x), ("eps_hat", eps_hat), ("noise", noise), ("coef_table", coef_table)):
+        _chk(t, "strided_step_wrap." + n)
+    _chk(t_dev, "strided_step_wrap.t_dev", torch.int64)
+    assert x.is_contiguous() and eps_hat.is_contiguous() and coef_table.is_contiguous() and eps_hat.shape == x.shape
+    assert noise is None or (noise.is_contiguous() and noise.shape == x.shape)
+    assert coef_table.dim() == 2 and coef_table.shape[1] == 8
+    if out is None:
+        out = torch.empty_like(x)
+    with _timed("strided_step_wrap"):
+        hip.check(hip.lib().e3d_strided_step_wrap(_p(x), _p(eps_hat), _p(noise), _p(coef_table), _p(t_dev),
+                                                  coef_table.shape[0], int(wrap), int(wrap_x0), _p(out), x.numel(),
+                                                  _stream()), "e3d_strided_step_wrap")
+    return out
+
+
 def q_sample_wrap(x0, noise, t, sqrt_ab, sqrt_1mab):
     for n, tt in (("x0", x0), ("noise", noise), ("sqrt_ab", sqrt_ab), ("sqrt_1mab", sqrt_1mab)):
         _chk(tt, "q_sample_wrap." + n)
@@ -908,6 +927,30 @@ def keyed_ddpm_step_wrap(x, eps_hat, coef_table, t_dev, row_keys, seed, wrap=Tru
         hip.check(hip.lib().e3d_keyed_ddpm_step_wrap(_p(x), _p(eps_hat), _p(coef_table), _p(t_dev), _p(row_keys),
                                                      keyed.check_seed(seed), int(wrap), _p(out), rows, F, _stream()),
                   "e3d_keyed_ddpm_step_wrap")
+    return out
+
+
+def keyed_strided_step_wrap(x, eps_hat, coef_table, t_dev, row_keys, seed, wrap=True, wrap_x0=False, out=None):
+    """strided_step_wrap with the N(0,1) draw generated in the kernel from (seed, row key, stream 1, t_dev[0]) -- the
+    draws of keyed_ddpm_step_wrap at the same step; x / eps_hat [.., F], rows = x.numel() // F, F % 4 == 0."""
+    for n, t in (("x", x), ("eps_hat", eps_hat), ("coef_table", coef_table)):
+        _chk(t, "keyed_strided_step_wrap." + n)
+    _chk(t_dev, "keyed_strided_step_wrap.t_dev", torch.int64)
+    F = x.shape[-1]
+    if F % 4:
+        raise ValueError(f"keyed_strided_step_wrap: the feature count must be a multiple of 4, got {F}")
+    rows = x.numel() // F
+    _chk_keys(row_keys, rows, "keyed_strided_step_wrap")
+    assert x.is_contiguous() and eps_hat.is_contiguous() and coef_table.is_contiguous() and eps_hat.shape == x.shape
+    assert coef_table.dim() == 2 and coef_table.shape[1] == 8
+    if coef_table.shape[0] - 1 > 65535:
+        raise ValueError(f"keyed_strided_step_wrap: keyed streams hold steps up to 65535, the table has {coef_table.shape[0]}")
+    if out is None:
+        out = torch.empty_like(x)
+    with _timed("keyed_strided_step_wrap"):
+        hip.check(hip.lib().e3d_keyed_strided_step_wrap(_p(x), _p(eps_hat), _p(coef_table), _p(t_dev), coef_table.shape[0],
+                                                        _p(row_keys), keyed.check_seed(seed), int(wrap), int(wrap_x0),
+                                                        _p(out), rows, F, _stream()), "e3d_keyed_strided_step_wrap")
     return out
 
 

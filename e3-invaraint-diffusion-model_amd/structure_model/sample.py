@@ -7,6 +7,10 @@ reference's structure_model/sample.py, restructured for the device:
   * update + wrap is one HIP kernel (``e3d_ddpm_step_wrap``) and the trajectory stays in HBM
     until the loop ends (the reference does a blocking D2H copy per step, sample.py:143).
 
+Beyond the reference: ``update="strided"`` (``UPDATE``) visits every STEP-th timestep with the schedule-consistent
+DDIM / respaced-ancestral update of Song et al. 2021 (``e3d_strided_step_wrap``, ``utils.StridedTables``) instead of
+applying one-step coefficients to a STEP-wide jump.
+
 Run as ``python sample.py`` from this directory after editing the constants, like the reference.
 """
 if __package__ in (None, ""):  # executed as a script from inside this directory
@@ -28,7 +32,7 @@ from ..bert import BertConfig
 from ..packing import trimmed_length  # noqa: F401  (S.trimmed_length: bench.py and the tests read it here)
 from .dataset import LigandBindingSiteDataset, NoisedAnglesDataset
 from .model import ConditionalBertForDiffusion
-from .utils import CosineTables
+from .utils import CosineTables, StridedTables
 
 MODEL_PATH = ""  # trained state_dict (same key names as the reference's checkpoints)
 OUTPUT = "./data/output.pkl"
@@ -40,6 +44,16 @@ STEP = 1  # stride over timesteps; >1 trades quality for speed (reference sample
 # samples at full fp32: ``sample()`` runs the fp32-grade f16x3 kernels (two fp16 terms per operand, see ops.py; 4.9e-6
 # from the CPU oracle end to end vs 3.2e-6 for the exact fp32 MFMA path) unless E3D_GEMM_MODE says otherwise.
 ARITHMETIC = "f16x3"
+# Update rule of the chain.  "ancestral": the reference's one-step DDPM update at every visited timestep, whatever STEP is.
+# "strided" (E3D_SAMPLE_UPDATE=strided): the generalised DDIM / respaced-ancestral jump from each visited timestep straight
+# to the next one (Song et al. 2021, eqs. 12 and 16; utils.StridedTables) -- the update that is consistent with the
+# schedule when STEP > 1.  ETA (E3D_SAMPLE_ETA) in [0, 1]: 0 = deterministic DDIM (no draws at all), 1 = the ancestral
+# variance of the respaced chain.  WRAP_X0 (E3D_SAMPLE_WRAP_X0=1): wrap the x0 estimate to [-pi, pi), the angle analogue
+# of clip_denoised -- 1/sqrt(ab_t) reaches 6.4e4 at t = 999 of the cosine schedule.  Sample quality under striding has
+# not been measured here (no trained checkpoint ships with the tree): tools/evaluate_samples.py measures it.
+UPDATE = os.environ.get("E3D_SAMPLE_UPDATE", "ancestral")
+ETA = float(os.environ.get("E3D_SAMPLE_ETA", "0"))
+WRAP_X0 = os.environ.get("E3D_SAMPLE_WRAP_X0", "0") == "1"
 # Packed chains (p_sample_loop(pack=True)): the batch runs on its valid rows only; off by default, E3D_SAMPLE_PACK=1 turns
 # it on for ``sample()``.
 PACK = os.environ.get("E3D_SAMPLE_PACK", "0") == "1"
@@ -80,7 +94,7 @@ def _tables(betas):
 @torch.no_grad()
 def p_sample(model, ligand_mask, ligand_angle_noise, receptor_seq, receptor_mask, receptor_angle,
              timestep, betas, noise=None, receptor_cache=None, out=None, wrap=False, seed=None,
-             item_ids=None) -> torch.Tensor:
+             item_ids=None, strided=None, wrap_x0=False) -> torch.Tensor:
     """One reverse step x_t -> x_{t-1} (reference sample.py:55-99).  Like the reference's
     p_sample the result is NOT wrapped unless ``wrap=True`` (p_sample_loop's sample.py:140-142
     fused into the same kernel).
@@ -90,18 +104,25 @@ def p_sample(model, ligand_mask, ligand_angle_noise, receptor_seq, receptor_mask
     ``noise``: optional injected N(0,1) draw (parity tests); default torch.randn_like on device.
     ``seed``: draw the noise from the keyed stream of (seed, item_ids[b], position) instead (``item_ids`` default
     0 .. B-1; see keyed.py); exclusive with ``noise``.
+    ``strided``: a StridedTables -- the step goes from ``timestep`` straight to its successor in that table's order with
+    the DDIM / respaced update (``wrap_x0``: wrap the x0 estimate); eta == 0 draws nothing.
     """
+    if strided is None and wrap_x0:
+        raise ValueError("p_sample: wrap_x0 belongs to the strided update; pass strided=StridedTables(...)")
     keyed_step = None
     if seed is not None:
         if noise is not None:
             raise ValueError("p_sample: pass either an injected noise or a seed, not both")
         x = ligand_angle_noise
         keyed_step = _keyed_step(seed, keyed.padded_keys(keyed.item_ids(item_ids, x.shape[0]), x.shape[1], x.device),
-                                 _tables(betas), x.device)
+                                 _tables(betas), x.device, strided is None)
     elif item_ids is not None:
         raise ValueError("p_sample: item_ids key the seeded draws; pass a seed with them")
+    if strided is not None:
+        strided = _strided_step(strided, ligand_angle_noise.device, wrap_x0)
     return _reverse_step(model, ligand_mask, ligand_angle_noise, receptor_seq, receptor_mask,
-                         receptor_angle, timestep, betas, noise, receptor_cache, out, wrap=wrap, keyed_step=keyed_step)
+                         receptor_angle, timestep, betas, noise, receptor_cache, out, wrap=wrap, keyed_step=keyed_step,
+                         strided=strided)
 
 
 def _coef_table(tab, dev):
@@ -110,10 +131,18 @@ def _coef_table(tab, dev):
                        dim=1).float().contiguous().to(dev)
 
 
-def _keyed_step(seed, row_keys, tab, dev):
-    """What a keyed reverse step needs besides the state: (row keys, seed, coefficient table)."""
+def _keyed_step(seed, row_keys, tab, dev, ancestral=True):
+    """What a keyed reverse step needs besides the state: (row keys, seed, coefficient table); a strided step brings its
+    own table (``ancestral=False``: None)."""
     keyed.check_steps(tab.betas.shape[0])
-    return row_keys, keyed.check_seed(seed), _coef_table(tab, dev)
+    return row_keys, keyed.check_seed(seed), _coef_table(tab, dev) if ancestral else None
+
+
+def _strided_step(st, dev, wrap_x0):
+    """What a strided reverse step needs besides the state: (StridedTables, its [T,8] table on the device, wrap_x0)."""
+    if not isinstance(st, StridedTables):
+        raise TypeError(f"strided: expected a StridedTables, got {type(st).__name__}")
+    return st, st.coef.contiguous().to(dev), bool(wrap_x0)
 
 
 def keyed_x_T(seed, item_ids, L, n_ft=8, scale=1.0, device=None):
@@ -126,7 +155,7 @@ def keyed_x_T(seed, item_ids, L, n_ft=8, scale=1.0, device=None):
 
 
 def _reverse_step(model, ligand_mask, x_t, receptor_seq, receptor_mask, receptor_angle, timestep,
-                  betas, noise, receptor_cache, out, wrap, mod=None, layout=None, keyed_step=None):
+                  betas, noise, receptor_cache, out, wrap, mod=None, layout=None, keyed_step=None, strided=None):
     tab = _tables(betas)
     if isinstance(timestep, int):
         t_index = timestep
@@ -142,6 +171,17 @@ def _reverse_step(model, ligand_mask, x_t, receptor_seq, receptor_mask, receptor
     beta = float(tab.betas[t_index])
     s1m = float(tab.sqrt_one_minus_alphas_cumprod[t_index])
     x_c = x_t.contiguous().float()
+    if strided is not None:        # t -> its successor in the table's order; the row is read at the device step index
+        st, coef8, wrap_x0 = strided
+        t_dev = timestep.to(device=x_c.device, dtype=torch.long).contiguous()
+        if keyed_step is not None:
+            return ops.keyed_strided_step_wrap(x_c, eps_hat.contiguous(), coef8, t_dev, keyed_step[0], keyed_step[1],
+                                               wrap=wrap, wrap_x0=wrap_x0, out=out)
+        if float(st.coef[t_index, 4]) == 0.0:     # eta == 0, or the last visited step: no draw
+            noise = None
+        else:
+            noise = torch.randn_like(x_c) if noise is None else noise.contiguous()
+        return ops.strided_step_wrap(x_c, eps_hat.contiguous(), noise, coef8, t_dev, wrap=wrap, wrap_x0=wrap_x0, out=out)
     if keyed_step is not None:     # the draw happens in the kernel, at the device step index
         row_keys, seed, coef = keyed_step
         t_dev = timestep.to(device=x_c.device, dtype=torch.long).contiguous()
@@ -161,6 +201,9 @@ class GraphedReverseStep:
     ``self.x`` and the noise draw.  Results are bit-identical to the eager path for the same noise.
     A keyed step (``row_keys`` and ``seed``) generates its draw inside the update kernel from the step index: no noise
     buffer, and bit-identical to the eager keyed step.
+    A strided step (``strided``: a StridedTables) holds that table's [T,8] rows instead and runs
+    ``e3d_strided_step_wrap`` / its keyed form: bit-identical to the eager strided step for the same noise; eta == 0 has
+    no noise buffer and draws nothing.
 
     Default for chains of at most packing.GRAPH_MAX_ROWS token rows (up to ~16 pockets of 64 residues),
     ``use_graph=True`` / E3D_SAMPLE_GRAPH=1 forces it, =0 turns it off.  Measured on MI355X, one 64-residue pocket
@@ -170,12 +213,13 @@ class GraphedReverseStep:
     takes 1.5 ms."""
 
     def __init__(self, model, ligand_mask, cache, tab, x_like, wrap=True, draw=True, mod_table=None, layout=None,
-                 row_keys=None, seed=None):
+                 row_keys=None, seed=None, strided=None, wrap_x0=False):
         """``draw``: the graph draws its own N(0,1) noise each replay; False: ``step`` takes the draw (parity tests).
         ``row_keys`` + ``seed`` (with ``draw``): the draw is the keyed stream of those rows (keyed.py).
         ``mod_table`` [T,6H]: row t = model.timestep_modulation(t), read on the device by the step index.
         ``layout``: the step runs on packed ligand rows (``x_like`` [rows,F]; a packed ``cache``); its segment and tile
-        tables are device tensors fixed for the chain, so the capture holds them like any other argument."""
+        tables are device tensors fixed for the chain, so the capture holds them like any other argument.
+        ``strided`` (+ ``wrap_x0``): the step is the strided update of that StridedTables; ``tab`` is then not read."""
         dev = x_like.device
         self.model, self.mask, self.cache, self.wrap, self.mod_table = model, ligand_mask, cache, wrap, mod_table
         self.layout = layout
@@ -184,9 +228,14 @@ class GraphedReverseStep:
         self.keyed = None if seed is None else (row_keys, keyed.check_seed(seed))
         self.x = torch.empty_like(x_like)
         self.out = torch.empty_like(x_like)
-        self.noise = None if self.keyed is not None else torch.zeros_like(x_like)
-        self.t = torch.zeros((x_like.shape[0],), device=dev, dtype=torch.long)
-        self.coef = _coef_table(tab, dev)
+        self.strided = None if strided is None else _strided_step(strided, dev, wrap_x0)
+        if strided is None and wrap_x0:
+            raise ValueError("wrap_x0 belongs to the strided update")
+        noiseless = self.keyed is not None or (strided is not None and strided.eta == 0.0)
+        self.noise = None if noiseless else torch.zeros_like(x_like)
+        # a valid row for the warm-up and the capture (unvisited rows of a strided table are NaN)
+        self.t = torch.full((x_like.shape[0],), 0 if strided is None else strided.order[-1], device=dev, dtype=torch.long)
+        self.coef = _coef_table(tab, dev) if strided is None else self.strided[1]
         self.draw = draw
         self.x.copy_(x_like)
         side = torch.cuda.Stream(device=dev)
@@ -201,6 +250,17 @@ class GraphedReverseStep:
     def _body(self):
         mod = None if self.mod_table is None else self.mod_table.index_select(0, self.t[:1])
         eps_hat = self.model.decode(self.t, self.x, self.mask, self.cache, mod=mod, layout=self.layout)
+        if self.strided is not None:
+            wrap_x0 = self.strided[2]
+            if self.keyed is not None:
+                ops.keyed_strided_step_wrap(self.x, eps_hat.contiguous(), self.coef, self.t, *self.keyed, wrap=self.wrap,
+                                            wrap_x0=wrap_x0, out=self.out)
+                return
+            if self.draw and self.noise is not None:
+                self.noise.normal_()
+            ops.strided_step_wrap(self.x, eps_hat.contiguous(), self.noise, self.coef, self.t, wrap=self.wrap,
+                                  wrap_x0=wrap_x0, out=self.out)
+            return
         if self.keyed is not None:
             ops.keyed_ddpm_step_wrap(self.x, eps_hat.contiguous(), self.coef, self.t, *self.keyed, wrap=self.wrap,
                                      out=self.out)
@@ -216,7 +276,7 @@ class GraphedReverseStep:
         self.t.fill_(i)
         if x is not self.x:
             self.x.copy_(x)
-        if noise is not None:
+        if noise is not None and self.noise is not None:      # a strided graph at eta == 0 has no noise term
             self.noise.copy_(noise)
         self.graph.replay()
         return self.out
@@ -226,7 +286,8 @@ class GraphedReverseStep:
 def p_sample_loop(model: nn.Module, ligand_mask, ligand_angle_noise, receptor_seq, receptor_mask,
                   receptor_angle, total_timesteps: int, betas, disable_pbar: bool = False,
                   noises=None, return_device: bool = False, step: int = None, use_graph: bool = None,
-                  trim_padding: bool = False, pack: bool = False, seed: int = None, item_ids=None) -> torch.Tensor:
+                  trim_padding: bool = False, pack: bool = False, seed: int = None, item_ids=None,
+                  update: str = "ancestral", eta: float = 0.0, wrap_x0: bool = False) -> torch.Tensor:
     """Full reverse chain; returns [T/STEP, B, L, n_ft] (on the host like the reference,
     sample.py:101-144, unless ``return_device``).  ``noises`` [T/STEP,B,L,n_ft] injects the draws.
     ``use_graph``: replay one captured HIP graph per step (None: by size, E3D_SAMPLE_GRAPH=0/1 overrides -- see
@@ -247,10 +308,23 @@ def p_sample_loop(model: nn.Module, ligand_mask, ligand_angle_noise, receptor_se
     a function of (seed, item_ids[b], i, l) alone, generated inside the update kernel -- the same whatever the batch, its
     order, the frame (padded / trimmed / packed) or eager / graph launches.  ``item_ids`` default to 0 .. B-1; pass
     each pocket's own id (the entry point uses the dataset index).  Exclusive with ``noises``.  x_T stays the caller's
-    (``keyed_x_T`` draws a keyed one)."""
+    (``keyed_x_T`` draws a keyed one).
+
+    ``update``: "ancestral" (default) applies the reference's one-step DDPM update at every visited timestep, whatever
+    ``step`` is.  "strided" jumps from each visited timestep straight to the next one with the DDIM / respaced-ancestral
+    update (utils.StridedTables, ``e3d_strided_step_wrap``): ``eta`` in [0, 1] scales its noise (0: deterministic, no
+    random number is drawn and torch's generator is left alone; 1: the ancestral variance of the respaced chain),
+    ``wrap_x0`` wraps each step's x0 estimate to [-pi, pi).  The last entry, t = 0, is the wrapped x0 estimate.  Seeded
+    strided chains draw the same stream-1 normals at timestep t as seeded ancestral ones.  ``eta`` / ``wrap_x0`` with
+    the ancestral update raise."""
+    if update not in ("ancestral", "strided"):
+        raise ValueError(f"p_sample_loop: update must be 'ancestral' or 'strided', got {update!r}")
+    if update == "ancestral" and (eta != 0.0 or wrap_x0):
+        raise ValueError("p_sample_loop: eta and wrap_x0 belong to update='strided'")
     step = STEP if step is None else step
     tab = _tables(betas)
     order = list(reversed(range(0, total_timesteps, step)))
+    strided = StridedTables(tab, order, eta) if update == "strided" else None
     x = ligand_angle_noise.contiguous().float()
     ids = None
     if seed is not None:
@@ -273,7 +347,8 @@ def p_sample_loop(model: nn.Module, ligand_mask, ligand_angle_noise, receptor_se
     if noises is not None:
         noises = frame.ligand(noises.to(x.device).float(), dim=1)
     row_keys = None if seed is None else frame.row_keys(ids, x.device)
-    keyed_step = None if seed is None else _keyed_step(seed, row_keys, tab, x.device)
+    keyed_step = None if seed is None else _keyed_step(seed, row_keys, tab, x.device, strided is None)
+    strided_step = None if strided is None else _strided_step(strided, x.device, wrap_x0)
     traj = torch.empty((len(order),) + tuple(x.shape), device=x.device, dtype=torch.float32)
     # what depends on the timestep alone, for the whole chain at once: row t of the table = timestep_modulation(t)
     mod_rows = model.timestep_modulation(torch.tensor(order, device=x.device, dtype=torch.long))
@@ -281,14 +356,16 @@ def p_sample_loop(model: nn.Module, ligand_mask, ligand_angle_noise, receptor_se
     mod_table[order] = mod_rows
     graphed = packing.capture_graph(
         lambda: GraphedReverseStep(model, mask, cache, tab, x, draw=noises is None, mod_table=mod_table, layout=layout,
-                                   row_keys=row_keys, seed=seed), frame.rows, len(order), use_graph)
+                                   row_keys=row_keys, seed=seed, strided=strided, wrap_x0=wrap_x0),
+        frame.rows, len(order), use_graph)
     for n, i in enumerate(order):
         if graphed is not None:
             x = graphed.step(i, graphed.out if n else x, None if noises is None else noises[n])
             traj[n].copy_(x)
         else:
             x = _reverse_step(model, mask, x, None, None, None, i, tab, None if noises is None else noises[n], cache,
-                              traj[n], wrap=True, mod=mod_table[i:i + 1], layout=layout, keyed_step=keyed_step)
+                              traj[n], wrap=True, mod=mod_table[i:i + 1], layout=layout, keyed_step=keyed_step,
+                              strided=strided_step)
     traj = frame.restore(traj, dim=1)                                     # [T/STEP, B, L, F], zeros outside the frame
     return traj if return_device else traj.cpu()
 
@@ -331,7 +408,7 @@ def sample(model, test_angle_ds, all_batches: bool = False, seed: int = None):
 
     ``seed`` (default ``SEED``, E3D_SAMPLE_SEED): keyed draws for x_T and the chain, keyed by the dataset index, so a
     pocket's sample does not depend on the batch size, on its place in the batch, on packing or on an arithmetic
-    re-run of its batch."""
+    re-run of its batch.  The chain's update rule comes from ``STEP``, ``UPDATE``, ``ETA`` and ``WRAP_X0``."""
     seed = SEED if seed is None else seed
     bs = CONFIG["batch_size"]
     items = [test_angle_ds[i] for i in range(len(test_angle_ds))]
@@ -358,7 +435,8 @@ def sample(model, test_angle_ds, all_batches: bool = False, seed: int = None):
                     receptor_seq=receptor_seq[idx].to(DEVICE), receptor_mask=receptor_mask[idx].to(DEVICE),
                     receptor_angle=receptor_angle[idx].to(DEVICE), total_timesteps=test_angle_ds.timesteps,
                     betas=test_angle_ds.alpha_beta_terms["betas"], trim_padding=True,   # sliced to l_i right below
-                    pack=PACK, seed=seed, item_ids=None if seed is None else ids)
+                    pack=PACK, seed=seed, item_ids=None if seed is None else ids, step=STEP, update=UPDATE, eta=ETA,
+                    wrap_x0=WRAP_X0)
 
         sampled = chain(ARITHMETIC)
         if ops.GEMM_MODES.get(ARITHMETIC) == 19 and "E3D_GEMM_MODE" not in os.environ and not bool(torch.isfinite(sampled).all()):

@@ -54,6 +54,56 @@ class CosineTables:
         return {k: getattr(self, k) for k in keys}
 
 
+class StridedTables:
+    """Coefficients of the strided (generalised DDIM / respaced-ancestral) update over a subset of the timesteps
+    (Song et al. 2021, eqs. 12 and 16): the schedule-consistent jump from ``t`` straight to its successor ``s < t``.
+
+    ``order``: the visited timesteps, strictly descending (``reversed(range(0, T, step))``); the successor of
+    ``order[k]`` is ``order[k + 1]``, the last entry's is "-1" (ab_s = 1: the step returns the x0 estimate).
+    ``eta`` in [0, 1]: 0 is deterministic DDIM, 1 the ancestral posterior variance of the respaced chain.
+
+    Derived in float64 from ``tab.betas`` with ab = cumprod(1 - betas), each coefficient rounded to fp32 once:
+
+        sigma = eta sqrt((1 - ab_s) / (1 - ab_t)) sqrt(1 - ab_t / ab_s)
+        s1m = sqrt(1 - ab_t)    rsa = 1 / sqrt(ab_t)    a_s = sqrt(ab_s)    c_dir = sqrt(max(0, 1 - ab_s - sigma^2))
+
+    ``coef`` fp32 [T, 8]: row t = (s1m, rsa, a_s, c_dir, sigma, 0, 0, 0) -- the table ``e3d_strided_step_wrap`` reads by
+    the device step index; rows of timesteps that are not visited are NaN, so a wrong index shows up as NaN.
+    """
+
+    def __init__(self, tab: CosineTables, order, eta: float = 0.0):
+        T = int(tab.betas.shape[0])
+        order = [int(t) for t in order]
+        eta = float(eta)
+        if not 0.0 <= eta <= 1.0:
+            raise ValueError(f"StridedTables: eta must be in [0, 1], got {eta}")
+        if not order:
+            raise ValueError("StridedTables: the order of timesteps is empty")
+        if any(t < 0 or t >= T for t in order):
+            raise ValueError(f"StridedTables: timesteps must lie in [0, {T}), got {order}")
+        if any(a <= b for a, b in zip(order, order[1:])):
+            raise ValueError(f"StridedTables: the order must be strictly descending, got {order}")
+        ab = torch.cumprod(1.0 - tab.betas.double(), dim=0)
+        idx = torch.tensor(order, dtype=torch.long)
+        ab_t = ab[idx]
+        ab_s = torch.cat([ab[idx[1:]], torch.ones(1, dtype=torch.float64)])
+        sigma = eta * torch.sqrt((1.0 - ab_s) / (1.0 - ab_t)) * torch.sqrt(1.0 - ab_t / ab_s)
+        rows = torch.zeros((len(order), 8), dtype=torch.float64)
+        rows[:, 0] = torch.sqrt(1.0 - ab_t)
+        rows[:, 1] = 1.0 / torch.sqrt(ab_t)
+        rows[:, 2] = torch.sqrt(ab_s)
+        rows[:, 3] = torch.sqrt(torch.clamp(1.0 - ab_s - sigma ** 2, min=0.0))
+        rows[:, 4] = sigma
+        self.timesteps, self.order, self.eta = T, order, eta
+        self.coef = torch.full((T, 8), float("nan"), dtype=torch.float32)
+        self.coef[idx] = rows.float()
+
+    def successor(self, t: int) -> int:
+        """The timestep the update at ``t`` lands on; -1 after the last visited one."""
+        k = self.order.index(int(t))
+        return self.order[k + 1] if k + 1 < len(self.order) else -1
+
+
 def cosine_beta_schedule(timesteps: int, s: float = 8e-3) -> torch.Tensor:
     return CosineTables(timesteps, s).betas
 

@@ -249,6 +249,18 @@ int e3d_ddpm_step_wrap_table(const float* x, const float* eps_hat, const float* 
                              const float* coef_table, const int64_t* t_dev, int wrap, float* out,
                              int64_t n, void* stream);
 
+/* One strided (DDIM / respaced-ancestral) update t -> s < t, the schedule-consistent jump of Song et al. 2021, eqs. 12
+ * and 16 (no counterpart in the reference, whose STEP > 1 applies the one-step coefficients).  Per element:
+ *   x0 = (x - s1m * eps_hat) * rsa;   wrap_x0: x0 = wrap_[-pi,pi)(x0)   (the angle analogue of clip_denoised)
+ *   v  = a_s * x0 + c_dir * eps_hat (+ sigma * noise);   out = wrap ? wrap_[-pi,pi)(v) : v
+ * with (s1m, rsa, a_s, c_dir, sigma, 0, 0, 0) = row t_dev[0] of coef_table [T,8] (structure_model/utils.py,
+ * StridedTables: sqrt(1 - ab_t), 1 / sqrt(ab_t), sqrt(ab_s), sqrt(1 - ab_s - sigma^2), sigma).  The step index is read
+ * on the device, so a captured graph replays it.  noise may be NULL (sigma is then taken as 0); nothing is read through
+ * noise when the row's sigma == 0.  t_dev[0] outside [0, T): no table row is read and every output is NaN.  out may
+ * alias x.  n = number of elements. */
+int e3d_strided_step_wrap(const float* x, const float* eps_hat, const float* noise, const float* coef_table,
+                          const int64_t* t_dev, int T, int wrap, int wrap_x0, float* out, int64_t n, void* stream);
+
 /* Forward noising q(x_t | x_0) with wrap (structure_model/dataset.py:211-228):
  *   out[b] = wrap(sqrt_ab[t[b]] * x0[b] + sqrt_1mab[t[b]] * noise[b]),  per = elements per item. */
 int e3d_q_sample_wrap(const float* x0, const float* noise, const int64_t* t,
@@ -285,6 +297,14 @@ int e3d_discrete_q_sample(const int32_t* x0_idx, const float* Qtb, const float* 
 int e3d_keyed_ddpm_step_wrap(const float* x, const float* eps_hat, const float* coef_table, const int64_t* t_dev,
                              const int64_t* row_keys, uint64_t seed, int wrap, float* out, int64_t rows, int F,
                              void* stream);
+
+/* e3d_strided_step_wrap with the noise generated in-register from stream 1 at step t_dev[0], keyed by (item, position,
+ * block) -- the stream of e3d_keyed_ddpm_step_wrap, so a pocket's draw at timestep t is the same under either update.
+ * Equals e3d_strided_step_wrap fed with those normals; rows of no item get no noise term; sigma == 0 draws nothing.
+ * x / eps_hat / out [rows, F], F % 4 == 0, F <= 1024; T <= 65536. */
+int e3d_keyed_strided_step_wrap(const float* x, const float* eps_hat, const float* coef_table, const int64_t* t_dev,
+                                int T, const int64_t* row_keys, uint64_t seed, int wrap, int wrap_x0, float* out,
+                                int64_t rows, int F, void* stream);
 
 /* e3d_discrete_posterior_sample in mode 1 with the uniform of row n = b * L + l drawn from stream 3 at step s_dev[0]
  * with key row_keys[n] (padded [B, L] batches, or a packed buffer as B = 1, L = rows); rows of no item draw u = 0. */

@@ -4,6 +4,7 @@
 (DiscreteUniformTransition, diverse=True) on the generated last-step angles, handed over on the device.
 
     python tools/bench_joint.py [--batch 128] [--seq-len 128] [--t-structure 1000] [--t-sequence 50] [--trim | --pack]
+    python tools/bench_joint.py --stride 20 --update strided [--eta E] [--wrap-x0]    # structure stage: 50 visited timesteps
 """
 import argparse
 import os
@@ -24,9 +25,13 @@ from e3diff_amd.bert import BertConfig  # noqa: E402
 DEV = "cuda:0"
 
 
-def run(batch=128, seq_len=128, t_structure=1000, t_sequence=50, trim=False, device=DEV, pack=False, seed=None):
+def run(batch=128, seq_len=128, t_structure=1000, t_sequence=50, trim=False, device=DEV, pack=False, seed=None,
+        update="ancestral", eta=0.0, wrap_x0=False, stride=1):
     """One GPU's share of BASELINE config 5 (sequence_model/sample_by_generated_angles.py:196-278): structure chain ->
-    hand-over on the device -> sequence chain.  Returns a dict (also the ``joint`` key of bench.py's line)."""
+    hand-over on the device -> sequence chain.  Returns a dict (also the ``joint`` key of bench.py's line).
+    ``update`` / ``eta`` / ``wrap_x0`` / ``stride``: the structure chain's update rule and p_sample_loop's ``step``."""
+    rule = dict(update=update, eta=eta, wrap_x0=wrap_x0) if update != "ancestral" else {}
+    visited = len(range(0, t_structure, stride))
     B, L = batch, seq_len
     from e3diff_amd.structure_model import sample as SS
     from e3diff_amd.structure_model.model import ConditionalBertForDiffusion as SM
@@ -58,11 +63,11 @@ def run(batch=128, seq_len=128, t_structure=1000, t_sequence=50, trim=False, dev
     # warm-up (first launches, allocator)
     SS.p_sample_loop(smodel, dpk["ligand_attn_mask"], x_T, dpk["receptor_seq"], dpk["receptor_attn_mask"],
                      dpk["receptor_angles"], 4, CosineTables(4), disable_pbar=True, return_device=True, step=1, trim_padding=trim,
-                     pack=pack)
+                     pack=pack, **rule)
     t0 = sync()
     traj = SS.p_sample_loop(smodel, dpk["ligand_attn_mask"], x_T, dpk["receptor_seq"], dpk["receptor_attn_mask"],
-                            dpk["receptor_angles"], t_structure, tab, disable_pbar=True, return_device=True, step=1,
-                            trim_padding=trim, pack=pack, seed=seed, item_ids=None if seed is None else range(B))
+                            dpk["receptor_angles"], t_structure, tab, disable_pbar=True, return_device=True, step=stride,
+                            trim_padding=trim, pack=pack, seed=seed, item_ids=None if seed is None else range(B), **rule)
     t1 = sync()
     angles = QJ.angles_from_trajectory(traj, dpk["ligand_attn_mask"])
     schedule = PredefinedNoiseScheduleDiscrete("cosine", t_sequence).to(device)
@@ -75,7 +80,8 @@ def run(batch=128, seq_len=128, t_structure=1000, t_sequence=50, trim=False, dev
     del traj, smodel, qmodel
     torch.cuda.empty_cache()
     return {"pockets": B, "seq_len": L, "frames": "packed valid rows" if pack else "trimmed to the longest ligand / pocket" if trim else "padded to seq_len",
-            "structure_steps": t_structure, "structure_s": t1 - t0, "structure_pocket_steps_per_s": B * t_structure / (t1 - t0),
+            "structure_steps": visited, "structure_timesteps": t_structure, "structure_update": update, "structure_eta": eta,
+            "structure_wrap_x0": wrap_x0, "structure_s": t1 - t0, "structure_pocket_steps_per_s": B * visited / (t1 - t0),
             "sequence_steps": t_sequence, "sequence_s": t2 - t1, "sequence_pocket_steps_per_s": B * t_sequence / (t2 - t1),
             "total_s": t2 - t0, "pockets_per_s": B / (t2 - t0), "trajectory_MiB_on_device": mib}
 
@@ -90,9 +96,15 @@ def main():
     ap.add_argument("--pack", action="store_true", help="pack=True in both chains (the valid rows of every item back to back)")
     ap.add_argument("--seed", type=int, default=None, help="keyed draws in both chains, items keyed 0 .. batch-1 "
                     "(default: torch's generator)")
+    ap.add_argument("--update", choices=("ancestral", "strided"), default="ancestral", help="structure chain; strided: the DDIM / "
+                    "respaced update between visited timesteps")
+    ap.add_argument("--eta", type=float, default=0.0, help="noise scale of the strided update in [0, 1] (0: deterministic)")
+    ap.add_argument("--wrap-x0", action="store_true", help="strided update: wrap the x0 estimate to [-pi, pi)")
+    ap.add_argument("--stride", type=int, default=1, help="structure chain: visit every STRIDE-th timestep")
     a = ap.parse_args()
-    r = run(a.batch, a.seq_len, a.t_structure, a.t_sequence, a.trim, pack=a.pack, seed=a.seed)
-    print(f"joint sampling ({r['frames']}), {r['pockets']} pockets x L={r['seq_len']} on one GPU: structure {r['structure_steps']} steps "
+    r = run(a.batch, a.seq_len, a.t_structure, a.t_sequence, a.trim, pack=a.pack, seed=a.seed, update=a.update, eta=a.eta,
+            wrap_x0=a.wrap_x0, stride=a.stride)
+    print(f"joint sampling ({r['frames']}), {r['pockets']} pockets x L={r['seq_len']} on one GPU: structure {r['structure_steps']} steps ({r['structure_update']}) "
           f"{r['structure_s']:.2f} s ({r['structure_pocket_steps_per_s']:.0f} pocket-steps/s, encoder cached), sequence "
           f"{r['sequence_steps']} steps {r['sequence_s']:.2f} s ({r['sequence_pocket_steps_per_s']:.0f} pocket-steps/s); total "
           f"{r['total_s']:.2f} s = {r['pockets_per_s']:.1f} pockets/s; trajectory kept on device ({r['trajectory_MiB_on_device']:.0f} MiB)",

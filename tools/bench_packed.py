@@ -9,6 +9,7 @@ noise.  Then the sequence chain at tools/bench_joint.py's size (``sequence_leg``
 
     python tools/bench_packed.py [--steps K] [--warmup W]
     python tools/bench_packed.py --leg packed|trimmed --steps K      # only that leg's eager steps (for rocprofv3)
+    python tools/bench_packed.py --update strided [--eta E] [--wrap-x0]   # the timed steps run the strided (DDIM) update
     python tools/bench_packed.py --summarize PACKED_STATS.csv TRIMMED_STATS.csv   # attention kernels of two traces
 
 ``--summarize`` reads two ``rocprofv3 --kernel-trace --stats`` kernel tables (one run per leg) and prints the attention
@@ -142,6 +143,10 @@ def main():
     ap.add_argument("--summarize", nargs=2, metavar=("PACKED_CSV", "TRIMMED_CSV"), default=None)
     ap.add_argument("--seed", type=int, default=None, help="keyed draws in the timed chains, items keyed 0 .. B-1 "
                     "(default: torch's generator)")
+    ap.add_argument("--update", choices=("ancestral", "strided"), default="ancestral", help="update kernel of the timed "
+                    "structure steps; strided: the DDIM / respaced update (table of all 1000 timesteps, as step=1)")
+    ap.add_argument("--eta", type=float, default=0.0, help="noise scale of the strided update in [0, 1] (0: deterministic)")
+    ap.add_argument("--wrap-x0", action="store_true", help="strided update: wrap the x0 estimate to [-pi, pi)")
     args = ap.parse_args()
     if args.summarize:
         s = summarize(*args.summarize, args.steps)
@@ -168,10 +173,11 @@ def main():
     model, pkg = build(device)
     from helpers import synthetic_pockets
     from e3diff_amd.structure_model import sample as S
-    from e3diff_amd.structure_model.utils import CosineTables, modulo_with_wrapped_range
+    from e3diff_amd.structure_model.utils import CosineTables, StridedTables, modulo_with_wrapped_range
 
     pk = {k: v.to(device) for k, v in synthetic_pockets(B, L, seed=1000).items() if torch.is_tensor(v)}
     tab = CosineTables(1000)
+    st = StridedTables(tab, list(reversed(range(1000))), args.eta) if args.update == "strided" else None
     gen = torch.Generator(device=device).manual_seed(0)
     x = modulo_with_wrapped_range(torch.randn(B, L, 8, device=device, generator=gen)).contiguous()
     lm, rm = pk["ligand_attn_mask"], pk["receptor_attn_mask"]
@@ -198,6 +204,7 @@ def main():
         mask, xa, cache, layout = frame(kind)
         keys = frame_keys(kind)
         ks = None if keys is None else S._keyed_step(args.seed, keys, tab, device)
+        ss = None if st is None else S._strided_step(st, device, args.wrap_x0)
         xb = torch.empty_like(xa)
         for k_steps in (args.warmup, steps):
             torch.cuda.synchronize()
@@ -205,7 +212,7 @@ def main():
             for j in range(k_steps):
                 i = 999 - j
                 y = S._reverse_step(model, mask, xa, None, None, None, i, tab, None, cache, xb, True,
-                                    mod=mod_table[i:i + 1], layout=layout, keyed_step=ks)
+                                    mod=mod_table[i:i + 1], layout=layout, keyed_step=ks, strided=ss)
                 xa, xb = y, xa
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
@@ -215,7 +222,8 @@ def main():
         mask, xa, cache, layout = frame(kind)
         keys = frame_keys(kind)
         g = S.GraphedReverseStep(model, None if mask is None else mask.contiguous().float(), cache, tab, xa,
-                                 mod_table=mod_table, layout=layout, row_keys=keys, seed=None if keys is None else args.seed)
+                                 mod_table=mod_table, layout=layout, row_keys=keys, seed=None if keys is None else args.seed,
+                                 strided=st, wrap_x0=args.wrap_x0)
         for k_steps in (args.warmup, steps):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -233,7 +241,7 @@ def main():
         return
 
     out = {"metric": "packed_structure_reverse_step", "unit": "pocket-steps/s", "B": B, "frame": L,
-           "rows": rows_of(frames)}
+           "update": args.update, "eta": args.eta, "wrap_x0": args.wrap_x0, "rows": rows_of(frames)}
     with torch.no_grad():
         out["eager"] = {k: eager(k, args.steps) for k in ("padded", "trimmed", "packed")}
         out["graph"] = {k: graphed(k, args.steps) for k in ("trimmed", "packed")}

@@ -3,6 +3,7 @@
 model (encoder cached, as `structure_model/sample.py` runs it), default arithmetic.  Prints ms per reverse step.
 
     python tools/bench_single.py [--seq-len 64] [--steps 50] [--graph]
+    python tools/bench_single.py --steps 1000 --stride 20 --update strided [--eta E] [--wrap-x0]   # 50 visited timesteps
 """
 import argparse
 import os
@@ -23,9 +24,11 @@ from e3diff_amd.bert import BertConfig  # noqa: E402
 DEV = "cuda:0"
 
 
-def run(seq_len=64, batch=1, steps=50, graph=None, chains=3, seed=None):
+def run(seq_len=64, batch=1, steps=50, graph=None, chains=3, seed=None, update="ancestral", eta=0.0, wrap_x0=False, stride=1):
     """Best of ``chains`` full reverse chains; returns a dict (also the ``single_pocket`` key of bench.py's line).
-    ``seed``: keyed draws (p_sample_loop(seed=...)): the noise is generated inside the update kernel."""
+    ``seed``: keyed draws (p_sample_loop(seed=...)): the noise is generated inside the update kernel.
+    ``update`` / ``eta`` / ``wrap_x0`` / ``stride``: p_sample_loop's update rule and its ``step``; a step of the result
+    is one visited timestep."""
     from e3diff_amd.structure_model import sample as S
     from e3diff_amd.structure_model.model import ConditionalBertForDiffusionBase
     from e3diff_amd.structure_model.utils import CosineTables, modulo_with_wrapped_range
@@ -36,11 +39,13 @@ def run(seq_len=64, batch=1, steps=50, graph=None, chains=3, seed=None):
     pk = {k: v.to(DEV) for k, v in synthetic_pockets(B, L, seed=1).items() if torch.is_tensor(v)}
     x_T = modulo_with_wrapped_range(torch.randn(B, L, 8, device=DEV))
     tab = CosineTables(T)
+    visited = len(range(0, T, stride))
+    rule = dict(update=update, eta=eta, wrap_x0=wrap_x0) if update != "ancestral" else {}
 
     def chain():
         return S.p_sample_loop(model, pk["ligand_attn_mask"], x_T, pk["receptor_seq"], pk["receptor_attn_mask"],
-                               pk["receptor_angles"], T, tab, disable_pbar=True, return_device=True, step=1,
-                               use_graph=None if graph is None else bool(graph), seed=seed)
+                               pk["receptor_angles"], T, tab, disable_pbar=True, return_device=True, step=stride,
+                               use_graph=None if graph is None else bool(graph), seed=seed, **rule)
 
     with pkg.ops.arithmetic(S.ARITHMETIC):
         chain()
@@ -55,7 +60,8 @@ def run(seq_len=64, batch=1, steps=50, graph=None, chains=3, seed=None):
         mode = pkg.ops.GEMM_MODE
     assert bool(torch.isfinite(out).all())
     return {"batch": B, "seq_len": L, "timesteps": T, "arithmetic": mode, "graph_replay": "sampler default" if graph is None else bool(graph),
-            "seed": seed, "ms_per_chain": best * 1e3, "ms_per_step": best / T * 1e3,
+            "seed": seed, "update": update, "eta": eta, "wrap_x0": wrap_x0, "stride": stride, "visited_timesteps": visited,
+            "ms_per_chain": best * 1e3, "ms_per_step": best / visited * 1e3,
             "note": "structure_model/sample.py p_sample_loop: encoder + cross K/V once per chain, 12-layer decoder + DDPM update per step"}
 
 
@@ -95,10 +101,16 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--graph", type=int, default=None, choices=(0, 1), help="1: replay one captured HIP graph per step, 0: eager launches (default: the sampler's own choice)")
     ap.add_argument("--seed", type=int, default=None, help="keyed draws with this seed (default: torch's generator)")
+    ap.add_argument("--update", choices=("ancestral", "strided"), default="ancestral", help="strided: the DDIM / respaced update between visited timesteps")
+    ap.add_argument("--eta", type=float, default=0.0, help="noise scale of the strided update in [0, 1] (0: deterministic)")
+    ap.add_argument("--wrap-x0", action="store_true", help="strided update: wrap the x0 estimate to [-pi, pi)")
+    ap.add_argument("--stride", type=int, default=1, help="visit every STRIDE-th timestep (p_sample_loop's step)")
     a = ap.parse_args()
-    r = run(a.seq_len, a.batch, a.steps, a.graph, seed=a.seed)
-    print(f"single-pocket sampling B={r['batch']} L={r['seq_len']} T={r['timesteps']} ({r['arithmetic']}, skinny GEMM M<={pkg.ops.SKINNY_MAX_M}, "
-          f"graph={a.graph}, seed={a.seed}): {r['ms_per_chain']:.1f} ms per chain = {r['ms_per_step']:.3f} ms per reverse step (encoder cached)", flush=True)
+    r = run(a.seq_len, a.batch, a.steps, a.graph, seed=a.seed, update=a.update, eta=a.eta, wrap_x0=a.wrap_x0, stride=a.stride)
+    print(f"single-pocket sampling B={r['batch']} L={r['seq_len']} T={r['timesteps']} stride={a.stride} update={a.update} eta={a.eta} "
+          f"wrap_x0={a.wrap_x0} ({r['arithmetic']}, skinny GEMM M<={pkg.ops.SKINNY_MAX_M}, graph={a.graph}, seed={a.seed}): "
+          f"{r['ms_per_chain']:.1f} ms per chain = {r['ms_per_step']:.3f} ms per reverse step over {r['visited_timesteps']} visited timesteps "
+          f"(encoder cached)", flush=True)
 
 
 if __name__ == "__main__":
