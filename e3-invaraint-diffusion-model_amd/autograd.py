@@ -601,11 +601,16 @@ def _needs_grad(*tensors):
 
 class functional:
     @staticmethod
-    def linear(x, weight, bias=None, act=ops.ACT_NONE, absmax=None):
+    def linear(x, weight, bias=None, act=ops.ACT_NONE, absmax=None, planes_for=None):
         """``absmax`` (ops.absmax_slot): raised to the largest |output| (act = none); the result then carries it as
-        ``_e3d_absmax`` for ``attention`` (q / k projections)."""
+        ``_e3d_absmax`` for ``attention`` (q / k projections).  ``planes_for`` = (weight, residual) of the
+        ``linear_residual_layernorm`` that is the result's only reader: in inference the result is then returned as
+        ``ops.ActPlanes`` wherever ``ops.gemm_planes_ok``."""
         if _needs_grad(x, weight, bias):
             out = _Linear.apply(x, weight, bias, act, absmax)
+        elif planes_for is not None and absmax is None and ops.gemm_planes_ok(x, weight, bias, act, planes_for[0].shape[0],
+                                                                              planes_for[1]):
+            return ops.gemm(x, weight, bias, act, planes_out=True)
         else:
             out = ops.gemm(x, weight, bias, act, absmax=absmax)
         if absmax is not None:
@@ -613,10 +618,13 @@ class functional:
         return out
 
     @staticmethod
-    def attention(q_src, kv_src, B, nh, Lq, Lk, key_mask=None, dist_emb=None, max_pos=0, drop_p=0.0, row_keys=None):
+    def attention(q_src, kv_src, B, nh, Lq, Lk, key_mask=None, dist_emb=None, max_pos=0, drop_p=0.0, row_keys=None,
+                  planes_for=None):
         """q_src = packed qkv [B*L,3H] (kv_src None, self-attention) or q [B*Lq,H] with packed kv [B*Lk,2H].
         ``drop_p`` > 0 (training): dropout on the attention probabilities.  ``row_keys`` (inside ``ops.keyed_dropout``, here
-        and in ``dropout`` / ``residual_layernorm``): the key table of the site's rows -- here the [B, Lq] query frame."""
+        and in ``dropout`` / ``residual_layernorm``): the key table of the site's rows -- here the [B, Lq] query frame.
+        ``planes_for`` = (out-projection weight, residual) of the ``linear_residual_layernorm`` that is the context's only
+        reader: in inference the context is then returned as ``ops.ActPlanes`` wherever ``ops.attention_planes_ok``."""
         # element bounds left by the projections (functional.linear(..., absmax=)): they let the kernels skip all-padding
         # key tiles when that is provably exact; absent (direct callers) = full sweep
         q_abs = getattr(q_src, "_e3d_absmax", None)
@@ -626,8 +634,10 @@ class functional:
             return _Attention.apply(q_src, kv_src, dist_emb, key_mask, B, nh, Lq, Lk, max_pos, drop_p, bounds, row_keys)
         q, k, v = _Attention._views(q_src, kv_src, nh * 64)
         drop = ops.site_drop(drop_p, row_keys) if drop_p > 0 else None
+        planes = (planes_for is not None and drop is None and
+                  ops.attention_planes_ok(q, k, v, nh, Lq, Lk, planes_for[0].shape[0], planes_for[1]))
         return ops.attention(q, k, v, B, nh, Lq, Lk, key_mask=key_mask, dist_emb=dist_emb, max_pos=max_pos, drop=drop,
-                             bounds=bounds)
+                             bounds=bounds, planes_out=planes)
 
     @staticmethod
     def dropout(x, p, training=True, row_keys=None):

@@ -216,6 +216,12 @@ def _attention_output(att, ctx, x, p_hidden=0.0, row_keys=None):
                                        att.output.LayerNorm.bias, att.eps, p_hidden, row_keys)
 
 
+def _planes_for(att, x, drop):
+    """The consumer of an attention context, for ``F.attention(planes_for=)``: without dropout (inference) the context's only
+    reader is ``_attention_output`` -- out-projection + residual x + LayerNorm -- which may take it as activation planes."""
+    return (att.output.dense.weight, x) if drop[0] == 0 and drop[1] == 0 else None
+
+
 def drop_keys(drop):
     """The row-key table of a ``drop`` value -- (hidden rate, attention rate) or, in a seeded step with keyed dropout,
     (hidden rate, attention rate, key table of the rows being processed: ``ops.KeyedDropout.row_keys``) -- or None."""
@@ -238,7 +244,8 @@ def run_self_attention(att, x, mask, B, L, drop=(0.0, 0.0), layout=None):
         return _attention_output(att, ctx, x)
     ctx = F.attention(qkv, None, B, att.num_heads, L, L, key_mask=mask,
                       dist_emb=sa.distance_embedding.weight if relkey else None,
-                      max_pos=sa.max_position_embeddings, drop_p=drop[1], row_keys=drop_keys(drop))
+                      max_pos=sa.max_position_embeddings, drop_p=drop[1], row_keys=drop_keys(drop),
+                      planes_for=_planes_for(att, x, drop))
     return _attention_output(att, ctx, x, drop[0], drop_keys(drop))
 
 
@@ -258,7 +265,8 @@ def run_cross_attention(att, x, kv, enc_mask, B, Lq, Lk, drop=(0.0, 0.0), layout
         H = att.num_heads * 64
         ctx = ops.attention_varlen(q, kv[:, :H], kv[:, H:], layout, enc_layout, att.num_heads)
         return _attention_output(att, ctx, x)
-    ctx = F.attention(q, kv, B, att.num_heads, Lq, Lk, key_mask=enc_mask, drop_p=drop[1], row_keys=drop_keys(drop))
+    ctx = F.attention(q, kv, B, att.num_heads, Lq, Lk, key_mask=enc_mask, drop_p=drop[1], row_keys=drop_keys(drop),
+                      planes_for=_planes_for(att, x, drop))
     return _attention_output(att, ctx, x, drop[0], drop_keys(drop))
 
 
@@ -273,7 +281,9 @@ def run_layer(layer, x, mask, B, L, cross_kv=None, enc_mask=None, Lk=None, drop=
             raise ValueError("decoder layer needs encoder states")
         x = run_cross_attention(layer.crossattention, x, cross_kv, enc_mask, B, L, Lk, drop, layout=layout,
                                 enc_layout=enc_layout)
-    inter = F.linear(x, layer.intermediate.dense.weight, layer.intermediate.dense.bias, ops.ACT_GELU)
+    # (without dropout -- inference -- the intermediate's only reader is the BertOutput below: it may leave as activation planes)
+    inter = F.linear(x, layer.intermediate.dense.weight, layer.intermediate.dense.bias, ops.ACT_GELU,
+                     planes_for=(layer.output.dense.weight, x) if drop[0] == 0 and drop[1] == 0 else None)
     return F.linear_residual_layernorm(inter, layer.output.dense.weight, layer.output.dense.bias, x,
                                        layer.output.LayerNorm.weight, layer.output.LayerNorm.bias, layer.eps, drop[0],
                                        drop_keys(drop))

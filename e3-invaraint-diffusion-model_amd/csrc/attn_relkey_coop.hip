@@ -172,7 +172,10 @@ __device__ long long e3d_attn_stamps[16][8];
 
 // DROP (training): dropout multipliers on the probabilities, regenerated from (seed, element index) exactly as the
 // per-wave kernel and the backward do (e3d_common.h); the row sum stays un-dropped (softmax first, then dropout).
-template <int W, bool RELKEY, typename E, bool DROP = false>
+// PLANES (inference): ``out`` receives the context as ACTIVATION PLANES of the [B * Lq, nh * 64] matrix -- the split terms in
+// MFMA-fragment order, [32-row block][k16 step][plane][lane] x 16 B (gemm_rowln.hip), the form its one
+// reader (the row-complete out-projection) consumes -- instead of fp32 rows: no transposition, 8 contiguous KB per wave.
+template <int W, bool RELKEY, typename E, bool DROP = false, bool PLANES = false>
 __global__ __launch_bounds__(W * 64, 2) void attn_coop_kernel(
     const float* __restrict__ q, int64_t q_bs, int64_t q_rs, const float* __restrict__ k, int64_t k_bs,
     int64_t k_rs, const float* __restrict__ v, int64_t v_bs, int64_t v_rs, const typename AV<E>::x8* __restrict__ e_frag,
@@ -509,6 +512,35 @@ __global__ __launch_bounds__(W * 64, 2) void attn_coop_kernel(
     KSTAMP(2);   // key sweep done
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     const float inv = 1.0f / l_tot;
+    if constexpr (PLANES) {
+        // o0 / o1 hold this lane's query: register 4 g + j = head dim 8 g + 4 half + j (+ 32 for o1).  A fragment lane wants
+        // the 8 consecutive dims 16 ks + 8 half ..: v_permlane32_swap of registers (8 kl + j, 8 kl + 4 + j) hands the lower
+        // half wave dims 16 kl + j, 16 kl + 4 + j and the upper one dims 16 kl + 8 + j, 16 kl + 12 + j (Lq % 32 == 0: the 32
+        // queries of a wave are one row block, the head's 64 columns its k16 steps 4 h .. 4 h + 3)
+        unsigned char* pb = reinterpret_cast<unsigned char*>(out) +
+                            ((((int64_t)b * Lq + q0) >> 5) * (nh * 4) + 4 * h) * 2048 + lane * 16;
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+            const int r0 = 8 * (ks & 1);
+            float x[8];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float a = (ks < 2 ? o0[r0 + j] : o1[r0 + j]) * inv, c = (ks < 2 ? o0[r0 + 4 + j] : o1[r0 + 4 + j]) * inv;
+                // pin the rounded fp32 products (the values the fp32 form stores) before the split: see the Q fragments above
+                asm volatile("" : "+v"(a));
+                asm volatile("" : "+v"(c));
+                const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(c), false, false);
+                x[j] = __uint_as_float(sw[0]);
+                x[4 + j] = __uint_as_float(sw[1]);
+            }
+            bf16x8 hi, lo;
+            split8x2(x, hi, lo);
+            *reinterpret_cast<bf16x8*>(pb + ks * 2048) = hi;
+            *reinterpret_cast<bf16x8*>(pb + ks * 2048 + 1024) = lo;
+        }
+        if (lse && half == 0 && q0 + qi < Lq) lse[((int64_t)b * nh + h) * Lq + q0 + qi] = m_run * LN2 + logf(l_tot);
+        return;
+    }
     // transpose the 64 x 32 O^T tile through the ring: out rows leave as 256-byte segments
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -542,9 +574,23 @@ template <int W, bool RELKEY, typename E>
 int launch_w(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs, int64_t k_rs, const float* v,
              int64_t v_bs, int64_t v_rs, const void* e_frag, int P, const float* key_mask,
              float* out, float* lse, int B, int nh, int Lq, int Lk, int q_tiles, int skip, E3dBounds bnd, E3dDrop drop,
-             bool dropping, hipStream_t s) {
+             bool dropping, bool planes, hipStream_t s) {
     const size_t lds = 2 * KV_BUF_B + (size_t)W * RING_F * sizeof(float);
     const int groups = q_tiles / W;
+    if (planes) {   // plane output: the 4-wave inference forms only (anything else is the caller's error, never a silent fp32 store)
+        if constexpr (W == 4) {
+            if (!dropping && Lq % 32 == 0) {
+                static std::atomic<uint64_t> lds_ok_p{0};
+                e3d_allow_lds(lds_ok_p, attn_coop_kernel<W, RELKEY, E, false, true>, lds);
+                hipLaunchKernelGGL((attn_coop_kernel<W, RELKEY, E, false, true>), dim3(B * nh * groups), dim3(W * 64), lds, s, q, q_bs,
+                                   q_rs, k, k_bs, k_rs, v, v_bs, v_rs, reinterpret_cast<const typename AV<E>::x8*>(e_frag), P,
+                                   key_mask, out, lse, nh, Lq, Lk, groups, skip, bnd, g_rescale_tau, drop);
+                return e3d_launch_status("e3d_relkey_attn_fwd_split_planes (cooperative)");
+            }
+        }
+        e3d_set_error("attn_coop: plane output exists for the 4-wave inference forms with Lq %% 32 == 0 only");
+        return -1;
+    }
     if constexpr (std::is_same<E, __bf16>::value) {   // dropout exists in the training arithmetic (bf16x3) only
         if (dropping) {
             static std::atomic<uint64_t> lds_ok_d{0};
@@ -566,11 +612,11 @@ template <bool RELKEY, typename E>
 int launch_any(int W, const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs, int64_t k_rs,
                const float* v, int64_t v_bs, int64_t v_rs, const void* e_frag, int P,
                const float* key_mask, float* out, float* lse, int B, int nh, int Lq, int Lk, int q_tiles, int skip,
-               E3dBounds bnd, E3dDrop drop, bool dropping, hipStream_t s) {
+               E3dBounds bnd, E3dDrop drop, bool dropping, bool planes, hipStream_t s) {
 #define E3D_COOP_CASE(w)                                                                                          \
     case w:                                                                                                       \
         return launch_w<w, RELKEY, E>(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, e_frag, P, key_mask, out, lse, B, nh, \
-                                   Lq, Lk, q_tiles, skip, bnd, drop, dropping, s)
+                                   Lq, Lk, q_tiles, skip, bnd, drop, dropping, planes, s)
     switch (W) {
         E3D_COOP_CASE(8);
         E3D_COOP_CASE(4);      // (two- and one-wave groups were lab forms: slower than the per-wave kernel, 20-88 B/lane of scratch)
@@ -585,7 +631,7 @@ template <typename E>
 static int coop_launch_t(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs, int64_t k_rs,
                          const float* v, int64_t v_bs, int64_t v_rs, const float* dist_emb, int P,
                          const float* key_mask, float* out, float* lse, int B, int nh, int Lq, int Lk, int skip,
-                         E3dBounds bnd, void* e_scratch, int e_ready, E3dDrop drop, bool dropping, hipStream_t s) {
+                         E3dBounds bnd, void* e_scratch, int e_ready, E3dDrop drop, bool dropping, bool planes, hipStream_t s) {
     const int q_tiles = (Lq + 31) / 32;
     // Waves per workgroup: 4 (the caller dispatches here for q_tiles % 4 == 0 only).  A 4-wave workgroup holds 78 KB of LDS, so
     // two of them share a CU -- one wave of each per SIMD, with barriers of their own: the two drift apart and one's matrix phases
@@ -601,7 +647,7 @@ static int coop_launch_t(const float* q, int64_t q_bs, int64_t q_rs, const float
     const int W = (w_pref == 8 && q_tiles % 8 == 0) ? 8 : 4;
     if (!dist_emb)
         return launch_any<false, E>(W, q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, nullptr, P, key_mask, out, lse, B, nh,
-                                    Lq, Lk, q_tiles, skip, bnd, drop, dropping, s);
+                                    Lq, Lk, q_tiles, skip, bnd, drop, dropping, planes, s);
     // distance table -> fragment-order hi / lo planes in the caller's scratch (e3d_attn_scratch_bytes(Lk) bytes)
     if (!e_scratch) {
         e3d_set_error("attn_coop: rel-key attention needs the caller's scratch for the distance-table planes");
@@ -612,7 +658,13 @@ static int coop_launch_t(const float* q, int64_t q_bs, int64_t q_rs, const float
         hipLaunchKernelGGL(e_fragments_kernel<E>, dim3((n_items + 255) / 256), dim3(256), 0, s, dist_emb,
                            reinterpret_cast<typename AV<E>::x8*>(e_scratch), P, J0, n_items, (float*)nullptr);
     return launch_any<true, E>(W, q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, e_scratch, P, key_mask, out, lse, B, nh, Lq,
-                               Lk, q_tiles, skip, bnd, drop, dropping, s);
+                               Lk, q_tiles, skip, bnd, drop, dropping, planes, s);
+}
+
+// waves per workgroup the dispatch above picks (plane output exists for 4)
+int e3d_attn_coop_waves(int Lq) {
+    const char* e = getenv("E3D_ATTN_W");
+    return ((e ? atoi(e) : 4) == 8 && ((Lq + 31) / 32) % 8 == 0) ? 8 : 4;
 }
 
 // bf16x3 / f16x3 attention, cooperative kernel.  Same contract as e3d_relkey_attn_fwd_split with terms = 3 / 19
@@ -620,12 +672,13 @@ static int coop_launch_t(const float* q, int64_t q_bs, int64_t q_rs, const float
 int e3d_attn_coop_launch(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs, int64_t k_rs,
                          const float* v, int64_t v_bs, int64_t v_rs, const float* dist_emb, int P,
                          const float* key_mask, float* out, float* lse, int B, int nh, int Lq, int Lk, int skip,
-                         E3dBounds bnd, void* e_scratch, int e_ready, int f16, E3dDrop drop, bool dropping, hipStream_t s) {
+                         E3dBounds bnd, void* e_scratch, int e_ready, int f16, E3dDrop drop, bool dropping, bool planes,
+                         hipStream_t s) {
     if (f16)
         return coop_launch_t<_Float16>(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, dist_emb, P, key_mask, out, lse, B, nh, Lq,
-                                       Lk, skip, bnd, e_scratch, e_ready, drop, dropping, s);
+                                       Lk, skip, bnd, e_scratch, e_ready, drop, dropping, planes, s);
     return coop_launch_t<__bf16>(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, dist_emb, P, key_mask, out, lse, B, nh, Lq, Lk,
-                                 skip, bnd, e_scratch, e_ready, drop, dropping, s);
+                                 skip, bnd, e_scratch, e_ready, drop, dropping, planes, s);
 }
 
 // Diagnostic (tests): threshold of the deferred rescale in log2 units; 0 = raise the maximum on every new one (classic

@@ -213,12 +213,32 @@ extern "C" int e3d_attn_skip_padded_tiles(int enable) {
     return prev;
 }
 
-// the body of e3d_relkey_attn_fwd_split_ex and of its keyed form: ``d`` = the decisions of drop_p
+// whether a call of these strides and lengths lands on the 4-wave cooperative kernel (the one form with a plane output)
+static bool attn_coop_ok(int64_t k_rs, int64_t v_bs, int64_t v_rs, int Lq, int Lk, int terms, bool dropping, bool have_scratch) {
+    static int coop = -1;   // E3D_ATTN_COOP=0: per-wave kernel below for every shape (A/B experiments)
+    if (coop < 0) {
+        const char* e = getenv("E3D_ATTN_COOP");
+        coop = e ? atoi(e) : 1;
+    }
+    // two-wave groups (q_tiles % 4 != 0) measured slower than the per-wave kernel: too little sharing per barrier
+    // the cooperative kernel reads the distance table as fragment-order bf16 planes from a CALLER-provided scratch
+    // (e3d_attn_scratch_bytes); without one the per-wave kernel below serves the call -- the library never allocates.
+    // With dropout (training) the cooperative kernel exists in bf16x3.
+    // (its staging goes through buffer descriptors of one key tile's rows: 32-bit byte offsets and record counts, i.e. an
+    //  item's K / V rows must span less than 2 GiB -- Lk x row stride x 4 bytes; the per-wave kernel serves anything wider)
+    const bool span_ok = (int64_t)Lk * (k_rs > v_rs ? k_rs : v_rs) * 4 < ((int64_t)1 << 31) && k_rs > 0 && v_rs > 0 &&
+                         k_rs < ((int64_t)1 << 24) && v_rs < ((int64_t)1 << 24);     // (a tile's 32 rows in a 32-bit offset)
+    return (terms == 3 || (terms == E3D_TERMS_F16X3 && !dropping)) && coop && span_ok && v_rs % 4 == 0 && v_bs % 4 == 0 &&
+           ((Lq + 31) / 32) % 4 == 0 && have_scratch;
+}
+
+// the body of e3d_relkey_attn_fwd_split_ex and of its keyed form: ``d`` = the decisions of drop_p; ``planes_out``: ``out``
+// receives activation planes (e3d_relkey_attn_fwd_split_planes)
 static int attn_fwd_dispatch(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs, int64_t k_rs,
                              const float* v, int64_t v_bs, int64_t v_rs, const float* dist_emb, int P, const float* key_mask,
                              float* out, float* lse, int B, int nh, int Lq, int Lk, int terms, float drop_p, const E3dDrop d,
                              void* e_scratch, int e_scratch_ready, const float* q_absmax, const float* k_absmax,
-                             float* e_absmax, void* stream) {
+                             float* e_absmax, void* stream, bool planes_out = false) {
     const E3dBounds bnd{q_absmax, k_absmax, dist_emb ? e_absmax : nullptr};
     E3D_REQUIRE(!dist_emb || !q_absmax || e_absmax, "attn_split: rel-key attention with element bounds needs e_absmax too");
     E3D_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "attn_split: drop_p=%g outside [0, 1)", (double)drop_p);
@@ -244,24 +264,11 @@ static int attn_fwd_dispatch(const float* q, int64_t q_bs, int64_t q_rs, const f
         if (rc) return rc;
         e_scratch_ready = 1;
     }
-    static int coop = -1;   // E3D_ATTN_COOP=0: per-wave kernel below for every shape (A/B experiments)
-    if (coop < 0) {
-        const char* e = getenv("E3D_ATTN_COOP");
-        coop = e ? atoi(e) : 1;
-    }
     const bool dropping = drop_p > 0.f;
-    // two-wave groups (q_tiles % 4 != 0) measured slower than the per-wave kernel: too little sharing per barrier
-    // the cooperative kernel reads the distance table as fragment-order bf16 planes from a CALLER-provided scratch
-    // (e3d_attn_scratch_bytes); without one the per-wave kernel below serves the call -- the library never allocates.
-    // With dropout (training) the cooperative kernel exists in bf16x3.
-    // (its staging goes through buffer descriptors of one key tile's rows: 32-bit byte offsets and record counts, i.e. an
-    //  item's K / V rows must span less than 2 GiB -- Lk x row stride x 4 bytes; the per-wave kernel serves anything wider)
-    const bool span_ok = (int64_t)Lk * (k_rs > v_rs ? k_rs : v_rs) * 4 < ((int64_t)1 << 31) && k_rs > 0 && v_rs > 0 &&
-                         k_rs < ((int64_t)1 << 24) && v_rs < ((int64_t)1 << 24);     // (a tile's 32 rows in a 32-bit offset)
-    if ((terms == 3 || (f16 && !dropping)) && coop && span_ok && v_rs % 4 == 0 && v_bs % 4 == 0 && ((Lq + 31) / 32) % 4 == 0 &&
-        (!dist_emb || e_scratch))
+    if (attn_coop_ok(k_rs, v_bs, v_rs, Lq, Lk, terms, dropping, !dist_emb || e_scratch))
         return e3d_attn_coop_launch(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, dist_emb, P, key_mask, out, lse, B, nh,
-                                    Lq, Lk, g_skip_padded, bnd, e_scratch, e_scratch_ready, f16, d, dropping, s);
+                                    Lq, Lk, g_skip_padded, bnd, e_scratch, e_scratch_ready, f16, d, dropping, planes_out, s);
+    E3D_REQUIRE(!planes_out, "attn_split: plane output needs the cooperative kernel (e3d_attn_planes_supported)");
     if (dropping) {   // training with attention-probability dropout, other shapes / arithmetics: per-wave kernel
         if (terms == 3)
             return launch<2, true>(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, dist_emb, P, key_mask, out, lse, B, nh, Lq, Lk, bnd, s, d);
@@ -326,4 +333,24 @@ extern "C" int e3d_relkey_attn_fwd_split_drop_keyed(const float* q, int64_t q_bs
     return e3d_relkey_attn_fwd_split_ex_keyed(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, dist_emb, P, key_mask, out, lse, B,
                                               nh, Lq, Lk, terms, drop_p, site, row_keys, nullptr, 0, nullptr, nullptr, nullptr,
                                               stream);
+}
+
+// Plane output (inference): the context leaves as ACTIVATION PLANES of the [B * Lq, nh * 64] matrix (e3d_activation_planes_f32_split's
+// format, bit for bit the split of what e3d_relkey_attn_fwd_split_ex stores), for e3d_gemm_residual_layernorm_planes_split.
+// Exists where the 4-wave cooperative kernel serves the call: e3d_attn_planes_supported says so beforehand, anything else is an error.
+extern "C" int e3d_attn_planes_supported(int64_t k_rs, int64_t v_bs, int64_t v_rs, int Lq, int Lk, int terms, int have_scratch) {
+    return (terms == 3 || terms == E3D_TERMS_F16X3) && Lq > 0 && Lq % 32 == 0 && Lk > 0 &&
+           attn_coop_ok(k_rs, v_bs, v_rs, Lq, Lk, terms, false, have_scratch != 0) && e3d_attn_coop_waves(Lq) == 4;
+}
+
+extern "C" int e3d_relkey_attn_fwd_split_planes(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs,
+                                                int64_t k_rs, const float* v, int64_t v_bs, int64_t v_rs,
+                                                const float* dist_emb, int P, const float* key_mask, void* out_planes,
+                                                int B, int nh, int Lq, int Lk, int terms, void* e_scratch, int e_scratch_ready,
+                                                const float* q_absmax, const float* k_absmax, float* e_absmax, void* stream) {
+    E3D_REQUIRE(e3d_attn_planes_supported(k_rs, v_bs, v_rs, Lq, Lk, terms, !dist_emb || e_scratch),
+                "attn_split (planes): this call does not land on the 4-wave cooperative kernel (Lq=%d Lk=%d terms=%d)", Lq, Lk, terms);
+    return attn_fwd_dispatch(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, dist_emb, P, key_mask, reinterpret_cast<float*>(out_planes),
+                             nullptr, B, nh, Lq, Lk, terms, 0.f, e3d_drop_make(0.f, 0), e_scratch, e_scratch_ready, q_absmax,
+                             k_absmax, e_absmax, stream, true);
 }

@@ -263,7 +263,10 @@ int e3d_attn_fill_planes(const float* dist_emb, int P, int Lk, void* scratch, in
 int e3d_attn_coop_launch(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs, int64_t k_rs,
                          const float* v, int64_t v_bs, int64_t v_rs, const float* dist_emb, int P,
                          const float* key_mask, float* out, float* lse, int B, int nh, int Lq, int Lk, int skip,
-                         E3dBounds bnd, void* e_scratch, int e_ready, int f16, E3dDrop drop, bool dropping, hipStream_t s);
+                         E3dBounds bnd, void* e_scratch, int e_ready, int f16, E3dDrop drop, bool dropping, bool planes,
+                         hipStream_t s);
+// ``planes``: ``out`` receives activation planes (gemm_rowln.hip) instead of fp32 rows -- 4-wave inference forms, Lq % 32 == 0
+int e3d_attn_coop_waves(int Lq);
 
 // attn_bwd_split.hip: launches A and B of the attention backward in bf16x3 arithmetic (internal)
 int e3d_attn_bwd_split_launch(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs, int64_t k_rs,

@@ -153,7 +153,10 @@ __device__ __forceinline__ int next_tile_rows(int left, int pattern, int group_r
     return left;
 }
 
-template <typename E>
+// A_PLANES: A arrives as activation planes (e3d_activation_planes_f32_split, or written by its producer: DESIGN.md section 2)
+// -- [row block][k16 step][plane][lane] x 16 B, the twin of the weight planes -- so a k32 pair of a 32-row block is 4
+// contiguous KB that land in LDS as they lie, hi and lo fragments are lane-linear ds_read_b128 and the k loop holds no split.
+template <typename E, bool A_PLANES = false>
 __global__ __launch_bounds__(512, 2) void gemm_rowln_kernel(const float* __restrict__ A, int64_t lda,
                                                             const unsigned char* __restrict__ Wp, const float* __restrict__ bias,
                                                             const float* __restrict__ res, int64_t ldr,
@@ -181,6 +184,11 @@ __global__ __launch_bounds__(512, 2) void gemm_rowln_kernel(const float* __restr
     auto a_offsets = [&](int rows) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
+            if (A_PLANES) {     // piece q = 1 KB: row block q >> 2 (clamped to the tile), k16 half (q >> 1) & 1, plane q & 1
+                const int q = wid + 8 * i;
+                a_lane[i] = (unsigned)(min(q >> 2, (rows >> 5) - 1) * (K >> 4) * 2048 + (q & 3) * 1024 + lane * 16);
+                continue;
+            }
             const int row = (wid + 8 * i) * 8 + (lane >> 3);
             a_lane[i] = (unsigned)(min(row, rows - 1) * (int)lda + (((lane & 7) ^ ((row >> 1) & 7)) << 2)) * 4u;
         }
@@ -191,7 +199,10 @@ __global__ __launch_bounds__(512, 2) void gemm_rowln_kernel(const float* __restr
     for (int j = 0; j < 2; ++j) r_lane[j] = (unsigned)((2 * wid + j) * (int)ldr + lane * 4) * 4u;
     // A fragment reads: row l31 of m-block m, chunk 4 ks + 2 half + j -- the swizzle acts on address bits 4..6 only, so the
     // chunk's address is the row's (2 half) ^ rx slot XOR-ed with the constants 64 ks and 16 j
-    const int a_roff = LDS_A + l31 * 128 + (((2 * half) ^ ((l31 >> 1) & 7)) << 4);      // m-block m: + m * 4096
+    // (planes: fragment (m, k16 half ks, plane j) of the pair is the lane-linear KB at m * 4096 + ks * 2048 + j * 1024)
+    const int a_roff = A_PLANES ? LDS_A + lane * 16 : LDS_A + l31 * 128 + (((2 * half) ^ ((l31 >> 1) & 7)) << 4);      // m-block m: + m * 4096
+    auto a_frag = [&](int ks, int j) { return A_PLANES ? a_roff + ks * 2048 + j * 1024 : a_roff ^ (64 * ks + 16 * j); };
+    constexpr int A_PAIR_F = A_PLANES ? 1024 : 32;      // floats from one k32 pair of a row (block) to the next
     const int b_roff = (wid * 3) * 2048 + lane * 16;
 
     // k16 step ``src`` of the weight into W buffer ``buf``
@@ -207,7 +218,7 @@ __global__ __launch_bounds__(512, 2) void gemm_rowln_kernel(const float* __restr
     };
     // k32 pair ``pair`` of the tile's rows into A buffer ``buf``
     auto issue_a = [&](const float* a_tile, int pair, int buf) {
-        const unsigned char* g = reinterpret_cast<const unsigned char*>(a_tile + pair * 32);
+        const unsigned char* g = reinterpret_cast<const unsigned char*>(a_tile + pair * A_PAIR_F);
         unsigned char* l = smem + LDS_A + buf * A_PAIR + wid * 1024;
         glds16<0>(g + a_lane[0], l);
         glds16<0>(g + a_lane[1], l + 8192);
@@ -280,8 +291,8 @@ __global__ __launch_bounds__(512, 2) void gemm_rowln_kernel(const float* __restr
             bh0[n] = *reinterpret_cast<const X8*>(smem + b_roff + n * 2048);
             bl0[n] = *reinterpret_cast<const X8*>(smem + b_roff + n * 2048 + 1024);
         }
-        x0 = *reinterpret_cast<const f32x4*>(smem + a_cur + a_roff);
-        x1 = *reinterpret_cast<const f32x4*>(smem + a_cur + (a_roff ^ 16));
+        x0 = *reinterpret_cast<const f32x4*>(smem + a_cur + a_frag(0, 0));      // (planes: the hi / lo fragments themselves)
+        x1 = *reinterpret_cast<const f32x4*>(smem + a_cur + a_frag(0, 1));
 
         const bool res_on = res != nullptr && !(ROWLN_LAB & 1);
         const unsigned char* res_tile = reinterpret_cast<const unsigned char*>(res + (int64_t)row0 * ldr);
@@ -303,10 +314,15 @@ __global__ __launch_bounds__(512, 2) void gemm_rowln_kernel(const float* __restr
 #pragma unroll
             for (int m = 0; m < NM; ++m) {
                 X8 ah, al;
-                split8(x0, x1, ah, al);
+                if constexpr (A_PLANES) {
+                    ah = __builtin_bit_cast(X8, x0);
+                    al = __builtin_bit_cast(X8, x1);
+                } else {
+                    split8(x0, x1, ah, al);
+                }
                 if (m + 1 < NM) {       // the next row block's fragment flies under this block's nine MFMAs
-                    x0 = *reinterpret_cast<const f32x4*>(smem + a_cur + ((a_roff ^ (64 * KS)) + (m + 1) * 4096));
-                    x1 = *reinterpret_cast<const f32x4*>(smem + a_cur + ((a_roff ^ (64 * KS + 16)) + (m + 1) * 4096));
+                    x0 = *reinterpret_cast<const f32x4*>(smem + a_cur + (a_frag(KS, 0) + (m + 1) * 4096));
+                    x1 = *reinterpret_cast<const f32x4*>(smem + a_cur + (a_frag(KS, 1) + (m + 1) * 4096));
                 }
 #pragma unroll
                 for (int n = 0; n < 3; ++n) {     // smallest terms first (the order of gemm_split.hip: bit-identical sums)
@@ -331,7 +347,7 @@ __global__ __launch_bounds__(512, 2) void gemm_rowln_kernel(const float* __restr
                         E3D_BARRIER();
                         RSTAMP(stamp_step, 4);
                         if (a_pair_next >= 0) {     // (the last pair fetches nothing: its buffer is the residual ring's third)
-                            const unsigned char* ga = reinterpret_cast<const unsigned char*>(a_tile + a_pair_next * 32);
+                            const unsigned char* ga = reinterpret_cast<const unsigned char*>(a_tile + a_pair_next * A_PAIR_F);
                             unsigned char* la = smem + LDS_A + a_nx2 + wid * 1024;
                             glds16<0>(ga + a_lane[0], la);
                             glds16<0>(ga + a_lane[1], la + 8192);
@@ -346,8 +362,8 @@ __global__ __launch_bounds__(512, 2) void gemm_rowln_kernel(const float* __restr
                         nl[n] = *reinterpret_cast<const X8*>(wn + n * 2048 + 1024);
                     }
                     const int an = KS == 0 ? a_cur : a_nxt;       // step s + 1: same pair (k16 half 1) / next pair (half 0)
-                    y0 = *reinterpret_cast<const f32x4*>(smem + an + (a_roff ^ (64 * (KS ^ 1))));
-                    y1 = *reinterpret_cast<const f32x4*>(smem + an + (a_roff ^ (64 * (KS ^ 1) + 16)));
+                    y0 = *reinterpret_cast<const f32x4*>(smem + an + a_frag(KS ^ 1, 0));
+                    y1 = *reinterpret_cast<const f32x4*>(smem + an + a_frag(KS ^ 1, 1));
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
@@ -572,20 +588,39 @@ __global__ __launch_bounds__(512, 2) void gemm_rowln_kernel(const float* __restr
 #endif
 }
 
-template <typename E>
+template <typename E, bool A_PLANES = false>
 int launch_rowln(const float* A, int64_t lda, const void* Wp, const float* bias, const float* res, int64_t ldr,
                  const float* gamma, const float* beta, float eps, float* out, int64_t ldo, int M, int K, float out_scale,
                  hipStream_t s) {
     static std::atomic<uint64_t> lds_ok{0};
-    e3d_allow_lds(lds_ok, gemm_rowln_kernel<E>, (size_t)LDS_TOTAL);
+    e3d_allow_lds(lds_ok, gemm_rowln_kernel<E, A_PLANES>, (size_t)LDS_TOTAL);
     // one contiguous row group per workgroup, one workgroup per CU: whole 32-row blocks, as even as M allows
     const int n_cu = e3d_cu_count();
     const int rows_per_wg = ((M + n_cu - 1) / n_cu + 31) / 32 * 32;
     const int grid = (M + rows_per_wg - 1) / rows_per_wg;
-    hipLaunchKernelGGL((gemm_rowln_kernel<E>), dim3(grid), dim3(512), LDS_TOTAL, s, A, lda,
+    hipLaunchKernelGGL((gemm_rowln_kernel<E, A_PLANES>), dim3(grid), dim3(512), LDS_TOTAL, s, A, lda,
                        reinterpret_cast<const unsigned char*>(Wp), bias, res, ldr, gamma, beta, eps, out, ldo, M, K, rows_per_wg,
                        out_scale);
-    return e3d_launch_status("e3d_gemm_residual_layernorm_f32_split");
+    return e3d_launch_status(A_PLANES ? "e3d_gemm_residual_layernorm_planes_split" : "e3d_gemm_residual_layernorm_f32_split");
+}
+
+// ---------------------------------------------------------------- activation planes (the format's definition; producers write it themselves)
+// out[((rb * (K / 16) + ks) * 2 + plane) * 1024 + lane * 16 + 2 j] = term_plane(X[rb * 32 + (lane & 31)][ks * 16 + 8 (lane >> 5) + j])
+template <typename E>
+__global__ __launch_bounds__(256) void activation_planes_kernel(const float* __restrict__ X, int64_t ldx, int M, int K,
+                                                                unsigned char* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int64_t piece = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);      // (rb, ks)
+    const int nks = K / 16;
+    if (piece >= (int64_t)(M / 32) * nks) return;
+    const int rb = (int)(piece / nks), ks = (int)(piece % nks);
+    const float* src = X + (int64_t)(rb * 32 + (lane & 31)) * ldx + ks * 16 + 8 * (lane >> 5);
+    const f32x4 a = *reinterpret_cast<const f32x4*>(src), b = *reinterpret_cast<const f32x4*>(src + 4);
+    typename V8<E>::t hi, lo;
+    split8(a, b, hi, lo);
+    unsigned char* dst = out + piece * 2048 + lane * 16;
+    *reinterpret_cast<typename V8<E>::t*>(dst) = hi;
+    *reinterpret_cast<typename V8<E>::t*>(dst + 1024) = lo;
 }
 
 }  // namespace
@@ -633,4 +668,40 @@ extern "C" int e3d_gemm_residual_layernorm_f32_split(const float* A, int64_t lda
     hipStream_t s = (hipStream_t)stream;
     if (terms == 3) return launch_rowln<__bf16>(A, lda, w_planes, bias, residual, ldr, gamma, beta, eps, out, ldo, M, K, out_scale, s);
     return launch_rowln<_Float16>(A, lda, w_planes, bias, residual, ldr, gamma, beta, eps, out, ldo, M, K, out_scale, s);
+}
+
+// ---- activation planes: an [M, K] fp32 activation as its two 16-bit terms in MFMA-fragment order, [row block][k16 step][plane]
+// [lane] x 16 B (as many bytes as the fp32 tensor); the A operand of e3d_gemm_residual_layernorm_planes_split
+extern "C" int64_t e3d_activation_planes_bytes(int M, int K) { return (M % 32 || K % 16 || M <= 0 || K <= 0) ? -1 : (int64_t)M * K * 4; }
+
+extern "C" int e3d_activation_planes_f32_split(const float* X, int64_t ldx, int M, int K, int terms, void* planes, void* stream) {
+    E3D_REQUIRE(X && planes, "activation_planes: null pointer");
+    E3D_REQUIRE(M > 0 && K > 0 && M % 32 == 0 && K % 16 == 0 && ldx >= K && ldx % 4 == 0 && ((uintptr_t)X % 16) == 0 &&
+                    ((uintptr_t)planes % 16) == 0,
+                "activation_planes: need M%%32==0, K%%16==0, ldx%%4==0, 16-byte alignment (M=%d K=%d)", M, K);
+    E3D_REQUIRE(terms == 3 || terms == E3D_TERMS_F16X3, "activation_planes: terms must be 3 or 19 (got %d)", terms);
+    const int64_t pieces = (int64_t)(M / 32) * (K / 16);
+    const dim3 grid((unsigned)((pieces + 3) / 4)), block(256);
+    if (terms == 3) hipLaunchKernelGGL(activation_planes_kernel<__bf16>, grid, block, 0, (hipStream_t)stream, X, ldx, M, K, (unsigned char*)planes);
+    else hipLaunchKernelGGL(activation_planes_kernel<_Float16>, grid, block, 0, (hipStream_t)stream, X, ldx, M, K, (unsigned char*)planes);
+    return e3d_launch_status("e3d_activation_planes_f32_split");
+}
+
+// e3d_gemm_residual_layernorm_f32_split with A given as activation planes of an [M, K] activation (same sums, bit for bit:
+// the kernel reads the terms it would otherwise form itself)
+extern "C" int e3d_gemm_residual_layernorm_planes_split(const void* a_planes, const void* w_planes, const float* bias,
+                                                        const float* residual, int64_t ldr, const float* gamma, const float* beta,
+                                                        float eps, float* out, int64_t ldo, int M, int N, int K, int terms,
+                                                        float out_scale, void* stream) {
+    E3D_REQUIRE(a_planes && w_planes && gamma && beta && out, "gemm_residual_layernorm (planes): null pointer");
+    E3D_REQUIRE(e3d_gemm_residual_layernorm_supported(M, N, K, K),
+                "gemm_residual_layernorm (planes): need M%%32==0, N==768, K%%32==0, K>=64 (M=%d N=%d K=%d)", M, N, K);
+    E3D_REQUIRE(((uintptr_t)a_planes % 16) == 0 && ((uintptr_t)w_planes % 16) == 0 && ldo >= N, "gemm_residual_layernorm (planes): alignment / ldo");
+    E3D_REQUIRE(!residual || (ldr >= N && ldr % 4 == 0 && ((uintptr_t)residual % 16) == 0 && 16 * ldr < (1ll << 31)),
+                "gemm_residual_layernorm (planes): residual needs ldr >= N, ldr%%4==0, 16-byte alignment");
+    E3D_REQUIRE(terms == 3 || terms == E3D_TERMS_F16X3, "gemm_residual_layernorm (planes): terms must be 3 or 19 (got %d)", terms);
+    hipStream_t s = (hipStream_t)stream;
+    const float* A = reinterpret_cast<const float*>(a_planes);
+    if (terms == 3) return launch_rowln<__bf16, true>(A, K, w_planes, bias, residual, ldr, gamma, beta, eps, out, ldo, M, K, out_scale, s);
+    return launch_rowln<_Float16, true>(A, K, w_planes, bias, residual, ldr, gamma, beta, eps, out, ldo, M, K, out_scale, s);
 }

@@ -875,7 +875,14 @@ __global__ __launch_bounds__(WR * WC * 64, 2) void gemm_split256_kernel(const fl
 #define E3D_STORE_OUT(ptr, val) (*(ptr) = (val))
 #endif
 
-template <int ACT, typename E>
+// PLANES (inference): ``out`` receives the [M, N] result as ACTIVATION PLANES (gemm_rowln.hip, DESIGN.md section 2: the two split
+// terms in MFMA-fragment order, [32-row block][k16 step][plane][lane] x 16 B), the form its one reader -- the row-complete
+// GEMM + LayerNorm -- consumes.  The MFMAs then take the weight fragment first and the activation fragment second (the same
+// products summed over the same k in the same order: bit-identical sums), so a lane owns one output ROW and 16 columns of
+// a 32-column block in quads; one v_permlane32_swap per register pair leaves it with 8 consecutive columns, i.e. with its
+// 16 bytes of a fragment: four 16-byte stores per lane and accumulator tile (each wave-store one contiguous KB) against 16
+// dword stores.
+template <int ACT, typename E, bool PLANES = false>
 __global__ __launch_bounds__(512, 2) void gemm_split256p_kernel(const float* __restrict__ A, int64_t lda,
                                                                  const float* __restrict__ W,
                                                                  const float* __restrict__ bias,
@@ -980,9 +987,15 @@ __global__ __launch_bounds__(512, 2) void gemm_split256p_kernel(const float* __r
                     item_load(g);
 #pragma unroll
                     for (int n = 0; n < 2; ++n) {
-                        acc[m][n] = mma16(fa[0][m], fb[1][n], acc[m][n]);
-                        acc[m][n] = mma16(fa[1][m], fb[0][n], acc[m][n]);
-                        acc[m][n] = mma16(fa[0][m], fb[0][n], acc[m][n]);
+                        if constexpr (PLANES) {     // acc^T: rows = output columns, this lane's column = output row a_row[m]
+                            acc[m][n] = mma16(fb[1][n], fa[0][m], acc[m][n]);
+                            acc[m][n] = mma16(fb[0][n], fa[1][m], acc[m][n]);
+                            acc[m][n] = mma16(fb[0][n], fa[0][m], acc[m][n]);
+                        } else {
+                            acc[m][n] = mma16(fa[0][m], fb[1][n], acc[m][n]);
+                            acc[m][n] = mma16(fa[1][m], fb[0][n], acc[m][n]);
+                            acc[m][n] = mma16(fa[0][m], fb[0][n], acc[m][n]);
+                        }
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -992,6 +1005,63 @@ __global__ __launch_bounds__(512, 2) void gemm_split256p_kernel(const float* __r
             cur ^= 1;
         }
 
+        if constexpr (PLANES) {
+            // register 4 g + j of acc[m][n] = output row a_row[m], column 32-block + 8 g + 4 half + j; k16 step kl of the block
+            // (columns 16 kl ..): registers 8 kl + j and 8 kl + 4 + j, swapped across the half waves
+            const int lid = xcd_remap(tile, total);
+            const int row0 = (lid / tiles_n) * BT, col0 = (lid % tiles_n) * BT;
+            unsigned char* const ob = reinterpret_cast<unsigned char*>(out) + lane * 16;
+            const int nks = N >> 4;
+#pragma unroll
+            for (int n = 0; n < 2; ++n) {
+                // the block's 32 bias values through SCALAR loads (a wave-uniform address): a vector load here would sit behind
+                // the stores of the tile before it in the one in-order memory counter, and every wait for it would drain them
+                const int colb = __builtin_amdgcn_readfirstlane(col0 + wc * 64 + n * 32);
+                float bs[32];
+#pragma unroll
+                for (int c = 0; c < 32; ++c) bs[c] = 0.f;
+                if (bias) {
+#pragma unroll
+                    for (int c = 0; c < 32; ++c) bs[c] = bias[colb + c];
+                }
+                float bl[16];      // this lane's bias per accumulator register: column 8 (r >> 2) + 4 half + (r & 3) of the block
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    bl[r] = half ? bs[8 * (r >> 2) + 4 + (r & 3)] : bs[8 * (r >> 2) + (r & 3)];
+                    asm volatile("" : "+v"(bl[r]));      // (selected once per column block, not once per row block)
+                }
+#pragma unroll
+                for (int m = 0; m < 4; ++m) {
+                    unsigned char* o = ob + ((int64_t)((row0 + wr * 128 + m * 32) >> 5) * nks + (colb >> 4)) * 2048;
+#pragma unroll
+                    for (int kl = 0; kl < 2; ++kl) {
+                        f32x4 x0, x1;
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            float a = fmaf(acc[m][n][8 * kl + j], out_scale, bl[8 * kl + j]);
+                            float c = fmaf(acc[m][n][8 * kl + 4 + j], out_scale, bl[8 * kl + 4 + j]);
+                            if (ACT == E3D_ACT_GELU) { a = gelu_erf(a); c = gelu_erf(c); }
+                            if (ACT == E3D_ACT_SILU) { a = silu(a); c = silu(c); }
+                            if (ACT == E3D_ACT_NONE && absmax) { e3d_absmax_accum(amax, a); e3d_absmax_accum(amax, c); }
+                            // pin the rounded fp32 values (what the fp32 form stores) before the split: hipcc may otherwise round
+                            // the hi term straight from an unrounded fused result and the lo term from the rounded one
+                            asm volatile("" : "+v"(a));
+                            asm volatile("" : "+v"(c));
+                            const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(c), false, false);
+                            x0[j] = __uint_as_float(sw[0]);
+                            x1[j] = __uint_as_float(sw[1]);
+                        }
+                        typename Vec<E>::x4 p0[2], p1[2];
+                        split4<2, E>(x0, p0);
+                        split4<2, E>(x1, p1);
+                        typedef typename Vec<E>::x8 X8;
+                        *reinterpret_cast<X8*>(o + kl * 2048) = __builtin_shufflevector(p0[0], p1[0], 0, 1, 2, 3, 4, 5, 6, 7);
+                        *reinterpret_cast<X8*>(o + kl * 2048 + 1024) = __builtin_shufflevector(p0[1], p1[1], 0, 1, 2, 3, 4, 5, 6, 7);
+                    }
+                }
+            }
+            continue;
+        }
         // epilogue: rows m * 32 .. of this wave's 128 x 64 part, one 32-row group at a time (this loop order keeps the
         // kernel free of scratch spills: the n-outer order with one bias load per column block cost 12-36 B/lane)
         const int lid = xcd_remap(tile, total);
@@ -1017,7 +1087,7 @@ __global__ __launch_bounds__(512, 2) void gemm_split256p_kernel(const float* __r
     if (ACT == E3D_ACT_NONE && absmax) e3d_absmax_commit(amax, absmax, lane);
 }
 
-template <int ACT, typename E>
+template <int ACT, typename E, bool PLANES = false>
 int launch256p(const float* A, int64_t lda, const float* W, const float* bias, float* out, int64_t ldc, int M, int N,
                int K, Epi epi, hipStream_t s) {
     const int tiles_m = M / BT, tiles_n = N / BT;
@@ -1025,10 +1095,10 @@ int launch256p(const float* A, int64_t lda, const float* W, const float* bias, f
     static std::atomic<uint64_t> lds_ok{0};
     const int n_cu = e3d_cu_count();
     const int total = tiles_m * tiles_n;
-    e3d_allow_lds(lds_ok, gemm_split256p_kernel<ACT, E>, lds);
-    hipLaunchKernelGGL((gemm_split256p_kernel<ACT, E>), dim3(total < n_cu ? total : n_cu), dim3(512), lds, s, A, lda, W, bias, out,
+    e3d_allow_lds(lds_ok, gemm_split256p_kernel<ACT, E, PLANES>, lds);
+    hipLaunchKernelGGL((gemm_split256p_kernel<ACT, E, PLANES>), dim3(total < n_cu ? total : n_cu), dim3(512), lds, s, A, lda, W, bias, out,
                        ldc, N, K, tiles_m, tiles_n, epi.absmax, epi.scale, epi.run_if);
-    return e3d_launch_status("e3d_gemm_f32_split (persistent 256x256)");
+    return e3d_launch_status(PLANES ? "e3d_gemm_bias_act_planes_split (persistent 256x256)" : "e3d_gemm_f32_split (persistent 256x256)");
 }
 
 int g_general_form = -1;   // E3D_GEMM_FORM, e3d_gemm_general_select: 0 = by shape
@@ -1062,6 +1132,23 @@ int p_min() {
     return v;
 }
 
+// whether a forward-layout 2-term launch of these sizes (form chosen for Mp rows) takes the persistent kernel
+// (``k_min``: the dispatch sends K < 2 k-tiles elsewhere; the kernel's k-tile stream itself runs across tile boundaries at
+//  any K >= one k-tile, which the plane-output entry point uses)
+bool persistent_ok(int M, int Mp, int N, int K, int64_t lda, int64_t ldb, int k_min = 2 * BK) {
+    if (g_tile_pref < 0) {
+        const char* e = getenv("E3D_GEMM_TILE");
+        g_tile_pref = e ? atoi(e) : 4;
+    }
+    // the persistent kernel from 160 tiles upwards -- and from 96 when the output is at least 6 tiles wide (N >= 1536):
+    // there the 128x128 form needs 1.5+ rounds of 256 CUs (M = 4096, N = 1536: 384 tiles), one 256x256 tile per CU
+    // is faster (structure training step 32.0 -> 31.1 ms); narrow outputs with 96-159 tiles (M = 8192, N = 768)
+    // measured 6 % slower on it (sequence step 25.0 -> 26.6 ms) and stay on the 128x128 form
+    const int64_t n_tiles = (int64_t)(Mp / BT) * (N / BT);
+    return N % BT == 0 && M % BT == 0 && Mp % BT == 0 && ldb == K && g_tile_pref >= 4 && K >= k_min && lda < (1 << 22) &&
+           (g_tile_pref >= 5 || n_tiles >= p_min() || (n_tiles >= 96 && N >= 6 * BT && !getenv("E3D_GEMM_P_MIN")));
+}
+
 template <int NS, int ACT, bool A_KMAJ, bool B_KMAJ, typename E>
 int launch(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias, float* out, int64_t ldc,
            int M, int N, int K, Epi epi, hipStream_t s) {
@@ -1072,13 +1159,7 @@ int launch(const float* A, int64_t lda, const float* B, int64_t ldb, const float
     const int Mp = epi.plan_m > 0 ? epi.plan_m : M;   // the row count the form is chosen for
     if constexpr (!A_KMAJ && !B_KMAJ) {
         if constexpr (NS == 2) {
-            // the persistent kernel from 160 tiles upwards -- and from 96 when the output is at least 6 tiles wide (N >= 1536):
-            // there the 128x128 form needs 1.5+ rounds of 256 CUs (M = 4096, N = 1536: 384 tiles), one 256x256 tile per CU
-            // is faster (structure training step 32.0 -> 31.1 ms); narrow outputs with 96-159 tiles (M = 8192, N = 768)
-            // measured 6 % slower on it (sequence step 25.0 -> 26.6 ms) and stay on the 128x128 form
-            const int64_t n_tiles = (int64_t)(Mp / BT) * (N / BT);
-            if (N % BT == 0 && M % BT == 0 && Mp % BT == 0 && ldb == K && g_tile_pref >= 4 && K >= 2 * BK && lda < (1 << 22) &&
-                (g_tile_pref >= 5 || n_tiles >= p_min() || (n_tiles >= 96 && N >= 6 * BT && !getenv("E3D_GEMM_P_MIN"))))
+            if (persistent_ok(M, Mp, N, K, lda, ldb))
                 return launch256p<ACT, E>(A, lda, B, bias, out, ldc, M, N, K, epi, s);
             if (N % BT == 0 && ldb == K && g_tile_pref >= 3 && (int64_t)((Mp + BT - 1) / BT) * (N / BT) >= 256)
                 return launch256<NS, ACT, 2, 4, 2, true, E>(A, lda, B, bias, out, ldc, M, N, K, epi, s);
@@ -1399,4 +1480,33 @@ extern "C" int e3d_gemm_bias_act_f32_split_gated(const float* A, int64_t lda, co
     E3D_REQUIRE(N % BN == 0, "gemm_split: need N%%128==0 (N=%d)", N);
     return gemm_split_general(A, lda, 0, W, (int64_t)K, 0, bias, out, ldc, M, N, K, act, terms, out_absmax, out_scale, stream,
                               plan_m, run_if);
+}
+
+// Plane output (inference): act(A W^T * out_scale + bias) leaves as ACTIVATION PLANES of the [M, N] result (e3d_activation_planes_f32_split's
+// format, bit for bit the split of what e3d_gemm_bias_act_f32_split_ex stores), for e3d_gemm_residual_layernorm_planes_split.
+// Exists on the persistent 256x256 kernel (terms 3 / 19, act none / GELU): e3d_gemm_planes_supported says beforehand whether a
+// launch of these sizes takes it; anything else is an error, never a silent fp32 store.
+extern "C" int e3d_gemm_planes_supported(int M, int N, int K, int64_t lda, int act, int terms) {
+    return (terms == 3 || terms == E3D_TERMS_F16X3) && (act == E3D_ACT_NONE || act == E3D_ACT_GELU) && M > 0 && N > 0 && K > 0 &&
+           K % BK == 0 && lda >= K && lda % 4 == 0 && persistent_ok(M, M, N, K, lda, K, BK);
+}
+
+extern "C" int e3d_gemm_bias_act_planes_split(const float* A, int64_t lda, const float* W, const float* bias, void* out_planes,
+                                              int M, int N, int K, int act, int terms, float* out_absmax, float out_scale,
+                                              void* stream) {
+    E3D_REQUIRE(A && W && out_planes, "gemm_split (planes): null pointer");
+    E3D_REQUIRE(e3d_gemm_planes_supported(M, N, K, lda, act, terms),
+                "gemm_split (planes): this launch does not take the persistent kernel (M=%d N=%d K=%d act=%d terms=%d)", M, N, K, act, terms);
+    E3D_REQUIRE(((uintptr_t)A % 16) == 0 && ((uintptr_t)W % 16) == 0 && ((uintptr_t)bias % 16) == 0 && ((uintptr_t)out_planes % 16) == 0,
+                "gemm_split (planes): A, W, bias and the planes must be 16-byte aligned");
+    E3D_REQUIRE(!out_absmax || act == E3D_ACT_NONE, "gemm_split (planes): out_absmax exists for act = none");
+    const Epi epi{out_absmax, out_scale, 0, nullptr};
+    hipStream_t s = (hipStream_t)stream;
+    float* out = reinterpret_cast<float*>(out_planes);
+    if (terms == 3) {
+        if (act == E3D_ACT_GELU) return launch256p<E3D_ACT_GELU, __bf16, true>(A, lda, W, bias, out, N, M, N, K, epi, s);
+        return launch256p<E3D_ACT_NONE, __bf16, true>(A, lda, W, bias, out, N, M, N, K, epi, s);
+    }
+    if (act == E3D_ACT_GELU) return launch256p<E3D_ACT_GELU, _Float16, true>(A, lda, W, bias, out, N, M, N, K, epi, s);
+    return launch256p<E3D_ACT_NONE, _Float16, true>(A, lda, W, bias, out, N, M, N, K, epi, s);
 }

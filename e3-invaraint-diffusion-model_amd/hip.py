@@ -58,6 +58,17 @@ _SIGNATURES = {
     "e3d_gemm_residual_layernorm_supported": (c_int, [c_int, c_int, c_int, c_int64]),
     "e3d_gemm_residual_layernorm_f32_split": (c_int, [_P, c_int64, _P, _P, _P, c_int64, _P, _P, c_float, _P, c_int64,
                                                       c_int, c_int, c_int, c_int, c_float, _P]),
+    # activation planes: A of the row-complete kernel as written by its producer (additions to ABI v5)
+    "e3d_activation_planes_bytes": (c_int64, [c_int, c_int]),
+    "e3d_activation_planes_f32_split": (c_int, [_P, c_int64, c_int, c_int, c_int, _P, _P]),
+    "e3d_gemm_residual_layernorm_planes_split": (c_int, [_P, _P, _P, _P, c_int64, _P, _P, c_float, _P, c_int64,
+                                                         c_int, c_int, c_int, c_int, c_float, _P]),
+    "e3d_gemm_planes_supported": (c_int, [c_int, c_int, c_int, c_int64, c_int, c_int]),
+    "e3d_gemm_bias_act_planes_split": (c_int, [_P, c_int64, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_float, _P]),
+    "e3d_attn_planes_supported": (c_int, [c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int]),
+    "e3d_relkey_attn_fwd_split_planes": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int64, c_int64,
+                                                 _P, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int,
+                                                 _P, _P, _P, _P]),
     "e3d_gemm_wgrad_ragged_f32_split": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_uint64, c_int, c_int, c_int, _P]),
     "e3d_relkey_attn_bwd_workspace_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
     "e3d_relkey_attn_bwd": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int, _P,

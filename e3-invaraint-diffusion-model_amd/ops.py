@@ -277,7 +277,8 @@ def gemm_is_tiled(M, mode=None):
     return terms != 0 and not (terms in (3, 19) and M <= min(SKINNY_MAX_M, SKINNY_GEMM_MAX_M))
 
 
-def gemm(a, weight, bias=None, act=ACT_NONE, out=None, mode=None, absmax=None, prescale=True, plan_m=None, run_if=None):
+def gemm(a, weight, bias=None, act=ACT_NONE, out=None, mode=None, absmax=None, prescale=True, plan_m=None, run_if=None,
+         planes_out=False):
     """out[M,N] = act(a[M,K] @ weight[N,K]^T + bias).  ``a`` may be a row-strided 2-D view; its start and row stride must
     stay 16-byte aligned (the kernels load float4s): a view that starts off alignment (``x[:, 1:1+K]``) raises a
     RuntimeError naming the alignment, nothing is copied.  ``absmax`` (1-element
@@ -287,16 +288,31 @@ def gemm(a, weight, bias=None, act=ACT_NONE, out=None, mode=None, absmax=None, p
     step (the training forward).  ``plan_m`` / ``run_if`` (tiled split kernels only -- ``gemm_is_tiled(plan_m)``; include/e3d_hip.h,
     e3d_gemm_bias_act_f32_split_gated): the kernel form a launch of plan_m rows would take, so that these rows equal the rows of
     that launch bit for bit; a one-int device word that, when zero, turns the launch into an empty dispatch (``out`` is
-    then not written)."""
+    then not written).  ``planes_out`` (inference; the caller has asked ``gemm_planes_ok``): the result is returned as
+    ``ActPlanes``, the form its one reader -- ``linear_residual_layernorm`` on the row-complete kernel -- consumes."""
     _chk(a, "gemm.a"); _chk(weight, "gemm.weight"); _chk(bias, "gemm.bias")
     assert a.dim() == 2 and a.stride(1) == 1 and weight.is_contiguous()
     M, K = a.shape
     N = weight.shape[0]
     assert weight.shape[1] == K, (a.shape, weight.shape)
+    terms = GEMM_MODES[GEMM_MODE if mode is None else mode]
+    if planes_out:
+        assert out is None and plan_m is None and run_if is None and prescale and terms in (3, 19)
+        if absmax is not None:
+            _chk(absmax, "gemm.absmax")
+            assert act == ACT_NONE and absmax.numel() == 1
+        scale = 1.0
+        if terms == 19:
+            weight, scale = f16_weight(weight)
+        out = torch.empty((M * N * 4,), device=a.device, dtype=torch.uint8)
+        with _timed("gemm", (M, N, K, act)):
+            hip.check(hip.lib().e3d_gemm_bias_act_planes_split(_p(a), a.stride(0), _p(weight), _p(bias), _p(out), M, N, K, act,
+                                                               terms, _p(absmax), scale, _stream()),
+                      "e3d_gemm_bias_act_planes_split")
+        return ActPlanes(out, M, N, terms)
     if out is None:
         out = torch.empty((M, N), device=a.device, dtype=torch.float32)
     assert out.dim() == 2 and out.stride(1) == 1 and out.shape == (M, N)
-    terms = GEMM_MODES[GEMM_MODE if mode is None else mode]
     if absmax is not None:
         _chk(absmax, "gemm.absmax")
         assert act == ACT_NONE and absmax.numel() == 1
@@ -518,14 +534,16 @@ def attn_dropout_mask(B, nh, Lq, Lk, p, seed, device="cuda"):
 
 
 def attention(q, k, v, B, nh, Lq, Lk, key_mask=None, dist_emb=None, max_pos=0, want_lse=False, mode=None, drop=None,
-              bounds=None):
+              bounds=None, planes_out=False):
     """q [B*Lq, >=nh*64] / k, v [B*Lk, ...] row-strided 2-D views (e.g. slices of a fused QKV
     buffer).  Returns ctx [B*Lq, nh*64] (and lse [B,nh,Lq]).  ``drop`` = (p, seed): dropout on the
     normalised probabilities (training); the exact-fp32 mode then runs its fp32-grade bf16x6 twin.  ``drop`` =
     (p, site, row_keys): keyed decisions, row_keys the table of the [B, Lq] query frame.
     ``bounds`` = (q_absmax, k_absmax): 1-element device tensors bounding |element| of the Q rows and of ALL K rows
     (``gemm(..., absmax=)``); with them the split kernels skip all-padding key tiles when that is provably exact,
-    without them every call sweeps all keys."""
+    without them every call sweeps all keys.
+    ``planes_out`` (inference; the caller has asked ``attention_planes_ok``): ctx is returned as ``ActPlanes``, the form
+    its one reader -- ``linear_residual_layernorm`` on the row-complete kernel -- consumes."""
     for n, t in (("q", q), ("k", k), ("v", v), ("key_mask", key_mask), ("dist_emb", dist_emb)):
         _chk(t, "attention." + n)
     assert q.stride(1) == 1 and k.stride(1) == 1 and v.stride(1) == 1
@@ -534,9 +552,13 @@ def attention(q, k, v, B, nh, Lq, Lk, key_mask=None, dist_emb=None, max_pos=0, w
         assert key_mask.is_contiguous() and key_mask.shape == (B, Lk)
     if dist_emb is not None:
         assert dist_emb.is_contiguous() and dist_emb.shape == (2 * max_pos - 1, 64), dist_emb.shape
-    out = torch.empty((B * Lq, nh * 64), device=q.device, dtype=torch.float32)
-    lse = torch.empty((B, nh, Lq), device=q.device, dtype=torch.float32) if want_lse else None
     terms = GEMM_MODES[ATTN_MODE if mode is None else mode]
+    if planes_out:
+        assert not want_lse and (drop is None or drop[0] <= 0) and terms in (3, 19)
+        out = torch.empty((B * Lq * nh * 64 * 4,), device=q.device, dtype=torch.uint8)
+    else:
+        out = torch.empty((B * Lq, nh * 64), device=q.device, dtype=torch.float32)
+    lse = torch.empty((B, nh, Lq), device=q.device, dtype=torch.float32) if want_lse else None
     with _timed("attn_relkey" if dist_emb is not None else "attn_cross", (B, nh, Lq, Lk)):
         args = (_p(q), Lq * q.stride(0), q.stride(0), _p(k), Lk * k.stride(0), k.stride(0),
                 _p(v), Lk * v.stride(0), v.stride(0), _p(dist_emb), max_pos, _p(key_mask), _p(out), _p(lse),
@@ -582,6 +604,11 @@ def attention(q, k, v, B, nh, Lq, Lk, key_mask=None, dist_emb=None, max_pos=0, w
             p, seed = (float(drop[0]), int(drop[1])) if dropping else (0.0, 0)
             if q_abs is None or k_abs is None or (dist_emb is not None and e_abs is None):
                 q_abs = k_abs = e_abs = None
+            if planes_out:
+                hip.check(hip.lib().e3d_relkey_attn_fwd_split_planes(*args[:12], _p(out), B, nh, Lq, Lk, terms, _p(scratch), ready,
+                                                                     _p(q_abs), _p(k_abs), _p(e_abs), _stream()),
+                          "e3d_relkey_attn_fwd_split_planes")
+                return ActPlanes(out, B * Lq, nh * 64, terms)
             if dropping and len(drop) == 3:
                 p, site, keys = _keyed_drop(drop, B * Lq, "attention", nh)
                 hip.check(hip.lib().e3d_relkey_attn_fwd_split_ex_keyed(*args, terms or 6, p, site, keys, _p(scratch), ready,
@@ -663,6 +690,10 @@ def residual_layernorm(x, residual, gamma, beta, eps, want_s=False, drop=None):
 # (tools/lab/rowln_ab.py, f16x3, K = 768 / 1024): M = 65536 257 / 319 us against 323 / 376, M = 32768 137 / 172 against
 # 168 / 208, M = 16384 66 / 83 against 84 / 98, M = 8192 41 / 51 against 53 / 61 (one 32-row tile per CU); smaller launches stay
 # on the skinny / 128 x 128 forms.  E3D_GEMM_ROWLN=0 switches the path off (A/B runs).
+# In inference the kernel's A operand arrives as ACTIVATION PLANES wherever its producer can write them (``ActPlanes`` below:
+# the attention context for BertSelfOutput, the GELU intermediate for BertOutput): the split then happens once in the
+# producer instead of once per consumer wave -- M = 65536: 259 -> 249 us at K = 768, 328 -> 313 us at K = 1024 inside the
+# sampling step, bit-identical (profiles/README.md "Activation planes"; E3D_ACT_PLANES=0 = fp32 rows).
 ROWLN_MIN_M = int(os.environ.get("E3D_GEMM_ROWLN_MIN_M", "8192")) if os.environ.get("E3D_GEMM_ROWLN", "1") == "1" else 1 << 62
 
 
@@ -691,10 +722,85 @@ def weight_planes(weight, terms):
 
 def rowln_ok(terms, M, H, K, a, residual=None):
     """Whether the row-complete kernel takes this call: its staging needs A (and the residual) 16-byte aligned, so a view
-    that starts off alignment goes to the pair instead."""
-    return (terms in (3, 19) and M >= ROWLN_MIN_M and a.stride(1) == 1 and a.data_ptr() % 16 == 0
+    that starts off alignment goes to the pair instead.  ``a`` None: A will come as planes (a fresh allocation)."""
+    return (terms in (3, 19) and M >= ROWLN_MIN_M and (a is None or (a.stride(1) == 1 and a.data_ptr() % 16 == 0))
             and (residual is None or (residual.stride(1) == 1 and residual.stride(0) % 4 == 0 and residual.data_ptr() % 16 == 0))
-            and bool(hip.lib().e3d_gemm_residual_layernorm_supported(M, H, K, a.stride(0))))
+            and bool(hip.lib().e3d_gemm_residual_layernorm_supported(M, H, K, K if a is None else a.stride(0))))
+
+
+# Activation planes (csrc/gemm_rowln.hip, DESIGN.md section 2): in inference the A operand of a row-complete launch is written
+# by exactly one kernel and read by nobody else, so the producer stores it as the consumer's MFMA fragments -- the two 16-bit
+# split terms, [32-row block][k16 step][plane][lane] x 16 B, byte for byte what every wave of the consumer would otherwise
+# form from the fp32 rows (eight times per element) -- and the results are bit-identical.  Producers: the 4-wave
+# cooperative attention kernel (BertSelfOutput's input) and the persistent GEMM (GELU: BertOutput's input).  E3D_ACT_PLANES=0 restores the fp32 launches (A/B runs).
+# (E3D_ACT_PLANES=gemm / attn: that producer only)
+ACT_PLANES = {"1": True, "0": False, "gemm": "gemm", "attn": "attn"}.get(os.environ.get("E3D_ACT_PLANES", "1"))
+if ACT_PLANES is None:
+    raise ValueError(f"E3D_ACT_PLANES must be 1, 0, gemm or attn, got {os.environ['E3D_ACT_PLANES']!r}")
+ACT_PLANES_CALLS = 0     # row-complete launches that read planes (tests: the path was taken)
+
+
+class ActPlanes:
+    """An [M, K] activation in the plane format: ``data`` is the uint8 buffer (M K 4 bytes), ``terms`` the split (3 / 19)."""
+    __slots__ = ("data", "shape", "terms")
+    requires_grad = False
+
+    def __init__(self, data, M, K, terms):
+        self.data, self.shape, self.terms = data, (M, K), terms
+
+    @property
+    def device(self):
+        return self.data.device
+
+    def decode(self):
+        """(hi, lo) as [M, K] fp16 / bf16 tensors (tests, debugging): the layout read back by index arithmetic."""
+        M, K = self.shape
+        dt = torch.float16 if self.terms == 19 else torch.bfloat16
+        t = self.data.view(dt).view(M // 32, K // 16, 2, 2, 32, 8)      # [rb][ks][plane][lane >> 5][lane & 31][j]
+        t = t.permute(2, 0, 4, 1, 3, 5).reshape(2, M, K)
+        return t[0], t[1]
+
+
+def activation_planes(x, mode=None):
+    """``x`` [M, K] fp32 (row-strided) -> ActPlanes, by the kernel that defines the format."""
+    _chk(x, "activation_planes.x")
+    M, K = x.shape
+    terms = GEMM_MODES[GEMM_MODE if mode is None else mode]
+    nbytes = hip.lib().e3d_activation_planes_bytes(M, K)
+    if nbytes < 0 or terms not in (3, 19) or x.stride(1) != 1:
+        raise ValueError(f"activation_planes: unsupported shape {tuple(x.shape)} / terms {terms}")
+    out = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
+    hip.check(hip.lib().e3d_activation_planes_f32_split(_p(x), x.stride(0), M, K, terms, _p(out), _stream()),
+              "e3d_activation_planes_f32_split")
+    return ActPlanes(out, M, K, terms)
+
+
+def gemm_planes_ok(a, weight, bias, act, out_features, residual=None, mode=None):
+    """Decided BEFORE the GEMM launch: whether ``gemm(a, weight, bias, act)`` may leave as planes -- the consumer
+    (``linear_residual_layernorm`` with ``out_features`` columns and this residual) takes the row-complete kernel, the GEMM
+    lands on the persistent kernel, and nothing needs gradients."""
+    if ACT_PLANES not in (True, "gemm") or torch.is_grad_enabled():
+        return False
+    terms = GEMM_MODES[GEMM_MODE if mode is None else mode]
+    M, K = a.shape
+    N = weight.shape[0]
+    return (terms in (3, 19) and rowln_ok(terms, M, out_features, N, None, residual) and a.stride(1) == 1
+            and a.data_ptr() % 16 == 0 and (bias is None or bias.data_ptr() % 16 == 0)
+            and not (_skinny_ok(terms, M, N, K, a) and M <= min(SKINNY_MAX_M, SKINNY_GEMM_MAX_M))
+            and bool(hip.lib().e3d_gemm_planes_supported(M, N, K, a.stride(0), act, terms)))
+
+
+def attention_planes_ok(q, k, v, nh, Lq, Lk, out_features, residual=None, mode=None):
+    """Decided BEFORE the attention launch: whether its context may leave as planes -- the consumer
+    (``linear_residual_layernorm`` with ``out_features`` columns and this residual) takes the row-complete kernel, the
+    attention lands on the 4-wave cooperative kernel, both run the same split, and nothing needs gradients."""
+    if ACT_PLANES not in (True, "attn") or torch.is_grad_enabled():
+        return False
+    terms = GEMM_MODES[ATTN_MODE if mode is None else mode]
+    if terms != GEMM_MODES[GEMM_MODE] or terms not in (3, 19):
+        return False
+    return (rowln_ok(terms, q.shape[0], out_features, nh * 64, None, residual) and v.stride(1) == 1 and k.stride(1) == 1
+            and bool(hip.lib().e3d_attn_planes_supported(k.stride(0), Lk * v.stride(0), v.stride(0), Lq, Lk, terms, 1)))
 
 
 def linear_residual_layernorm(a, weight, bias, residual, gamma, beta, eps, mode=None):
@@ -704,6 +810,23 @@ def linear_residual_layernorm(a, weight, bias, residual, gamma, beta, eps, mode=
     M, K = a.shape
     H = weight.shape[0]
     terms = GEMM_MODES[GEMM_MODE if mode is None else mode]
+    if isinstance(a, ActPlanes):
+        global ACT_PLANES_CALLS
+        if a.terms != terms or not rowln_ok(terms, M, H, K, None, residual):
+            raise RuntimeError(f"linear_residual_layernorm: no kernel reads activation planes at M={M} H={H} K={K} terms={terms}")
+        _chk(a.data, "linear_residual_layernorm.a", torch.uint8)
+        for t, n in ((weight, "weight"), (bias, "bias"), (residual, "residual"), (gamma, "gamma"), (beta, "beta")):
+            _chk(t, "linear_residual_layernorm." + n)
+        assert weight.is_contiguous() and weight.shape[1] == K and (residual is None or residual.shape == (M, H))
+        planes, scale = weight_planes(weight, terms)
+        out = torch.empty((M, H), device=a.device, dtype=torch.float32)
+        with _timed("gemm_layernorm", (M, H, K)):
+            hip.check(hip.lib().e3d_gemm_residual_layernorm_planes_split(
+                _p(a.data), _p(planes), _p(bias), _p(residual), residual.stride(0) if residual is not None else 0,
+                _p(gamma), _p(beta), eps, _p(out), out.stride(0), M, H, K, terms, scale, _stream()),
+                "e3d_gemm_residual_layernorm_planes_split")
+        ACT_PLANES_CALLS += 1
+        return out
     if rowln_ok(terms, M, H, K, a, residual):
         for t, n in ((a, "a"), (weight, "weight"), (bias, "bias"), (residual, "residual"), (gamma, "gamma"), (beta, "beta")):
             _chk(t, "linear_residual_layernorm." + n)

@@ -552,6 +552,35 @@ int e3d_gemm_residual_layernorm_f32_split(const float* A, int64_t lda, const voi
                                           const float* residual, int64_t ldr, const float* gamma, const float* beta, float eps,
                                           float* out, int64_t ldo, int M, int N, int K, int terms, float out_scale, void* stream);
 
+/* ---- activation planes (inference; additions to ABI v5) ----------------------------------------------------------------
+ * The A operand of the row-complete kernel in the form it consumes: an [M, K] fp32 activation stored as its two 16-bit
+ * terms (hi, lo: the 2-term split of terms = 3 / 19) in MFMA-fragment order, as many bytes as the fp32 tensor:
+ *     planes[((rb * (K / 16) + ks) * 2 + plane) * 1024 + lane * 16 + 2 j] = term_plane(X[32 rb + (lane & 31)][16 ks + 8 (lane >> 5) + j])
+ * (rb = 32-row block, ks = k16 step, lane < 64, j < 8; M % 32 == 0, K % 16 == 0).  A tensor in this form is written by its
+ * producer and read by e3d_gemm_residual_layernorm_planes_split only; the sums are bit-identical to the fp32-A entry point.
+ *   e3d_activation_planes_f32_split: the format's definition as a kernel (tests, callers without a plane-writing producer);
+ *   e3d_gemm_bias_act_planes_split: e3d_gemm_bias_act_f32_split_ex (act none / GELU, terms 3 / 19) whose [M, N] result leaves as
+ *     planes -- bit for bit the split of the fp32 result.  Exists where the launch takes the persistent 256x256 kernel:
+ *     e3d_gemm_planes_supported says so beforehand; anything else is an error.  bias must be 16-byte aligned.
+ *   e3d_relkey_attn_fwd_split_planes: e3d_relkey_attn_fwd_split_ex (no dropout, no lse) whose context leaves as planes of
+ *     the [B * Lq, nh * 64] matrix -- bit for bit the split of the fp32 context.  Exists where the call lands on the 4-wave
+ *     cooperative kernel and Lq % 32 == 0: e3d_attn_planes_supported (strides of k / v in floats, have_scratch = no dist_emb or
+ *     an e_scratch) says so beforehand; anything else is an error, never a silent fp32 store. */
+int64_t e3d_activation_planes_bytes(int M, int K);
+int e3d_activation_planes_f32_split(const float* X, int64_t ldx, int M, int K, int terms, void* planes, void* stream);
+int e3d_gemm_residual_layernorm_planes_split(const void* a_planes, const void* w_planes, const float* bias,
+                                             const float* residual, int64_t ldr, const float* gamma, const float* beta, float eps,
+                                             float* out, int64_t ldo, int M, int N, int K, int terms, float out_scale, void* stream);
+int e3d_gemm_planes_supported(int M, int N, int K, int64_t lda, int act, int terms);
+int e3d_gemm_bias_act_planes_split(const float* A, int64_t lda, const float* W, const float* bias, void* out_planes,
+                                   int M, int N, int K, int act, int terms, float* out_absmax, float out_scale, void* stream);
+int e3d_attn_planes_supported(int64_t k_rs, int64_t v_bs, int64_t v_rs, int Lq, int Lk, int terms, int have_scratch);
+int e3d_relkey_attn_fwd_split_planes(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs,
+                                     int64_t k_rs, const float* v, int64_t v_bs, int64_t v_rs,
+                                     const float* dist_emb, int P, const float* key_mask, void* out_planes,
+                                     int B, int nh, int Lq, int Lk, int terms, void* e_scratch, int e_scratch_ready,
+                                     const float* q_absmax, const float* k_absmax, float* e_absmax, void* stream);
+
 /* ---- optimizer step (ABI v3) ------------------------------------------------------------------------------------------
  * Global-norm gradient clip + AdamW over ALL parameters in three launches: what Lightning's gradient_clip_val = 1.0
  * (structure_model/train_model.py:99-110) and torch.optim.AdamW (structure_model/model.py:361-366,
