@@ -22,6 +22,11 @@
 // Streams 8 and 9 yield keys, not draws: E3D_STREAM_* above stays the list of the streams that draws are mapped from.
 #define E3D_DROP_STREAM_LIGAND 8         // dropout on ligand rows (attention rows: the query's)
 #define E3D_DROP_STREAM_POCKET 9         // dropout on pocket (receptor) rows
+// partial redesign (replacement conditioning): the forward-noised copies of the held positions, step field = the chain's
+// step index.  Named apart from E3D_STREAM_* like the dropout streams; streams 1 and 3 are untouched, so the free
+// positions of a seeded chain make the draws they made before.
+#define E3D_KNOWN_STREAM_STRUCT 10       // structure: forward noise of the held angles, laid out as stream 1
+#define E3D_KNOWN_STREAM_SEQ 11          // sequence: forward-noising uniform of the held residues
 
 struct E3dU32x4 { uint32_t w[4]; };
 

@@ -422,6 +422,127 @@ __global__ __launch_bounds__(256) void keyed_q_sample_wrap_kernel(
     }
 }
 
+// ---------------------------------------------------------------- partial redesign: replacement conditioning
+// After the update that lands the state on noise level s, the held elements (mask != 0) are overwritten in place with a
+// forward-noised copy of their known values at level s: x = q_sample_wrap_elem(a, s1m, x0, wrap_pi(scale * z)) with
+// (a, s1m) = row t_dev[0] of the [T,2] level table (structure_model/utils.py, KnownLevels) -- the forward law the model
+// was trained on.  s1m == 0 (the clean level): x = x0, a copy.  A step index outside [0, T), a NaN row (a timestep that is
+// not visited) or a noisy level without draws: the held elements become NaN.  Elements with mask == 0 are not written.
+struct KnownLevel { float a, s1m; int kind; };   // kind 0: copy x0, 1: noised copy, 2: NaN
+
+__device__ __forceinline__ KnownLevel known_level(const float* __restrict__ level_table, const int64_t* __restrict__ t_dev,
+                                                  int T, bool have_draws) {
+    const int64_t t = t_dev[0];
+    if (t < 0 || t >= T) return KnownLevel{0.f, 0.f, 2};
+    const float a = level_table[2 * t], s1m = level_table[2 * t + 1];
+    if (a != a || s1m != s1m) return KnownLevel{a, s1m, 2};
+    if (s1m == 0.f) return KnownLevel{a, s1m, 0};
+    return KnownLevel{a, s1m, have_draws ? 1 : 2};
+}
+
+__device__ __forceinline__ float known_elem(const KnownLevel lv, float scale, float x0, float z) {
+    if (lv.kind == 0) return x0;
+    if (lv.kind == 2) return __builtin_nanf("");
+    return q_sample_wrap_elem(lv.a, lv.s1m, x0, wrap_pi(scale * z));
+}
+
+// the four mask bytes of float4 group i as one word (0: the group is free); byte j != 0: element j is held
+__device__ __forceinline__ uint32_t known_mask4(const uint8_t* __restrict__ mask, int64_t i) {
+    return reinterpret_cast<const uint32_t*>(mask)[i];
+}
+
+__device__ __forceinline__ void known_store4(float* x, int64_t i, uint32_t m4, const f32x4 v) {
+    if (((m4 & 0xFFu) != 0) && ((m4 & 0xFF00u) != 0) && ((m4 & 0xFF0000u) != 0) && ((m4 & 0xFF000000u) != 0)) {
+        reinterpret_cast<f32x4*>(x)[i] = v;
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if ((m4 >> (8 * j)) & 0xFFu) x[4 * i + j] = v[j];
+}
+
+__global__ __launch_bounds__(256) void known_compose_wrap_kernel(
+    float* x, const float* __restrict__ x0, const uint8_t* __restrict__ mask, const float* __restrict__ noise,
+    const float* __restrict__ level_table, const int64_t* __restrict__ t_dev, int T, float scale, int64_t n4, int64_t n) {
+    const KnownLevel lv = known_level(level_table, t_dev, T, noise != nullptr);
+    const bool noisy = lv.kind == 1;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        const uint32_t m4 = known_mask4(mask, i);
+        if (m4 == 0u) continue;
+        const f32x4 kv = reinterpret_cast<const f32x4*>(x0)[i];
+        f32x4 nv = {0.f, 0.f, 0.f, 0.f};
+        if (noisy) nv = reinterpret_cast<const f32x4*>(noise)[i];
+        f32x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = known_elem(lv, scale, kv[j], nv[j]);
+        known_store4(x, i, m4, o);
+    }
+    // tail (n % 4)
+    const int64_t r = n4 * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < n && mask[r]) x[r] = known_elem(lv, scale, x0[r], noisy ? noise[r] : 0.f);
+}
+
+// The draws generated in-register: z = the normals of (seed, item, stream 10, step t_dev[0], position, block), laid out
+// as stream 1.  Same arithmetic per element, so the result equals the buffer form fed with these normals.  Rows of no
+// item are left alone; a float4 group with no held element makes no Philox call.
+__global__ __launch_bounds__(256) void keyed_known_compose_wrap_kernel(
+    float* x, const float* __restrict__ x0, const uint8_t* __restrict__ mask, const float* __restrict__ level_table,
+    const int64_t* __restrict__ t_dev, int T, float scale, const int64_t* __restrict__ row_keys, uint64_t seed, int64_t n4,
+    int nb) {
+    const KnownLevel lv = known_level(level_table, t_dev, T, true);
+    const uint32_t t = (uint32_t)t_dev[0];
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        const uint32_t m4 = known_mask4(mask, i);
+        if (m4 == 0u) continue;
+        const int64_t row = i / nb;
+        uint64_t item;
+        uint32_t pos;
+        if (!keyed_row(row_keys, row, item, pos)) continue;
+        float nv[4] = {0.f, 0.f, 0.f, 0.f};
+        if (lv.kind == 1) e3d_keyed_normal4(e3d_keyed_words(seed, item, E3D_KNOWN_STREAM_STRUCT, t, pos,
+                                                            (uint32_t)(i - row * nb)), nv);
+        const f32x4 kv = reinterpret_cast<const f32x4*>(x0)[i];
+        f32x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = known_elem(lv, scale, kv[j], nv[j]);
+        known_store4(x, i, m4, o);
+    }
+}
+
+// Sequence chain: the class index of a held row (mask != 0, x0 >= 0) is redrawn in place from column x0 of Qsb, the
+// forward law at the level the step lands on -- p[c] = Qsb[b][c][x0], discrete_q_sample_kernel's convention and
+// arithmetic.  KEYED: the uniform is word 0 of stream 11 at step s_dev[0] with the row's key; rows of no item are left alone.
+template <bool KEYED>
+__global__ __launch_bounds__(256) void discrete_known_compose_kernel(
+    int32_t* idx, const int32_t* __restrict__ x0_idx, const uint8_t* __restrict__ mask, const float* __restrict__ Qsb,
+    const float* __restrict__ u, int mode, int L, int C, int64_t n_rows, const int64_t* __restrict__ row_keys, uint64_t seed,
+    const int64_t* __restrict__ s_dev) {
+    const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= n_rows || mask[n] == 0) return;
+    const int x0 = x0_idx[n];
+    if (x0 < 0 || x0 >= C) return;
+    const float* q = Qsb + (n / L) * C * C;
+    float p[CMAX];
+    float tot = 0.f;
+#pragma unroll
+    for (int c = 0; c < CMAX; ++c) {
+        p[c] = c < C ? q[c * C + x0] : 0.f;
+        tot += p[c];
+    }
+    float un = 0.f;
+    if (KEYED) {
+        const int64_t pos = row_keys[2 * n + 1];
+        if (pos < 0) return;
+        un = e3d_keyed_uniform(e3d_keyed_words(seed, (uint64_t)row_keys[2 * n], E3D_KNOWN_STREAM_SEQ, (uint32_t)s_dev[0],
+                                               (uint32_t)pos, 0).w[0]);
+    } else if (u) {
+        un = u[n];
+    }
+    idx[n] = pick_class(p, C, tot, mode, un);
+}
+
 }  // namespace
 
 extern "C" int e3d_ddpm_step_wrap(const float* x, const float* eps_hat, const float* noise,
@@ -551,7 +672,8 @@ extern "C" int e3d_keyed_discrete_posterior_sample(const int32_t* xt_idx, const 
 extern "C" int e3d_keyed_draws(const int64_t* row_keys, uint64_t seed, int stream_id, int t, int kind, int width,
                                int wrap, float scale, void* out, int64_t rows, void* stream) {
     E3D_REQUIRE(row_keys && out && rows > 0, "keyed_draws: bad arguments");
-    E3D_REQUIRE(stream_id >= 0 && stream_id <= 3 && t >= 0 && t <= 65535,
+    E3D_REQUIRE(((stream_id >= 0 && stream_id <= 3) || stream_id == E3D_KNOWN_STREAM_STRUCT ||
+                 stream_id == E3D_KNOWN_STREAM_SEQ) && t >= 0 && t <= 65535,
                 "keyed_draws: stream %d / step %d out of range", stream_id, t);
     E3D_REQUIRE(kind >= 0 && kind <= 3, "keyed_draws: kind %d", kind);
     E3D_REQUIRE(kind != 0 || (width > 0 && width % 4 == 0 && width / 4 <= 256 && ((uintptr_t)out % 16) == 0),
@@ -602,4 +724,55 @@ extern "C" int e3d_keyed_discrete_q_sample(const int32_t* x0_idx, const float* Q
     hipLaunchKernelGGL(discrete_q_sample_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, x0_idx, Qtb, nullptr, 1, out_idx, L, C, n, item_ids, epoch_dev, seed);
     return e3d_launch_status("e3d_keyed_discrete_q_sample");
+}
+
+// ---------------------------------------------------------------- partial redesign (entry points)
+extern "C" int e3d_known_compose_wrap(float* x, const float* x0, const uint8_t* mask, const float* noise,
+                                      const float* level_table, const int64_t* t_dev, int T, float scale, int64_t n,
+                                      void* stream) {
+    E3D_REQUIRE(x && x0 && mask && level_table && t_dev && n > 0 && T > 0, "known_compose_wrap: bad arguments");
+    E3D_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)x0 % 16) == 0 && ((uintptr_t)noise % 16) == 0 &&
+                    ((uintptr_t)mask % 4) == 0, "known_compose_wrap: x, x0, noise must be 16B and mask 4B aligned");
+    const int64_t n4 = n / 4;
+    hipLaunchKernelGGL(known_compose_wrap_kernel, dim3(keyed_blocks(n4)), dim3(256), 0, (hipStream_t)stream, x, x0, mask,
+                       noise, level_table, t_dev, T, scale, n4, n);
+    return e3d_launch_status("e3d_known_compose_wrap");
+}
+
+extern "C" int e3d_keyed_known_compose_wrap(float* x, const float* x0, const uint8_t* mask, const float* level_table,
+                                            const int64_t* t_dev, int T, float scale, const int64_t* row_keys,
+                                            uint64_t seed, int64_t rows, int F, void* stream) {
+    E3D_REQUIRE(x && x0 && mask && level_table && t_dev && row_keys && rows > 0 && T > 0,
+                "keyed_known_compose_wrap: bad arguments");
+    E3D_REQUIRE(F > 0 && F % 4 == 0 && F / 4 <= 256, "keyed_known_compose_wrap: F must be a multiple of 4 in [4, 1024] (F=%d)", F);
+    E3D_REQUIRE(T <= 65536, "keyed_known_compose_wrap: keyed streams hold steps up to 65535 (T=%d)", T);
+    E3D_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)x0 % 16) == 0 && ((uintptr_t)mask % 4) == 0,
+                "keyed_known_compose_wrap: x, x0 must be 16B and mask 4B aligned");
+    const int64_t n4 = rows * (F / 4);
+    hipLaunchKernelGGL(keyed_known_compose_wrap_kernel, dim3(keyed_blocks(n4)), dim3(256), 0, (hipStream_t)stream, x, x0,
+                       mask, level_table, t_dev, T, scale, row_keys, seed, n4, F / 4);
+    return e3d_launch_status("e3d_keyed_known_compose_wrap");
+}
+
+extern "C" int e3d_discrete_known_compose(int32_t* idx, const int32_t* x0_idx, const uint8_t* mask, const float* Qsb,
+                                          const float* u, int mode, int B, int L, int C, void* stream) {
+    E3D_REQUIRE(idx && x0_idx && mask && Qsb && B > 0 && L > 0, "discrete_known_compose: bad arguments");
+    E3D_REQUIRE(C >= 2 && C <= CMAX, "discrete_known_compose: C must be in [2,%d] (C=%d)", CMAX, C);
+    E3D_REQUIRE(mode == 0 || (mode == 1 && u), "discrete_known_compose: mode 1 needs uniforms");
+    const int64_t n = (int64_t)B * L;
+    hipLaunchKernelGGL(discrete_known_compose_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream, idx, x0_idx, mask, Qsb, u, mode, L, C, n, nullptr, 0ull, nullptr);
+    return e3d_launch_status("e3d_discrete_known_compose");
+}
+
+extern "C" int e3d_keyed_discrete_known_compose(int32_t* idx, const int32_t* x0_idx, const uint8_t* mask,
+                                                const float* Qsb, const int64_t* row_keys, uint64_t seed,
+                                                const int64_t* s_dev, int B, int L, int C, void* stream) {
+    E3D_REQUIRE(idx && x0_idx && mask && Qsb && row_keys && s_dev && B > 0 && L > 0,
+                "keyed_discrete_known_compose: bad arguments");
+    E3D_REQUIRE(C >= 2 && C <= CMAX, "keyed_discrete_known_compose: C must be in [2,%d] (C=%d)", CMAX, C);
+    const int64_t n = (int64_t)B * L;
+    hipLaunchKernelGGL(discrete_known_compose_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream, idx, x0_idx, mask, Qsb, nullptr, 1, L, C, n, row_keys, seed, s_dev);
+    return e3d_launch_status("e3d_keyed_discrete_known_compose");
 }

@@ -122,6 +122,11 @@ _SIGNATURES = {
     # strided (DDIM / respaced) structure update: [T,8] coefficient table, step index on the device
     "e3d_strided_step_wrap": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P, c_int64, _P]),
     "e3d_keyed_strided_step_wrap": (c_int, [_P, _P, _P, _P, c_int, _P, c_uint64, c_int, c_int, _P, c_int64, c_int, _P]),
+    # partial redesign: held positions overwritten in place after the update (additions, no signature changed)
+    "e3d_known_compose_wrap": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_float, c_int64, _P]),
+    "e3d_keyed_known_compose_wrap": (c_int, [_P, _P, _P, _P, _P, c_int, c_float, _P, c_uint64, c_int64, c_int, _P]),
+    "e3d_discrete_known_compose": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "e3d_keyed_discrete_known_compose": (c_int, [_P, _P, _P, _P, _P, c_uint64, _P, c_int, c_int, c_int, _P]),
     # keyed training and validation draws (ids and epoch read from device memory)
     "e3d_keyed_timesteps": (c_int, [_P, _P, c_uint64, c_int, c_int, _P, c_int, _P]),
     "e3d_keyed_q_sample_wrap": (c_int, [_P, _P, _P, _P, c_int, c_float, _P, _P, c_uint64, _P, _P, c_int, c_int, c_int, _P]),

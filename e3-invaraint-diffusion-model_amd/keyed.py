@@ -31,6 +31,9 @@ MAX_EPOCH = VALIDATION_EPOCH - 1
 # dropout decisions of a seeded training step: a frame row's 64-bit key is w0 | w1 << 32 of (seed, item id, stream, epoch,
 # position, block 0); an item's ligand position l and pocket position l must not share decisions, hence two streams
 DROP_LIGAND, DROP_POCKET = 8, 9
+# partial redesign (replacement conditioning): the forward-noised copies of the held ligand positions, drawn at the step
+# index of the chain; streams 1 and 3 stay as they are, so the free positions draw what they drew before
+KNOWN_STRUCT, KNOWN_SEQ = 10, 11
 
 
 def check_seed(seed):

@@ -1094,6 +1094,102 @@ def keyed_discrete_posterior_sample(xt_idx, logits, qsb, qtb, row_keys, seed, s_
     return out
 
 
+# ------------------------------------------------------------------------ partial redesign (replacement conditioning)
+# Held ligand positions are overwritten in place after the update of a step, by launches of their own on its stream.
+
+def _chk_known(x, x0, mask, name):
+    _chk(x, name + ".x"); _chk(x0, name + ".x0"); _chk(mask, name + ".mask", torch.uint8)
+    if not (x.is_contiguous() and x0.is_contiguous() and mask.is_contiguous()):
+        raise ValueError(f"{name}: x, x0 and mask must be contiguous")
+    if x0.shape != x.shape or mask.shape != x.shape:
+        raise ValueError(f"{name}: x {tuple(x.shape)}, x0 {tuple(x0.shape)} and mask {tuple(mask.shape)} must agree")
+
+
+def _chk_levels(level_table, t_dev, name):
+    _chk(level_table, name + ".level_table"); _chk(t_dev, name + ".t_dev", torch.int64)
+    if not (level_table.is_contiguous() and level_table.dim() == 2 and level_table.shape[1] == 2):
+        raise ValueError(f"{name}: level_table must be a contiguous [T, 2] table, got {tuple(level_table.shape)}")
+
+
+def known_compose_wrap(x, x0, mask, noise, level_table, t_dev, scale=1.0):
+    """In place on ``x``: where ``mask`` (uint8, x's shape) is set, x = the forward-noised copy of ``x0`` at the level
+    row ``t_dev[0]`` of ``level_table`` [T,2] names (structure_model.utils.KnownLevels.levels) with the N(0,1) draws
+    ``noise`` -- wrap(a x0 + s1m wrap(scale noise)); x0 itself at the clean level (s1m == 0).  ``noise`` None at a noisy
+    level, a NaN row or a step index outside the table: the held elements become NaN.  Returns ``x``."""
+    _chk_known(x, x0, mask, "known_compose_wrap")
+    _chk_levels(level_table, t_dev, "known_compose_wrap")
+    _chk(noise, "known_compose_wrap.noise")
+    if noise is not None and not (noise.is_contiguous() and noise.shape == x.shape):
+        raise ValueError("known_compose_wrap: noise must be contiguous and of x's shape")
+    if x.numel():
+        with _timed("known_compose_wrap"):
+            hip.check(hip.lib().e3d_known_compose_wrap(_p(x), _p(x0), _p(mask), _p(noise), _p(level_table), _p(t_dev),
+                                                       level_table.shape[0], float(scale), x.numel(), _stream()),
+                      "e3d_known_compose_wrap")
+    return x
+
+
+def keyed_known_compose_wrap(x, x0, mask, level_table, t_dev, row_keys, seed, scale=1.0):
+    """known_compose_wrap with the draws generated in the kernel from (seed, row key, stream 10, t_dev[0]); x [.., F],
+    rows = x.numel() // F, F % 4 == 0.  Rows of no item are left alone."""
+    _chk_known(x, x0, mask, "keyed_known_compose_wrap")
+    _chk_levels(level_table, t_dev, "keyed_known_compose_wrap")
+    F = x.shape[-1]
+    if F % 4:
+        raise ValueError(f"keyed_known_compose_wrap: the feature count must be a multiple of 4, got {F}")
+    rows = x.numel() // F
+    _chk_keys(row_keys, rows, "keyed_known_compose_wrap")
+    if level_table.shape[0] - 1 > 65535:
+        raise ValueError(f"keyed_known_compose_wrap: keyed streams hold steps up to 65535, the table has {level_table.shape[0]}")
+    with _timed("keyed_known_compose_wrap"):
+        hip.check(hip.lib().e3d_keyed_known_compose_wrap(_p(x), _p(x0), _p(mask), _p(level_table), _p(t_dev),
+                                                         level_table.shape[0], float(scale), _p(row_keys),
+                                                         keyed.check_seed(seed), rows, F, _stream()),
+                  "e3d_keyed_known_compose_wrap")
+    return x
+
+
+def _chk_discrete_known(idx, x0_idx, mask, qsb, name):
+    _chk(idx, name + ".idx", torch.int32); _chk(x0_idx, name + ".x0_idx", torch.int32)
+    _chk(mask, name + ".mask", torch.uint8); _chk(qsb, name + ".qsb")
+    if idx.dim() != 2 or x0_idx.shape != idx.shape or mask.shape != idx.shape:
+        raise ValueError(f"{name}: idx {tuple(idx.shape)}, x0_idx {tuple(x0_idx.shape)} and mask {tuple(mask.shape)} must be "
+                         "the same [B, L]")
+    B, L = idx.shape
+    C = qsb.shape[-1]
+    if qsb.shape != (B, C, C):
+        raise ValueError(f"{name}: qsb must be [{B}, C, C], got {tuple(qsb.shape)}")
+    if not (idx.is_contiguous() and x0_idx.is_contiguous() and mask.is_contiguous() and qsb.is_contiguous()):
+        raise ValueError(f"{name}: arguments must be contiguous")
+    return B, L, C
+
+
+def discrete_known_compose(idx, x0_idx, mask, qsb, u=None):
+    """In place on ``idx`` int32 [B,L]: a row with ``mask`` (uint8) set and x0_idx >= 0 is redrawn from column x0_idx of
+    ``qsb`` [B,C,C] -- discrete_q_sample's law; u [B,L] uniforms or None (argmax).  Returns ``idx``."""
+    B, L, C = _chk_discrete_known(idx, x0_idx, mask, qsb, "discrete_known_compose")
+    _chk(u, "discrete_known_compose.u")
+    if u is not None and not (u.is_contiguous() and u.numel() == B * L):
+        raise ValueError("discrete_known_compose: u must be contiguous [B, L]")
+    with _timed("discrete_known_compose"):
+        hip.check(hip.lib().e3d_discrete_known_compose(_p(idx), _p(x0_idx), _p(mask), _p(qsb), _p(u), 0 if u is None else 1,
+                                                       B, L, C, _stream()), "e3d_discrete_known_compose")
+    return idx
+
+
+def keyed_discrete_known_compose(idx, x0_idx, mask, qsb, row_keys, seed, s_dev):
+    """discrete_known_compose (categorical draw) with the uniforms from (seed, row key, stream 11, s_dev[0]);
+    row_keys [B * L, 2]."""
+    B, L, C = _chk_discrete_known(idx, x0_idx, mask, qsb, "keyed_discrete_known_compose")
+    _chk(s_dev, "keyed_discrete_known_compose.s_dev", torch.int64)
+    _chk_keys(row_keys, B * L, "keyed_discrete_known_compose")
+    with _timed("discrete_known_compose"):
+        hip.check(hip.lib().e3d_keyed_discrete_known_compose(_p(idx), _p(x0_idx), _p(mask), _p(qsb), _p(row_keys),
+                                                             keyed.check_seed(seed), _p(s_dev), B, L, C, _stream()),
+                  "e3d_keyed_discrete_known_compose")
+    return idx
+
+
 KEYED_NORMAL, KEYED_UNIFORM, KEYED_ONEHOT, KEYED_CLASS = 0, 1, 2, 3
 
 

@@ -208,6 +208,48 @@ class Frame:
         return keyed.padded_keys(ids, self.Ll, device)
 
 
+def parse_keep(spec):
+    """A position list such as "0-3,7" -> the sorted 0-based positions it names (inclusive ranges; "" -> none).  A
+    malformed list raises ``ValueError`` with the offending token."""
+    if not isinstance(spec, str):
+        raise TypeError(f"keep: expected a position list such as '0-3,7', got {type(spec).__name__}")
+    positions = set()
+    for token in spec.split(","):
+        tok = token.strip()
+        if not tok:
+            if spec.strip():
+                raise ValueError(f"keep: empty entry in position list {spec!r}")
+            continue
+        lo, dash, hi = tok.partition("-")
+        lo, hi = lo.strip(), hi.strip()
+        if not (lo.isdigit() and lo.isascii()) or (dash and not (hi.isdigit() and hi.isascii())):
+            raise ValueError(f"keep: malformed entry {tok!r} in position list {spec!r} (expected N or N-M)")
+        a, b = int(lo), int(hi) if dash else int(lo)
+        if b < a:
+            raise ValueError(f"keep: descending range {tok!r} in position list {spec!r}")
+        positions.update(range(a, b + 1))
+    return sorted(positions)
+
+
+def keep_mask(keep, index, L, length=None):
+    """bool [L]: the ligand positions of dataset item ``index`` that a partial redesign holds.  ``keep``: a position list
+    (``parse_keep``; applied to every item, positions at or beyond ``length`` -- default L -- ignored) or a callable
+    index -> bool [L]."""
+    length = L if length is None else min(int(length), L)
+    if callable(keep):
+        m = torch.as_tensor(keep(index))
+        if m.dtype != torch.bool or tuple(m.shape) != (L,):
+            raise ValueError(f"keep({index}) must return a bool [{L}] mask, got {m.dtype} {tuple(m.shape)}")
+        m = m.clone().cpu()
+    else:
+        m = torch.zeros(L, dtype=torch.bool)
+        pos = [p for p in parse_keep(keep) if p < length]
+        if pos:
+            m[pos] = True
+    m[length:] = False
+    return m
+
+
 def capture_graph(capture, rows, steps, use_graph=None, what="the reverse step"):
     """The captured step ``capture()`` of a chain of ``steps`` steps on ``rows`` ligand rows, or None: eager launches.
     ``use_graph`` None: replay for at most GRAPH_MAX_ROWS rows (E3D_SAMPLE_GRAPH=0/1 overrides); chains of at most 4

@@ -36,6 +36,9 @@ PACK = os.environ.get("E3D_SAMPLE_PACK", "0") == "1"
 # Keyed draws (``run(seed=...)``): the initial one-hots and the posterior uniforms of a ligand are a function of
 # (seed, dataset index), whatever its batch, order or frame.  None (default): torch's generator, as before.
 SEED = int(os.environ["E3D_SAMPLE_SEED"], 0) if os.environ.get("E3D_SAMPLE_SEED") else None
+# Partial redesign (``run(keep=...)``, E3D_SAMPLE_KEEP): ligand positions held at the record's own residues while the rest
+# is sampled, e.g. "0-3,7" (packing.keep_mask).  "" (default): the whole sequence is designed, as before.
+KEEP = os.environ.get("E3D_SAMPLE_KEEP", "")
 
 CONFIG = {
     "pocket_ext": 0,
@@ -121,12 +124,16 @@ def compute_batched_over0_posterior_distribution(X_t, Q_t, Qsb, Qtb, batch):
 
 
 def sample_p_zs_given_zt_discrete(t, s, noised_data, pred_noise, noise_schedule, transition, diverse,
-                                  is_last_step, u=None, keyed_draw=None):
+                                  is_last_step, u=None, keyed_draw=None, known=None):
     """z_s ~ p(z_s | z_t) for every residue (reference sample.py:141-179).  ``diverse`` draws
     from the categorical (inverse CDF with uniforms ``u`` [B,L], default torch.rand on device),
     otherwise argmax; the last step returns the raw logits, as the reference does.
     ``keyed_draw`` = (row keys [B*L, 2], seed, int64 step on the device): the uniforms are the keyed stream 3 of those
-    rows at that step, generated inside the posterior kernel (keyed.py); exclusive with ``u``."""
+    rows at that step, generated inside the posterior kernel (keyed.py); exclusive with ``u``.
+    ``known`` = (x0 class indices int32 [B,L], uint8 mask [B,L], uniforms [B,L] or None): the held rows of z_s are redrawn
+    from q(z_s | x0) -- column x0 of Qsb, ``PeptideDiff.apply_aa_noise``'s law at level ``s`` -- on the class indices,
+    before the one-hot (``e3d_discrete_known_compose``; with ``keyed_draw`` its uniforms are keyed stream 11).  The last
+    step returns the logits untouched: ``denoise`` puts the held residues there itself, once per chain."""
     if is_last_step:
         return pred_noise
     B, L, C = noised_data.shape
@@ -138,12 +145,19 @@ def sample_p_zs_given_zt_discrete(t, s, noised_data, pred_noise, noise_schedule,
             raise ValueError("sample_p_zs_given_zt_discrete: pass either uniforms or a keyed draw, not both")
         idx = ops.keyed_discrete_posterior_sample(noised_data.argmax(dim=-1).to(torch.int32).contiguous(),
                                                   pred_noise.contiguous().float(), qsb, qtb, *keyed_draw)
+        if known is not None:
+            ops.keyed_discrete_known_compose(idx, known[0], known[1], qsb, *keyed_draw)
         return F.one_hot(idx.long(), num_classes=C).float()
     if diverse and u is None:
         u = torch.rand(B, L, device=dev)
     idx = ops.discrete_posterior_sample(noised_data.argmax(dim=-1).to(torch.int32).contiguous(),
                                         pred_noise.contiguous().float(), qsb, qtb,
                                         u.contiguous().float() if diverse else None)
+    if known is not None:
+        ku = None
+        if diverse:
+            ku = torch.rand(B, L, device=dev) if known[2] is None else known[2].contiguous().float()
+        ops.discrete_known_compose(idx, known[0], known[1], qsb, ku)
     return F.one_hot(idx.long(), num_classes=C).float()
 
 
@@ -158,11 +172,13 @@ class GraphedDenoiseStep:
     E3D_SAMPLE_GRAPH override."""
 
     def __init__(self, model, x_like, ligand_angles, ligand_mask, receptor_seq, receptor_angles, receptor_mask, noise_schedule,
-                 transition, diverse, T, inject_u=False, layouts=None, row_keys=None, seed=None):
+                 transition, diverse, T, inject_u=False, layouts=None, row_keys=None, seed=None, known=None):
         """``layouts`` = (ligand, pocket) packing.PackedLayout: the step runs ``model.forward_packed`` on packed rows
         (``x_like`` [1, rows, C], packed angles and pocket inputs; the masks are not read).  The layouts' device tables
         are fixed for the chain, so the capture holds them like any other argument.
-        ``row_keys`` + ``seed``: the uniforms are the keyed stream of those rows at the integer step ``self.s_idx``."""
+        ``row_keys`` + ``seed``: the uniforms are the keyed stream of those rows at the integer step ``self.s_idx``.
+        ``known`` = (x0 class indices, uint8 mask), both like ``x_like``'s first two dimensions: the held rows are composed
+        inside the body; with ``inject_u`` their uniforms are injected too (``self.known_u``)."""
         dev = x_like.device
         if (row_keys is None) != (seed is None) or (seed is not None and inject_u):
             raise ValueError("a keyed graph needs row_keys and a seed, and no injected uniforms")
@@ -174,6 +190,8 @@ class GraphedDenoiseStep:
         self.x = x_like.clone()
         self.s = torch.zeros((x_like.shape[0], 1), device=dev)
         self.u = torch.zeros(x_like.shape[:2], device=dev) if (inject_u and diverse) else None
+        self.known_u = torch.zeros(x_like.shape[:2], device=dev) if (known is not None and self.u is not None) else None
+        self.known = None if known is None else (known[0], known[1], self.known_u)
         self.out = None
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
@@ -197,9 +215,10 @@ class GraphedDenoiseStep:
             ang, _, rseq, rang, _ = self.args
             logits = self.model.forward_packed(self.s, self.x, ang, rseq, rang, *self.layouts)[None]
         return sample_p_zs_given_zt_discrete((self.s + 1) / self.T, self.s / self.T, self.x, logits, self.schedule, self.transition,
-                                             self.diverse, is_last_step=False, u=self.u, keyed_draw=self.keyed_draw)
+                                             self.diverse, is_last_step=False, u=self.u, keyed_draw=self.keyed_draw,
+                                             known=self.known)
 
-    def step(self, s_int, x, u=None):
+    def step(self, s_int, x, u=None, known_u=None):
         """z_t -> z_s for the step index ``s_int`` (> 0); returns the graph's output buffer (overwritten by the next call)."""
         if (u is not None) != (self.u is not None):
             raise ValueError("this graph was captured %s injected uniforms" % ("with" if self.u is not None else "without"))
@@ -209,6 +228,11 @@ class GraphedDenoiseStep:
             self.x.copy_(x)
         if u is not None:
             self.u.copy_(u)
+        if (known_u is not None) != (self.known_u is not None):
+            raise ValueError("this graph was captured %s injected uniforms for the held rows"
+                             % ("with" if self.known_u is not None else "without"))
+        if known_u is not None:
+            self.known_u.copy_(known_u)
         self.graph.replay()
         return self.out
 
@@ -216,7 +240,7 @@ class GraphedDenoiseStep:
 @torch.no_grad()
 def denoise(batch, model: PeptideDiff, noise_schedule, transition, diverse, x_T=None, us=None,
             generated_angles=None, timesteps=None, trim_padding=False, use_graph=None, pack=False, seed=None,
-            item_ids=None):
+            item_ids=None, known_mask=None, known_us=None):
     """Full reverse chain over CONFIG["timesteps"] steps + recovery metrics (reference
     sample.py:181-229).  ``x_T`` / ``us`` inject the initial one-hot noise and the per-step
     uniforms (parity tests); ``generated_angles`` replaces the dataset's ligand angles
@@ -233,9 +257,32 @@ def denoise(batch, model: PeptideDiff, noise_schedule, transition, diverse, x_T=
     ``seed``: keyed draws (keyed.py, DESIGN.md "Keyed sampling streams"): x_T and the uniforms of item b are functions
     of (seed, item_ids[b], step, position) alone, so they do not depend on the batch, its order, the frame (padded /
     trimmed / packed) or eager / graph launches.  ``item_ids`` default to 0 .. B-1 (``run`` uses the dataset index).
-    Exclusive with ``x_T`` / ``us``."""
+    Exclusive with ``x_T`` / ``us``.
+
+    Partial redesign -- ``known_mask`` bool [B, L]: the masked ligand positions are held at ``batch["ligand_seq"]`` while
+    the rest is sampled (replacement conditioning).  After every step the held rows are redrawn from q(z_s | x0), the
+    forward law at the level the step landed on (``e3d_discrete_known_compose``); the last step's held rows become the
+    one-hot of the true residue.  The mask is and-ed with the padding mask.  ``known_us`` is the counterpart of ``us``
+    for the held rows (a list of T [B, L] tensors; with ``us``); with a ``seed`` the uniforms are keyed stream 11 and
+    stream 3 -- the free rows' draws -- is untouched.  The recovery rates returned and printed then cover the FREE
+    positions only (the held ones recover by construction); an item with no free position reports NaN.  A mask with
+    nothing set runs the chain exactly as without the argument.  No resampling loop; sample quality has not been measured
+    here (no trained checkpoint ships with the tree)."""
     T = CONFIG["timesteps"] if timesteps is None else timesteps
     B, max_len, C = batch["ligand_seq"].shape
+    if known_mask is None and known_us is not None:
+        raise ValueError("denoise: known_us are the uniforms of the held positions; pass known_mask")
+    if known_mask is not None:
+        if known_us is not None and seed is not None:
+            raise ValueError("denoise: pass either injected known_us or a seed, not both")
+        if not torch.is_tensor(known_mask) or known_mask.dtype != torch.bool:
+            raise ValueError(f"denoise: known_mask must be a bool tensor, got {getattr(known_mask, 'dtype', type(known_mask))}")
+        if tuple(known_mask.shape) != (B, max_len):
+            raise ValueError(f"denoise: known_mask must be {(B, max_len)}, got {tuple(known_mask.shape)}")
+        if (known_us is None) != (us is None) and seed is None and diverse:
+            raise ValueError("denoise: inject us and known_us together, or neither")
+        if known_us is not None and len(known_us) != T:
+            raise ValueError(f"denoise: known_us must hold {T} entries, one per step, got {len(known_us)}")
     dev = next(model.parameters()).device
     ids = None
     if seed is not None:
@@ -269,14 +316,26 @@ def denoise(batch, model: PeptideDiff, noise_schedule, transition, diverse, x_T=
     rseq, rang = frame.pocket(receptor_seq.float()), frame.pocket(receptor_angles.float())
     lmask, rmask = (None, None) if layouts is not None else (frame.ligand(ligand_mask), frame.pocket(receptor_mask))
     row_keys = None if seed is None else frame.row_keys(ids, dev)
+    held = known = None
+    if known_mask is not None:
+        held = known_mask.to(dev) & (ligand_mask != 0)
+        if not bool(held.any()):
+            held = None
+    if held is not None:      # class indices and mask into the frame like the state
+        known = (state(ligand_seq.argmax(dim=-1)).to(torch.int32).contiguous(), state(held).to(torch.uint8).contiguous())
+        if known_us is not None:
+            known_us = [state(u.to(dev)).contiguous() if u is not None else u for u in known_us]
+    else:
+        known_us = None
     graphed = packing.capture_graph(
         lambda: GraphedDenoiseStep(model, x, ang, lmask, rseq, rang, rmask, noise_schedule, transition, diverse, T,
-                                   inject_u=us is not None, layouts=layouts, row_keys=row_keys, seed=seed),
+                                   inject_u=us is not None, layouts=layouts, row_keys=row_keys, seed=seed, known=known),
         frame.rows, T, use_graph, "the sequence reverse step")
     for n, s_int in enumerate(reversed(range(T))):
         u = None if us is None else us[n]
+        ku = None if known_us is None else known_us[n]
         if graphed is not None and s_int > 0:
-            x = graphed.step(s_int, x, u)
+            x = graphed.step(s_int, x, u, ku if graphed.known_u is not None else None)
             continue
         s_array = torch.full((x.shape[0], 1), float(s_int), device=dev)     # [1, 1] packed: every item shares the step
         if layouts is None:
@@ -285,14 +344,19 @@ def denoise(batch, model: PeptideDiff, noise_schedule, transition, diverse, x_T=
             logits = model.forward_packed(s_array, x, ang, rseq, rang, *layouts)[None]
         x = sample_p_zs_given_zt_discrete((s_array + 1) / T, s_array / T, x, logits, noise_schedule, transition,
                                           diverse, is_last_step=s_int == 0, u=u,
-                                          keyed_draw=_keyed_draw(row_keys, seed, s_int, dev))
+                                          keyed_draw=_keyed_draw(row_keys, seed, s_int, dev),
+                                          known=None if known is None else known + (ku,))
     x = frame.restore(x if layouts is None else x[0])
+    if held is not None:      # the last step returned logits: the held rows are the true residues, once per chain
+        x = torch.where(held[..., None], ligand_seq.float(), x)
     pred_idx, true_idx = x.argmax(dim=-1).cpu(), ligand_seq.argmax(dim=-1).cpu()
     mask = ligand_mask.bool().cpu()
+    free = mask if held is None else mask & ~held.cpu()      # recovery over the positions that were designed
     ids, true_sequences, pred_sequences, recovery_rates = [], [], [], []
     for i in range(B):
         m = mask[i]
-        recovery_rates.append(((pred_idx[i][m] == true_idx[i][m]).sum() / m.sum()).item())
+        f = free[i]
+        recovery_rates.append(((pred_idx[i][f] == true_idx[i][f]).sum() / f.sum()).item())
         pred_sequences.append("".join(AA_VOCAB[j] for j in pred_idx[i][m]))
         true_sequences.append("".join(AA_VOCAB[j] for j in true_idx[i][m]))
         sid = batch.get("structure_ids")
@@ -306,10 +370,23 @@ def _keyed_draw(row_keys, seed, s_int, dev):
     return None if seed is None else (row_keys, seed, torch.full((1,), s_int, device=dev, dtype=torch.long))
 
 
-def run(transition, diverse=True, seed=None):
-    """Sample every test ligand.  ``seed`` (default ``SEED``, E3D_SAMPLE_SEED): keyed draws by dataset index."""
+def batch_keep_mask(keep, batch, first_index):
+    """``known_mask`` [B, L] of a loader batch whose first item has dataset index ``first_index`` (packing.keep_mask per
+    item, cut at the ligand's length); None when ``keep`` names nothing."""
+    if not (callable(keep) or keep):
+        return None
+    B, L = batch["ligand_seq"].shape[:2]
+    lengths = batch["ligand_attn_mask"].sum(dim=1).int().tolist()
+    return torch.stack([packing.keep_mask(keep, first_index + b, L, lengths[b]) for b in range(B)])
+
+
+def run(transition, diverse=True, seed=None, keep=None):
+    """Sample every test ligand.  ``seed`` (default ``SEED``, E3D_SAMPLE_SEED): keyed draws by dataset index.
+    ``keep`` (default ``KEEP``, E3D_SAMPLE_KEEP): partial redesign -- a position list such as "0-3,7" or a callable
+    dataset index -> bool [L] (packing.keep_mask); those residues are held at the record's own ``ligand_seq``."""
     import pandas as pd
     seed = SEED if seed is None else seed
+    keep = KEEP if keep is None else keep
     loader = get_dataloader(DATA_PATH)
     model = get_model(len(loader))
     schedule = PredefinedNoiseScheduleDiscrete(CONFIG["noise_schedule"], CONFIG["timesteps"]).to(DEVICE)
@@ -318,8 +395,9 @@ def run(transition, diverse=True, seed=None):
         print(f"Generating Batch {idx}")
         n = batch["ligand_seq"].shape[0]
         ids = None if seed is None else list(range(idx * CONFIG["batch_size"], idx * CONFIG["batch_size"] + n))
+        known_mask = batch_keep_mask(keep, batch, idx * CONFIG["batch_size"])
         for acc, part in zip(cols, denoise(batch, model, schedule, transition, diverse, pack=PACK, seed=seed,
-                                           item_ids=ids)):
+                                           item_ids=ids, known_mask=known_mask)):
             acc.extend(part)
     res = pd.DataFrame(zip(*cols), columns=["structure_ids", "true_sequence", "predict_sequence", "recovery_rate"])
     res.to_pickle(OUTPUT_PATH)

@@ -56,7 +56,8 @@ def angles_from_trajectory(traj, ligand_mask):
 
 def denoise(batch, generated_angles, model, noise_schedule, transition, diverse, **kw):
     """reference lines 196-243: sample.denoise with the ligand angles replaced.  ``seed`` / ``item_ids`` (and every
-    other keyword of sample.denoise) pass through: a seeded joint run keys both stages by the same item ids."""
+    other keyword of sample.denoise, ``pack`` and the partial redesign's ``known_mask`` among them) pass through: a seeded
+    joint run keys both stages by the same item ids, and holds the same positions in both."""
     return _denoise(batch, model, noise_schedule, transition, diverse, generated_angles=generated_angles, **kw)
 
 
@@ -72,7 +73,9 @@ if __name__ == "__main__":
     cols = ([], [], [], [])
     for idx, batch in enumerate(loader):
         print(f"Generating Batch {idx}")
-        for acc, part in zip(cols, denoise(batch, generated_angles[idx], model, schedule, transition, True)):
+        known_mask = _sample.batch_keep_mask(_sample.KEEP, batch, idx * CONFIG["batch_size"])     # E3D_SAMPLE_KEEP
+        for acc, part in zip(cols, denoise(batch, generated_angles[idx], model, schedule, transition, True,
+                                           known_mask=known_mask)):
             acc.extend(part)
     res = pd.DataFrame(zip(*cols), columns=["structure_ids", "true_sequence", "predict_sequence", "recovery_rate"])
     res.to_pickle(OUTPUT_PATH)

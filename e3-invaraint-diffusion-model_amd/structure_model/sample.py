@@ -32,7 +32,7 @@ from ..bert import BertConfig
 from ..packing import trimmed_length  # noqa: F401  (S.trimmed_length: bench.py and the tests read it here)
 from .dataset import LigandBindingSiteDataset, NoisedAnglesDataset
 from .model import ConditionalBertForDiffusion
-from .utils import CosineTables, StridedTables
+from .utils import CosineTables, KnownLevels, StridedTables
 
 MODEL_PATH = ""  # trained state_dict (same key names as the reference's checkpoints)
 OUTPUT = "./data/output.pkl"
@@ -60,6 +60,10 @@ PACK = os.environ.get("E3D_SAMPLE_PACK", "0") == "1"
 # Keyed draws (``sample(seed=...)``): every random number of a pocket's chain is a function of (seed, dataset index), so
 # batch size, order, frame and launch mode do not change its sample.  None (default): torch's generator, as before.
 SEED = int(os.environ["E3D_SAMPLE_SEED"], 0) if os.environ.get("E3D_SAMPLE_SEED") else None
+# Partial redesign (``sample(keep=...)``, E3D_SAMPLE_KEEP): ligand positions held at the record's own angles while the
+# rest is sampled, e.g. "0-3,7" (0-based, inclusive ranges, applied to every ligand; packing.keep_mask).  "" (default):
+# the whole peptide is designed, as before.
+KEEP = os.environ.get("E3D_SAMPLE_KEEP", "")
 
 CONFIG = {
     "pocket_ext": 0,
@@ -94,7 +98,8 @@ def _tables(betas):
 @torch.no_grad()
 def p_sample(model, ligand_mask, ligand_angle_noise, receptor_seq, receptor_mask, receptor_angle,
              timestep, betas, noise=None, receptor_cache=None, out=None, wrap=False, seed=None,
-             item_ids=None, strided=None, wrap_x0=False) -> torch.Tensor:
+             item_ids=None, strided=None, wrap_x0=False, known=None, known_mask=None, known_noise=None,
+             known_levels=None, known_scale=1.0) -> torch.Tensor:
     """One reverse step x_t -> x_{t-1} (reference sample.py:55-99).  Like the reference's
     p_sample the result is NOT wrapped unless ``wrap=True`` (p_sample_loop's sample.py:140-142
     fused into the same kernel).
@@ -106,7 +111,17 @@ def p_sample(model, ligand_mask, ligand_angle_noise, receptor_seq, receptor_mask
     0 .. B-1; see keyed.py); exclusive with ``noise``.
     ``strided``: a StridedTables -- the step goes from ``timestep`` straight to its successor in that table's order with
     the DDIM / respaced update (``wrap_x0``: wrap the x0 estimate); eta == 0 draws nothing.
+    ``known`` [B,L,F] + ``known_mask`` (bool [B,L] or [B,L,F]) + ``known_levels`` (a KnownLevels of the chain's order):
+    the held positions of the result are overwritten with the forward-noised copy of ``known`` at the level the step lands
+    on (``p_sample_loop``, "partial redesign"); ``known_noise`` injects its N(0,1) draw, a ``seed`` keys it (stream 10).
     """
+    held = _known_chain(known, known_mask, known_noise, seed, ligand_mask, ligand_angle_noise, None, "p_sample")
+    if held is not None:
+        if not isinstance(known_levels, KnownLevels):
+            raise ValueError("p_sample: held positions need known_levels=KnownLevels(tables, order of the chain)")
+        x0, m8, kn = held
+        held = (x0.contiguous(), m8.contiguous(), known_levels, known_levels.levels.to(x0.device), float(known_scale),
+                None if kn is None else kn.contiguous())
     if strided is None and wrap_x0:
         raise ValueError("p_sample: wrap_x0 belongs to the strided update; pass strided=StridedTables(...)")
     keyed_step = None
@@ -122,7 +137,49 @@ def p_sample(model, ligand_mask, ligand_angle_noise, receptor_seq, receptor_mask
         strided = _strided_step(strided, ligand_angle_noise.device, wrap_x0)
     return _reverse_step(model, ligand_mask, ligand_angle_noise, receptor_seq, receptor_mask,
                          receptor_angle, timestep, betas, noise, receptor_cache, out, wrap=wrap, keyed_step=keyed_step,
-                         strided=strided)
+                         strided=strided, known=held)
+
+
+def _known_chain(known, known_mask, known_noises, seed, ligand_mask, x, steps, who):
+    """The held positions of a chain, checked: None (nothing held: the chain runs as without the arguments), or
+    (known float [B,L,F], mask uint8 [B,L,F] -- and-ed with the padding mask --, injected noises or None), padded frame."""
+    if known is None and known_mask is None:
+        if known_noises is not None:
+            raise ValueError(f"{who}: known_noises are the draws of the held positions; pass known and known_mask")
+        return None
+    if known is None or known_mask is None:
+        raise ValueError(f"{who}: known and known_mask go together")
+    if known_noises is not None and seed is not None:
+        raise ValueError(f"{who}: pass either injected known_noises or a seed, not both")
+    if known_mask.dtype != torch.bool:
+        raise ValueError(f"{who}: known_mask must be a bool tensor, got {known_mask.dtype}")
+    shape = tuple(x.shape)
+    if tuple(known.shape) != shape:
+        raise ValueError(f"{who}: known must be {shape} like the state, got {tuple(known.shape)}")
+    if tuple(known_mask.shape) not in (shape[:2], shape):
+        raise ValueError(f"{who}: known_mask must be {shape[:2]} or {shape}, got {tuple(known_mask.shape)}")
+    want = shape if steps is None else (steps,) + shape
+    if known_noises is not None and tuple(known_noises.shape) != want:
+        raise ValueError(f"{who}: known_noises must be {want}, got {tuple(known_noises.shape)}")
+    dev = x.device
+    m = known_mask.to(dev)
+    m = (m if m.dim() == 3 else m[..., None]) & (ligand_mask.to(dev) != 0)[..., None]
+    if not bool(m.any()):
+        return None
+    return (known.to(dev).float(), m.expand(shape).to(torch.uint8).contiguous(),
+            None if known_noises is None else known_noises.to(dev).float())
+
+
+def _compose_known(x, t_dev, t_index, known, keyed_step):
+    """Overwrite the held positions of ``x`` (the update's result) in place for the step at ``t_index``."""
+    x0, m8, kl, levels, scale, noise = known
+    if keyed_step is not None:
+        return ops.keyed_known_compose_wrap(x, x0, m8, levels, t_dev, keyed_step[0], keyed_step[1], scale)
+    if float(kl.levels[t_index, 1]) == 0.0:       # the clean level: a copy, no draw
+        noise = None
+    elif noise is None:
+        noise = torch.randn_like(x)
+    return ops.known_compose_wrap(x, x0, m8, noise, levels, t_dev, scale)
 
 
 def _coef_table(tab, dev):
@@ -155,7 +212,16 @@ def keyed_x_T(seed, item_ids, L, n_ft=8, scale=1.0, device=None):
 
 
 def _reverse_step(model, ligand_mask, x_t, receptor_seq, receptor_mask, receptor_angle, timestep,
-                  betas, noise, receptor_cache, out, wrap, mod=None, layout=None, keyed_step=None, strided=None):
+                  betas, noise, receptor_cache, out, wrap, mod=None, layout=None, keyed_step=None, strided=None,
+                  known=None):
+    if known is not None:      # the update as ever, then the held positions on top of its result, on the same stream
+        x = _reverse_step(model, ligand_mask, x_t, receptor_seq, receptor_mask, receptor_angle, timestep, betas, noise,
+                          receptor_cache, out, wrap, mod=mod, layout=layout, keyed_step=keyed_step, strided=strided)
+        if isinstance(timestep, int):
+            t_index, t_dev = timestep, torch.full((1,), timestep, device=x.device, dtype=torch.long)
+        else:
+            t_index, t_dev = int(timestep.reshape(-1)[0].item()), timestep.to(device=x.device, dtype=torch.long).contiguous()
+        return _compose_known(x, t_dev, t_index, known, keyed_step)
     tab = _tables(betas)
     if isinstance(timestep, int):
         t_index = timestep
@@ -204,6 +270,9 @@ class GraphedReverseStep:
     A strided step (``strided``: a StridedTables) holds that table's [T,8] rows instead and runs
     ``e3d_strided_step_wrap`` / its keyed form: bit-identical to the eager strided step for the same noise; eta == 0 has
     no noise buffer and draws nothing.
+    Held positions (``known``) add one launch after the update, on the same stream -- ``e3d_known_compose_wrap`` or its
+    keyed form on ``self.out`` -- and, unseeded, a second noise buffer filled inside the graph; the captured step stays one
+    serial chain.
 
     Default for chains of at most packing.GRAPH_MAX_ROWS token rows (up to ~16 pockets of 64 residues),
     ``use_graph=True`` / E3D_SAMPLE_GRAPH=1 forces it, =0 turns it off.  Measured on MI355X, one 64-residue pocket
@@ -213,13 +282,15 @@ class GraphedReverseStep:
     takes 1.5 ms."""
 
     def __init__(self, model, ligand_mask, cache, tab, x_like, wrap=True, draw=True, mod_table=None, layout=None,
-                 row_keys=None, seed=None, strided=None, wrap_x0=False):
+                 row_keys=None, seed=None, strided=None, wrap_x0=False, known=None):
         """``draw``: the graph draws its own N(0,1) noise each replay; False: ``step`` takes the draw (parity tests).
         ``row_keys`` + ``seed`` (with ``draw``): the draw is the keyed stream of those rows (keyed.py).
         ``mod_table`` [T,6H]: row t = model.timestep_modulation(t), read on the device by the step index.
         ``layout``: the step runs on packed ligand rows (``x_like`` [rows,F]; a packed ``cache``); its segment and tile
         tables are device tensors fixed for the chain, so the capture holds them like any other argument.
-        ``strided`` (+ ``wrap_x0``): the step is the strided update of that StridedTables; ``tab`` is then not read."""
+        ``strided`` (+ ``wrap_x0``): the step is the strided update of that StridedTables; ``tab`` is then not read.
+        ``known`` = (x0, uint8 mask -- both like ``x_like`` --, KnownLevels, scale): the held positions; ``step`` then
+        takes their draw next to the update's when the graph was captured without draws of its own."""
         dev = x_like.device
         self.model, self.mask, self.cache, self.wrap, self.mod_table = model, ligand_mask, cache, wrap, mod_table
         self.layout = layout
@@ -237,6 +308,11 @@ class GraphedReverseStep:
         self.t = torch.full((x_like.shape[0],), 0 if strided is None else strided.order[-1], device=dev, dtype=torch.long)
         self.coef = _coef_table(tab, dev) if strided is None else self.strided[1]
         self.draw = draw
+        self.known = self.known_noise = None
+        if known is not None:
+            x0, m8, kl, scale = known
+            self.known = (x0.contiguous(), m8.contiguous(), kl.levels.to(dev), float(scale))
+            self.known_noise = None if self.keyed is not None else torch.zeros_like(x_like)
         self.x.copy_(x_like)
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
@@ -248,6 +324,18 @@ class GraphedReverseStep:
             self._body()
 
     def _body(self):
+        self._update()
+        if self.known is None:
+            return
+        x0, m8, levels, scale = self.known
+        if self.keyed is not None:
+            ops.keyed_known_compose_wrap(self.out, x0, m8, levels, self.t, *self.keyed, scale)
+            return
+        if self.draw:
+            self.known_noise.normal_()
+        ops.known_compose_wrap(self.out, x0, m8, self.known_noise, levels, self.t, scale)
+
+    def _update(self):
         mod = None if self.mod_table is None else self.mod_table.index_select(0, self.t[:1])
         eps_hat = self.model.decode(self.t, self.x, self.mask, self.cache, mod=mod, layout=self.layout)
         if self.strided is not None:
@@ -269,10 +357,16 @@ class GraphedReverseStep:
             self.noise.normal_()
         ops.ddpm_step_wrap_table(self.x, eps_hat.contiguous(), self.noise, self.coef, self.t, wrap=self.wrap, out=self.out)
 
-    def step(self, i, x, noise=None):
+    def step(self, i, x, noise=None, known_noise=None):
         """x_t -> x_{t-1} for step index i; returns the graph's output buffer (overwritten by the next call)."""
         if (noise is not None) == self.draw:
             raise ValueError("this graph was captured %s injected noise" % ("without" if self.draw else "with"))
+        if known_noise is not None:
+            if self.known_noise is None or self.draw:
+                raise ValueError("this graph takes no injected draw for held positions")
+            self.known_noise.copy_(known_noise)
+        elif self.known_noise is not None and not self.draw:
+            raise ValueError("this graph was captured with injected noise: pass the held positions' draw too")
         self.t.fill_(i)
         if x is not self.x:
             self.x.copy_(x)
@@ -287,7 +381,8 @@ def p_sample_loop(model: nn.Module, ligand_mask, ligand_angle_noise, receptor_se
                   receptor_angle, total_timesteps: int, betas, disable_pbar: bool = False,
                   noises=None, return_device: bool = False, step: int = None, use_graph: bool = None,
                   trim_padding: bool = False, pack: bool = False, seed: int = None, item_ids=None,
-                  update: str = "ancestral", eta: float = 0.0, wrap_x0: bool = False) -> torch.Tensor:
+                  update: str = "ancestral", eta: float = 0.0, wrap_x0: bool = False, known=None, known_mask=None,
+                  known_noises=None, known_scale: float = 1.0) -> torch.Tensor:
     """Full reverse chain; returns [T/STEP, B, L, n_ft] (on the host like the reference,
     sample.py:101-144, unless ``return_device``).  ``noises`` [T/STEP,B,L,n_ft] injects the draws.
     ``use_graph``: replay one captured HIP graph per step (None: by size, E3D_SAMPLE_GRAPH=0/1 overrides -- see
@@ -316,7 +411,21 @@ def p_sample_loop(model: nn.Module, ligand_mask, ligand_angle_noise, receptor_se
     random number is drawn and torch's generator is left alone; 1: the ancestral variance of the respaced chain),
     ``wrap_x0`` wraps each step's x0 estimate to [-pi, pi).  The last entry, t = 0, is the wrapped x0 estimate.  Seeded
     strided chains draw the same stream-1 normals at timestep t as seeded ancestral ones.  ``eta`` / ``wrap_x0`` with
-    the ancestral update raise."""
+    the ancestral update raise.
+
+    Partial redesign -- ``known`` [B, L, n_ft] + ``known_mask`` (bool [B, L]: whole residues, or [B, L, n_ft]: per
+    element, e.g. hold a residue's dihedrals and free its bond angles): the masked ligand positions are held at ``known``
+    while the rest is sampled (replacement conditioning: Song et al. 2021, section I.2; Lugmayr et al. 2022).  After every
+    step the held elements are overwritten with a fresh forward-noised copy of ``known`` at the level the step landed on --
+    wrap(sqrt(ab_s) known + sqrt(1 - ab_s) wrap(known_scale z)), the law the model was trained on (``known_scale``: the
+    dataset's ``angular_var_scale``) -- and after the last step with ``known`` itself, by ``e3d_known_compose_wrap``
+    (utils.KnownLevels), a launch of its own after the update; the decoder reads the held content through
+    self-attention.  Every entry of the result is the composed state and the last one holds ``known`` bit for bit; x_T
+    stays the caller's.  The mask is and-ed with ``ligand_mask``.  Works with either update, any ``step``, every frame,
+    eager or graph.  ``known_noises`` [T/STEP, B, L, n_ft] injects the N(0,1) draws z (with ``noises``); with a ``seed``
+    they are keyed stream 10 at the step's index, and streams 0 / 1 -- the free positions' draws -- are untouched.  A mask
+    with nothing set runs the chain exactly as without these arguments.  There is no resampling loop (RePaint's jumps
+    back), and sample quality has not been measured here (no trained checkpoint ships with the tree)."""
     if update not in ("ancestral", "strided"):
         raise ValueError(f"p_sample_loop: update must be 'ancestral' or 'strided', got {update!r}")
     if update == "ancestral" and (eta != 0.0 or wrap_x0):
@@ -327,6 +436,9 @@ def p_sample_loop(model: nn.Module, ligand_mask, ligand_angle_noise, receptor_se
     strided = StridedTables(tab, order, eta) if update == "strided" else None
     x = ligand_angle_noise.contiguous().float()
     ids = None
+    held = _known_chain(known, known_mask, known_noises, seed, ligand_mask, x, len(order), "p_sample_loop")
+    if held is not None and (noises is None) != (held[2] is None) and seed is None:
+        raise ValueError("p_sample_loop: inject noises and known_noises together, or neither")
     if seed is not None:
         if noises is not None:
             raise ValueError("p_sample_loop: pass either injected noises or a seed, not both")
@@ -349,6 +461,13 @@ def p_sample_loop(model: nn.Module, ligand_mask, ligand_angle_noise, receptor_se
     row_keys = None if seed is None else frame.row_keys(ids, x.device)
     keyed_step = None if seed is None else _keyed_step(seed, row_keys, tab, x.device, strided is None)
     strided_step = None if strided is None else _strided_step(strided, x.device, wrap_x0)
+    known_graph = known_step = known_noises = None
+    if held is not None:       # into the frame like the state; packed tails and trimmed-off rows hold nothing
+        kl = KnownLevels(tab, order)
+        x0, m8 = frame.ligand(held[0]).contiguous(), frame.ligand(held[1]).contiguous()
+        known_noises = None if held[2] is None else frame.ligand(held[2], dim=1)
+        known_graph = (x0, m8, kl, float(known_scale))
+        known_step = (x0, m8, kl, kl.levels.to(x.device), float(known_scale))
     traj = torch.empty((len(order),) + tuple(x.shape), device=x.device, dtype=torch.float32)
     # what depends on the timestep alone, for the whole chain at once: row t of the table = timestep_modulation(t)
     mod_rows = model.timestep_modulation(torch.tensor(order, device=x.device, dtype=torch.long))
@@ -356,16 +475,17 @@ def p_sample_loop(model: nn.Module, ligand_mask, ligand_angle_noise, receptor_se
     mod_table[order] = mod_rows
     graphed = packing.capture_graph(
         lambda: GraphedReverseStep(model, mask, cache, tab, x, draw=noises is None, mod_table=mod_table, layout=layout,
-                                   row_keys=row_keys, seed=seed, strided=strided, wrap_x0=wrap_x0),
+                                   row_keys=row_keys, seed=seed, strided=strided, wrap_x0=wrap_x0, known=known_graph),
         frame.rows, len(order), use_graph)
     for n, i in enumerate(order):
+        kn = None if known_noises is None else known_noises[n].contiguous()
         if graphed is not None:
-            x = graphed.step(i, graphed.out if n else x, None if noises is None else noises[n])
+            x = graphed.step(i, graphed.out if n else x, None if noises is None else noises[n], kn)
             traj[n].copy_(x)
         else:
             x = _reverse_step(model, mask, x, None, None, None, i, tab, None if noises is None else noises[n], cache,
                               traj[n], wrap=True, mod=mod_table[i:i + 1], layout=layout, keyed_step=keyed_step,
-                              strided=strided_step)
+                              strided=strided_step, known=None if known_step is None else known_step + (kn,))
     traj = frame.restore(traj, dim=1)                                     # [T/STEP, B, L, F], zeros outside the frame
     return traj if return_device else traj.cpu()
 
@@ -401,15 +521,21 @@ def load_model(dataset, model_path=None):
     return model.eval().to(DEVICE)
 
 
-def sample(model, test_angle_ds, all_batches: bool = False, seed: int = None):
+def sample(model, test_angle_ds, all_batches: bool = False, seed: int = None, keep=None):
     """Sample the test pockets in batches of CONFIG["batch_size"]; returns a list of
     [T, l_i, 8] arrays trimmed to each ligand's length.  Like the reference (sample.py:237) only
     the first batch is generated unless ``all_batches``.
 
     ``seed`` (default ``SEED``, E3D_SAMPLE_SEED): keyed draws for x_T and the chain, keyed by the dataset index, so a
     pocket's sample does not depend on the batch size, on its place in the batch, on packing or on an arithmetic
-    re-run of its batch.  The chain's update rule comes from ``STEP``, ``UPDATE``, ``ETA`` and ``WRAP_X0``."""
+    re-run of its batch.  The chain's update rule comes from ``STEP``, ``UPDATE``, ``ETA`` and ``WRAP_X0``.
+
+    ``keep`` (default ``KEEP``, E3D_SAMPLE_KEEP): partial redesign -- a position list such as "0-3,7" (0-based ligand
+    positions, inclusive ranges, applied to every ligand; positions beyond a ligand's length are ignored) or a callable
+    dataset index -> bool [L].  Those residues are held at the record's own clean ``ligand_angles`` while the rest is
+    sampled (``p_sample_loop(known=...)``)."""
     seed = SEED if seed is None else seed
+    keep = KEEP if keep is None else keep
     bs = CONFIG["batch_size"]
     items = [test_angle_ds[i] for i in range(len(test_angle_ds))]
 
@@ -424,6 +550,11 @@ def sample(model, test_angle_ds, all_batches: bool = False, seed: int = None):
         print(f"Generating Batch {idx}/{len(ligand_mask)}")
         lengths = lm.sum(dim=1).int()
         ids = list(range(idx * bs, idx * bs + len(lengths)))      # dataset indices of the batch
+        held = {}
+        if callable(keep) or keep:
+            held = dict(known=torch.stack([items[i]["ligand_angles"] for i in ids]).float().to(DEVICE),
+                        known_mask=torch.stack([packing.keep_mask(keep, i, pad, int(l)) for i, l in zip(ids, lengths)]).to(DEVICE),
+                        known_scale=test_angle_ds.angular_var_scale)
         if seed is None:
             x_T = test_angle_ds.sample_noise(torch.zeros((len(lengths), pad, feature_size)))
         else:
@@ -436,7 +567,7 @@ def sample(model, test_angle_ds, all_batches: bool = False, seed: int = None):
                     receptor_angle=receptor_angle[idx].to(DEVICE), total_timesteps=test_angle_ds.timesteps,
                     betas=test_angle_ds.alpha_beta_terms["betas"], trim_padding=True,   # sliced to l_i right below
                     pack=PACK, seed=seed, item_ids=None if seed is None else ids, step=STEP, update=UPDATE, eta=ETA,
-                    wrap_x0=WRAP_X0)
+                    wrap_x0=WRAP_X0, **held)
 
         sampled = chain(ARITHMETIC)
         if ops.GEMM_MODES.get(ARITHMETIC) == 19 and "E3D_GEMM_MODE" not in os.environ and not bool(torch.isfinite(sampled).all()):

@@ -104,6 +104,41 @@ class StridedTables:
         return self.order[k + 1] if k + 1 < len(self.order) else -1
 
 
+class KnownLevels:
+    """Noise levels of the held positions of a partial redesign (replacement conditioning; sample.py, ``known=``): the
+    level the state is on AFTER the step at each visited timestep, whatever the update rule and the stride are.
+
+    ``order``: the visited timesteps, strictly descending, as for ``StridedTables``.  After the step at ``order[k]`` the
+    state is a sample at level ``s = order[k + 1]``, so the held positions get a forward-noised copy of their known values
+    at ``s``; after the step at the last visited timestep the state is the sample itself and they get the known values.
+
+    Derived in float64 from ``tab.betas`` with ab = cumprod(1 - betas), each entry rounded to fp32 once:
+
+    ``levels`` fp32 [T, 2]: row order[k] = (sqrt(ab_s), sqrt(1 - ab_s)); the last visited timestep's row is (1, 0); rows of
+    timesteps that are not visited are NaN -- the table ``e3d_known_compose_wrap`` reads by the device step index.
+    """
+
+    def __init__(self, tab: CosineTables, order):
+        T = int(tab.betas.shape[0])
+        order = [int(t) for t in order]
+        if not order:
+            raise ValueError("KnownLevels: the order of timesteps is empty")
+        if any(t < 0 or t >= T for t in order):
+            raise ValueError(f"KnownLevels: timesteps must lie in [0, {T}), got {order}")
+        if any(a <= b for a, b in zip(order, order[1:])):
+            raise ValueError(f"KnownLevels: the order must be strictly descending, got {order}")
+        ab = torch.cumprod(1.0 - tab.betas.double(), dim=0)
+        idx = torch.tensor(order, dtype=torch.long)
+        ab_s = ab[idx[1:]]
+        rows = torch.empty((len(order), 2), dtype=torch.float64)
+        rows[:-1, 0] = torch.sqrt(ab_s)
+        rows[:-1, 1] = torch.sqrt(1.0 - ab_s)
+        rows[-1, 0], rows[-1, 1] = 1.0, 0.0
+        self.timesteps, self.order = T, order
+        self.levels = torch.full((T, 2), float("nan"), dtype=torch.float32)
+        self.levels[idx] = rows.float()
+
+
 def cosine_beta_schedule(timesteps: int, s: float = 8e-3) -> torch.Tensor:
     return CosineTables(timesteps, s).betas
 

@@ -286,7 +286,7 @@ int e3d_discrete_q_sample(const int32_t* x0_idx, const float* Qtb, const float* 
  * Every random number of a seeded chain is Philox4x32-10 of the counter (item id lo, item id hi, stream << 16 | step,
  * position << 8 | block) under the key (seed lo, seed hi), mapped to fp32 from 24-bit fields ("Keyed
  * sampling streams"; csrc/e3d_philox.h).  Streams: 0 structure x_T, 1 structure reverse-step noise, 2 sequence initial
- * one-hot, 3 sequence posterior uniforms.  ``row_keys`` int64 [rows, 2] = (item id, position) per row; a negative
+ * one-hot, 3 sequence posterior uniforms (10 and 11: the held positions of a partial redesign, further down).  ``row_keys`` int64 [rows, 2] = (item id, position) per row; a negative
  * position marks a row of no item (a packed buffer's tail), which draws nothing.  The caller guarantees positions
  * < 2^24 and steps <= 65535.  Step indices are read from DEVICE memory (``t_dev`` / ``s_dev``, first element), so a
  * captured graph replays them. */
@@ -319,6 +319,44 @@ int e3d_keyed_discrete_posterior_sample(const int32_t* xt_idx, const float* logi
  *   kind 3: the same classes as int32 [rows]. */
 int e3d_keyed_draws(const int64_t* row_keys, uint64_t seed, int stream_id, int t, int kind, int width, int wrap,
                     float scale, void* out, int64_t rows, void* stream);
+
+/* ------------------------------------------------------------------ partial redesign (replacement conditioning)
+ * Holding chosen ligand positions fixed during a reverse chain (Song et al. 2021, section I.2; Lugmayr et al. 2022,
+ * without the resampling loop): after the update that lands the state on noise level s, the held elements are
+ * overwritten with a fresh forward-noised copy of their known values at level s; after the last step with the known
+ * values themselves.  These are launches of their own, after the update kernel of the step and on its stream: the
+ * update kernels, their signatures and their results stay bit for bit, and these entry points are additions to ABI v5. */
+
+/* In place on x [n]: for every element with mask[i] != 0 (uint8, per element), with (a, s1m) = row t_dev[0] of
+ * level_table [T,2] (structure_model/utils.py, KnownLevels: the level the state is on AFTER the step at t):
+ *   s1m == 0 (the clean level):  x = x0                                (a copy: bit for bit)
+ *   otherwise:                   x = wrap_[-pi,pi)(a * x0 + s1m * wrap_[-pi,pi)(scale * noise))
+ * -- the arithmetic of e3d_q_sample_wrap on the noise of NoisedAnglesDataset.sample_noise.  t_dev[0] outside [0, T), a
+ * NaN row (a timestep the chain does not visit), or noise == NULL at a level with s1m != 0: the held elements become NaN.
+ * Elements with mask == 0 are not written.  x, x0, noise 16 B aligned, mask 4 B aligned. */
+int e3d_known_compose_wrap(float* x, const float* x0, const uint8_t* mask, const float* noise, const float* level_table,
+                           const int64_t* t_dev, int T, float scale, int64_t n, void* stream);
+
+/* The same with the normals generated in-register: row r, features 4j .. 4j+3 take those of (seed, row_keys[r], stream
+ * 10, t_dev[0], block j), the block layout of stream 1.  Equals e3d_known_compose_wrap fed with those normals.  Rows of
+ * no item are left alone; a group of four features with no held element makes no Philox call.  x / x0 / mask [rows, F],
+ * F % 4 == 0, F <= 1024; T <= 65536. */
+int e3d_keyed_known_compose_wrap(float* x, const float* x0, const uint8_t* mask, const float* level_table,
+                                 const int64_t* t_dev, int T, float scale, const int64_t* row_keys, uint64_t seed,
+                                 int64_t rows, int F, void* stream);
+
+/* Sequence chain, in place on the class indices idx [B*L] that e3d_discrete_posterior_sample wrote: a row n with
+ * mask[n] != 0 and 0 <= x0_idx[n] < C is redrawn from prob[c] = Qsb[b][c][x0_idx[n]] (b = n / L), the convention and
+ * arithmetic of e3d_discrete_q_sample at the level the step lands on.  mode 0: argmax; mode 1: inverse-CDF draw with
+ * u [B*L].  Every other row is left alone. */
+int e3d_discrete_known_compose(int32_t* idx, const int32_t* x0_idx, const uint8_t* mask, const float* Qsb,
+                               const float* u, int mode, int B, int L, int C, void* stream);
+
+/* The same in mode 1 with the uniform of row n taken from word 0 of stream 11 at step s_dev[0] with key row_keys[n]
+ * (a packed buffer: B = 1, L = rows); rows of no item are left alone. */
+int e3d_keyed_discrete_known_compose(int32_t* idx, const int32_t* x0_idx, const uint8_t* mask, const float* Qsb,
+                                     const int64_t* row_keys, uint64_t seed, const int64_t* s_dev, int B, int L,
+                                     int C, void* stream);
 
 /* ------------------------------------------------------------------ keyed training and validation draws
  * The same generator and counter layout with the EPOCH in the step field (training epochs 0 .. 65534; 65535 is the

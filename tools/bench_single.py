@@ -4,6 +4,7 @@ model (encoder cached, as `structure_model/sample.py` runs it), default arithmet
 
     python tools/bench_single.py [--seq-len 64] [--steps 50] [--graph]
     python tools/bench_single.py --steps 1000 --stride 20 --update strided [--eta E] [--wrap-x0]   # 50 visited timesteps
+    python tools/bench_single.py --keep 0-31                # partial redesign: those positions held at the pocket's ligand
 """
 import argparse
 import os
@@ -24,11 +25,14 @@ from e3diff_amd.bert import BertConfig  # noqa: E402
 DEV = "cuda:0"
 
 
-def run(seq_len=64, batch=1, steps=50, graph=None, chains=3, seed=None, update="ancestral", eta=0.0, wrap_x0=False, stride=1):
+def run(seq_len=64, batch=1, steps=50, graph=None, chains=3, seed=None, update="ancestral", eta=0.0, wrap_x0=False, stride=1,
+        keep=None):
     """Best of ``chains`` full reverse chains; returns a dict (also the ``single_pocket`` key of bench.py's line).
     ``seed``: keyed draws (p_sample_loop(seed=...)): the noise is generated inside the update kernel.
     ``update`` / ``eta`` / ``wrap_x0`` / ``stride``: p_sample_loop's update rule and its ``step``; a step of the result
-    is one visited timestep."""
+    is one visited timestep.  ``keep``: a position list ("0-31"): those ligand positions are held at the synthetic
+    pocket's own ligand angles (p_sample_loop(known=...)); the ligand then fills the frame, so that every listed position
+    is a held one."""
     from e3diff_amd.structure_model import sample as S
     from e3diff_amd.structure_model.model import ConditionalBertForDiffusionBase
     from e3diff_amd.structure_model.utils import CosineTables, modulo_with_wrapped_range
@@ -41,6 +45,11 @@ def run(seq_len=64, batch=1, steps=50, graph=None, chains=3, seed=None, update="
     tab = CosineTables(T)
     visited = len(range(0, T, stride))
     rule = dict(update=update, eta=eta, wrap_x0=wrap_x0) if update != "ancestral" else {}
+    if keep:
+        full = synthetic_pockets(B, L, seed=1, lig_range=(L, L))
+        pk["ligand_attn_mask"], known = full["ligand_attn_mask"].to(DEV), full["ligand_angles"].to(DEV)
+        held = torch.stack([pkg.packing.keep_mask(keep, b, L) for b in range(B)]).to(DEV)
+        rule.update(known=known, known_mask=held)
 
     def chain():
         return S.p_sample_loop(model, pk["ligand_attn_mask"], x_T, pk["receptor_seq"], pk["receptor_attn_mask"],
@@ -60,7 +69,7 @@ def run(seq_len=64, batch=1, steps=50, graph=None, chains=3, seed=None, update="
         mode = pkg.ops.GEMM_MODE
     assert bool(torch.isfinite(out).all())
     return {"batch": B, "seq_len": L, "timesteps": T, "arithmetic": mode, "graph_replay": "sampler default" if graph is None else bool(graph),
-            "seed": seed, "update": update, "eta": eta, "wrap_x0": wrap_x0, "stride": stride, "visited_timesteps": visited,
+            "seed": seed, "keep": keep or None, "update": update, "eta": eta, "wrap_x0": wrap_x0, "stride": stride, "visited_timesteps": visited,
             "ms_per_chain": best * 1e3, "ms_per_step": best / visited * 1e3,
             "note": "structure_model/sample.py p_sample_loop: encoder + cross K/V once per chain, 12-layer decoder + DDPM update per step"}
 
@@ -105,10 +114,11 @@ def main():
     ap.add_argument("--eta", type=float, default=0.0, help="noise scale of the strided update in [0, 1] (0: deterministic)")
     ap.add_argument("--wrap-x0", action="store_true", help="strided update: wrap the x0 estimate to [-pi, pi)")
     ap.add_argument("--stride", type=int, default=1, help="visit every STRIDE-th timestep (p_sample_loop's step)")
+    ap.add_argument("--keep", default="", help="partial redesign: ligand positions held fixed, e.g. 0-31 (the ligand then fills the frame)")
     a = ap.parse_args()
-    r = run(a.seq_len, a.batch, a.steps, a.graph, seed=a.seed, update=a.update, eta=a.eta, wrap_x0=a.wrap_x0, stride=a.stride)
+    r = run(a.seq_len, a.batch, a.steps, a.graph, seed=a.seed, update=a.update, eta=a.eta, wrap_x0=a.wrap_x0, stride=a.stride, keep=a.keep)
     print(f"single-pocket sampling B={r['batch']} L={r['seq_len']} T={r['timesteps']} stride={a.stride} update={a.update} eta={a.eta} "
-          f"wrap_x0={a.wrap_x0} ({r['arithmetic']}, skinny GEMM M<={pkg.ops.SKINNY_MAX_M}, graph={a.graph}, seed={a.seed}): "
+          f"wrap_x0={a.wrap_x0} ({r['arithmetic']}, skinny GEMM M<={pkg.ops.SKINNY_MAX_M}, graph={a.graph}, seed={a.seed}, keep={a.keep or None}): "
           f"{r['ms_per_chain']:.1f} ms per chain = {r['ms_per_step']:.3f} ms per reverse step over {r['visited_timesteps']} visited timesteps "
           f"(encoder cached)", flush=True)
 
