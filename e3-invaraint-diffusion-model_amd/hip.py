@@ -112,6 +112,10 @@ _SIGNATURES = {
     "e3d_adamw_step_dev": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P]),
     "e3d_dropout_set_epoch_ptr": (c_int, [_P]),
     "e3d_adamw_step": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, _P, c_float, c_float, c_float, c_float, c_float, c_int, _P]),
+    # the same update carrying the weight EMA (training.WeightEMA): one more pointer table, d_n from the host / the device block
+    "e3d_adamw_ema_step": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, c_float, c_float, c_float, c_float, c_float, c_int,
+                                   c_float, _P]),
+    "e3d_adamw_ema_step_dev": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P]),
     # attention over variable-length segments (ABI v5)
     "e3d_attn_varlen_fwd": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, _P, _P, _P, _P, _P, c_int, _P, c_int, _P,
                                     c_int64, c_int, c_int, c_int, c_int, _P]),

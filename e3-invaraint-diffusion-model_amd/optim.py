@@ -9,6 +9,10 @@ param_group keys), so optimizer checkpoints move between the two; LR schedulers 
 ``Optimizer``.  Anything the kernels do not cover (amsgrad, maximize, non-fp32 or non-contiguous tensors, CPU
 parameters, a closure-free ``step`` on a box without the HIP library) falls back to ``torch.optim.AdamW.step`` after a
 ``clip_grad_norm_``.
+
+``attach_ema(training.WeightEMA)``: the update launch also averages every parameter it writes into the EMA's shadow
+(``e3d_adamw_ema_step`` / ``_dev``: 8 B per parameter more in the same launch, nothing new to launch or capture); a step
+that falls back updates the shadows through ``WeightEMA.update()``.  Without an attached EMA nothing here changes.
 """
 import torch
 
@@ -25,6 +29,7 @@ class ClipAdamW(torch.optim.AdamW):
         self.device_scalars = False  # learning rate and step counts read from device memory (graph replay): use_device_scalars
         self._e3d_tab = None         # device tables of the current parameter partition
         self.last_norm = None        # total gradient norm of the last clipped step (0-dim device tensor)
+        self.ema = None              # training.WeightEMA averaged inside the update launch (attach_ema)
 
     # ------------------------------------------------------------------------------------------------ public
     def step_clipped(self, max_norm, closure=None):
@@ -44,6 +49,28 @@ class ClipAdamW(torch.optim.AdamW):
         if bool(on) != self.device_scalars:
             self.device_scalars = bool(on)
             self._e3d_tab = None
+
+    def attach_ema(self, ema):
+        """Average the weights into ``ema`` (a ``training.WeightEMA`` over parameters of this optimizer) inside the update
+        launch of every step from now on.  The tables are rebuilt with the shadows' pointers -- checked one by one in
+        ``_tables`` -- and a ``GraphedStep`` captures again."""
+        for attr in ("shadow_of", "update", "decay", "warmup", "num_updates"):
+            if not hasattr(ema, attr):
+                raise TypeError(f"attach_ema needs a training.WeightEMA (no {attr!r})")
+        self.ema = ema
+        self._e3d_tab = None
+
+    def detach_ema(self):
+        """Back to the plain update; returns the EMA that was attached (its shadows stay as they are)."""
+        ema, self.ema = self.ema, None
+        self._e3d_tab = None
+        return ema
+
+    def ema_words_current(self):
+        """False when an attached EMA's count or law no longer is what the device words of the tables hold (it was loaded
+        from a state_dict): the next eager ``step`` rebuilds the tables, a captured step must not be replayed before."""
+        tab, ema = self._e3d_tab, self.ema
+        return tab is None or ema is None or (tab["ema_n"], tab["ema_law"]) == (ema.num_updates, (ema.decay, ema.warmup))
 
     def sync_lr(self):
         tab = self._e3d_tab
@@ -72,6 +99,9 @@ class ClipAdamW(torch.optim.AdamW):
             return
         tab["ranges"] = [[(c0, c1, step + delta) for (c0, c1, step) in rs] for rs in tab["ranges"]]
         torch._foreach_add_(tab["step_tensors"], delta)
+        if self.ema is not None:
+            self.ema.num_updates += delta
+            tab["ema_n"] += delta
         tab["gptr_host"] = None      # the graph re-copies ITS gradient pointers: an eager step must upload its own again
         self._opt_called = True      # what LR schedulers look at to order scheduler.step() after optimizer.step()
 
@@ -109,7 +139,10 @@ class ClipAdamW(torch.optim.AdamW):
         #  hooked torch.optim.AdamW.step -- patched as soon as a plain AdamW exists in the process -- would fire every
         #  optimizer pre / post hook twice)
         plain = getattr(torch.optim.AdamW.step, "__wrapped__", torch.optim.AdamW.step)
-        return plain(self, closure)
+        out = plain(self, closure)
+        if self.ema is not None:      # the same law, per tensor (parameters that took the step: those with a gradient)
+            self.ema.update()
+        return out
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -154,6 +187,9 @@ class ClipAdamW(torch.optim.AdamW):
                                                tab["chunk_first"].data_ptr(), tab["n_chunks"], self._e3d_clip,
                                                tab["partial"].data_ptr(), nc.data_ptr(), stream), "e3d_grad_global_norm")
             self.last_norm = nc[0]
+        ema = self.ema
+        if ema is not None and not self.device_scalars:
+            ema_decay = ema.decay_at(ema.num_updates + 1)     # d_n of this update (fp32 value), the one the device form derives
         r = -1
         for k, (gi, ps) in enumerate(parts):
             group = self.param_groups[gi]
@@ -161,6 +197,21 @@ class ClipAdamW(torch.optim.AdamW):
                 b1, b2 = group["betas"]
                 lr = group["lr"]
                 r += 1
+                if ema is not None:
+                    if self.device_scalars:
+                        hip.check(lib.e3d_adamw_ema_step_dev(
+                            tab["pptr"].data_ptr(), tab["gptr"].data_ptr(), tab["mptr"].data_ptr(), tab["vptr"].data_ptr(),
+                            tab["eptr"].data_ptr(), tab["numel"].data_ptr(), tab["chunk_tensor"].data_ptr() + 4 * c0,
+                            tab["chunk_first"].data_ptr() + 8 * c0, c1 - c0, nc.data_ptr() if nc is not None else None,
+                            tab["dyn"].data_ptr() + 4 * DYN_STRIDE * r, stream), "e3d_adamw_ema_step_dev")
+                    else:
+                        hip.check(lib.e3d_adamw_ema_step(
+                            tab["pptr"].data_ptr(), tab["gptr"].data_ptr(), tab["mptr"].data_ptr(), tab["vptr"].data_ptr(),
+                            tab["eptr"].data_ptr(), tab["numel"].data_ptr(), tab["chunk_tensor"].data_ptr() + 4 * c0,
+                            tab["chunk_first"].data_ptr() + 8 * c0, c1 - c0, nc.data_ptr() if nc is not None else None,
+                            float(lr), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), step + 1,
+                            ema_decay, stream), "e3d_adamw_ema_step")
+                    continue
                 if self.device_scalars:
                     hip.check(lib.e3d_adamw_step_dev(
                         tab["pptr"].data_ptr(), tab["gptr"].data_ptr(), tab["mptr"].data_ptr(), tab["vptr"].data_ptr(),
@@ -174,16 +225,23 @@ class ClipAdamW(torch.optim.AdamW):
                     c1 - c0, nc.data_ptr() if nc is not None else None, float(lr), float(b1), float(b2), float(group["eps"]),
                     float(group["weight_decay"]), step + 1, stream), "e3d_adamw_step")
             tab["ranges"][k] = [(c0, c1, step + 1) for (c0, c1, step) in tab["ranges"][k]]
-        if self.device_scalars:
+        if self.device_scalars and ema is not None:
+            tab["dyn"][:, 1::6] += 1.0                   # words 1 and 7: step counts and EMA updates, in one launch
+        elif self.device_scalars:
             tab["dyn"][:, 1] += 1.0                      # the device-side step counts (captured with the step)
         torch._foreach_add_(tab["step_tensors"], 1)
+        if ema is not None:
+            ema.num_updates += 1
+            tab["ema_n"] += 1
         return loss
 
     # ------------------------------------------------------------------------------------------------ tables
     def _tables(self, parts):
         sig = tuple((gi, tuple(id(p) for p in ps)) for gi, ps in parts)
+        ema = self.ema
         tab = self._e3d_tab
-        if tab is not None and tab["sig"] == sig and all(p.data_ptr() == q for p, q in zip(tab["params"], tab["pptr_host"])):
+        if tab is not None and tab["sig"] == sig and all(p.data_ptr() == q for p, q in zip(tab["params"], tab["pptr_host"])) \
+                and self.ema_words_current():      # (an EMA loaded from a state_dict gets new device words)
             return tab
         chunk = hip.lib().e3d_optim_chunk_elems()
         dev = parts[0][1][0].device
@@ -246,12 +304,34 @@ class ClipAdamW(torch.optim.AdamW):
             # (the state tensors the device tables point into: kept alive with the tables)
             "keep": [(self.state[p]["exp_avg"], self.state[p]["exp_avg_sq"]) for p in params],
         }
+        if ema is not None:
+            # a wrong entry of this table is a GPU fault, not a failed test: every shadow is checked before its address goes in
+            shadows = []
+            for p in params:
+                e = ema.shadow_of(p)
+                if e is None:
+                    raise ValueError("attach_ema: the EMA holds no shadow of a parameter this optimizer steps")
+                if not (torch.is_tensor(e) and e.is_cuda and e.device == dev and e.dtype == torch.float32 and e.is_contiguous()
+                        and e.numel() == p.numel() and not e.requires_grad):
+                    raise ValueError(f"attach_ema: shadow {tuple(e.shape)} {e.dtype} on {e.device} does not fit a parameter "
+                                     f"{tuple(p.shape)} on {dev} (need contiguous fp32 of the same numel on the same device)")
+                if e.data_ptr() == p.data_ptr():
+                    raise ValueError("attach_ema: a shadow aliases its parameter")
+                shadows.append(e)
+            tab["eptr"] = dev_i64([e.data_ptr() for e in shadows])
+            tab["ema_n"], tab["ema_law"] = ema.num_updates, (ema.decay, ema.warmup)     # what the device words will hold
+            tab["keep"].append(tuple(shadows))
         if self.device_scalars:
+            if ema is not None:      # words 6 / 7 of the block: decay (sign bit set: no warm-up) and the updates made so far
+                enc = float(ema.decay) if ema.warmup else -float(ema.decay)
+                pad = (enc, float(ema.num_updates))
+            else:
+                pad = (0.0, 0.0)
             flat = [(gi, c0, st) for (gi, _), rs in zip(parts, ranges) for (c0, c1, st) in rs]
             tab["dyn_ranges"] = flat
             tab["dyn_hyper"] = [self._hyper(self.param_groups[gi]) for gi, _, _ in flat]
-            # per range: lr, steps taken, beta1, beta2, eps, weight_decay, (2 pad) -- e3d_adamw_step_dev's ``hyper`` block
-            tab["dyn"] = torch.tensor([[h[0], float(st), h[1], h[2], h[3], h[4], 0.0, 0.0] for h, (_, _, st) in zip(tab["dyn_hyper"], flat)],
+            # per range: lr, steps taken, beta1, beta2, eps, weight_decay, (2 pad: the EMA's) -- e3d_adamw_step_dev's ``hyper`` block
+            tab["dyn"] = torch.tensor([[h[0], float(st), h[1], h[2], h[3], h[4], pad[0], pad[1]] for h, (_, _, st) in zip(tab["dyn_hyper"], flat)],
                                       dtype=torch.float32).to(dev)
         self._e3d_tab = tab
         return tab

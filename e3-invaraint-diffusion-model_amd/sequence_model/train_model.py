@@ -30,6 +30,10 @@ GPU_ID = [0]
 NUM_THREAD = 16
 # keyed training and validation draws (training.fit(seed=)); unset: torch's generator, as the reference
 SEED = int(os.environ["E3D_TRAIN_SEED"], 0) if os.environ.get("E3D_TRAIN_SEED") else None
+# weight EMA (training.fit(ema_decay=)): E3D_TRAIN_EMA=<decay in [0, 1)>, E3D_TRAIN_EMA_WARMUP=0 for a constant decay; unset: none.
+# Validation, ./best_val_model.pt and MODEL_PATH then hold the EMA weights, under the model's own state_dict keys.
+EMA_DECAY = float(os.environ["E3D_TRAIN_EMA"]) if os.environ.get("E3D_TRAIN_EMA") else None
+EMA_WARMUP = os.environ.get("E3D_TRAIN_EMA_WARMUP", "1") != "0"
 
 CONFIG = {
     "pocket_ext": 4,
@@ -96,7 +100,7 @@ def train_model(encoder_config, decoder_config, train_dataloader, val_dataloader
     history = training.fit(model, train_dataloader, val_dataloader, min_epochs=CONFIG["min_epochs"],
                            max_epochs=CONFIG["max_epochs"], gradient_clip=CONFIG["gradient_clip"], device=device,
                            checkpoint_path="./best_val_model.pt", checkpoint_mode="max", max_steps=max_steps,
-                           seed=SEED if seed is None else seed)
+                           seed=SEED if seed is None else seed, ema_decay=EMA_DECAY, ema_warmup=EMA_WARMUP)
     return history, model
 
 
@@ -107,4 +111,5 @@ if __name__ == "__main__":
     encoder_config, decoder_config = build_configs()
     history, model = train_model(encoder_config, decoder_config, train_dataloader, val_dataloader)
     if int(os.environ.get("RANK", "0")) == 0 and MODEL_PATH:
-        torch.save(model.state_dict(), MODEL_PATH)
+        ema = history.get("ema")
+        torch.save(model.state_dict() if ema is None else ema.model_state_dict(model), MODEL_PATH)

@@ -35,9 +35,121 @@ def adamw(params, lr, weight_decay):
         return torch.optim.AdamW(params, lr=lr, weight_decay=weight_decay)
 
 
-def clip_and_step(params, optim, max_norm, fold=None):
+def ema_decay_at(n, decay, warmup=True):
+    """THE law of the weight EMA: the decay d_n of its n-th update, n = 1, 2, ...:  min(decay, (1 + n) / (10 + n)) with
+    ``warmup`` (the average follows the weights closely while few of them have been seen), ``decay`` without -- computed
+    in double and rounded ONCE to fp32 (returned as a Python float holding that fp32 value).  The update of an element,
+    after the optimizer update of the same step:  w = 1.0f - d_n (fp32);  e <- e + (p_new - e) * w.
+    ``decay`` lies in [0, 1) (as an fp32 value too: 1 - 1e-9 rounds to 1.0f and is refused); anything else raises ValueError.
+    csrc/optim.hip (``ema_decay_dev``) forms the same value from the same double expression on the device."""
+    decay = float(decay)
+    if not (0.0 <= decay < 1.0) or float(torch.tensor(decay, dtype=torch.float32)) >= 1.0:
+        raise ValueError(f"ema decay must lie in [0, 1), got {decay!r}")
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"ema updates are counted from 1, got n={n}")
+    d = min(decay, (1.0 + n) / (10.0 + n)) if warmup else decay
+    return float(torch.tensor(d, dtype=torch.float64).to(torch.float32))
+
+
+class WeightEMA:
+    """Exponential moving average of a model's trainable parameters (``ema_decay_at`` is its law): one fp32 contiguous
+    shadow per parameter, a fresh clone at construction, keyed by the parameter's ``state_dict`` name, plus the number of
+    updates made.  Buffers are not averaged.  Two routes make an update, and a step takes exactly one of them:
+    ``optim.ClipAdamW.attach_ema(self)`` -- the update launch averages every parameter it writes (csrc/optim.hip) -- and
+    ``update()`` in plain torch for everything else.  Either way only parameters that took the optimizer step (those with a
+    gradient) are averaged: one without has not moved, and its shadow started as a copy of it.
+
+    ``model_state_dict(model)`` is the drop-in point for the samplers: the model's ``state_dict()`` with the EMA weights."""
+
+    def __init__(self, model_or_named_params, decay, warmup=True):
+        ema_decay_at(1, decay, warmup)                   # (raises on a decay outside [0, 1))
+        self.decay, self.warmup, self.num_updates = float(decay), bool(warmup), 0
+        named = model_or_named_params.named_parameters() if isinstance(model_or_named_params, torch.nn.Module) \
+            else model_or_named_params
+        self.shadows, self._params = {}, {}
+        for name, p in named:
+            if p.requires_grad:
+                self.shadows[name] = p.detach().to(torch.float32, copy=True).contiguous()
+                self._params[name] = p
+        self._by_id = {id(p): name for name, p in self._params.items()}
+
+    def decay_at(self, n):
+        return ema_decay_at(n, self.decay, self.warmup)
+
+    def shadow_of(self, param):
+        """The shadow of one of the parameters this EMA was built over (None: not one of them)."""
+        name = self._by_id.get(id(param))
+        return None if name is None else self.shadows[name]
+
+    @torch.no_grad()
+    def update(self):
+        """One update in plain torch, after the optimizer step (and before the next ``zero_grad``): the route of every
+        optimizer that is not a ClipAdamW, of CPU parameters, and of a ClipAdamW step that fell back."""
+        pairs = [(self.shadows[name], p) for name, p in self._params.items() if p.grad is not None]
+        if not pairs:
+            return
+        d = self.decay_at(self.num_updates + 1)
+        w = float(torch.tensor(1.0, dtype=torch.float32) - torch.tensor(d, dtype=torch.float32))    # 1.0f - d_n
+        shadows = [e for e, _ in pairs]
+        diff = torch._foreach_sub([p.detach().to(torch.float32).reshape(e.shape) for e, p in pairs], shadows)
+        torch._foreach_mul_(diff, w)
+        torch._foreach_add_(shadows, diff)
+        self.num_updates += 1
+
+    def state_dict(self):
+        return {"shadows": {k: v.clone() for k, v in self.shadows.items()}, "num_updates": self.num_updates,
+                "decay": self.decay, "warmup": self.warmup}
+
+    def load_state_dict(self, state):
+        """In place: the shadows keep their storage (an attached optimizer's tables and captured graphs point into it)."""
+        got = state["shadows"]
+        if set(got) != set(self.shadows):
+            raise KeyError(f"ema state_dict: shadow names differ: {sorted(set(got) ^ set(self.shadows))}")
+        ema_decay_at(1, state["decay"], state["warmup"])
+        with torch.no_grad():
+            for k, e in self.shadows.items():
+                if got[k].shape != e.shape:
+                    raise ValueError(f"ema state_dict: {k}: shape {tuple(got[k].shape)}, expected {tuple(e.shape)}")
+                e.copy_(got[k])
+        self.num_updates, self.decay, self.warmup = int(state["num_updates"]), float(state["decay"]), bool(state["warmup"])
+
+    def model_state_dict(self, model):
+        """``model.state_dict()`` with every averaged entry replaced by (a copy of) its shadow, in the entry's dtype: the
+        same keys, buffers as they are -- what ``load_state_dict`` and the samplers' ``MODEL_PATH`` take unchanged."""
+        out = {}
+        for k, v in model.state_dict(keep_vars=True).items():
+            name = self._by_id.get(id(v)) if isinstance(v, torch.nn.Parameter) else None
+            if name is None and k in self.shadows and isinstance(v, torch.nn.Parameter) and v.requires_grad:
+                name = k                                  # (another instance of the model: by name)
+            out[k] = v.detach() if name is None else self.shadows[name].to(v.dtype, copy=True).reshape(v.shape)
+        return out
+
+    @contextlib.contextmanager
+    def swapped(self, model):
+        """The model's parameters hold the EMA weights inside the block and are restored bit for bit on exit.  Copies in
+        place and never rebinds ``.data``: packed parameter views (bert.py), optimizer tables and captured graphs keep
+        their pointers.  Derived-weight caches are invalidated on entry and on exit."""
+        pairs = [(p, self.shadows[name]) for name, p in model.named_parameters() if name in self.shadows and p.requires_grad]
+        saved = [p.detach().clone() for p, _ in pairs]
+        with torch.no_grad():
+            for p, e in pairs:
+                p.copy_(e.reshape(p.shape))
+        ops.invalidate_weight_caches()
+        try:
+            yield model
+        finally:
+            with torch.no_grad():
+                for (p, _), old in zip(pairs, saved):
+                    p.copy_(old)
+            ops.invalidate_weight_caches()
+
+
+def clip_and_step(params, optim, max_norm, fold=None, ema=None):
     """``clip_grad_norm_(params, max_norm)`` + ``optim.step()`` -- what Lightning's ``gradient_clip_val`` does around the
     reference's AdamW (structure_model/train_model.py:99-110).  Returns the total gradient norm (device tensor).
+    ``ema`` (a ``WeightEMA``): updated after the step -- by the step itself where it is a ClipAdamW with this EMA attached
+    (inside the update launch, or through ``update()`` when that step falls back), by ``ema.update()`` here otherwise.
     ``fold`` (E3D_FOLD_CLIP=1): hand torch's fused AdamW 1 / clip_coef as its ``grad_scale`` (the GradScaler hook) so that
     the clip happens inside the update kernel instead of a separate multi-tensor pass.  Measured on MI355X (146 M
     parameters, rocprofv3): the multiply pass it removes costs 0.27 ms, but the fused kernel with a grad_scale also writes
@@ -46,7 +158,14 @@ def clip_and_step(params, optim, max_norm, fold=None):
     give the same parameters)."""
     from .optim import ClipAdamW
     if isinstance(optim, ClipAdamW):                  # norm, clip and update in three launches (csrc/optim.hip)
-        return optim.step_clipped(max_norm)
+        norm = optim.step_clipped(max_norm)
+        if ema is not None and optim.ema is not ema:
+            ema.update()
+        return norm
+    if ema is not None:
+        norm = clip_and_step(params, optim, max_norm, fold)
+        ema.update()
+        return norm
     if fold is None:
         fold = os.environ.get("E3D_FOLD_CLIP", "0") == "1"
     grads = [p.grad for p in params if p.grad is not None]
@@ -82,8 +201,9 @@ def backward(loss, averager=None):
         loss.backward()
 
 
-def train_step(model, optim, params, clip, batch, batch_idx=0, averager=None):
-    """THE training step, eagerly, on the current stream (CPU parameters and any optimizer included); returns the loss."""
+def train_step(model, optim, params, clip, batch, batch_idx=0, averager=None, ema=None):
+    """THE training step, eagerly, on the current stream (CPU parameters and any optimizer included); returns the loss.
+    ``ema``: the run's ``WeightEMA``, updated with the step (``clip_and_step``)."""
     loss = model.training_step(batch, batch_idx)
     optim.zero_grad(set_to_none=True)
     if averager is not None:
@@ -91,7 +211,10 @@ def train_step(model, optim, params, clip, batch, batch_idx=0, averager=None):
     backward(loss, averager)
     if averager is not None:
         averager.average()                       # RCCL all-reduce (no-op for one process)
-    clip_and_step(params, optim, clip)           # global-norm clip of the averaged grads, then AdamW
+    if ema is None:
+        clip_and_step(params, optim, clip)       # global-norm clip of the averaged grads, then AdamW
+    else:
+        clip_and_step(params, optim, clip, ema=ema)   # ... and the weight EMA of the step
     return loss
 
 
@@ -101,15 +224,16 @@ class EagerStep:
 
     graph = None                                     # nothing captured
 
-    def __init__(self, model, optim, params, gradient_clip, averager=None):
+    def __init__(self, model, optim, params, gradient_clip, averager=None, ema=None):
         self.model, self.optim, self.params, self.clip, self.averager = model, optim, params, gradient_clip, averager
+        self.ema = ema                                   # the run's WeightEMA (None: none), updated with every step
 
     def _replayed(self, batch):
         """The loss of the step if a captured graph ran it, None if it has yet to run (eagerly)."""
         return None
 
     def _eager(self, batch, batch_idx):
-        loss = train_step(self.model, self.optim, self.params, self.clip, batch, batch_idx, self.averager)
+        loss = train_step(self.model, self.optim, self.params, self.clip, batch, batch_idx, self.averager, self.ema)
         ops.invalidate_weight_caches()               # belt and braces beside the global optimizer hook (ops.py)
         return loss.detach()
 
@@ -140,11 +264,14 @@ class GraphedStep(EagerStep):
     REPLAY_ON_SIDE_STREAM = False                    # replays run on the caller's current stream, eager steps on self.stream
     CAPTURE_FAILED = "training step could not be captured in a HIP graph"
 
-    def __init__(self, model, optim, params, gradient_clip, warmup=2):
+    def __init__(self, model, optim, params, gradient_clip, warmup=2, ema=None):
         from .optim import ClipAdamW
         if not isinstance(optim, ClipAdamW):
             raise TypeError("GraphedStep needs optim.ClipAdamW (device-side learning rate and step counts)")
-        super().__init__(model, optim, params, gradient_clip)
+        if ema is not None and optim.ema is not ema:
+            # the EMA of a replayed step lives in the captured update launch: its decay and count are device words
+            raise ValueError("GraphedStep: attach the EMA to the optimizer first (ClipAdamW.attach_ema)")
+        super().__init__(model, optim, params, gradient_clip, ema=ema)
         self.warmup, self.seen = warmup, {}
         self.graphs = {}                             # signature -> the captured step (graph segments, static batch, loss, grads)
         self.segments = self.key = self.static = self.loss = None   # ... and the one used last
@@ -170,7 +297,7 @@ class GraphedStep(EagerStep):
         """Capture the step on ``static``: (graph segments, loss tensor)."""
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, stream=self.stream):
-            loss = train_step(self.model, self.optim, self.params, self.clip, static)
+            loss = train_step(self.model, self.optim, self.params, self.clip, static, ema=self.ema)
             self.epoch.add_(1)
         return (graph,), loss
 
@@ -203,8 +330,10 @@ class GraphedStep(EagerStep):
 
     def _stale(self):
         """The graph carries raw pointers: parameters that moved (``module.to()``) or optimizer state that was replaced
-        (``load_state_dict``: ClipAdamW drops its tables) invalidate it -- warm up and capture again."""
-        return self.optim._e3d_tab is not self.tab or any(p.data_ptr() != q for p, q in zip(self.params, self.ptrs))
+        (``load_state_dict``: ClipAdamW drops its tables) invalidate it, and so does an attached EMA whose count or law
+        was set from outside (``WeightEMA.load_state_dict``: the device words are behind) -- warm up and capture again."""
+        return (self.optim._e3d_tab is not self.tab or any(p.data_ptr() != q for p, q in zip(self.params, self.ptrs))
+                or not self.optim.ema_words_current())
 
     def _may_capture(self, key):
         return (self.failed is None and key not in self.graphs and len(self.graphs) < self.MAX_GRAPHS
@@ -267,7 +396,7 @@ class GraphedStep(EagerStep):
         return self._on_stream(self._replay, batch) if self.REPLAY_ON_SIDE_STREAM else self._replay(batch)
 
     def _eager_body(self, batch, batch_idx):
-        loss = train_step(self.model, self.optim, self.params, self.clip, batch, batch_idx, self.averager).detach()
+        loss = train_step(self.model, self.optim, self.params, self.clip, batch, batch_idx, self.averager, self.ema).detach()
         self.epoch.add_(1)
         return loss
 
@@ -287,8 +416,8 @@ class GraphedDDPStep(GraphedStep):
     REPLAY_ON_SIDE_STREAM = True                     # replay and eager alike inside self.stream
     CAPTURE_FAILED = "data-parallel training step could not be captured in HIP graphs"
 
-    def __init__(self, model, optim, params, gradient_clip, averager, warmup=2):
-        super().__init__(model, optim, params, gradient_clip, warmup)
+    def __init__(self, model, optim, params, gradient_clip, averager, warmup=2, ema=None):
+        super().__init__(model, optim, params, gradient_clip, warmup, ema=ema)
         self.averager = averager
         self.world = torch.distributed.get_world_size()
 
@@ -304,24 +433,27 @@ class GraphedDDPStep(GraphedStep):
         with torch.cuda.graph(g2, stream=self.stream, pool=g1.pool()):
             for flat in avg.flats():
                 flat.div_(self.world)
-            clip_and_step(self.params, self.optim, self.clip)
+            clip_and_step(self.params, self.optim, self.clip, ema=self.ema)   # (the EMA rides in the update launch)
         return (g1, g2), loss
 
     def _between_segments(self):
         self.averager.all_reduce_flats()             # the only eager launches of the step
 
 
-def make_stepper(model, optim, params, gradient_clip, averager=None, graph=None):
+def make_stepper(model, optim, params, gradient_clip, averager=None, graph=None, ema=None):
     """The stepper a run gets: the step replayed from HIP graphs where that is possible (GPU parameters under ClipAdamW;
     ``graph`` None: E3D_TRAIN_GRAPH) -- ``GraphedStep`` for one process, ``GraphedDDPStep`` under an active averager whose
-    hooks are in place -- and ``EagerStep`` everywhere else."""
+    hooks are in place -- and ``EagerStep`` everywhere else.  ``ema``: the run's ``WeightEMA``, attached to a ClipAdamW
+    here (its update then rides in the optimizer's launch, captured with it) and updated in plain torch otherwise."""
     from .optim import ClipAdamW
+    if ema is not None and isinstance(optim, ClipAdamW) and optim.ema is not ema:
+        optim.attach_ema(ema)
     if (GRAPH_TRAIN if graph is None else graph) and params and params[0].is_cuda and isinstance(optim, ClipAdamW):
         if averager is None or not averager._active():
-            return GraphedStep(model, optim, params, gradient_clip)
+            return GraphedStep(model, optim, params, gradient_clip, ema=ema)
         if averager._hooked:
-            return GraphedDDPStep(model, optim, params, gradient_clip, averager)
-    return EagerStep(model, optim, params, gradient_clip, averager)
+            return GraphedDDPStep(model, optim, params, gradient_clip, averager, ema=ema)
+    return EagerStep(model, optim, params, gradient_clip, averager, ema=ema)
 
 
 # the tensors of a dataset.py batch that are laid out [B, L, ...] over the ligand / the pocket frame
@@ -463,15 +595,16 @@ class BestCheckpoint:
     """ModelCheckpoint(monitor='val_loss', save_top_k=1, mode=...) semantics; the reference passes
     mode='max', i.e. it keeps the HIGHEST validation loss -- reproduced by default."""
 
-    def __init__(self, path, mode="max"):
+    def __init__(self, path, mode="max", ema=None):
         self.path, self.mode, self.best = path, mode, None
+        self.ema = ema                                   # a WeightEMA: the file holds ITS weights (model_state_dict)
 
     def update(self, model, val_loss, rank=0):
         better = self.best is None or (val_loss > self.best if self.mode == "max" else val_loss < self.best)
         if better:
             self.best = val_loss
             if rank == 0 and self.path:
-                torch.save(model.state_dict(), self.path)
+                torch.save(model.state_dict() if self.ema is None else self.ema.model_state_dict(model), self.path)
         return better
 
 
@@ -494,7 +627,8 @@ def _step_batch(batch, device, draws, trim, frame=None):
 
 def fit(model, train_loader, val_loader=None, *, max_epochs, min_epochs=0, gradient_clip=1.0, device="cuda:0",
         log_every_n_steps=30, checkpoint_path="./best_val_model.pt", checkpoint_mode="max", max_steps=None,
-        log=print, trim_padding=None, seed=None, noise_tables=None, noise_scale=None, keyed_dropout=None):
+        log=print, trim_padding=None, seed=None, noise_tables=None, noise_scale=None, keyed_dropout=None,
+        ema_decay=None, ema_warmup=True):
     """Returns a history dict.  ``model`` provides training_step / validation_step /
     configure_optimizers (the reference's LightningModule surface).
     ``seed`` (default None: torch's generators, as ever): keyed training and validation draws ("Keyed sampling
@@ -510,7 +644,13 @@ def fit(model, train_loader, val_loader=None, *, max_epochs, min_epochs=0, gradi
     torch-seeded dropout under the seed.  Without a seed it has no effect.
     ``trim_padding`` (None: E3D_TRAIN_TRIM, default off = the reference's padded frames): run every training and
     validation step on the frame of the batch's longest ligand / pocket (``trim_batch``; under a process group the frame
-    is the maximum over the ranks, agreed on the host, so that every rank replays the same kind of step)."""
+    is the maximum over the ranks, agreed on the host, so that every rank replays the same kind of step).
+    ``ema_decay`` (None: none, today's run): keep a ``WeightEMA`` of the trainable parameters with this decay
+    (``ema_warmup``: the warm-up of ``ema_decay_at``), updated with every step -- inside the update launch of a ClipAdamW,
+    in plain torch otherwise.  Validation then runs on the EMA weights (``WeightEMA.swapped``), the checkpoint file holds
+    them (``model_state_dict``: the model's own keys, so the samplers load it as ever), ``history["ema_updates"]`` counts
+    the updates and ``history["ema"]`` is the instance, for the caller to save or carry on.  Data-parallel runs need no
+    collective for it: the ranks apply identical averaged gradients and hold identical shadows."""
     trim = TRIM_TRAIN if trim_padding is None else bool(trim_padding)
     with contextlib.ExitStack() as whole_run:
         whole_run.enter_context(ops.arithmetic(TRAIN_ARITHMETIC))
@@ -526,8 +666,12 @@ def fit(model, train_loader, val_loader=None, *, max_epochs, min_epochs=0, gradi
         optim = conf["optimizer"]
         sched = conf.get("lr_scheduler") or {}
         params = [p for p in model.parameters() if p.requires_grad]
-        stepper = make_stepper(model, optim, params, gradient_clip, sharding.GradientAverager(model.parameters()))
-        ckpt = BestCheckpoint(checkpoint_path, checkpoint_mode)
+        ema = None if ema_decay is None else WeightEMA(model, ema_decay, ema_warmup)
+        averager = sharding.GradientAverager(model.parameters())
+        stepper = make_stepper(model, optim, params, gradient_clip, averager) if ema is None else \
+            make_stepper(model, optim, params, gradient_clip, averager, ema=ema)
+        ckpt = BestCheckpoint(checkpoint_path, checkpoint_mode) if ema is None else \
+            BestCheckpoint(checkpoint_path, checkpoint_mode, ema=ema)
         history = {"train_loss": [], "val_loss": [], "steps": 0, "seconds": 0.0}
         t0 = time.perf_counter()
         step = 0
@@ -563,7 +707,7 @@ def fit(model, train_loader, val_loader=None, *, max_epochs, min_epochs=0, gradi
                 vals = []
                 if draws is not None:
                     draws.set_epoch(None)                # the validation value: the same draws after every epoch
-                with torch.no_grad():
+                with torch.no_grad(), (contextlib.nullcontext() if ema is None else ema.swapped(model)):
                     for batch_idx, batch in enumerate(val_loader):
                         out = model.validation_step(_step_batch(batch, device, draws, trim), batch_idx)
                         vals.append(float(out["val_loss"] if isinstance(out, dict) else out))
@@ -581,4 +725,6 @@ def fit(model, train_loader, val_loader=None, *, max_epochs, min_epochs=0, gradi
                 break
         history["steps"] = step
         history["seconds"] = time.perf_counter() - t0
+        if ema is not None:
+            history["ema_updates"], history["ema"] = ema.num_updates, ema
         return history

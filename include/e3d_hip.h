@@ -657,6 +657,27 @@ int e3d_adamw_step(float* const* params, const float* const* grads, float* const
                    const float* norm_and_clip, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                    void* stream);
 
+/* ---- weight EMA inside the update launch (training.WeightEMA; additions to ABI v5, nothing above changed)
+ * The two forms of the update that optim.ClipAdamW launches, each also averaging the parameter it just wrote into a
+ * shadow: e <- e + (p_new - e) * w, w = 1.0f - d_n (fp32).  ``ema``: one more pointer table in device memory, ``count``
+ * fp32 shadows with the element counts of ``params``; each is read and written once per element (8 B on top of the
+ * update's 28 B) and joins the 16-byte alignment test of the float4 path.  Parameters and both moments come out bit-equal
+ * to e3d_adamw_step / e3d_adamw_step_dev.  A NULL ``ema`` is rejected.
+ *   e3d_adamw_ema_step: ``ema_decay`` = d_n of THIS update, from the host (training.ema_decay_at); outside [0, 1) is
+ *     rejected.
+ *   e3d_adamw_ema_step_dev: d_n from the range's 8-float ``hyper`` block, whose two pad words it uses: hyper[6] = decay
+ *     in [0, 1) with its SIGN BIT set when the warm-up is off (-0.0f for decay 0), hyper[7] = EMA updates made before this
+ *     one, as a float (exact below 2^24); d_n = (float)min(decay, (1 + n) / (10 + n)) with n = hyper[7] + 1, in double --
+ *     or (float)decay without warm-up.  The caller advances hyper[7] on the device after the launch, next to hyper[1].
+ *     The block is device memory: its decay cannot be checked at the entry point.  */
+int e3d_adamw_ema_step(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                       float* const* ema, const int64_t* numel, const int* chunk_tensor, const int64_t* chunk_first,
+                       int n_chunks, const float* norm_and_clip, float lr, float beta1, float beta2, float eps,
+                       float weight_decay, int step, float ema_decay, void* stream);
+int e3d_adamw_ema_step_dev(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                           float* const* ema, const int64_t* numel, const int* chunk_tensor, const int64_t* chunk_first,
+                           int n_chunks, const float* norm_and_clip, const float* hyper, void* stream);
+
 /* ---- keyed dropout decisions (seeded training; additions to ABI v5)
  * With a seed, every dropout decision of a training step is a pure function of (seed, item id, epoch, site, position, head,
  * column or key) -- not of the batch, the row, the frame or the number of steps run before.

@@ -24,7 +24,7 @@ DEV = "cuda:0"
 
 
 def run(model_name="structure", batch=None, seq_len=128, steps=8, dropout=0.0, warmup=2, device=DEV, ddp=False, layers=None,
-        seed=0, arithmetic=None, graph=None, trim=False, train_seed=None):
+        seed=0, arithmetic=None, graph=None, trim=False, train_seed=None, ema=None, ema_unfused=False):
     """One GPU's training step of BASELINE config 2 (structure, B=32) / config 4 (sequence, B=64): forward + loss +
     backward + gradient-norm clip + fused AdamW on synthetic BioLiP-shaped batches.  Returns a dict.
     ``ddp``: the step of ``training.fit`` under an initialised process group (BASELINE config 4: one rank per GPU,
@@ -32,6 +32,8 @@ def run(model_name="structure", batch=None, seq_len=128, steps=8, dropout=0.0, w
     ``train_seed``: keyed training draws as ``training.fit(seed=)`` makes them, items keyed 0 .. B-1, the epoch word
     advanced every step -- the structure batch noised from streams 4 / 5 before the step, the sequence model drawing from
     streams 6 / 7 inside it, dropout decisions (``dropout`` > 0) keyed from streams 8 / 9.
+    ``ema``: a weight EMA of this decay kept with the step as ``training.fit(ema_decay=)`` keeps it (inside the update launch);
+    ``ema_unfused``: the comparison -- the plain step followed by one ``torch._foreach_lerp_`` over all shadows.
     -- weights broadcast from rank 0, gradients as views of the all-reduce buckets, the buckets sent
     (RCCL; gloo in rehearsals) while the deferred weight-gradient launches of the later layers still run; timed between
     barriers, max over ranks by the caller."""
@@ -84,7 +86,13 @@ def run(model_name="structure", batch=None, seq_len=128, steps=8, dropout=0.0, w
 
     # the stepper training.fit would use (a single process: the step replayed from a HIP graph after two eager steps; under
     # a process group: two graph segments around the eager all-reduce); ``graph=False`` / E3D_TRAIN_GRAPH=0: eager
-    stepper = pkg.training.make_stepper(model, optim, params, 1.0, averager, graph=graph)
+    weight_ema = lerp_w = None
+    if ema is not None:
+        weight_ema = pkg.training.WeightEMA(model, ema)
+        if ema_unfused:      # (a constant weight: the cost of the pass is what is compared, not the warm-up)
+            lerp_w, lerp_e, lerp_p = 1.0 - ema, list(weight_ema.shadows.values()), [p.detach() for p in params]
+    stepper = pkg.training.make_stepper(model, optim, params, 1.0, averager, graph=graph,
+                                        ema=None if ema_unfused else weight_ema)
     if isinstance(stepper, pkg.training.GraphedStep):
         warmup = max(warmup, 4)
 
@@ -98,7 +106,10 @@ def run(model_name="structure", batch=None, seq_len=128, steps=8, dropout=0.0, w
             batch_ = dict(pk, **noise_batch_on_device(pk["ligand_angles"], tab))
         else:
             batch_ = pk
-        return stepper.step(batch_)
+        loss = stepper.step(batch_)
+        if lerp_w is not None:
+            torch._foreach_lerp_(lerp_e, lerp_p, lerp_w)
+        return loss
 
     with pkg.ops.arithmetic(arithmetic or pkg.training.TRAIN_ARITHMETIC):   # bf16x3 unless E3D_GEMM_MODE says otherwise
         mode = pkg.ops.GEMM_MODE
@@ -134,7 +145,8 @@ def run(model_name="structure", batch=None, seq_len=128, steps=8, dropout=0.0, w
         dist.all_gather(ws, w)
         assert all(float(t) == float(ws[0]) for t in ws), "ranks diverged"
     return {"model": model_name, **({"train_seed": train_seed} if train_seed is not None else {}), "batch": B, "seq_len": L, "frame": list(frame), "layers": layers, "params_M": sum(p.numel() for p in params) / 1e6,
-            "arithmetic": mode, "dropout": dropout, "graph_replay": stepper.graph is not None,
+            "arithmetic": mode, "dropout": dropout, "ema": ema, "ema_route": None if ema is None else ("unfused" if ema_unfused else "fused"),
+            "ema_updates": None if weight_ema is None else weight_ema.num_updates, "graph_replay": stepper.graph is not None,
             "ms_per_step": dt * 1e3, "samples_per_s": B / dt, "host_enqueue_ms": host_ms,
             **({"ranks": dist.get_world_size(), "global_batch": B * dist.get_world_size(),
                 "global_samples_per_s": B * dist.get_world_size() / dt, "backend": dist.get_backend(),
@@ -155,11 +167,14 @@ def main():
     ap.add_argument("--trim", action="store_true", help="the batch on the frame of its longest ligand / pocket (training.trim_batch)")
     ap.add_argument("--seed", type=int, default=None, help="keyed training draws in the timed step, items keyed 0 .. B-1 "
                     "(default: torch's generator)")
+    ap.add_argument("--ema", type=float, default=None, metavar="D", help="keep a weight EMA of decay D with the step (inside the AdamW launch)")
+    ap.add_argument("--ema-unfused", action="store_true", help="with --ema: a torch._foreach_lerp_ after the plain step instead (comparison)")
     args = ap.parse_args()
     r = run(args.model, args.batch, args.seq_len, args.steps, args.dropout, arithmetic=args.arithmetic,
-            graph=False if args.eager else None, trim=args.trim, train_seed=args.seed)
+            graph=False if args.eager else None, trim=args.trim, train_seed=args.seed, ema=args.ema,
+            ema_unfused=args.ema_unfused)
     print(f"{r['model']} training step: B={r['batch']} L={r['seq_len']} frame={r['frame'][0]}x{r['frame'][1]} layers={r['layers']} params={r['params_M']:.1f}M "
-          f"gemm_mode={r['arithmetic']} dropout={r['dropout']} graph={r['graph_replay']} seed={r.get('train_seed')}: {r['ms_per_step']:.1f} ms/step = {r['samples_per_s']:.1f} samples/s "
+          f"gemm_mode={r['arithmetic']} dropout={r['dropout']} graph={r['graph_replay']} seed={r.get('train_seed')} ema={r['ema']}{'/' + r['ema_route'] if r['ema_route'] else ''}: {r['ms_per_step']:.1f} ms/step = {r['samples_per_s']:.1f} samples/s "
           f"(loss {r['loss']:.4f}, peak mem {r['peak_mem_GiB']:.1f} GiB; host enqueue {r['host_enqueue_ms']:.1f} ms)", flush=True)
 
 
