@@ -357,7 +357,7 @@ def test_adaln_gate(pkg, hip, rows_per_cond, branch):
     mod = torch.randn(M // rows_per_cond, 6 * H, generator=g(3))
     sh, sc, ga = [mod[:, (3 * branch + i) * H:(3 * branch + i + 1) * H].repeat_interleave(rows_per_cond, 0)
                   for i in range(3)]
-    ref = x + ga * (F.layer_norm(y, (H,)) * (1 + sc) + sh)
+    ref = (x.double() + ga.double() * (F.layer_norm(y.double(), (H,)) * (1 + sc.double()) + sh.double())).float()      # fp64 statement
     got = pkg.ops.adaln_gate(x.to(DEV), y.to(DEV), mod.to(DEV), branch, rows_per_cond)
     assert rel_err(got, ref) < 2e-6
 
@@ -370,11 +370,11 @@ def test_embed_layernorm(pkg, hip, Fin, H, M):
     w, b = torch.randn(H, Fin, generator=g(2)), torch.randn(H, generator=g(3))
     ga, be = 1 + 0.1 * torch.randn(H, generator=g(4)), torch.randn(H, generator=g(5))
     add = torch.randn(M // L, H, generator=g(6))
-    ref = F.layer_norm(F.linear(x, w, b), (H,), ga, be, 1e-12)
+    ref = F.layer_norm(F.linear(x.double(), w.double(), b.double()), (H,), ga.double(), be.double(), 1e-12)      # fp64 statement
     d = lambda t: t.to(DEV)  # noqa: E731
-    assert rel_err(pkg.ops.embed_layernorm(d(x), d(w), d(b), d(ga), d(be), 1e-12), ref) < 2e-6
+    assert rel_err(pkg.ops.embed_layernorm(d(x), d(w), d(b), d(ga), d(be), 1e-12), ref.float()) < 2e-6
     got = pkg.ops.embed_layernorm(d(x), d(w), d(b), d(ga), d(be), 1e-12, d(add), L)
-    assert rel_err(got, ref + add.repeat_interleave(L, 0)) < 2e-6
+    assert rel_err(got, (ref + add.double().repeat_interleave(L, 0)).float()) < 2e-6
     if M > 512:   # the two forms do the same arithmetic in the same order
         few = pkg.ops.embed_layernorm(d(x[:48]), d(w), d(b), d(ga), d(be), 1e-12, d(add[:3]), L)
         assert torch.equal(few, got[:48])
