@@ -484,10 +484,9 @@ class _Attention(torch.autograd.Function):
         lib = hip.lib()
         ws = torch.empty((lib.e3d_relkey_attn_bwd_workspace_floats(B, nh, Lq, Lk, int(dist_emb is not None)),),
                          device=q.device, dtype=torch.float32)
-        args = (_p(q), Lq * q.stride(0), q.stride(0), _p(k), Lk * k.stride(0), k.stride(0), _p(v), Lk * v.stride(0),
-                v.stride(0), _p(dist_emb), max_pos, _p(key_mask), _p(out), _p(lse), _p(dout),
-                _p(dq), Lq * dq.stride(0), dq.stride(0), _p(dk), Lk * dk.stride(0), dk.stride(0),
-                _p(dv), Lk * dv.stride(0), dv.stride(0), _p(dE), _p(ws), B, nh, Lq, Lk, ctx.terms)
+        args = (*ops._attn_inputs(q, k, v, Lq, Lk, dist_emb, max_pos, key_mask), _p(out), _p(lse), _p(dout),
+                *ops._attn_view(dq, Lq), *ops._attn_view(dk, Lk), *ops._attn_view(dv, Lk), _p(dE), _p(ws), B, nh, Lq, Lk,
+                ctx.terms)
         with ops._timed("attn_bwd", (B, nh, Lq, Lk)):
             if len(ctx.drop) == 3:               # keyed decisions: (p, site, row_keys) of the forward
                 hip.check(lib.e3d_relkey_attn_bwd_ex_keyed(*args, *ops._keyed_drop(ctx.drop, B * Lq, "attention backward", nh),

@@ -338,86 +338,62 @@ __global__ __launch_bounds__(64) void dist_emb_reduce_kernel(const float* __rest
 }  // namespace
 
 extern "C" int64_t e3d_relkey_attn_bwd_workspace_floats(int B, int nh, int Lq, int Lk, int relkey) {
-    const int64_t q_tiles = (Lq + 31) / 32, k_tiles = (Lk + 31) / 32;
-    const int64_t pm = (int64_t)B * nh * Lq * Lk;
-    const int64_t part = relkey ? (int64_t)B * nh * q_tiles * (k_tiles + 1) * 32 * D : 0;
-    // [P | dS] of the two-launch kernels; the fused kernel parks the distance-table planes in the same region
-    const int64_t head = relkey ? (e3d_attn_bwd_coop_scratch_bytes(Lk) + 3) / 4 : 0;
-    // (+ one liveness word per (b, head, query tile) of the fused kernel: after the chunk sums)
-    return (2 * pm > head ? 2 * pm : head) + part + (relkey ? e3d_attn_bwd_coop_de_floats(Lq, Lk) + (int64_t)B * nh * q_tiles : 0);
+    return e3d_attn_bwd_layout(B, nh, Lq, Lk, relkey).total;
 }
 
-// the body of e3d_relkey_attn_bwd_ex and of its keyed form: ``drop`` = the decisions of drop_p
-static int attn_bwd_dispatch(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs, int64_t k_rs,
-                             const float* v, int64_t v_bs, int64_t v_rs, const float* dist_emb, int P, const float* key_mask,
-                             const float* out, const float* lse, const float* dout, float* dq, int64_t dq_bs, int64_t dq_rs,
-                             float* dk, int64_t dk_bs, int64_t dk_rs, float* dv, int64_t dv_bs, int64_t dv_rs,
-                             float* d_dist_emb, float* workspace, int B, int nh, int Lq, int Lk, int terms, float drop_p,
-                             const E3dDrop drop, void* stream) {
+// the body of e3d_relkey_attn_bwd_ex and of its keyed form
+static int attn_bwd_dispatch(const E3dAttnBwd& a, float* workspace, int terms, const E3dAttnDrop& drop, void* stream) {
     E3D_REQUIRE(terms == 0 || terms == 3 || terms == 6, "attn_bwd: terms must be 0 (fp32 MFMA), 3 or 6 (got %d)", terms);
-    E3D_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "attn_bwd: drop_p=%g outside [0, 1)", (double)drop_p);
-    E3D_REQUIRE(q && k && v && out && lse && dout && dq && dk && dv && workspace, "attn_bwd: null pointer");
-    E3D_REQUIRE(B > 0 && nh > 0 && Lq > 0 && Lk > 0, "attn_bwd: bad shape");
-    E3D_REQUIRE(q_rs % 4 == 0 && k_rs % 4 == 0 && v_rs % 4 == 0 && dq_rs % 4 == 0 && dk_rs % 4 == 0 && dv_rs % 4 == 0 &&
-                    q_bs % 4 == 0 && k_bs % 4 == 0 && v_bs % 4 == 0 && dq_bs % 4 == 0 && dk_bs % 4 == 0 && dv_bs % 4 == 0,
+    E3D_REQUIRE(drop.p >= 0.f && drop.p < 1.f, "attn_bwd: drop_p=%g outside [0, 1)", (double)drop.p);
+    E3D_REQUIRE(a.q.p && a.k.p && a.v.p && a.out && a.lse && a.dout && a.dq.p && a.dk.p && a.dv.p && workspace,
+                "attn_bwd: null pointer");
+    E3D_REQUIRE(a.B > 0 && a.nh > 0 && a.Lq > 0 && a.Lk > 0, "attn_bwd: bad shape");
+    E3D_REQUIRE(a.q.rs % 4 == 0 && a.k.rs % 4 == 0 && a.v.rs % 4 == 0 && a.dq.rs % 4 == 0 && a.dk.rs % 4 == 0 &&
+                    a.dv.rs % 4 == 0 && a.q.bs % 4 == 0 && a.k.bs % 4 == 0 && a.v.bs % 4 == 0 && a.dq.bs % 4 == 0 &&
+                    a.dk.bs % 4 == 0 && a.dv.bs % 4 == 0,
                 "attn_bwd: strides must keep 16B alignment");
-    if (dist_emb) {
-        E3D_REQUIRE(Lq == Lk && Lq <= P && d_dist_emb, "attn_bwd: relative_key needs Lq == Lk <= P and d_dist_emb");
+    if (a.dist_emb) {
+        E3D_REQUIRE(a.Lq == a.Lk && a.Lq <= a.P && a.d_dist_emb, "attn_bwd: relative_key needs Lq == Lk <= P and d_dist_emb");
     }
     hipStream_t s = (hipStream_t)stream;
-    const int q_tiles = (Lq + 31) / 32, k_tiles = (Lk + 31) / 32;
-    const int64_t pm = (int64_t)B * nh * Lq * Lk;
-    const int64_t head = dist_emb ? (e3d_attn_bwd_coop_scratch_bytes(Lk) + 3) / 4 : 0;
-    float* Pm = workspace;
-    float* dSm = workspace + pm;
-    float* part = workspace + (2 * pm > head ? 2 * pm : head);
+    const int q_tiles = (a.Lq + 31) / 32, k_tiles = (a.Lk + 31) / 32;
+    const E3dBwdLayout w = e3d_attn_bwd_layout(a.B, a.nh, a.Lq, a.Lk, a.dist_emb != nullptr);
+    float *Pm = workspace + w.Pm, *dSm = workspace + w.dSm, *part = workspace + w.part;
     const int wpb = 4;
-    if (terms == 3 && e3d_attn_bwd_coop_supported(Lq, Lk, drop_p > 0.f)) {
+    if (terms == 3 && e3d_attn_bwd_coop_supported(a.Lq, a.Lk, drop.on())) {
         // fused recomputing kernel (attn_bwd_coop.hip): one launch, P / dS never reach HBM
         E3D_REQUIRE(((uintptr_t)workspace % 16) == 0, "attn_bwd: workspace must be 16-byte aligned");
-        const int rc = e3d_attn_bwd_coop_launch(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, dist_emb, P, key_mask, out, lse, dout,
-                                                dq, dq_bs, dq_rs, dk, dk_bs, dk_rs, dv, dv_bs, dv_rs, d_dist_emb, workspace, part,
-                                                B, nh, Lq, Lk, drop, drop_p > 0.f, s);
-        return rc;     // (incl. the dE reduction: streaming, deterministic)
+        return e3d_attn_bwd_coop_launch(a, workspace, w, drop, s);     // (incl. the dE reduction: streaming, deterministic)
     } else if (terms == 3) {   // bf16x3 arithmetic (attn_bwd_split.hip); 0 and 6 keep the fp32 MFMA kernels below
-        const int rc = e3d_attn_bwd_split_launch(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, dist_emb, P, key_mask, out, lse,
-                                                 dout, dq, dq_bs, dq_rs, dk, dk_bs, dk_rs, dv, dv_bs, dv_rs, Pm, dSm, part, B,
-                                                 nh, Lq, Lk, drop, drop_p > 0.f, s);
+        const int rc = e3d_attn_bwd_split_launch(a, workspace, w, drop, s);
         if (rc) return rc;
     } else {
     {
-        const int n_units = B * nh * q_tiles;
+        const int n_units = a.B * a.nh * q_tiles;
         const int n_blocks = (n_units + wpb - 1) / wpb;
         const size_t lds = (size_t)wpb * WAVE_LDS_F * sizeof(float);
-#define E3D_BWD_DQ(RK, DR)                                                                                              \
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<RK, DR>), dim3(n_blocks), dim3(64 * wpb), lds, s, q, q_bs, q_rs, k, k_bs, k_rs, v, \
-                       v_bs, v_rs, dist_emb, P, key_mask, dout, out, lse, dq, dq_bs, dq_rs, Pm, dSm, part, nh, Lq, Lk,      \
-                       q_tiles, n_units, drop)
-        if (dist_emb) {
-            if (drop_p > 0.f) E3D_BWD_DQ(true, true);
-            else E3D_BWD_DQ(true, false);
-        } else {
-            if (drop_p > 0.f) E3D_BWD_DQ(false, true);
-            else E3D_BWD_DQ(false, false);
-        }
-#undef E3D_BWD_DQ
+        e3d_attn_form(a.dist_emb, drop.on(), [&](auto rk, auto dr) {
+            hipLaunchKernelGGL((attn_bwd_dq_kernel<decltype(rk)::value, decltype(dr)::value>), dim3(n_blocks), dim3(64 * wpb), lds,
+                               s, E3D_VIEW(a.q), E3D_VIEW(a.k), E3D_VIEW(a.v), a.dist_emb, a.P, a.key_mask, a.dout, a.out, a.lse,
+                               E3D_VIEW(a.dq), Pm, dSm, part, a.nh, a.Lq, a.Lk, q_tiles, n_units, drop.d);
+        });
         int rc = e3d_launch_status("e3d_relkey_attn_bwd (dq)");
         if (rc) return rc;
     }
     {
-        const int n_units = B * nh * k_tiles;
-        hipLaunchKernelGGL(attn_bwd_dkv_kernel, dim3((n_units + wpb - 1) / wpb), dim3(64 * wpb), 0, s, q, q_bs, q_rs, dout, Pm,
-                           dSm, dk, dk_bs, dk_rs, dv, dv_bs, dv_rs, nh, Lq, Lk, k_tiles, n_units);
+        const int n_units = a.B * a.nh * k_tiles;
+        hipLaunchKernelGGL(attn_bwd_dkv_kernel, dim3((n_units + wpb - 1) / wpb), dim3(64 * wpb), 0, s, E3D_VIEW(a.q), a.dout, Pm,
+                           dSm, E3D_VIEW(a.dk), E3D_VIEW(a.dv), a.nh, a.Lq, a.Lk, k_tiles, n_units);
         int rc = e3d_launch_status("e3d_relkey_attn_bwd (dkv)");
         if (rc) return rc;
     }
     }
-    if (dist_emb) {
-        hipError_t e = e3d_zero_async(d_dist_emb, (size_t)(2 * P - 1) * D, s);
+    if (a.dist_emb) {
+        hipError_t e = e3d_zero_async(a.d_dist_emb, (size_t)(2 * a.P - 1) * D, s);
         E3D_REQUIRE(e == hipSuccess, "attn_bwd: memset failed: %s", hipGetErrorString(e));
-        const int n_units = B * nh * q_tiles, upb = 64;
-        hipLaunchKernelGGL(dist_emb_reduce_kernel, dim3(2 * P - 1, (n_units + upb - 1) / upb), dim3(64), 0, s, part,
-                           d_dist_emb, P, q_tiles, k_tiles, n_units, upb);
+        const int n_units = a.B * a.nh * q_tiles, upb = 64;
+        hipLaunchKernelGGL(dist_emb_reduce_kernel, dim3(2 * a.P - 1, (n_units + upb - 1) / upb), dim3(64), 0, s, part,
+                           a.d_dist_emb, a.P, q_tiles, k_tiles, n_units, upb);
         return e3d_launch_status("e3d_relkey_attn_bwd (dE)");
     }
     return 0;
@@ -430,9 +406,9 @@ extern "C" int e3d_relkey_attn_bwd_ex(const float* q, int64_t q_bs, int64_t q_rs
                                       int64_t dk_bs, int64_t dk_rs, float* dv, int64_t dv_bs, int64_t dv_rs,
                                       float* d_dist_emb, float* workspace, int B, int nh, int Lq, int Lk, int terms,
                                       float drop_p, uint64_t drop_seed, void* stream) {
-    return attn_bwd_dispatch(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, dist_emb, P, key_mask, out, lse, dout, dq, dq_bs,
-                             dq_rs, dk, dk_bs, dk_rs, dv, dv_bs, dv_rs, d_dist_emb, workspace, B, nh, Lq, Lk, terms, drop_p,
-                             e3d_drop_make(drop_p, drop_seed), stream);
+    return attn_bwd_dispatch({{q, q_bs, q_rs}, {k, k_bs, k_rs}, {v, v_bs, v_rs}, dist_emb, P, key_mask, out, lse, dout, {dq, dq_bs, dq_rs},
+                              {dk, dk_bs, dk_rs}, {dv, dv_bs, dv_rs}, d_dist_emb, B, nh, Lq, Lk},
+                             workspace, terms, {drop_p, e3d_drop_make(drop_p, drop_seed)}, stream);
 }
 
 // As e3d_relkey_attn_bwd_ex with the keyed decisions of e3d_relkey_attn_fwd_split_ex_keyed (same p, site and row keys)
@@ -445,9 +421,9 @@ extern "C" int e3d_relkey_attn_bwd_ex_keyed(const float* q, int64_t q_bs, int64_
                                             float drop_p, uint32_t site, const uint64_t* row_keys, void* stream) {
     E3D_REQUIRE(row_keys && drop_p > 0.f, "attn_bwd (keyed): row keys and drop_p > 0 required");
     E3D_REQUIRE(site < E3D_DROP_MAX_SITE && nh < E3D_DROP_MAX_HEADS, "attn_bwd (keyed): site %u / %d heads out of range", site, nh);
-    return attn_bwd_dispatch(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, dist_emb, P, key_mask, out, lse, dout, dq, dq_bs,
-                             dq_rs, dk, dk_bs, dk_rs, dv, dv_bs, dv_rs, d_dist_emb, workspace, B, nh, Lq, Lk, terms, drop_p,
-                             e3d_drop_make_keyed(drop_p, site, row_keys), stream);
+    return attn_bwd_dispatch({{q, q_bs, q_rs}, {k, k_bs, k_rs}, {v, v_bs, v_rs}, dist_emb, P, key_mask, out, lse, dout, {dq, dq_bs, dq_rs},
+                              {dk, dk_bs, dk_rs}, {dv, dv_bs, dv_rs}, d_dist_emb, B, nh, Lq, Lk},
+                             workspace, terms, {drop_p, e3d_drop_make_keyed(drop_p, site, row_keys)}, stream);
 }
 
 extern "C" int e3d_relkey_attn_bwd(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs,

@@ -683,8 +683,21 @@ __global__ __launch_bounds__(64) void de_final_sum_kernel(const float* __restric
 
 }  // namespace
 
-// bytes of scratch the fused kernel needs for the two plane orders of the distance table (inside the caller's workspace)
-int64_t e3d_attn_bwd_coop_scratch_bytes(int Lk) { return (int64_t)2 * 2 * ((Lk + 31) / 32) * 512 * 16; }
+// The one statement of the backward workspace layout (e3d_common.h).  Head region: [P | dS], or the fused kernel's two
+// plane orders of the distance table where those are larger; a unit block / chunk-sum slab is 32 * D floats.
+E3dBwdLayout e3d_attn_bwd_layout(int B, int nh, int Lq, int Lk, bool relkey) {
+    const int64_t q_tiles = (Lq + 31) / 32, k_tiles = (Lk + 31) / 32, slabs = q_tiles * (k_tiles + 1);
+    const int64_t pm = (int64_t)B * nh * Lq * Lk;
+    const int64_t e_planes = relkey ? 2 * 2 * k_tiles * 512 * 16 / 4 : 0;   // two orders x hi / lo x 512 bf16x8 per block
+    E3dBwdLayout w;
+    w.Pm = 0;
+    w.dSm = pm;
+    w.part = 2 * pm > e_planes ? 2 * pm : e_planes;
+    w.chunk_sums = w.part + (relkey ? (int64_t)B * nh * slabs * 32 * D : 0);
+    w.unit_live = w.chunk_sums + (relkey ? DE_CHUNKS * slabs * 32 * D : 0);
+    w.total = w.unit_live + (relkey ? (int64_t)B * nh * q_tiles : 0);
+    return w;
+}
 
 bool e3d_attn_bwd_coop_supported(int Lq, int Lk, bool dropping) {
     static int on = -1;   // E3D_ATTN_BWD_COOP=0: the two-launch kernels of attn_bwd_split.hip for every shape (A/B timing)
@@ -696,53 +709,33 @@ bool e3d_attn_bwd_coop_supported(int Lq, int Lk, bool dropping) {
     return on && Lq <= 32 * MAX_TILES && Lk <= 32 * MAX_TILES;
 }
 
-// chunk partial sums of the dE reduction: floats appended to the unit blocks in the caller's workspace
-int64_t e3d_attn_bwd_coop_de_floats(int Lq, int Lk) {
-    return (int64_t)DE_CHUNKS * ((Lq + 31) / 32) * ((Lk + 31) / 32 + 1) * 2048;
-}
-
-// The fused backward, bf16x3 (arguments validated by e3d_relkey_attn_bwd_ex; ``e_scratch``: 16-byte aligned,
-// e3d_attn_bwd_coop_scratch_bytes(Lk) bytes, only read / written when dist_emb is given; ``part``: the unit blocks
-// followed by e3d_attn_bwd_coop_de_floats(Lq, Lk) floats; writes every row of d_dist_emb).
-int e3d_attn_bwd_coop_launch(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs, int64_t k_rs,
-                             const float* v, int64_t v_bs, int64_t v_rs, const float* dist_emb, int P,
-                             const float* key_mask, const float* out, const float* lse, const float* dout, float* dq,
-                             int64_t dq_bs, int64_t dq_rs, float* dk, int64_t dk_bs, int64_t dk_rs, float* dv,
-                             int64_t dv_bs, int64_t dv_rs, float* d_dist_emb, void* e_scratch, float* part, int B, int nh,
-                             int Lq, int Lk, E3dDrop drop, bool dropping, hipStream_t s) {
-    const int J0 = (Lk + 31) / 32, n_items = 2 * J0 * 512;
-    bf16x8* e_row = reinterpret_cast<bf16x8*>(e_scratch);
-    bf16x8* e_tr = e_row ? e_row + n_items : nullptr;
-    if (dist_emb)
-        hipLaunchKernelGGL(e_planes_kernel, dim3((n_items + 255) / 256), dim3(256), 0, s, dist_emb, e_row, e_tr, P, J0, n_items);
-    // liveness words of the (b, head, query tile) units: after the chunk sums (e3d_relkey_attn_bwd_workspace_floats)
-    int* unit_live = dist_emb ? reinterpret_cast<int*>(part + (int64_t)B * nh * ((Lq + 31) / 32) * ((Lk + 31) / 32 + 1) * 2048 +
-                                                       e3d_attn_bwd_coop_de_floats(Lq, Lk))
-                              : nullptr;
+// The fused backward, bf16x3 (arguments validated by e3d_relkey_attn_bwd_ex; ``workspace``: 16-byte aligned, laid out as
+// ``w``; its plane, unit-block, chunk-sum and liveness regions are only read / written when dist_emb is given; writes every
+// row of d_dist_emb).
+int e3d_attn_bwd_coop_launch(const E3dAttnBwd& a, float* workspace, const E3dBwdLayout& w, const E3dAttnDrop& drop,
+                             hipStream_t s) {
+    const int J0 = (a.Lk + 31) / 32, n_items = 2 * J0 * 512;
+    bf16x8* e_row = reinterpret_cast<bf16x8*>(workspace);
+    bf16x8* e_tr = e_row + n_items;
+    if (a.dist_emb)
+        hipLaunchKernelGGL(e_planes_kernel, dim3((n_items + 255) / 256), dim3(256), 0, s, a.dist_emb, e_row, e_tr, a.P, J0, n_items);
+    float *part = workspace + w.part, *chunk_sums = workspace + w.chunk_sums;
+    int* unit_live = a.dist_emb ? reinterpret_cast<int*>(workspace + w.unit_live) : nullptr;
     static std::atomic<uint64_t> ok[4];
-#define E3D_BWD_COOP(RK, DR)                                                                                               \
-    do {                                                                                                                   \
-        constexpr size_t lds = LDS_BYTES + (DR ? DROP_ROWS_B : 0);                                                         \
-        e3d_allow_lds(ok[2 * RK + DR], attn_bwd_coop_kernel<RK, DR>, lds);                                                 \
-        hipLaunchKernelGGL((attn_bwd_coop_kernel<RK, DR>), dim3(B * nh, 2), dim3(256), lds, s, q, q_bs, q_rs, k, k_bs,      \
-                           k_rs, v, v_bs, v_rs, e_row, e_tr, P, key_mask, dout, out, lse, dq, dq_bs, dq_rs, dk, dk_bs,      \
-                           dk_rs, dv, dv_bs, dv_rs, part, unit_live, nh, Lq, Lk, drop);                                    \
-    } while (0)
-    if (dist_emb) {
-        if (dropping) E3D_BWD_COOP(true, true);
-        else E3D_BWD_COOP(true, false);
-    } else {
-        if (dropping) E3D_BWD_COOP(false, true);
-        else E3D_BWD_COOP(false, false);
-    }
-#undef E3D_BWD_COOP
-    if (dist_emb) {
-        const int q_tiles = (Lq + 31) / 32, k_tiles = (Lk + 31) / 32, slabs = q_tiles * (k_tiles + 1), n_bh = B * nh;
+    e3d_attn_form(a.dist_emb, drop.on(), [&](auto rk, auto dr) {
+        constexpr bool RK = decltype(rk)::value, DR = decltype(dr)::value;
+        constexpr size_t lds = LDS_BYTES + (DR ? DROP_ROWS_B : 0);
+        e3d_allow_lds(ok[2 * RK + DR], attn_bwd_coop_kernel<RK, DR>, lds);
+        hipLaunchKernelGGL((attn_bwd_coop_kernel<RK, DR>), dim3(a.B * a.nh, 2), dim3(256), lds, s, E3D_VIEW(a.q), E3D_VIEW(a.k),
+                           E3D_VIEW(a.v), e_row, e_tr, a.P, a.key_mask, a.dout, a.out, a.lse, E3D_VIEW(a.dq), E3D_VIEW(a.dk),
+                           E3D_VIEW(a.dv), part, unit_live, a.nh, a.Lq, a.Lk, drop.d);
+    });
+    if (a.dist_emb) {
+        const int q_tiles = (a.Lq + 31) / 32, k_tiles = (a.Lk + 31) / 32, slabs = q_tiles * (k_tiles + 1), n_bh = a.B * a.nh;
         const int per = (n_bh + DE_CHUNKS - 1) / DE_CHUNKS, n_chunks = (n_bh + per - 1) / per;
-        float* chunk_sums = part + (int64_t)n_bh * slabs * 2048;
         hipLaunchKernelGGL(de_chunk_sum_kernel, dim3(slabs, n_chunks), dim3(256), 0, s, part, chunk_sums, unit_live, slabs,
                            k_tiles + 1, n_bh, per);
-        hipLaunchKernelGGL(de_final_sum_kernel, dim3(2 * P - 1), dim3(64), 0, s, chunk_sums, d_dist_emb, P, q_tiles, k_tiles,
+        hipLaunchKernelGGL(de_final_sum_kernel, dim3(2 * a.P - 1), dim3(64), 0, s, chunk_sums, a.d_dist_emb, a.P, q_tiles, k_tiles,
                            n_chunks);
     }
     return e3d_launch_status("e3d_relkey_attn_bwd (fused, bf16x3)");

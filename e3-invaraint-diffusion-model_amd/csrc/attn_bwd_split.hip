@@ -376,37 +376,28 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_split_kernel(
 
 // Launches A and B of the backward in bf16x3 arithmetic (arguments validated by e3d_relkey_attn_bwd_ex, which
 // also runs launch C afterwards).
-int e3d_attn_bwd_split_launch(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs, int64_t k_rs,
-                              const float* v, int64_t v_bs, int64_t v_rs, const float* dist_emb, int P,
-                              const float* key_mask, const float* out, const float* lse, const float* dout, float* dq,
-                              int64_t dq_bs, int64_t dq_rs, float* dk, int64_t dk_bs, int64_t dk_rs, float* dv,
-                              int64_t dv_bs, int64_t dv_rs, float* Pm, float* dSm, float* part, int B, int nh, int Lq,
-                              int Lk, E3dDrop drop, bool dropping, hipStream_t s) {
-    const int q_tiles = (Lq + 31) / 32, k_tiles = (Lk + 31) / 32;
+int e3d_attn_bwd_split_launch(const E3dAttnBwd& a, float* workspace, const E3dBwdLayout& w, const E3dAttnDrop& drop,
+                              hipStream_t s) {
+    const int q_tiles = (a.Lq + 31) / 32, k_tiles = (a.Lk + 31) / 32;
+    float *Pm = workspace + w.Pm, *dSm = workspace + w.dSm;
     const int wpb = 4;
     {
-        const int n_units = B * nh * q_tiles;
+        const int n_units = a.B * a.nh * q_tiles;
         const int n_blocks = (n_units + wpb - 1) / wpb;
         const size_t lds = (size_t)wpb * WAVE_LDS_F * sizeof(float);
-#define E3D_BWD_DQ(RK, DR)                                                                                          \
-    hipLaunchKernelGGL((attn_bwd_dq_split_kernel<RK, DR>), dim3(n_blocks), dim3(64 * wpb), lds, s, q, q_bs, q_rs, k, \
-                       k_bs, k_rs, v, v_bs, v_rs, dist_emb, P, key_mask, dout, out, lse, dq, dq_bs, dq_rs, Pm, dSm,  \
-                       part, nh, Lq, Lk, q_tiles, n_units, drop)
-        if (dist_emb) {
-            if (dropping) E3D_BWD_DQ(true, true);
-            else E3D_BWD_DQ(true, false);
-        } else {
-            if (dropping) E3D_BWD_DQ(false, true);
-            else E3D_BWD_DQ(false, false);
-        }
-#undef E3D_BWD_DQ
+        e3d_attn_form(a.dist_emb, drop.on(), [&](auto rk, auto dr) {
+            hipLaunchKernelGGL((attn_bwd_dq_split_kernel<decltype(rk)::value, decltype(dr)::value>), dim3(n_blocks),
+                               dim3(64 * wpb), lds, s, E3D_VIEW(a.q), E3D_VIEW(a.k), E3D_VIEW(a.v), a.dist_emb, a.P, a.key_mask,
+                               a.dout, a.out, a.lse, E3D_VIEW(a.dq), Pm, dSm, workspace + w.part, a.nh, a.Lq, a.Lk, q_tiles,
+                               n_units, drop.d);
+        });
         int rc = e3d_launch_status("e3d_relkey_attn_bwd (dq, bf16x3)");
         if (rc) return rc;
     }
     {
-        const int n_units = B * nh * k_tiles;
-        hipLaunchKernelGGL(attn_bwd_dkv_split_kernel, dim3((n_units + wpb - 1) / wpb), dim3(64 * wpb), 0, s, q, q_bs, q_rs,
-                           dout, Pm, dSm, dk, dk_bs, dk_rs, dv, dv_bs, dv_rs, nh, Lq, Lk, k_tiles, n_units);
+        const int n_units = a.B * a.nh * k_tiles;
+        hipLaunchKernelGGL(attn_bwd_dkv_split_kernel, dim3((n_units + wpb - 1) / wpb), dim3(64 * wpb), 0, s, E3D_VIEW(a.q),
+                           a.dout, Pm, dSm, E3D_VIEW(a.dk), E3D_VIEW(a.dv), a.nh, a.Lq, a.Lk, k_tiles, n_units);
         return e3d_launch_status("e3d_relkey_attn_bwd (dkv, bf16x3)");
     }
 }

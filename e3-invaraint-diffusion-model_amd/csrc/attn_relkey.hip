@@ -180,6 +180,35 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
     }
 }
 
+// validates and launches (the body of e3d_relkey_attn_fwd)
+int attn_fwd_launch(const E3dAttnFwd& a, hipStream_t s) {
+    E3D_REQUIRE(a.q.p && a.k.p && a.v.p && a.out, "attn: null pointer");
+    E3D_REQUIRE(a.B > 0 && a.nh > 0 && a.Lq > 0 && a.Lk > 0, "attn: bad shape B=%d nh=%d Lq=%d Lk=%d", a.B, a.nh, a.Lq, a.Lk);
+    E3D_REQUIRE(a.q.rs % 4 == 0 && a.k.rs % 4 == 0 && a.v.rs % 2 == 0 && a.q.bs % 4 == 0 && a.k.bs % 4 == 0 && a.v.bs % 2 == 0,
+                "attn: strides must keep 16B (q,k) / 8B (v) alignment");
+    E3D_REQUIRE(((uintptr_t)a.q.p % 16) == 0 && ((uintptr_t)a.k.p % 16) == 0 && ((uintptr_t)a.v.p % 16) == 0 &&
+                    ((uintptr_t)a.out % 16) == 0, "attn: pointers must be 16B aligned");
+    if (a.dist_emb) {
+        // the distance_embedding lookup l - r + P - 1 must stay inside [0, 2P-2] (SURVEY section 5)
+        E3D_REQUIRE(a.Lq == a.Lk && a.Lq <= a.P, "attn: relative_key needs Lq == Lk <= P (Lq=%d Lk=%d P=%d)", a.Lq, a.Lk, a.P);
+        E3D_REQUIRE(((uintptr_t)a.dist_emb % 16) == 0, "attn: dist_emb must be 16B aligned");
+    }
+    const int q_tiles = (a.Lq + 31) / 32;
+    const int64_t n_units64 = (int64_t)a.B * a.nh * q_tiles;
+    E3D_REQUIRE(n_units64 < (1ll << 30), "attn: too many tiles");
+    const int n_units = (int)n_units64;
+    const int wpb = 4;
+    const int n_blocks = (n_units + wpb - 1) / wpb;
+    const size_t lds = a.dist_emb ? (size_t)wpb * RING_F * sizeof(float) : 0;
+    if (a.dist_emb)
+        hipLaunchKernelGGL(attn_fwd_kernel<true>, dim3(n_blocks), dim3(64 * wpb), lds, s, E3D_VIEW(a.q), E3D_VIEW(a.k),
+                           E3D_VIEW(a.v), a.dist_emb, a.P, a.key_mask, a.out, a.lse, a.nh, a.Lq, a.Lk, q_tiles, n_units);
+    else
+        hipLaunchKernelGGL(attn_fwd_kernel<false>, dim3(n_blocks), dim3(64 * wpb), lds, s, E3D_VIEW(a.q), E3D_VIEW(a.k),
+                           E3D_VIEW(a.v), a.dist_emb, a.P, a.key_mask, a.out, a.lse, a.nh, a.Lq, a.Lk, q_tiles, n_units);
+    return e3d_launch_status("e3d_relkey_attn_fwd");
+}
+
 }  // namespace
 
 extern "C" int e3d_relkey_attn_fwd(const float* q, int64_t q_bs, int64_t q_rs, const float* k,
@@ -187,30 +216,6 @@ extern "C" int e3d_relkey_attn_fwd(const float* q, int64_t q_bs, int64_t q_rs, c
                                    int64_t v_rs, const float* dist_emb, int P,
                                    const float* key_mask, float* out, float* lse, int B, int nh,
                                    int Lq, int Lk, void* stream) {
-    E3D_REQUIRE(q && k && v && out, "attn: null pointer");
-    E3D_REQUIRE(B > 0 && nh > 0 && Lq > 0 && Lk > 0, "attn: bad shape B=%d nh=%d Lq=%d Lk=%d", B, nh, Lq, Lk);
-    E3D_REQUIRE(q_rs % 4 == 0 && k_rs % 4 == 0 && v_rs % 2 == 0 && q_bs % 4 == 0 && k_bs % 4 == 0 && v_bs % 2 == 0,
-                "attn: strides must keep 16B (q,k) / 8B (v) alignment");
-    E3D_REQUIRE(((uintptr_t)q % 16) == 0 && ((uintptr_t)k % 16) == 0 && ((uintptr_t)v % 16) == 0 &&
-                    ((uintptr_t)out % 16) == 0, "attn: pointers must be 16B aligned");
-    if (dist_emb) {
-        // the distance_embedding lookup l - r + P - 1 must stay inside [0, 2P-2] (SURVEY section 5)
-        E3D_REQUIRE(Lq == Lk && Lq <= P, "attn: relative_key needs Lq == Lk <= P (Lq=%d Lk=%d P=%d)", Lq, Lk, P);
-        E3D_REQUIRE(((uintptr_t)dist_emb % 16) == 0, "attn: dist_emb must be 16B aligned");
-    }
-    const int q_tiles = (Lq + 31) / 32;
-    const int64_t n_units64 = (int64_t)B * nh * q_tiles;
-    E3D_REQUIRE(n_units64 < (1ll << 30), "attn: too many tiles");
-    const int n_units = (int)n_units64;
-    const int wpb = 4;
-    const int n_blocks = (n_units + wpb - 1) / wpb;
-    const size_t lds = dist_emb ? (size_t)wpb * RING_F * sizeof(float) : 0;
-    hipStream_t s = (hipStream_t)stream;
-    if (dist_emb)
-        hipLaunchKernelGGL(attn_fwd_kernel<true>, dim3(n_blocks), dim3(64 * wpb), lds, s, q, q_bs, q_rs, k, k_bs,
-                           k_rs, v, v_bs, v_rs, dist_emb, P, key_mask, out, lse, nh, Lq, Lk, q_tiles, n_units);
-    else
-        hipLaunchKernelGGL(attn_fwd_kernel<false>, dim3(n_blocks), dim3(64 * wpb), lds, s, q, q_bs, q_rs, k, k_bs,
-                           k_rs, v, v_bs, v_rs, dist_emb, P, key_mask, out, lse, nh, Lq, Lk, q_tiles, n_units);
-    return e3d_launch_status("e3d_relkey_attn_fwd");
+    return attn_fwd_launch({{q, q_bs, q_rs}, {k, k_bs, k_rs}, {v, v_bs, v_rs}, dist_emb, P, key_mask, out, lse, B, nh, Lq, Lk},
+                           (hipStream_t)stream);
 }

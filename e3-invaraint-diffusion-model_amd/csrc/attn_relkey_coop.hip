@@ -571,68 +571,49 @@ __global__ __launch_bounds__(W * 64, 2) void attn_coop_kernel(
 }
 
 template <int W, bool RELKEY, typename E>
-int launch_w(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs, int64_t k_rs, const float* v,
-             int64_t v_bs, int64_t v_rs, const void* e_frag, int P, const float* key_mask,
-             float* out, float* lse, int B, int nh, int Lq, int Lk, int q_tiles, int skip, E3dBounds bnd, E3dDrop drop,
-             bool dropping, bool planes, hipStream_t s) {
+int launch_w(const E3dAttnFwd& a, const void* e_frag, int skip, E3dBounds bnd, const E3dAttnDrop& drop, bool planes,
+             hipStream_t s) {
     const size_t lds = 2 * KV_BUF_B + (size_t)W * RING_F * sizeof(float);
-    const int groups = q_tiles / W;
+    const int groups = (a.Lq + 31) / 32 / W;
+    // one form of the kernel: dynamic-LDS opt-in (once per device, ``ok``) and launch
+    auto go = [&](auto kernel, std::atomic<uint64_t>& ok, const char* what) {
+        e3d_allow_lds(ok, kernel, lds);
+        hipLaunchKernelGGL(kernel, dim3(a.B * a.nh * groups), dim3(W * 64), lds, s, E3D_VIEW(a.q), E3D_VIEW(a.k), E3D_VIEW(a.v),
+                           reinterpret_cast<const typename AV<E>::x8*>(e_frag), a.P, a.key_mask, a.out, a.lse, a.nh, a.Lq, a.Lk,
+                           groups, skip, bnd, g_rescale_tau, drop.d);
+        return e3d_launch_status(what);
+    };
     if (planes) {   // plane output: the 4-wave inference forms only (anything else is the caller's error, never a silent fp32 store)
         if constexpr (W == 4) {
-            if (!dropping && Lq % 32 == 0) {
-                static std::atomic<uint64_t> lds_ok_p{0};
-                e3d_allow_lds(lds_ok_p, attn_coop_kernel<W, RELKEY, E, false, true>, lds);
-                hipLaunchKernelGGL((attn_coop_kernel<W, RELKEY, E, false, true>), dim3(B * nh * groups), dim3(W * 64), lds, s, q, q_bs,
-                                   q_rs, k, k_bs, k_rs, v, v_bs, v_rs, reinterpret_cast<const typename AV<E>::x8*>(e_frag), P,
-                                   key_mask, out, lse, nh, Lq, Lk, groups, skip, bnd, g_rescale_tau, drop);
-                return e3d_launch_status("e3d_relkey_attn_fwd_split_planes (cooperative)");
-            }
+            static std::atomic<uint64_t> lds_ok_p{0};
+            if (!drop.on() && a.Lq % 32 == 0)
+                return go(attn_coop_kernel<W, RELKEY, E, false, true>, lds_ok_p, "e3d_relkey_attn_fwd_split_planes (cooperative)");
         }
         e3d_set_error("attn_coop: plane output exists for the 4-wave inference forms with Lq %% 32 == 0 only");
         return -1;
     }
     if constexpr (std::is_same<E, __bf16>::value) {   // dropout exists in the training arithmetic (bf16x3) only
-        if (dropping) {
-            static std::atomic<uint64_t> lds_ok_d{0};
-            e3d_allow_lds(lds_ok_d, attn_coop_kernel<W, RELKEY, E, true>, lds);
-            hipLaunchKernelGGL((attn_coop_kernel<W, RELKEY, E, true>), dim3(B * nh * groups), dim3(W * 64), lds, s, q, q_bs, q_rs,
-                               k, k_bs, k_rs, v, v_bs, v_rs, reinterpret_cast<const typename AV<E>::x8*>(e_frag), P, key_mask,
-                               out, lse, nh, Lq, Lk, groups, skip, bnd, g_rescale_tau, drop);
-            return e3d_launch_status("e3d_relkey_attn_fwd_split (cooperative, dropout)");
-        }
+        static std::atomic<uint64_t> lds_ok_d{0};
+        if (drop.on()) return go(attn_coop_kernel<W, RELKEY, E, true>, lds_ok_d, "e3d_relkey_attn_fwd_split (cooperative, dropout)");
     }
     static std::atomic<uint64_t> lds_ok{0};
-    e3d_allow_lds(lds_ok, attn_coop_kernel<W, RELKEY, E>, lds);
-    hipLaunchKernelGGL((attn_coop_kernel<W, RELKEY, E>), dim3(B * nh * groups), dim3(W * 64), lds, s, q, q_bs, q_rs, k, k_bs,
-                       k_rs, v, v_bs, v_rs, reinterpret_cast<const typename AV<E>::x8*>(e_frag), P, key_mask, out, lse, nh, Lq, Lk, groups, skip, bnd, g_rescale_tau, drop);
-    return e3d_launch_status("e3d_relkey_attn_fwd_split (cooperative)");
+    return go(attn_coop_kernel<W, RELKEY, E>, lds_ok, "e3d_relkey_attn_fwd_split (cooperative)");
 }
 
+// W waves per workgroup (two- and one-wave groups were lab forms: slower than the per-wave kernel, 20-88 B/lane of scratch)
 template <bool RELKEY, typename E>
-int launch_any(int W, const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs, int64_t k_rs,
-               const float* v, int64_t v_bs, int64_t v_rs, const void* e_frag, int P,
-               const float* key_mask, float* out, float* lse, int B, int nh, int Lq, int Lk, int q_tiles, int skip,
-               E3dBounds bnd, E3dDrop drop, bool dropping, bool planes, hipStream_t s) {
-#define E3D_COOP_CASE(w)                                                                                          \
-    case w:                                                                                                       \
-        return launch_w<w, RELKEY, E>(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, e_frag, P, key_mask, out, lse, B, nh, \
-                                   Lq, Lk, q_tiles, skip, bnd, drop, dropping, planes, s)
-    switch (W) {
-        E3D_COOP_CASE(8);
-        E3D_COOP_CASE(4);      // (two- and one-wave groups were lab forms: slower than the per-wave kernel, 20-88 B/lane of scratch)
-    }
-#undef E3D_COOP_CASE
-    return -1;
+int launch_any(int W, const E3dAttnFwd& a, const void* e_frag, int skip, E3dBounds bnd, const E3dAttnDrop& drop, bool planes,
+               hipStream_t s) {
+    if (W == 8) return launch_w<8, RELKEY, E>(a, e_frag, skip, bnd, drop, planes, s);
+    return launch_w<4, RELKEY, E>(a, e_frag, skip, bnd, drop, planes, s);
 }
 
 }  // namespace
 
 template <typename E>
-static int coop_launch_t(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs, int64_t k_rs,
-                         const float* v, int64_t v_bs, int64_t v_rs, const float* dist_emb, int P,
-                         const float* key_mask, float* out, float* lse, int B, int nh, int Lq, int Lk, int skip,
-                         E3dBounds bnd, void* e_scratch, int e_ready, E3dDrop drop, bool dropping, bool planes, hipStream_t s) {
-    const int q_tiles = (Lq + 31) / 32;
+static int coop_launch_t(const E3dAttnFwd& a, int skip, E3dBounds bnd, void* e_scratch, int e_ready, const E3dAttnDrop& drop,
+                         bool planes, hipStream_t s) {
+    const int q_tiles = (a.Lq + 31) / 32;
     // Waves per workgroup: 4 (the caller dispatches here for q_tiles % 4 == 0 only).  A 4-wave workgroup holds 78 KB of LDS, so
     // two of them share a CU -- one wave of each per SIMD, with barriers of their own: the two drift apart and one's matrix phases
     // fall beside the other's LDS / vector phases, and one's prologue (cold loads, first distance blocks) runs under the other's
@@ -645,20 +626,17 @@ static int coop_launch_t(const float* q, int64_t q_bs, int64_t q_rs, const float
         w_pref = e ? atoi(e) : 4;
     }
     const int W = (w_pref == 8 && q_tiles % 8 == 0) ? 8 : 4;
-    if (!dist_emb)
-        return launch_any<false, E>(W, q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, nullptr, P, key_mask, out, lse, B, nh,
-                                    Lq, Lk, q_tiles, skip, bnd, drop, dropping, planes, s);
+    if (!a.dist_emb) return launch_any<false, E>(W, a, nullptr, skip, bnd, drop, planes, s);
     // distance table -> fragment-order hi / lo planes in the caller's scratch (e3d_attn_scratch_bytes(Lk) bytes)
     if (!e_scratch) {
         e3d_set_error("attn_coop: rel-key attention needs the caller's scratch for the distance-table planes");
         return -1;
     }
-    const int J0 = (Lk + 31) / 32, n_items = 2 * J0 * 512;
+    const int J0 = (a.Lk + 31) / 32, n_items = 2 * J0 * 512;
     if (!e_ready)   // e_ready: the caller kept the planes of this (dist_emb, Lk, terms) from an earlier call
-        hipLaunchKernelGGL(e_fragments_kernel<E>, dim3((n_items + 255) / 256), dim3(256), 0, s, dist_emb,
-                           reinterpret_cast<typename AV<E>::x8*>(e_scratch), P, J0, n_items, (float*)nullptr);
-    return launch_any<true, E>(W, q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, e_scratch, P, key_mask, out, lse, B, nh, Lq,
-                               Lk, q_tiles, skip, bnd, drop, dropping, planes, s);
+        hipLaunchKernelGGL(e_fragments_kernel<E>, dim3((n_items + 255) / 256), dim3(256), 0, s, a.dist_emb,
+                           reinterpret_cast<typename AV<E>::x8*>(e_scratch), a.P, J0, n_items, (float*)nullptr);
+    return launch_any<true, E>(W, a, e_scratch, skip, bnd, drop, planes, s);
 }
 
 // waves per workgroup the dispatch above picks (plane output exists for 4)
@@ -669,16 +647,10 @@ int e3d_attn_coop_waves(int Lq) {
 
 // bf16x3 / f16x3 attention, cooperative kernel.  Same contract as e3d_relkey_attn_fwd_split with terms = 3 / 19
 // (arguments already validated there); v rows must be 16-byte aligned (v_rs % 4 == 0).
-int e3d_attn_coop_launch(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs, int64_t k_rs,
-                         const float* v, int64_t v_bs, int64_t v_rs, const float* dist_emb, int P,
-                         const float* key_mask, float* out, float* lse, int B, int nh, int Lq, int Lk, int skip,
-                         E3dBounds bnd, void* e_scratch, int e_ready, int f16, E3dDrop drop, bool dropping, bool planes,
-                         hipStream_t s) {
-    if (f16)
-        return coop_launch_t<_Float16>(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, dist_emb, P, key_mask, out, lse, B, nh, Lq,
-                                       Lk, skip, bnd, e_scratch, e_ready, drop, dropping, planes, s);
-    return coop_launch_t<__bf16>(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, dist_emb, P, key_mask, out, lse, B, nh, Lq, Lk,
-                                 skip, bnd, e_scratch, e_ready, drop, dropping, planes, s);
+int e3d_attn_coop_launch(const E3dAttnFwd& a, int skip, E3dBounds bnd, void* e_scratch, int e_ready, int f16,
+                         const E3dAttnDrop& drop, bool planes, hipStream_t s) {
+    if (f16) return coop_launch_t<_Float16>(a, skip, bnd, e_scratch, e_ready, drop, planes, s);
+    return coop_launch_t<__bf16>(a, skip, bnd, e_scratch, e_ready, drop, planes, s);
 }
 
 // Diagnostic (tests): threshold of the deferred rescale in log2 units; 0 = raise the maximum on every new one (classic

@@ -188,20 +188,20 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_split_kernel(
 int g_skip_padded = 1;
 
 template <int NS, bool DROP = false, typename E = __bf16>
-int launch(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs, int64_t k_rs, const float* v,
-           int64_t v_bs, int64_t v_rs, const float* dist_emb, int P, const float* key_mask, float* out, float* lse,
-           int B, int nh, int Lq, int Lk, E3dBounds bnd, hipStream_t s, E3dDrop drop = E3dDrop{0, 0, 1.f}) {
-    const int q_tiles = (Lq + 31) / 32;
-    const int n_units = B * nh * q_tiles;
+int launch(const E3dAttnFwd& a, E3dBounds bnd, hipStream_t s, E3dDrop drop = E3dDrop{0, 0, 1.f}) {
+    const int q_tiles = (a.Lq + 31) / 32;
+    const int n_units = a.B * a.nh * q_tiles;
     const int wpb = 4;
     const int n_blocks = (n_units + wpb - 1) / wpb;
     const size_t lds = (size_t)wpb * WAVE_LDS_F * sizeof(float);
-    if (dist_emb)
-        hipLaunchKernelGGL((attn_fwd_split_kernel<NS, true, DROP, E>), dim3(n_blocks), dim3(64 * wpb), lds, s, q, q_bs, q_rs, k,
-                           k_bs, k_rs, v, v_bs, v_rs, dist_emb, P, key_mask, out, lse, nh, Lq, Lk, q_tiles, n_units, g_skip_padded, bnd, drop);
+    if (a.dist_emb)
+        hipLaunchKernelGGL((attn_fwd_split_kernel<NS, true, DROP, E>), dim3(n_blocks), dim3(64 * wpb), lds, s, E3D_VIEW(a.q),
+                           E3D_VIEW(a.k), E3D_VIEW(a.v), a.dist_emb, a.P, a.key_mask, a.out, a.lse, a.nh, a.Lq, a.Lk, q_tiles,
+                           n_units, g_skip_padded, bnd, drop);
     else
-        hipLaunchKernelGGL((attn_fwd_split_kernel<NS, false, DROP, E>), dim3(n_blocks), dim3(64 * wpb), lds, s, q, q_bs, q_rs, k,
-                           k_bs, k_rs, v, v_bs, v_rs, dist_emb, P, key_mask, out, lse, nh, Lq, Lk, q_tiles, n_units, g_skip_padded, bnd, drop);
+        hipLaunchKernelGGL((attn_fwd_split_kernel<NS, false, DROP, E>), dim3(n_blocks), dim3(64 * wpb), lds, s, E3D_VIEW(a.q),
+                           E3D_VIEW(a.k), E3D_VIEW(a.v), a.dist_emb, a.P, a.key_mask, a.out, a.lse, a.nh, a.Lq, a.Lk, q_tiles,
+                           n_units, g_skip_padded, bnd, drop);
     return e3d_launch_status("e3d_relkey_attn_fwd_split");
 }
 
@@ -232,54 +232,45 @@ static bool attn_coop_ok(int64_t k_rs, int64_t v_bs, int64_t v_rs, int Lq, int L
            ((Lq + 31) / 32) % 4 == 0 && have_scratch;
 }
 
-// the body of e3d_relkey_attn_fwd_split_ex and of its keyed form: ``d`` = the decisions of drop_p; ``planes_out``: ``out``
-// receives activation planes (e3d_relkey_attn_fwd_split_planes)
-static int attn_fwd_dispatch(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs, int64_t k_rs,
-                             const float* v, int64_t v_bs, int64_t v_rs, const float* dist_emb, int P, const float* key_mask,
-                             float* out, float* lse, int B, int nh, int Lq, int Lk, int terms, float drop_p, const E3dDrop d,
-                             void* e_scratch, int e_scratch_ready, const float* q_absmax, const float* k_absmax,
-                             float* e_absmax, void* stream, bool planes_out = false) {
-    const E3dBounds bnd{q_absmax, k_absmax, dist_emb ? e_absmax : nullptr};
-    E3D_REQUIRE(!dist_emb || !q_absmax || e_absmax, "attn_split: rel-key attention with element bounds needs e_absmax too");
-    E3D_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "attn_split: drop_p=%g outside [0, 1)", (double)drop_p);
-    E3D_REQUIRE(q && k && v && out, "attn_split: null pointer");
-    E3D_REQUIRE(B > 0 && nh > 0 && Lq > 0 && Lk > 0, "attn_split: bad shape B=%d nh=%d Lq=%d Lk=%d", B, nh, Lq, Lk);
-    E3D_REQUIRE(q_rs % 4 == 0 && k_rs % 4 == 0 && v_rs % 2 == 0 && q_bs % 4 == 0 && k_bs % 4 == 0 && v_bs % 2 == 0,
+// the body of e3d_relkey_attn_fwd_split_ex and of its keyed form; ``planes_out``: ``a.out`` receives activation planes
+// (e3d_relkey_attn_fwd_split_planes)
+static int attn_fwd_dispatch(const E3dAttnFwd& a, int terms, const E3dAttnDrop& drop, void* e_scratch, int e_scratch_ready,
+                             const float* q_absmax, const float* k_absmax, float* e_absmax, void* stream,
+                             bool planes_out = false) {
+    const E3dBounds bnd{q_absmax, k_absmax, a.dist_emb ? e_absmax : nullptr};
+    E3D_REQUIRE(!a.dist_emb || !q_absmax || e_absmax, "attn_split: rel-key attention with element bounds needs e_absmax too");
+    E3D_REQUIRE(drop.p >= 0.f && drop.p < 1.f, "attn_split: drop_p=%g outside [0, 1)", (double)drop.p);
+    E3D_REQUIRE(a.q.p && a.k.p && a.v.p && a.out, "attn_split: null pointer");
+    E3D_REQUIRE(a.B > 0 && a.nh > 0 && a.Lq > 0 && a.Lk > 0, "attn_split: bad shape B=%d nh=%d Lq=%d Lk=%d", a.B, a.nh, a.Lq,
+                a.Lk);
+    E3D_REQUIRE(a.q.rs % 4 == 0 && a.k.rs % 4 == 0 && a.v.rs % 2 == 0 && a.q.bs % 4 == 0 && a.k.bs % 4 == 0 && a.v.bs % 2 == 0,
                 "attn_split: strides must keep 16B (q,k) / 8B (v) alignment");
-    E3D_REQUIRE(((uintptr_t)q % 16) == 0 && ((uintptr_t)k % 16) == 0 && ((uintptr_t)v % 16) == 0 &&
-                    ((uintptr_t)out % 16) == 0, "attn_split: pointers must be 16B aligned");
+    E3D_REQUIRE(((uintptr_t)a.q.p % 16) == 0 && ((uintptr_t)a.k.p % 16) == 0 && ((uintptr_t)a.v.p % 16) == 0 &&
+                    ((uintptr_t)a.out % 16) == 0, "attn_split: pointers must be 16B aligned");
     E3D_REQUIRE(terms == 3 || terms == 6 || terms == E3D_TERMS_F16X3, "attn_split: terms must be 3, 6 or 19 (got %d)", terms);
     const int f16 = terms == E3D_TERMS_F16X3;
-    E3D_REQUIRE((int64_t)Lk * k_rs < (1ll << 30) && (int64_t)Lk * v_rs < (1ll << 30),
+    E3D_REQUIRE((int64_t)a.Lk * a.k.rs < (1ll << 30) && (int64_t)a.Lk * a.v.rs < (1ll << 30),
                 "attn_split: one batch item's K/V slab must stay below 2^30 elements (32-bit lane offsets)");
-    if (dist_emb) {
-        E3D_REQUIRE(Lq == Lk && Lq <= P, "attn_split: relative_key needs Lq == Lk <= P (Lq=%d Lk=%d P=%d)", Lq, Lk, P);
-        E3D_REQUIRE(((uintptr_t)dist_emb % 16) == 0, "attn_split: dist_emb must be 16B aligned");
+    if (a.dist_emb) {
+        E3D_REQUIRE(a.Lq == a.Lk && a.Lq <= a.P, "attn_split: relative_key needs Lq == Lk <= P (Lq=%d Lk=%d P=%d)", a.Lq, a.Lk,
+                    a.P);
+        E3D_REQUIRE(((uintptr_t)a.dist_emb % 16) == 0, "attn_split: dist_emb must be 16B aligned");
     }
-    E3D_REQUIRE((int64_t)B * nh * ((Lq + 31) / 32) < (1ll << 30), "attn_split: too many tiles");
+    E3D_REQUIRE((int64_t)a.B * a.nh * ((a.Lq + 31) / 32) < (1ll << 30), "attn_split: too many tiles");
     hipStream_t s = (hipStream_t)stream;
-    if (dist_emb && e_scratch && !e_scratch_ready) {
+    if (a.dist_emb && e_scratch && !e_scratch_ready) {
         // whichever kernel serves this call, a scratch handed in is valid afterwards (callers cache it)
-        const int rc = e3d_attn_fill_planes(dist_emb, P, Lk, e_scratch, f16, e_absmax, s);   // (also raises *e_absmax)
+        const int rc = e3d_attn_fill_planes(a.dist_emb, a.P, a.Lk, e_scratch, f16, e_absmax, s);   // (also raises *e_absmax)
         if (rc) return rc;
         e_scratch_ready = 1;
     }
-    const bool dropping = drop_p > 0.f;
-    if (attn_coop_ok(k_rs, v_bs, v_rs, Lq, Lk, terms, dropping, !dist_emb || e_scratch))
-        return e3d_attn_coop_launch(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, dist_emb, P, key_mask, out, lse, B, nh,
-                                    Lq, Lk, g_skip_padded, bnd, e_scratch, e_scratch_ready, f16, d, dropping, planes_out, s);
+    if (attn_coop_ok(a.k.rs, a.v.bs, a.v.rs, a.Lq, a.Lk, terms, drop.on(), !a.dist_emb || e_scratch))
+        return e3d_attn_coop_launch(a, g_skip_padded, bnd, e_scratch, e_scratch_ready, f16, drop, planes_out, s);
     E3D_REQUIRE(!planes_out, "attn_split: plane output needs the cooperative kernel (e3d_attn_planes_supported)");
-    if (dropping) {   // training with attention-probability dropout, other shapes / arithmetics: per-wave kernel
-        if (terms == 3)
-            return launch<2, true>(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, dist_emb, P, key_mask, out, lse, B, nh, Lq, Lk, bnd, s, d);
-        return launch<3, true>(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, dist_emb, P, key_mask, out, lse, B, nh, Lq, Lk, bnd, s, d);
-    }
-    if (f16)
-        return launch<2, false, _Float16>(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, dist_emb, P, key_mask, out, lse, B, nh,
-                                          Lq, Lk, bnd, s);
-    if (terms == 3)
-        return launch<2>(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, dist_emb, P, key_mask, out, lse, B, nh, Lq, Lk, bnd, s);
-    return launch<3>(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, dist_emb, P, key_mask, out, lse, B, nh, Lq, Lk, bnd, s);
+    if (drop.on())   // training with attention-probability dropout, other shapes / arithmetics: per-wave kernel
+        return terms == 3 ? launch<2, true>(a, bnd, s, drop.d) : launch<3, true>(a, bnd, s, drop.d);
+    if (f16) return launch<2, false, _Float16>(a, bnd, s);
+    return terms == 3 ? launch<2>(a, bnd, s) : launch<3>(a, bnd, s);
 }
 
 extern "C" int e3d_relkey_attn_fwd_split_ex(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs,
@@ -288,9 +279,9 @@ extern "C" int e3d_relkey_attn_fwd_split_ex(const float* q, int64_t q_bs, int64_
                                             float* lse, int B, int nh, int Lq, int Lk, int terms, float drop_p,
                                             uint64_t drop_seed, void* e_scratch, int e_scratch_ready, const float* q_absmax,
                                             const float* k_absmax, float* e_absmax, void* stream) {
-    return attn_fwd_dispatch(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, dist_emb, P, key_mask, out, lse, B, nh, Lq, Lk, terms,
-                             drop_p, e3d_drop_make(drop_p, drop_seed), e_scratch, e_scratch_ready, q_absmax, k_absmax, e_absmax,
-                             stream);
+    return attn_fwd_dispatch({{q, q_bs, q_rs}, {k, k_bs, k_rs}, {v, v_bs, v_rs}, dist_emb, P, key_mask, out, lse, B, nh, Lq, Lk},
+                             terms, {drop_p, e3d_drop_make(drop_p, drop_seed)}, e_scratch, e_scratch_ready, q_absmax, k_absmax,
+                             e_absmax, stream);
 }
 
 // As e3d_relkey_attn_fwd_split_ex with keyed dropout decisions (drop_p > 0): ``row_keys`` uint64 [B * Lq], the table of the
@@ -303,9 +294,9 @@ extern "C" int e3d_relkey_attn_fwd_split_ex_keyed(const float* q, int64_t q_bs, 
                                                   const float* q_absmax, const float* k_absmax, float* e_absmax, void* stream) {
     E3D_REQUIRE(row_keys && drop_p > 0.f, "attn_split (keyed): row keys and drop_p > 0 required");
     E3D_REQUIRE(site < E3D_DROP_MAX_SITE && nh < E3D_DROP_MAX_HEADS, "attn_split (keyed): site %u / %d heads out of range", site, nh);
-    return attn_fwd_dispatch(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, dist_emb, P, key_mask, out, lse, B, nh, Lq, Lk, terms,
-                             drop_p, e3d_drop_make_keyed(drop_p, site, row_keys), e_scratch, e_scratch_ready, q_absmax, k_absmax,
-                             e_absmax, stream);
+    return attn_fwd_dispatch({{q, q_bs, q_rs}, {k, k_bs, k_rs}, {v, v_bs, v_rs}, dist_emb, P, key_mask, out, lse, B, nh, Lq, Lk},
+                             terms, {drop_p, e3d_drop_make_keyed(drop_p, site, row_keys)}, e_scratch, e_scratch_ready, q_absmax,
+                             k_absmax, e_absmax, stream);
 }
 
 extern "C" int e3d_relkey_attn_fwd_split(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs,
@@ -350,7 +341,8 @@ extern "C" int e3d_relkey_attn_fwd_split_planes(const float* q, int64_t q_bs, in
                                                 const float* q_absmax, const float* k_absmax, float* e_absmax, void* stream) {
     E3D_REQUIRE(e3d_attn_planes_supported(k_rs, v_bs, v_rs, Lq, Lk, terms, !dist_emb || e_scratch),
                 "attn_split (planes): this call does not land on the 4-wave cooperative kernel (Lq=%d Lk=%d terms=%d)", Lq, Lk, terms);
-    return attn_fwd_dispatch(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, dist_emb, P, key_mask, reinterpret_cast<float*>(out_planes),
-                             nullptr, B, nh, Lq, Lk, terms, 0.f, e3d_drop_make(0.f, 0), e_scratch, e_scratch_ready, q_absmax,
-                             k_absmax, e_absmax, stream, true);
+    return attn_fwd_dispatch({{q, q_bs, q_rs}, {k, k_bs, k_rs}, {v, v_bs, v_rs}, dist_emb, P, key_mask,
+                              reinterpret_cast<float*>(out_planes), nullptr, B, nh, Lq, Lk},
+                             terms, {0.f, e3d_drop_make(0.f, 0)}, e_scratch, e_scratch_ready, q_absmax, k_absmax, e_absmax, stream,
+                             true);
 }

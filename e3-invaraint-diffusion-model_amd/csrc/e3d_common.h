@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <math.h>
 #include <atomic>
+#include <type_traits>
 
 #include "../../include/e3d_hip.h"
 
@@ -258,34 +259,68 @@ __device__ __forceinline__ void e3d_drop_mult4(const E3dDrop d, uint64_t idx4, f
 
 int e3d_attn_fill_planes(const float* dist_emb, int P, int Lk, void* scratch, int f16, float* e_absmax, hipStream_t s);
 
+// ---------------------------------------------------------------- attention host records
+// One padded attention call as the host functions hand it on.  Each extern "C" entry point fills its record once;
+// only the hipLaunchKernelGGL sites take it apart again (E3D_VIEW).
+template <typename T>
+struct E3dViewT { T* p; int64_t bs, rs; };   // rows of [B, L, heads * 64]: batch stride and row stride, in floats
+typedef E3dViewT<const float> E3dView;
+typedef E3dViewT<float> E3dGradView;
+#define E3D_VIEW(x) (x).p, (x).bs, (x).rs
+struct E3dAttnFwd {
+    E3dView q, k, v;
+    const float* dist_emb; int P; const float* key_mask;
+    float *out, *lse;
+    int B, nh, Lq, Lk;
+};
+struct E3dAttnBwd {   // (the order of the C ABI: the forward's tensors are inputs here)
+    E3dView q, k, v;
+    const float* dist_emb; int P; const float* key_mask;
+    const float *out, *lse, *dout;
+    E3dGradView dq, dk, dv;
+    float* d_dist_emb;
+    int B, nh, Lq, Lk;
+};
+// Dropout on the probabilities of one call: ``p`` as the caller gave it (the dispatch validates it) and its decisions
+struct E3dAttnDrop {
+    float p;
+    E3dDrop d;
+    bool on() const { return p > 0.f; }
+};
+// f(relkey, dropping) with both as std::bool_constant: the kernel form of a call with / without a distance table and dropout
+template <typename F>
+static inline void e3d_attn_form(bool relkey, bool dropping, F&& f) {
+    if (relkey) {
+        if (dropping) f(std::true_type{}, std::true_type{});
+        else f(std::true_type{}, std::false_type{});
+    } else {
+        if (dropping) f(std::false_type{}, std::true_type{});
+        else f(std::false_type{}, std::false_type{});
+    }
+}
+
 // attn_relkey_coop.hip: workgroup-cooperative bf16x3 / f16x3 attention forward (internal; arguments validated by the
-// caller); ``dropping``: dropout on the probabilities (bf16x3 only)
-int e3d_attn_coop_launch(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs, int64_t k_rs,
-                         const float* v, int64_t v_bs, int64_t v_rs, const float* dist_emb, int P,
-                         const float* key_mask, float* out, float* lse, int B, int nh, int Lq, int Lk, int skip,
-                         E3dBounds bnd, void* e_scratch, int e_ready, int f16, E3dDrop drop, bool dropping, bool planes,
-                         hipStream_t s);
-// ``planes``: ``out`` receives activation planes (gemm_rowln.hip) instead of fp32 rows -- 4-wave inference forms, Lq % 32 == 0
+// caller); dropout on the probabilities: bf16x3 only.  ``planes``: ``a.out`` receives activation planes (gemm_rowln.hip)
+// instead of fp32 rows -- 4-wave inference forms, Lq % 32 == 0
+int e3d_attn_coop_launch(const E3dAttnFwd& a, int skip, E3dBounds bnd, void* e_scratch, int e_ready, int f16,
+                         const E3dAttnDrop& drop, bool planes, hipStream_t s);
 int e3d_attn_coop_waves(int Lq);
 
+// Float offsets of the regions of the backward workspace (e3d_relkey_attn_bwd_workspace_floats = ``total``):
+// [P | dS] of the two-launch kernels, the fused kernel's distance-table planes in the same head region, then -- with a
+// distance table only -- the unit blocks of dE, the chunk sums of its reduction and one liveness word per
+// (b, head, query tile)
+struct E3dBwdLayout { int64_t Pm, dSm, part, chunk_sums, unit_live, total; };
+E3dBwdLayout e3d_attn_bwd_layout(int B, int nh, int Lq, int Lk, bool relkey);   // attn_bwd_coop.hip
+
 // attn_bwd_split.hip: launches A and B of the attention backward in bf16x3 arithmetic (internal)
-int e3d_attn_bwd_split_launch(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs, int64_t k_rs,
-                              const float* v, int64_t v_bs, int64_t v_rs, const float* dist_emb, int P,
-                              const float* key_mask, const float* out, const float* lse, const float* dout, float* dq,
-                              int64_t dq_bs, int64_t dq_rs, float* dk, int64_t dk_bs, int64_t dk_rs, float* dv,
-                              int64_t dv_bs, int64_t dv_rs, float* Pm, float* dSm, float* part, int B, int nh, int Lq,
-                              int Lk, E3dDrop drop, bool dropping, hipStream_t s);
+int e3d_attn_bwd_split_launch(const E3dAttnBwd& a, float* workspace, const E3dBwdLayout& w, const E3dAttnDrop& drop,
+                              hipStream_t s);
 
 // attn_bwd_coop.hip: the fused, recomputing backward (bf16x3, Lq, Lk <= 128); internal
-int64_t e3d_attn_bwd_coop_scratch_bytes(int Lk);
-int64_t e3d_attn_bwd_coop_de_floats(int Lq, int Lk);
 bool e3d_attn_bwd_coop_supported(int Lq, int Lk, bool dropping);
-int e3d_attn_bwd_coop_launch(const float* q, int64_t q_bs, int64_t q_rs, const float* k, int64_t k_bs, int64_t k_rs,
-                             const float* v, int64_t v_bs, int64_t v_rs, const float* dist_emb, int P,
-                             const float* key_mask, const float* out, const float* lse, const float* dout, float* dq,
-                             int64_t dq_bs, int64_t dq_rs, float* dk, int64_t dk_bs, int64_t dk_rs, float* dv,
-                             int64_t dv_bs, int64_t dv_rs, float* d_dist_emb, void* e_scratch, float* part, int B, int nh,
-                             int Lq, int Lk, E3dDrop drop, bool dropping, hipStream_t s);
+int e3d_attn_bwd_coop_launch(const E3dAttnBwd& a, float* workspace, const E3dBwdLayout& w, const E3dAttnDrop& drop,
+                             hipStream_t s);
 
 // XCD-aware remap (cdna_hip_programming.md T1, bijective form): consecutive logical ids
 // land on one XCD so that workgroups sharing operands share an L2.

@@ -13,6 +13,16 @@ LIB_PATH = os.environ.get("E3D_HIP_LIB", os.path.join(_HERE, "libe3d_hip.so"))  
 ABI_VERSION = 5
 
 _P = c_void_p
+# The padded-attention entry points share their leading arguments (e3d_hip.h); their signatures are put together from these.
+_VIEW = [_P, c_int64, c_int64]                      # pointer, batch stride, row stride
+_QKV = 3 * _VIEW + [_P, c_int, _P]                  # q, k, v views, dist_emb, P, key_mask
+_SHAPE = 4 * [c_int]                                # B, nh, Lq, Lk
+_ATTN_FWD = _QKV + [_P, _P] + _SHAPE                # ..., out, lse, shape
+_ATTN_BWD = _QKV + 3 * [_P] + 3 * _VIEW + [_P, _P] + _SHAPE   # ..., out, lse, dout, dq, dk, dv views, d_dist_emb, workspace, shape
+_STREAM = [_P]
+_DROP = [c_float, c_uint64]                         # drop_p, drop_seed
+_DROP_KEYED = [c_float, c_uint32, _P]               # drop_p, site, row_keys
+_BOUNDS = [_P, c_int, _P, _P, _P]                   # e_scratch, e_scratch_ready, q / k / e absmax
 _SIGNATURES = {
     "e3d_abi_version": (c_int, []),
     "e3d_last_error": (c_char_p, []),
@@ -22,10 +32,8 @@ _SIGNATURES = {
     "e3d_gemm_bias_act_f32_split_gated": (c_int, [_P, c_int64, _P, _P, _P, c_int64, c_int, c_int, c_int, c_int, c_int, _P, c_float,
                                                   c_int, _P, _P]),
     "e3d_absmax_f32": (c_int, [_P, c_int64, _P, _P]),
-    "e3d_relkey_attn_fwd": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int64, c_int64,
-                                    _P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
-    "e3d_relkey_attn_fwd_split": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int64, c_int64,
-                                          _P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "e3d_relkey_attn_fwd": (c_int, _ATTN_FWD + _STREAM),
+    "e3d_relkey_attn_fwd_split": (c_int, _ATTN_FWD + [c_int] + _STREAM),
     "e3d_gemm_skinny_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
     "e3d_gemm_skinny_f32_split": (c_int, [_P, c_int64, _P, _P, _P, c_int64, c_int, c_int, c_int, c_int, c_int, _P, c_int64, _P]),
     "e3d_gemm_skinny_f32_split_ex": (c_int, [_P, c_int64, _P, _P, _P, c_int64, c_int, c_int, c_int, c_int, c_int, _P, c_int64, _P, c_float, _P]),
@@ -66,29 +74,17 @@ _SIGNATURES = {
     "e3d_gemm_planes_supported": (c_int, [c_int, c_int, c_int, c_int64, c_int, c_int]),
     "e3d_gemm_bias_act_planes_split": (c_int, [_P, c_int64, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_float, _P]),
     "e3d_attn_planes_supported": (c_int, [c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int]),
-    "e3d_relkey_attn_fwd_split_planes": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int64, c_int64,
-                                                 _P, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int,
-                                                 _P, _P, _P, _P]),
+    "e3d_relkey_attn_fwd_split_planes": (c_int, _QKV + [_P] + _SHAPE + [c_int] + _BOUNDS + _STREAM),
     "e3d_gemm_wgrad_ragged_f32_split": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_uint64, c_int, c_int, c_int, _P]),
     "e3d_relkey_attn_bwd_workspace_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
-    "e3d_relkey_attn_bwd": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int, _P,
-                                    _P, _P, _P, _P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int64, c_int64,
-                                    _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "e3d_relkey_attn_bwd": (c_int, _ATTN_BWD + _STREAM),
     "e3d_dropout_f32": (c_int, [_P, c_float, c_uint64, _P, c_int64, _P]),
-    "e3d_relkey_attn_fwd_split_drop": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int64, c_int64,
-                                               _P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float,
-                                               c_uint64, _P]),
-    "e3d_relkey_attn_fwd_split_ex": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int64, c_int64,
-                                             _P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float,
-                                             c_uint64, _P, c_int, _P, _P, _P, _P]),
+    "e3d_relkey_attn_fwd_split_drop": (c_int, _ATTN_FWD + [c_int] + _DROP + _STREAM),
+    "e3d_relkey_attn_fwd_split_ex": (c_int, _ATTN_FWD + [c_int] + _DROP + _BOUNDS + _STREAM),
     "e3d_attn_scratch_bytes": (c_int64, [c_int]),
     "e3d_ddpm_step_wrap_table": (c_int, [_P, _P, _P, _P, _P, c_int, _P, c_int64, _P]),
-    "e3d_relkey_attn_bwd_drop": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int, _P,
-                                         _P, _P, _P, _P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int64, c_int64,
-                                         _P, _P, c_int, c_int, c_int, c_int, c_float, c_uint64, _P]),
-    "e3d_relkey_attn_bwd_ex": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int, _P,
-                                       _P, _P, _P, _P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int64, c_int64,
-                                       _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, c_uint64, _P]),
+    "e3d_relkey_attn_bwd_drop": (c_int, _ATTN_BWD + _DROP + _STREAM),
+    "e3d_relkey_attn_bwd_ex": (c_int, _ATTN_BWD + [c_int] + _DROP + _STREAM),
     "e3d_attn_dropout_mask": (c_int, [c_int, c_int, c_int, c_int, c_float, c_uint64, _P, _P]),
     "e3d_layernorm_bwd": (c_int, [_P, _P, _P, c_float, _P, _P, _P, c_int, c_int, _P]),
     "e3d_layernorm_bwd_workspace_floats": (c_int64, [c_int, c_int]),
@@ -143,18 +139,10 @@ _SIGNATURES = {
     "e3d_layernorm_bwd_drop_keyed": (c_int, [_P, _P, _P, c_float, _P, _P, _P, _P, c_int, c_int, c_float, c_uint32, _P, _P]),
     "e3d_layernorm_bwd_ws_keyed": (c_int, [_P, _P, _P, c_float, _P, _P, _P, _P, c_int, c_int, c_float, c_uint32, _P, _P, c_int64,
                                            _P]),
-    "e3d_relkey_attn_fwd_split_drop_keyed": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int64, c_int64,
-                                                     _P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float,
-                                                     c_uint32, _P, _P]),
-    "e3d_relkey_attn_fwd_split_ex_keyed": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int64, c_int64,
-                                                   _P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float,
-                                                   c_uint32, _P, _P, c_int, _P, _P, _P, _P]),
-    "e3d_relkey_attn_bwd_drop_keyed": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int, _P,
-                                               _P, _P, _P, _P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int64, c_int64,
-                                               _P, _P, c_int, c_int, c_int, c_int, c_float, c_uint32, _P, _P]),
-    "e3d_relkey_attn_bwd_ex_keyed": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int, _P,
-                                             _P, _P, _P, _P, c_int64, c_int64, _P, c_int64, c_int64, _P, c_int64, c_int64,
-                                             _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, c_uint32, _P, _P]),
+    "e3d_relkey_attn_fwd_split_drop_keyed": (c_int, _ATTN_FWD + [c_int] + _DROP_KEYED + _STREAM),
+    "e3d_relkey_attn_fwd_split_ex_keyed": (c_int, _ATTN_FWD + [c_int] + _DROP_KEYED + _BOUNDS + _STREAM),
+    "e3d_relkey_attn_bwd_drop_keyed": (c_int, _ATTN_BWD + _DROP_KEYED + _STREAM),
+    "e3d_relkey_attn_bwd_ex_keyed": (c_int, _ATTN_BWD + [c_int] + _DROP_KEYED + _STREAM),
     # featurization of PDB coordinates (featurize.py)
     "e3d_backbone_angles": (c_int, [_P, _P, _P, _P, c_int, c_float, _P]),
     "e3d_contact_residues": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P]),

@@ -533,6 +533,17 @@ def attn_dropout_mask(B, nh, Lq, Lk, p, seed, device="cuda"):
     return out
 
 
+def _attn_view(t, L):
+    """(pointer, batch stride, row stride) of a [B * L, ...] row-strided view, as the attention entry points take it."""
+    rs = t.stride(0)
+    return _p(t), L * rs, rs
+
+
+def _attn_inputs(q, k, v, Lq, Lk, dist_emb, max_pos, key_mask):
+    """The arguments every padded-attention entry point, forward or backward, starts with."""
+    return (*_attn_view(q, Lq), *_attn_view(k, Lk), *_attn_view(v, Lk), _p(dist_emb), max_pos, _p(key_mask))
+
+
 def attention(q, k, v, B, nh, Lq, Lk, key_mask=None, dist_emb=None, max_pos=0, want_lse=False, mode=None, drop=None,
               bounds=None, planes_out=False):
     """q [B*Lq, >=nh*64] / k, v [B*Lk, ...] row-strided 2-D views (e.g. slices of a fused QKV
@@ -560,9 +571,8 @@ def attention(q, k, v, B, nh, Lq, Lk, key_mask=None, dist_emb=None, max_pos=0, w
         out = torch.empty((B * Lq, nh * 64), device=q.device, dtype=torch.float32)
     lse = torch.empty((B, nh, Lq), device=q.device, dtype=torch.float32) if want_lse else None
     with _timed("attn_relkey" if dist_emb is not None else "attn_cross", (B, nh, Lq, Lk)):
-        args = (_p(q), Lq * q.stride(0), q.stride(0), _p(k), Lk * k.stride(0), k.stride(0),
-                _p(v), Lk * v.stride(0), v.stride(0), _p(dist_emb), max_pos, _p(key_mask), _p(out), _p(lse),
-                B, nh, Lq, Lk)
+        inputs = _attn_inputs(q, k, v, Lq, Lk, dist_emb, max_pos, key_mask)
+        args = (*inputs, _p(out), _p(lse), B, nh, Lq, Lk)
         dropping = drop is not None and drop[0] > 0
         if terms == 0 and not dropping:
             hip.check(hip.lib().e3d_relkey_attn_fwd(*args, _stream()), "e3d_relkey_attn_fwd")
@@ -605,7 +615,7 @@ def attention(q, k, v, B, nh, Lq, Lk, key_mask=None, dist_emb=None, max_pos=0, w
             if q_abs is None or k_abs is None or (dist_emb is not None and e_abs is None):
                 q_abs = k_abs = e_abs = None
             if planes_out:
-                hip.check(hip.lib().e3d_relkey_attn_fwd_split_planes(*args[:12], _p(out), B, nh, Lq, Lk, terms, _p(scratch), ready,
+                hip.check(hip.lib().e3d_relkey_attn_fwd_split_planes(*inputs, _p(out), B, nh, Lq, Lk, terms, _p(scratch), ready,
                                                                      _p(q_abs), _p(k_abs), _p(e_abs), _stream()),
                           "e3d_relkey_attn_fwd_split_planes")
                 return ActPlanes(out, B * Lq, nh * 64, terms)

@@ -474,6 +474,109 @@ def test_backward_writes_every_row_and_nothing_else_into_strided_frames(pkg, hip
     _report(figures)
 
 
+# --------------------------------------- 3b. Q, K, V and dq, dk, dv in frames of their own, no two strides alike
+# Through ops.attention K and V share one buffer and Q / K / V one row stride, so the library could swap the strides of
+# two views and every other test would still pass.  Here each view has a frame [B, L + gap, row stride] of its own:
+# row strides are distinct multiples of 4 floats (16-byte rows) above H = 128, gaps differ, so do the batch strides.
+SEPARATE = {"q": (132, 8), "k": (136, 5), "v": (144, 3), "dq": (140, 6), "dk": (148, 2), "dv": (152, 7)}   # row stride, gap
+
+
+def _separate_input(x, B, L, name):
+    """[B L, H] -> (device frame [B, L + gap, row stride], view triple); pad columns and gap rows are NaN."""
+    rs, gap = SEPARATE[name]
+    f = torch.full((B, L + gap, rs), float("nan"))
+    f[:, :L, :H] = x.reshape(B, L, H)
+    f = f.to(DEV)
+    return f, (f.data_ptr(), (L + gap) * rs, rs)
+
+
+def _separate_output(B, L, name):
+    """(buffer, bool element index of the item elements, view triple): the item elements are NaN; pad columns, gap rows
+    and TAIL rows behind the frame hold the sentinel."""
+    rs, gap = SEPARATE[name]
+    rows = B * (L + gap)
+    buf = torch.full((rows + TAIL, rs), SENTINEL, device=DEV)
+    item = torch.zeros_like(buf, dtype=torch.bool)
+    item[:rows].view(B, L + gap, rs)[:, :L, :H] = True
+    buf[item] = float("nan")
+    return buf, item, (buf.data_ptr(), (L + gap) * rs, rs)
+
+
+class _DirectSeparate(_Direct):
+    def __init__(self, pkg, lib, c):
+        self.pkg, self.lib, self.c = pkg, lib, c
+        q, k, v = c.views(c.q_src, c.kv_src)
+        self.frames, self.in_args = [], ()        # (the frames are kept alive)
+        for name, t, L in (("q", q, c.Lq), ("k", k, c.Lk), ("v", v, c.Lk)):
+            f, triple = _separate_input(t, c.B, L, name)
+            self.frames.append(f)
+            self.in_args += triple
+        assert len(set(self.in_args[1::3])) == 3 and len(set(self.in_args[2::3])) == 3
+        self.E = c.E.to(DEV) if c.E is not None else None
+        self.mask = c.mask.to(DEV)
+        self.stream = torch.cuda.current_stream().cuda_stream
+        self.out, self.out_item = _guarded(c.B * c.Lq, H)
+        self.lse, self.lse_item = _guarded(c.B * NH, c.Lq)
+
+
+_separate_refs = {}
+
+
+def _separate_reference(name):
+    """(case, fp64 out, fp64 lse, fp64 gradients) of a DIRECT_SHAPES case, computed once."""
+    if name not in _separate_refs:
+        c = _direct_case(name)
+        _, s = c.reference(c.q_src.double(), c.kv_src.double() if c.cross else None, c.E.double() if c.E is not None else None)
+        out, want = c.reference_grads()
+        _separate_refs[name] = (c, out, torch.logsumexp(s, -1).float().reshape(c.B * NH, c.Lq), want)
+    return _separate_refs[name]
+
+
+@pytest.mark.parametrize("mode,tol", FWD_MODES)
+@pytest.mark.parametrize("name", sorted(DIRECT_SHAPES))
+def test_forward_from_separate_frames_of_pairwise_different_strides(pkg, hip, name, mode, tol):
+    """test_forward_writes_every_row_and_nothing_else_from_strided_frames with Q, K and V in three frames whose row
+    strides (132, 136, 144) and batch strides all differ: a batch or row stride taken from the wrong view reads NaN
+    (pad columns, gap rows) or the wrong rows."""
+    c, ref, ref_lse, _ = _separate_reference(name)
+    d = _DirectSeparate(pkg, hip, c)
+    d.forward(pkg.ops.GEMM_MODES[mode])
+    figures = []
+    _check_guarded(figures, f"{mode} out", d.out, d.out_item, ref, tol)
+    _check_guarded(figures, f"{mode} lse", d.lse, d.lse_item, ref_lse, tol)
+    _report(figures)
+
+
+@pytest.mark.parametrize("terms,tol", [(0, 2e-5), (6, 2e-5), (3, 1e-4)])
+@pytest.mark.parametrize("name", sorted(DIRECT_SHAPES))
+def test_backward_into_separate_frames_of_pairwise_different_strides(pkg, hip, name, terms, tol):
+    """test_backward_writes_every_row_and_nothing_else_into_strided_frames with Q, K, V and dq, dk, dv in six frames, no
+    two row strides and no two batch strides alike: every gradient element of an item finite and equal to fp64; pad
+    columns, gap rows, the rows behind every frame and behind the workspace untouched."""
+    c, _, _, want = _separate_reference(name)
+    d = _DirectSeparate(pkg, hip, c)
+    d.forward(terms)
+    assert torch.isfinite(d.out[d.out_item]).all() and torch.isfinite(d.lse[d.lse_item]).all()
+    lib, p = hip, pkg.ops._p
+    grads = {n: _separate_output(c.B, L, n) for n, L in (("dq", c.Lq), ("dk", c.Lk), ("dv", c.Lk))}
+    out_args = grads["dq"][2] + grads["dk"][2] + grads["dv"][2]
+    assert len(set((d.in_args + out_args)[1::3])) == 6 and len(set((d.in_args + out_args)[2::3])) == 6
+    dE, dE_item = _guarded(2 * c.P - 1, 64) if c.E is not None else (None, None)
+    n_ws = lib.e3d_relkey_attn_bwd_workspace_floats(c.B, NH, c.Lq, c.Lk, int(c.E is not None))
+    ws = torch.full((n_ws + TAIL * 64,), float("nan"), device=DEV)
+    ws[n_ws:] = SENTINEL
+    dout = c.go.to(DEV)
+    pkg.hip.check(lib.e3d_relkey_attn_bwd_ex(*d.in_args, p(d.E), c.P, p(d.mask), p(d.out), p(d.lse), p(dout), *out_args, p(dE),
+                                             p(ws), c.B, NH, c.Lq, c.Lk, terms, 0.0, 0, d.stream), "e3d_relkey_attn_bwd_ex")
+    assert torch.equal(ws[n_ws:], torch.full_like(ws[n_ws:], SENTINEL)), "written past the workspace"
+    figures = []
+    for n, (buf, item, _) in grads.items():
+        _check_guarded(figures, f"terms {terms} {n}", buf, item, want[n], tol)
+    if c.E is not None:
+        _check_guarded(figures, f"terms {terms} dE", dE, dE_item, want["dE"], tol)
+    _report(figures)
+
+
 # ------------------------------------------------------------------- 4. dropout on the ragged cooperative shapes
 @pytest.mark.parametrize("name", ["self100", "cross128x70"])
 def test_dropout_on_ragged_cooperative_shapes(pkg, hip, Fm, name):
