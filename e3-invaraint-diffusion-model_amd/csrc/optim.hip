@@ -80,7 +80,9 @@ __device__ __forceinline__ void adamw_one(float& p, float g, float& m, float& v,
     // torch's fused AdamW (torch/csrc .. fused_adam_utils.cuh, ADAMW mode), in the same order of operations
     p -= a.lr * a.weight_decay * p;
     m = m + (g - m) * (1.0f - a.beta1);                       // lerp(exp_avg, grad, 1 - beta1)
-    v = a.beta2 * v + (1.0f - a.beta2) * g * g;
+    // one contraction, spelled out: left to the compiler, the float4 loop fused beta2 * v into the sum and the scalar loop
+    // fused the g * g product instead, so an element's exp_avg_sq depended in its last place on the path its tensor took
+    v = fmaf(a.beta2, v, __fmul_rn(__fmul_rn(1.0f - a.beta2, g), g));
     const float step_size = a.lr / a.bc1;
     const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
     p -= step_size * m / denom;

@@ -201,13 +201,17 @@ def test_structure_sample_entry_point_and_its_f16x3_safety_net(pkg, hip, monkeyp
     assert all(bool(torch.isfinite(torch.from_numpy(o)).all()) for o in out2)
 
 
-def test_clip_adamw_three_launch_step_matches_torch(pkg, hip):
+@pytest.mark.parametrize("device_scalars", [False, True])
+def test_clip_adamw_three_launch_step_matches_torch(pkg, hip, device_scalars):
     """optim.ClipAdamW (what ``training.adamw`` / ``configure_optimizers`` return on the GPU): gradient-norm clip + AdamW
     in three HIP launches against torch's clip_grad_norm_ + AdamW (single-tensor implementation) over several steps --
     clip active and inactive, element counts that are not multiples of 4 or of the chunk, a parameter that is a view at
     an address that is not 16-byte aligned, a parameter that never receives a gradient, two parameter groups with
     different lr / weight decay, a parameter that starts receiving gradients two steps late (its own step count), and
-    the optimizer state moving to a plain torch.optim.AdamW through state_dict."""
+    the optimizer state moving to a plain torch.optim.AdamW through state_dict.  With host scalars (e3d_adamw_step) and
+    with ``use_device_scalars`` (e3d_adamw_step_dev, what the graphed steps run: the late parameter is then a second hyper
+    block of its group with a step count of its own); lr and beta1 of both groups change every step through
+    ``param_groups``, on the torch twin too, so ``sync_lr`` has something to push before every step."""
     from e3diff_amd.optim import ClipAdamW
     from e3diff_amd.training import adamw, clip_and_step
     dev = "cuda:0"
@@ -226,8 +230,13 @@ def test_clip_adamw_three_launch_step_matches_torch(pkg, hip):
             late = torch.nn.Parameter(base[1].clone())                        # first gradient at step 2
             groups = [dict(params=ps[:3] + [odd, idle], lr=1e-2, weight_decay=0.1), dict(params=ps[3:] + [late], lr=3e-3, weight_decay=0.0)]
             opt = torch.optim.AdamW(groups, foreach=False) if impl == "torch" else ClipAdamW(groups)
+            if impl == "hip":
+                opt.use_device_scalars(device_scalars)
             norms = []
             for step in range(5):
+                for gi, gr in enumerate(opt.param_groups):
+                    gr["lr"] = (1e-2, 3e-3)[gi] * (1 + 0.25 * step)
+                    gr["betas"] = (0.95 - 0.02 * step - 0.01 * gi, 0.999)
                 g = torch.Generator(device=dev).manual_seed(100 + step)
                 for p in ps + [odd] + ([late] if step >= 2 else []):
                     p.grad = torch.randn(p.shape, device=dev, generator=g) * scale
@@ -240,6 +249,13 @@ def test_clip_adamw_three_launch_step_matches_torch(pkg, hip):
                 opt.zero_grad(set_to_none=True)
             models.append((ps + [odd, late, idle], norms, opt))
         (pa, na, oa), (pb, nb, ob) = models
+        assert ob.device_scalars == device_scalars and ("dyn" in ob._e3d_tab) == device_scalars
+        if device_scalars:      # group 0, group 1, and the late parameter's own block: lr, steps taken, beta1 as last set
+            dyn = ob._e3d_tab["dyn"].cpu()
+            assert dyn[:, 1].tolist() == [5.0, 3.0, 5.0]
+            last = [ClipAdamW._hyper(ob.param_groups[gi]) for gi in (0, 1, 1)]
+            assert dyn[:, 0].tolist() == [h[0] for h in last] and dyn[:, 2].tolist() == [h[1] for h in last]
+            assert last[0][:2] != last[1][:2] and last[0][0] == float(torch.tensor(1e-2 * 2.0, dtype=torch.float32))
         for x, y in zip(na, nb):
             assert abs(float(x) - float(y)) <= 2e-6 * float(x)
         for x, y in zip(pa, pb):
