@@ -6,10 +6,13 @@ the C-ABI of include/e3d_hip.h (csrc/, loaded by hip.py).  No CPU fallback.
 """
 from . import hip  # noqa: F401
 
-__all__ = ["hip", "ops", "bert", "blocks", "training", "optim", "sharding", "autograd", "biolip", "featurize", "evaluate", "packing", "structure_model", "sequence_model"]
+__all__ = ["hip", "ops", "bert", "blocks", "training", "optim", "sharding", "autograd", "biolip", "featurize", "evaluate", "packing", "design", "structure_model", "sequence_model", "DesignControls"]
 
 
 def __getattr__(name):
+    if name == "DesignControls":        # the record of design.py, under the package's own name too
+        from .design import DesignControls
+        return DesignControls
     if name in __all__:
         import importlib
         return importlib.import_module(f"{__name__}.{name}")

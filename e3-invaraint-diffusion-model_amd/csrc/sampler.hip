@@ -154,16 +154,27 @@ __device__ __forceinline__ int pick_class(const float (&p)[CMAX], int C, float t
     return best;
 }
 
+// Design controls: the effective logit z = (logit + bias) * inv_temp, one add and then one multiply in fp32.  A sum
+// times a factor has no fused form, and contraction is switched off here so that the product is rounded before anything
+// is subtracted from it: z is a function of the three fp32 inputs alone.  bias -inf forbids the class (z = -inf).
+__device__ __forceinline__ float effective_logit(float logit, float bias, float inv_temp) {
+#pragma clang fp contract(off)
+    const float sum = logit + bias;
+    return sum * inv_temp;
+}
+
 // One workgroup per batch item: the three CxC matrices of the item live in LDS, each thread
 // walks rows l = tid, tid+256, ...
 // KEYED: the uniform of row n = b * L + l is drawn from stream 3 at step s_dev[0] with the row's key (row_keys[n]);
 // rows of no item draw u = 0.
-template <bool KEYED>
+// CTL: the softmax runs over the effective logits (bias [B*L, C] or NULL for zero, inv_temp > 0); a forbidden class
+// has pred == 0 exactly, a row with every class forbidden has pred == 0 everywhere and takes the zero-total rule below.
+template <bool KEYED, bool CTL>
 __global__ __launch_bounds__(256) void discrete_posterior_kernel(
     const int32_t* __restrict__ xt_idx, const float* __restrict__ logits, const float* __restrict__ Qsb,
     const float* __restrict__ Qtb, const float* __restrict__ u, int mode, int32_t* __restrict__ out_idx,
     float* __restrict__ prob_out, int L, int C, const int64_t* __restrict__ row_keys, uint64_t seed,
-    const int64_t* __restrict__ s_dev) {
+    const int64_t* __restrict__ s_dev, const float* __restrict__ bias, float inv_temp) {
     __shared__ float s_qsb[CMAX * CMAX], s_qtb[CMAX * CMAX], s_qt[CMAX * CMAX], s_rs[CMAX];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int CC = C * C;
@@ -190,17 +201,19 @@ __global__ __launch_bounds__(256) void discrete_posterior_kernel(
         float mx = -INFINITY;
 #pragma unroll
         for (int c = 0; c < CMAX; ++c) {
-            pred[c] = c < C ? lg[c] : -INFINITY;
+            if (CTL) pred[c] = c < C ? effective_logit(lg[c], bias ? bias[n * C + c] : 0.f, inv_temp) : -INFINITY;
+            else pred[c] = c < C ? lg[c] : -INFINITY;
             mx = fmaxf(mx, pred[c]);
         }
+        const bool none = CTL && mx == -INFINITY;   // every class forbidden: -inf - -inf is NaN, so no exponential is taken
         float se = 0.f;
 #pragma unroll
         for (int c = 0; c < CMAX; ++c) {
-            pred[c] = c < C ? expf(pred[c] - mx) : 0.f;
+            pred[c] = (c < C && !none) ? expf(pred[c] - mx) : 0.f;
             se += pred[c];
         }
 #pragma unroll
-        for (int c = 0; c < CMAX; ++c) { pred[c] = pred[c] / se; prob[c] = 0.f; }
+        for (int c = 0; c < CMAX; ++c) { pred[c] = none ? 0.f : pred[c] / se; prob[c] = 0.f; }
         // prob[c] = sum_x0 pred[x0] * (Qt[c][xt] * Qsb[x0][c]) / Qtb[x0][xt]   (sample.py:129-139,162-165)
 #pragma unroll 1
         for (int x0 = 0; x0 < C; ++x0) {
@@ -244,6 +257,50 @@ __global__ __launch_bounds__(256) void discrete_posterior_kernel(
             un = u[n];
         }
         out_idx[n] = pick_class(prob, C, ntot, mode, un);
+    }
+}
+
+// The last step's pick under design controls, one thread per row: out_idx = the first maximum of the effective logits z,
+// logp = log_softmax(z)[out_idx], entropy = -sum p log p of softmax(z) with 0 log 0 = 0.  The entropy is summed as
+// p[c] * (lse - (z[c] - mx)): every term is non-negative, so nothing cancels.  A row with every class forbidden:
+// out_idx = 0, logp = entropy = NaN.
+__global__ __launch_bounds__(256) void discrete_final_pick_kernel(
+    const float* __restrict__ logits, const float* __restrict__ bias, float inv_temp, int32_t* __restrict__ out_idx,
+    float* __restrict__ logp, float* __restrict__ entropy, int64_t n_rows, int C) {
+    const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= n_rows) return;
+    const float* lg = logits + n * C;
+    float z[CMAX];
+    float mx = -INFINITY;
+    int best = 0;
+#pragma unroll
+    for (int c = 0; c < CMAX; ++c) {
+        z[c] = c < C ? effective_logit(lg[c], bias ? bias[n * C + c] : 0.f, inv_temp) : -INFINITY;
+        if (z[c] > mx) { mx = z[c]; best = c; }
+    }
+    out_idx[n] = best;
+    if (!logp && !entropy) return;
+    if (mx == -INFINITY) {
+        if (logp) logp[n] = __builtin_nanf("");
+        if (entropy) entropy[n] = __builtin_nanf("");
+        return;
+    }
+    float e[CMAX];
+    float se = 0.f;
+#pragma unroll
+    for (int c = 0; c < CMAX; ++c) {
+        z[c] = z[c] - mx;
+        e[c] = c < C ? expf(z[c]) : 0.f;
+        se += e[c];
+    }
+    const float lse = logf(se);
+    if (logp) logp[n] = 0.f - lse;   // z[best] - mx is exactly 0: the pick is the maximum
+    if (entropy) {
+        float h = 0.f;
+#pragma unroll
+        for (int c = 0; c < CMAX; ++c)
+            if (e[c] > 0.f) h += (e[c] / se) * (lse - z[c]);
+        entropy[n] = h;
     }
 }
 
@@ -607,8 +664,8 @@ extern "C" int e3d_discrete_posterior_sample(const int32_t* xt_idx, const float*
     E3D_REQUIRE(xt_idx && logits && Qsb && Qtb && out_idx && B > 0 && L > 0, "discrete_posterior: bad arguments");
     E3D_REQUIRE(C >= 2 && C <= CMAX, "discrete_posterior: C must be in [2,%d] (C=%d)", CMAX, C);
     E3D_REQUIRE(mode == 0 || (mode == 1 && u), "discrete_posterior: mode 1 needs uniforms");
-    hipLaunchKernelGGL(discrete_posterior_kernel<false>, dim3(B), dim3(256), 0, (hipStream_t)stream, xt_idx, logits, Qsb,
-                       Qtb, u, mode, out_idx, prob_out, L, C, nullptr, 0ull, nullptr);
+    hipLaunchKernelGGL((discrete_posterior_kernel<false, false>), dim3(B), dim3(256), 0, (hipStream_t)stream, xt_idx, logits,
+                       Qsb, Qtb, u, mode, out_idx, prob_out, L, C, nullptr, 0ull, nullptr, nullptr, 1.f);
     return e3d_launch_status("e3d_discrete_posterior_sample");
 }
 
@@ -664,8 +721,8 @@ extern "C" int e3d_keyed_discrete_posterior_sample(const int32_t* xt_idx, const 
     E3D_REQUIRE(xt_idx && logits && Qsb && Qtb && row_keys && s_dev && out_idx && B > 0 && L > 0,
                 "keyed_discrete_posterior: bad arguments");
     E3D_REQUIRE(C >= 2 && C <= CMAX, "keyed_discrete_posterior: C must be in [2,%d] (C=%d)", CMAX, C);
-    hipLaunchKernelGGL(discrete_posterior_kernel<true>, dim3(B), dim3(256), 0, (hipStream_t)stream, xt_idx, logits, Qsb,
-                       Qtb, nullptr, 1, out_idx, nullptr, L, C, row_keys, seed, s_dev);
+    hipLaunchKernelGGL((discrete_posterior_kernel<true, false>), dim3(B), dim3(256), 0, (hipStream_t)stream, xt_idx, logits,
+                       Qsb, Qtb, nullptr, 1, out_idx, nullptr, L, C, row_keys, seed, s_dev, nullptr, 1.f);
     return e3d_launch_status("e3d_keyed_discrete_posterior_sample");
 }
 
@@ -775,4 +832,48 @@ extern "C" int e3d_keyed_discrete_known_compose(int32_t* idx, const int32_t* x0_
     hipLaunchKernelGGL(discrete_known_compose_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, idx, x0_idx, mask, Qsb, nullptr, 1, L, C, n, row_keys, seed, s_dev);
     return e3d_launch_status("e3d_keyed_discrete_known_compose");
+}
+
+// ---------------------------------------------------------------- design controls (entry points)
+// inv_temp must be a positive finite number (NaN fails the first comparison)
+static bool good_inv_temp(float inv_temp) { return inv_temp > 0.f && inv_temp <= 3.402823466e38f; }
+
+extern "C" int e3d_discrete_posterior_sample_ctl(const int32_t* xt_idx, const float* logits, const float* bias,
+                                                 float inv_temp, const float* Qsb, const float* Qtb, const float* u,
+                                                 int mode, int32_t* out_idx, float* prob_out, int B, int L, int C,
+                                                 void* stream) {
+    E3D_REQUIRE(xt_idx && logits && Qsb && Qtb && out_idx && B > 0 && L > 0, "discrete_posterior_ctl: bad arguments");
+    E3D_REQUIRE(C >= 1 && C <= CMAX, "discrete_posterior_ctl: C must be in [1,%d] (C=%d)", CMAX, C);
+    E3D_REQUIRE(good_inv_temp(inv_temp), "discrete_posterior_ctl: inv_temp must be positive and finite (inv_temp=%g)",
+                (double)inv_temp);
+    E3D_REQUIRE(mode == 0 || (mode == 1 && u), "discrete_posterior_ctl: mode 1 needs uniforms");
+    hipLaunchKernelGGL((discrete_posterior_kernel<false, true>), dim3(B), dim3(256), 0, (hipStream_t)stream, xt_idx, logits,
+                       Qsb, Qtb, u, mode, out_idx, prob_out, L, C, nullptr, 0ull, nullptr, bias, inv_temp);
+    return e3d_launch_status("e3d_discrete_posterior_sample_ctl");
+}
+
+extern "C" int e3d_keyed_discrete_posterior_sample_ctl(const int32_t* xt_idx, const float* logits, const float* bias,
+                                                       float inv_temp, const float* Qsb, const float* Qtb,
+                                                       const int64_t* row_keys, uint64_t seed, const int64_t* s_dev,
+                                                       int32_t* out_idx, int B, int L, int C, void* stream) {
+    E3D_REQUIRE(xt_idx && logits && Qsb && Qtb && row_keys && s_dev && out_idx && B > 0 && L > 0,
+                "keyed_discrete_posterior_ctl: bad arguments");
+    E3D_REQUIRE(C >= 1 && C <= CMAX, "keyed_discrete_posterior_ctl: C must be in [1,%d] (C=%d)", CMAX, C);
+    E3D_REQUIRE(good_inv_temp(inv_temp), "keyed_discrete_posterior_ctl: inv_temp must be positive and finite (inv_temp=%g)",
+                (double)inv_temp);
+    hipLaunchKernelGGL((discrete_posterior_kernel<true, true>), dim3(B), dim3(256), 0, (hipStream_t)stream, xt_idx, logits,
+                       Qsb, Qtb, nullptr, 1, out_idx, nullptr, L, C, row_keys, seed, s_dev, bias, inv_temp);
+    return e3d_launch_status("e3d_keyed_discrete_posterior_sample_ctl");
+}
+
+extern "C" int e3d_discrete_final_pick(const float* logits, const float* bias, float inv_temp, int32_t* out_idx,
+                                       float* logp, float* entropy, int64_t rows, int C, void* stream) {
+    E3D_REQUIRE(logits && out_idx && rows > 0, "discrete_final_pick: bad arguments");
+    E3D_REQUIRE(rows <= (int64_t)2147483647 * 256,"discrete_final_pick: too many rows (rows=%lld)", (long long)rows);
+    E3D_REQUIRE(C >= 1 && C <= CMAX, "discrete_final_pick: C must be in [1,%d] (C=%d)", CMAX, C);
+    E3D_REQUIRE(good_inv_temp(inv_temp), "discrete_final_pick: inv_temp must be positive and finite (inv_temp=%g)",
+                (double)inv_temp);
+    hipLaunchKernelGGL(discrete_final_pick_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       logits, bias, inv_temp, out_idx, logp, entropy, rows, C);
+    return e3d_launch_status("e3d_discrete_final_pick");
 }

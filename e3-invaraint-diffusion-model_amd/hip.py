@@ -127,6 +127,11 @@ _SIGNATURES = {
     "e3d_keyed_known_compose_wrap": (c_int, [_P, _P, _P, _P, _P, c_int, c_float, _P, c_uint64, c_int64, c_int, _P]),
     "e3d_discrete_known_compose": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "e3d_keyed_discrete_known_compose": (c_int, [_P, _P, _P, _P, _P, c_uint64, _P, c_int, c_int, c_int, _P]),
+    # sequence design controls: the posterior over (logits + bias) * inv_temp, and the last step's pick with its scores
+    "e3d_discrete_posterior_sample_ctl": (c_int, [_P, _P, _P, c_float, _P, _P, _P, c_int, _P, _P, c_int, c_int, c_int, _P]),
+    "e3d_keyed_discrete_posterior_sample_ctl": (c_int, [_P, _P, _P, c_float, _P, _P, _P, c_uint64, _P, _P, c_int, c_int, c_int,
+                                                        _P]),
+    "e3d_discrete_final_pick": (c_int, [_P, _P, c_float, _P, _P, _P, c_int64, c_int, _P]),
     # keyed training and validation draws (ids and epoch read from device memory)
     "e3d_keyed_timesteps": (c_int, [_P, _P, c_uint64, c_int, c_int, _P, c_int, _P]),
     "e3d_keyed_q_sample_wrap": (c_int, [_P, _P, _P, _P, c_int, c_float, _P, _P, c_uint64, _P, _P, c_int, c_int, c_int, _P]),

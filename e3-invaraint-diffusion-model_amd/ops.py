@@ -1104,6 +1104,73 @@ def keyed_discrete_posterior_sample(xt_idx, logits, qsb, qtb, row_keys, seed, s_
     return out
 
 
+# ------------------------------------------------------------------------------------------ sequence design controls
+# The posterior and the last step's pick over the effective logits (logits + bias) * inv_temp (design.DesignControls).
+
+def _chk_ctl(logits, bias, inv_temp, name):
+    """The checks the design-control launches share; returns inv_temp as a Python float (an exact fp32 value)."""
+    _chk(logits, name + ".logits"); _chk(bias, name + ".bias")
+    if logits.dim() != 3 or not logits.is_contiguous():
+        raise ValueError(f"{name}: logits must be contiguous [B, L, C], got {tuple(logits.shape)}")
+    if bias is not None and not (bias.is_contiguous() and bias.shape == logits.shape):
+        raise ValueError(f"{name}: bias must be contiguous and of the logits' shape {tuple(logits.shape)}, got "
+                         f"{tuple(bias.shape)}")
+    inv_temp = float(inv_temp)
+    if not (0.0 < inv_temp < float("inf")):
+        raise ValueError(f"{name}: inv_temp must be positive and finite, got {inv_temp}")
+    return inv_temp
+
+
+def discrete_posterior_sample_ctl(xt_idx, logits, bias, inv_temp, qsb, qtb, u=None, want_prob=False):
+    """discrete_posterior_sample with the softmax over (logits + bias) * inv_temp: bias contiguous [B,L,C] (-inf forbids
+    a class) or None for zero; inv_temp > 0."""
+    _chk(xt_idx, "xt_idx", torch.int32); _chk(qsb, "qsb"); _chk(qtb, "qtb"); _chk(u, "u")
+    inv_temp = _chk_ctl(logits, bias, inv_temp, "discrete_posterior_sample_ctl")
+    B, L, C = logits.shape
+    assert xt_idx.is_contiguous() and qsb.is_contiguous() and qtb.is_contiguous()
+    assert qsb.shape == (B, C, C) and qtb.shape == (B, C, C) and xt_idx.shape == (B, L)
+    out = torch.empty((B, L), device=logits.device, dtype=torch.int32)
+    prob = torch.empty((B, L, C), device=logits.device, dtype=torch.float32) if want_prob else None
+    with _timed("discrete_posterior"):
+        hip.check(hip.lib().e3d_discrete_posterior_sample_ctl(
+            _p(xt_idx), _p(logits), _p(bias), inv_temp, _p(qsb), _p(qtb), _p(u), 0 if u is None else 1, _p(out), _p(prob),
+            B, L, C, _stream()), "e3d_discrete_posterior_sample_ctl")
+    return (out, prob) if want_prob else out
+
+
+def keyed_discrete_posterior_sample_ctl(xt_idx, logits, bias, inv_temp, qsb, qtb, row_keys, seed, s_dev):
+    """keyed_discrete_posterior_sample with the softmax over (logits + bias) * inv_temp; stream 3, the same counters."""
+    _chk(xt_idx, "xt_idx", torch.int32); _chk(qsb, "qsb"); _chk(qtb, "qtb")
+    _chk(s_dev, "s_dev", torch.int64)
+    inv_temp = _chk_ctl(logits, bias, inv_temp, "keyed_discrete_posterior_sample_ctl")
+    B, L, C = logits.shape
+    _chk_keys(row_keys, B * L, "keyed_discrete_posterior_sample_ctl")
+    assert xt_idx.is_contiguous() and qsb.is_contiguous() and qtb.is_contiguous()
+    assert qsb.shape == (B, C, C) and qtb.shape == (B, C, C) and xt_idx.shape == (B, L)
+    out = torch.empty((B, L), device=logits.device, dtype=torch.int32)
+    with _timed("discrete_posterior"):
+        hip.check(hip.lib().e3d_keyed_discrete_posterior_sample_ctl(
+            _p(xt_idx), _p(logits), _p(bias), inv_temp, _p(qsb), _p(qtb), _p(row_keys), keyed.check_seed(seed), _p(s_dev),
+            _p(out), B, L, C, _stream()), "e3d_keyed_discrete_posterior_sample_ctl")
+    return out
+
+
+def discrete_final_pick(logits, bias=None, inv_temp=1.0, want_scores=True):
+    """The last step's pick on logits [B,L,C]: (idx int32 [B,L], logp [B,L], entropy [B,L]) -- the first maximum of
+    (logits + bias) * inv_temp, its log-probability under the softmax of those, and that softmax's entropy; a row whose
+    classes are all forbidden gives index 0 and NaN scores.  ``want_scores`` False: (idx, None, None)."""
+    inv_temp = _chk_ctl(logits, bias, inv_temp, "discrete_final_pick")
+    B, L, C = logits.shape
+    idx = torch.empty((B, L), device=logits.device, dtype=torch.int32)
+    logp = torch.empty((B, L), device=logits.device, dtype=torch.float32) if want_scores else None
+    ent = torch.empty((B, L), device=logits.device, dtype=torch.float32) if want_scores else None
+    if B * L:
+        with _timed("discrete_final_pick"):
+            hip.check(hip.lib().e3d_discrete_final_pick(_p(logits), _p(bias), inv_temp, _p(idx), _p(logp), _p(ent), B * L, C,
+                                                        _stream()), "e3d_discrete_final_pick")
+    return idx, logp, ent
+
+
 # ------------------------------------------------------------------------ partial redesign (replacement conditioning)
 # Held ligand positions are overwritten in place after the update of a step, by launches of their own on its stream.
 

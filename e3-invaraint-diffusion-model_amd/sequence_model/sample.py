@@ -39,6 +39,12 @@ SEED = int(os.environ["E3D_SAMPLE_SEED"], 0) if os.environ.get("E3D_SAMPLE_SEED"
 # Partial redesign (``run(keep=...)``, E3D_SAMPLE_KEEP): ligand positions held at the record's own residues while the rest
 # is sampled, e.g. "0-3,7" (packing.keep_mask).  "" (default): the whole sequence is designed, as before.
 KEEP = os.environ.get("E3D_SAMPLE_KEEP", "")
+# Design controls (``run(temperature=..., omit=..., allow=...)``; design.DesignControls): the sampling temperature of the
+# steps s > 0, residue letters forbidden at every position ("CM"), and the residues allowed at chosen 0-based ligand
+# positions ("3:LIV;7:DE").  Unset (default): the chain runs the launches it always ran.
+TEMPERATURE = float(os.environ["E3D_SAMPLE_TEMPERATURE"]) if os.environ.get("E3D_SAMPLE_TEMPERATURE") else None
+OMIT = os.environ.get("E3D_SAMPLE_OMIT", "")
+ALLOW = os.environ.get("E3D_SAMPLE_ALLOW", "")
 
 CONFIG = {
     "pocket_ext": 0,
@@ -124,7 +130,7 @@ def compute_batched_over0_posterior_distribution(X_t, Q_t, Qsb, Qtb, batch):
 
 
 def sample_p_zs_given_zt_discrete(t, s, noised_data, pred_noise, noise_schedule, transition, diverse,
-                                  is_last_step, u=None, keyed_draw=None, known=None):
+                                  is_last_step, u=None, keyed_draw=None, known=None, controls=None):
     """z_s ~ p(z_s | z_t) for every residue (reference sample.py:141-179).  ``diverse`` draws
     from the categorical (inverse CDF with uniforms ``u`` [B,L], default torch.rand on device),
     otherwise argmax; the last step returns the raw logits, as the reference does.
@@ -133,26 +139,32 @@ def sample_p_zs_given_zt_discrete(t, s, noised_data, pred_noise, noise_schedule,
     ``known`` = (x0 class indices int32 [B,L], uint8 mask [B,L], uniforms [B,L] or None): the held rows of z_s are redrawn
     from q(z_s | x0) -- column x0 of Qsb, ``PeptideDiff.apply_aa_noise``'s law at level ``s`` -- on the class indices,
     before the one-hot (``e3d_discrete_known_compose``; with ``keyed_draw`` its uniforms are keyed stream 11).  The last
-    step returns the logits untouched: ``denoise`` puts the held residues there itself, once per chain."""
+    step returns the logits untouched: ``denoise`` puts the held residues there itself, once per chain.
+    ``controls``: a design.DesignControls whose bias, if any, has ``pred_noise``'s shape (``DesignControls.in_frame``).
+    When active, the x0 prediction inside the posterior is softmax((pred_noise + bias) * inv_temp)
+    (``e3d_discrete_posterior_sample_ctl`` and its keyed form, same draws); None or inactive: the launches above.  The
+    last step returns the raw logits either way: ``denoise`` picks from them under the controls."""
     if is_last_step:
         return pred_noise
     B, L, C = noised_data.shape
     dev = noised_data.device
+    ctl = () if controls is None or not controls.active else (controls.bias, controls.inv_temp)
     qtb = transition.get_Qt_bar(noise_schedule.get_alpha_bar(t_normalized=t), dev).contiguous()
     qsb = transition.get_Qt_bar(noise_schedule.get_alpha_bar(t_normalized=s), dev).contiguous()
     if diverse and keyed_draw is not None:
         if u is not None:
             raise ValueError("sample_p_zs_given_zt_discrete: pass either uniforms or a keyed draw, not both")
-        idx = ops.keyed_discrete_posterior_sample(noised_data.argmax(dim=-1).to(torch.int32).contiguous(),
-                                                  pred_noise.contiguous().float(), qsb, qtb, *keyed_draw)
+        post = ops.keyed_discrete_posterior_sample_ctl if ctl else ops.keyed_discrete_posterior_sample
+        idx = post(noised_data.argmax(dim=-1).to(torch.int32).contiguous(), pred_noise.contiguous().float(), *ctl, qsb, qtb,
+                   *keyed_draw)
         if known is not None:
             ops.keyed_discrete_known_compose(idx, known[0], known[1], qsb, *keyed_draw)
         return F.one_hot(idx.long(), num_classes=C).float()
     if diverse and u is None:
         u = torch.rand(B, L, device=dev)
-    idx = ops.discrete_posterior_sample(noised_data.argmax(dim=-1).to(torch.int32).contiguous(),
-                                        pred_noise.contiguous().float(), qsb, qtb,
-                                        u.contiguous().float() if diverse else None)
+    post = ops.discrete_posterior_sample_ctl if ctl else ops.discrete_posterior_sample
+    idx = post(noised_data.argmax(dim=-1).to(torch.int32).contiguous(), pred_noise.contiguous().float(), *ctl, qsb, qtb,
+               u.contiguous().float() if diverse else None)
     if known is not None:
         ku = None
         if diverse:
@@ -172,14 +184,17 @@ class GraphedDenoiseStep:
     E3D_SAMPLE_GRAPH override."""
 
     def __init__(self, model, x_like, ligand_angles, ligand_mask, receptor_seq, receptor_angles, receptor_mask, noise_schedule,
-                 transition, diverse, T, inject_u=False, layouts=None, row_keys=None, seed=None, known=None):
+                 transition, diverse, T, inject_u=False, layouts=None, row_keys=None, seed=None, known=None, controls=None):
         """``layouts`` = (ligand, pocket) packing.PackedLayout: the step runs ``model.forward_packed`` on packed rows
         (``x_like`` [1, rows, C], packed angles and pocket inputs; the masks are not read).  The layouts' device tables
         are fixed for the chain, so the capture holds them like any other argument.
         ``row_keys`` + ``seed``: the uniforms are the keyed stream of those rows at the integer step ``self.s_idx``.
         ``known`` = (x0 class indices, uint8 mask), both like ``x_like``'s first two dimensions: the held rows are composed
-        inside the body; with ``inject_u`` their uniforms are injected too (``self.known_u``)."""
+        inside the body; with ``inject_u`` their uniforms are injected too (``self.known_u``).
+        ``controls``: a design.DesignControls in the frame of ``x_like``; its bias is copied into a buffer the capture
+        holds, like the state."""
         dev = x_like.device
+        self.controls = None if controls is None or not controls.active else controls.in_frame(torch.clone, dev)
         if (row_keys is None) != (seed is None) or (seed is not None and inject_u):
             raise ValueError("a keyed graph needs row_keys and a seed, and no injected uniforms")
         self.s_idx = torch.zeros((1,), device=dev, dtype=torch.long)
@@ -216,7 +231,7 @@ class GraphedDenoiseStep:
             logits = self.model.forward_packed(self.s, self.x, ang, rseq, rang, *self.layouts)[None]
         return sample_p_zs_given_zt_discrete((self.s + 1) / self.T, self.s / self.T, self.x, logits, self.schedule, self.transition,
                                              self.diverse, is_last_step=False, u=self.u, keyed_draw=self.keyed_draw,
-                                             known=self.known)
+                                             known=self.known, controls=self.controls)
 
     def step(self, s_int, x, u=None, known_u=None):
         """z_t -> z_s for the step index ``s_int`` (> 0); returns the graph's output buffer (overwritten by the next call)."""
@@ -240,7 +255,7 @@ class GraphedDenoiseStep:
 @torch.no_grad()
 def denoise(batch, model: PeptideDiff, noise_schedule, transition, diverse, x_T=None, us=None,
             generated_angles=None, timesteps=None, trim_padding=False, use_graph=None, pack=False, seed=None,
-            item_ids=None, known_mask=None, known_us=None):
+            item_ids=None, known_mask=None, known_us=None, controls=None, details=None):
     """Full reverse chain over CONFIG["timesteps"] steps + recovery metrics (reference
     sample.py:181-229).  ``x_T`` / ``us`` inject the initial one-hot noise and the per-step
     uniforms (parity tests); ``generated_angles`` replaces the dataset's ligand angles
@@ -267,9 +282,28 @@ def denoise(batch, model: PeptideDiff, noise_schedule, transition, diverse, x_T=
     stream 3 -- the free rows' draws -- is untouched.  The recovery rates returned and printed then cover the FREE
     positions only (the held ones recover by construction); an item with no free position reports NaN.  A mask with
     nothing set runs the chain exactly as without the argument.  No resampling loop; sample quality has not been measured
-    here (no trained checkpoint ships with the tree)."""
+    here (no trained checkpoint ships with the tree).
+
+    Design controls -- ``controls``: a design.DesignControls built for this batch (temperature, ``omit``, ``allow``,
+    bias).  None, or a record with nothing set, runs the chain exactly as without the argument.  When active, the bias
+    goes through the frame as the state does, every posterior launch takes the x0 prediction over
+    (logits + bias) / temperature, and the last step picks on the device (``e3d_discrete_final_pick``: the argmax of the
+    biased logits).  The controls shape the x0 prediction; the intermediate states are noisy by construction and may pass
+    through a forbidden class.  The guarantee is on the output: a designed position of the returned sequence never holds
+    a forbidden residue.  The temperature acts on the steps s > 0 only.  Held positions (``known_mask``) win over the
+    controls.  Under a ``seed`` an item's design depends on (seed, item id, its own controls) alone.
+    ``details``: a dict, filled with ``"logp"`` and ``"entropy"`` [B, L] (the log-probability of the picked residue and
+    the entropy of the last step's distribution, padded frame, NaN off the ligand) and ``"score"`` [B], the mean of
+    -logp over the designed positions (valid and not held; NaN when there are none), all on the CPU; it takes the
+    device pick even without controls.  The four return values keep their meaning."""
     T = CONFIG["timesteps"] if timesteps is None else timesteps
     B, max_len, C = batch["ligand_seq"].shape
+    if details is not None and not isinstance(details, dict):
+        raise ValueError(f"denoise: details must be a dict to fill, got {type(details).__name__}")
+    if controls is not None and not controls.active:
+        controls = None
+    if controls is not None and controls.bias is not None and tuple(controls.bias.shape) != (B, max_len, C):
+        raise ValueError(f"denoise: the controls were built for {tuple(controls.bias.shape)}, the batch is {(B, max_len, C)}")
     if known_mask is None and known_us is not None:
         raise ValueError("denoise: known_us are the uniforms of the held positions; pass known_mask")
     if known_mask is not None:
@@ -316,6 +350,8 @@ def denoise(batch, model: PeptideDiff, noise_schedule, transition, diverse, x_T=
     rseq, rang = frame.pocket(receptor_seq.float()), frame.pocket(receptor_angles.float())
     lmask, rmask = (None, None) if layouts is not None else (frame.ligand(ligand_mask), frame.pocket(receptor_mask))
     row_keys = None if seed is None else frame.row_keys(ids, dev)
+    if controls is not None:      # the bias into the frame like the state
+        controls = controls.in_frame(state, dev)
     held = known = None
     if known_mask is not None:
         held = known_mask.to(dev) & (ligand_mask != 0)
@@ -329,7 +365,8 @@ def denoise(batch, model: PeptideDiff, noise_schedule, transition, diverse, x_T=
         known_us = None
     graphed = packing.capture_graph(
         lambda: GraphedDenoiseStep(model, x, ang, lmask, rseq, rang, rmask, noise_schedule, transition, diverse, T,
-                                   inject_u=us is not None, layouts=layouts, row_keys=row_keys, seed=seed, known=known),
+                                   inject_u=us is not None, layouts=layouts, row_keys=row_keys, seed=seed, known=known,
+                                   controls=controls),
         frame.rows, T, use_graph, "the sequence reverse step")
     for n, s_int in enumerate(reversed(range(T))):
         u = None if us is None else us[n]
@@ -345,13 +382,24 @@ def denoise(batch, model: PeptideDiff, noise_schedule, transition, diverse, x_T=
         x = sample_p_zs_given_zt_discrete((s_array + 1) / T, s_array / T, x, logits, noise_schedule, transition,
                                           diverse, is_last_step=s_int == 0, u=u,
                                           keyed_draw=_keyed_draw(row_keys, seed, s_int, dev),
-                                          known=None if known is None else known + (ku,))
+                                          known=None if known is None else known + (ku,), controls=controls)
+    logp = entropy = None
+    if controls is not None or details is not None:      # x holds the last step's logits: pick on the device
+        idx, logp, entropy = ops.discrete_final_pick(x.contiguous().float(), None if controls is None else controls.bias,
+                                                     1.0 if controls is None else controls.inv_temp,
+                                                     want_scores=details is not None)
+        x = F.one_hot(idx.long(), num_classes=C).float()
     x = frame.restore(x if layouts is None else x[0])
     if held is not None:      # the last step returned logits: the held rows are the true residues, once per chain
         x = torch.where(held[..., None], ligand_seq.float(), x)
     pred_idx, true_idx = x.argmax(dim=-1).cpu(), ligand_seq.argmax(dim=-1).cpu()
     mask = ligand_mask.bool().cpu()
     free = mask if held is None else mask & ~held.cpu()      # recovery over the positions that were designed
+    if details is not None:
+        nan = torch.full((B, max_len), float("nan"))
+        for key, v in (("logp", logp), ("entropy", entropy)):
+            details[key] = torch.where(mask, frame.restore(v if layouts is None else v[0]).cpu(), nan)
+        details["score"] = torch.where(free, -details["logp"], torch.zeros(())).sum(dim=1) / free.sum(dim=1)
     ids, true_sequences, pred_sequences, recovery_rates = [], [], [], []
     for i in range(B):
         m = mask[i]
@@ -380,10 +428,29 @@ def batch_keep_mask(keep, batch, first_index):
     return torch.stack([packing.keep_mask(keep, first_index + b, L, lengths[b]) for b in range(B)])
 
 
-def run(transition, diverse=True, seed=None, keep=None):
+def batch_controls(batch, first_index, temperature=None, omit=None, allow=None):
+    """The design.DesignControls of a loader batch whose first item has dataset index ``first_index``; an argument left
+    None takes the module's default (``TEMPERATURE`` / ``OMIT`` / ``ALLOW``, the E3D_SAMPLE_* variables).  None when
+    nothing is set, so that the chain runs the launches it always ran."""
+    temperature = TEMPERATURE if temperature is None else temperature
+    omit = OMIT if omit is None else omit
+    allow = ALLOW if allow is None else allow
+    if temperature is None and not omit and not (callable(allow) or allow):
+        return None
+    from ..design import DesignControls
+    controls = DesignControls.build(batch, temperature=1.0 if temperature is None else temperature, omit=omit,
+                                    allow=allow if (callable(allow) or allow) else None, first_index=first_index)
+    return controls if controls.active else None
+
+
+def run(transition, diverse=True, seed=None, keep=None, temperature=None, omit=None, allow=None, scores=False):
     """Sample every test ligand.  ``seed`` (default ``SEED``, E3D_SAMPLE_SEED): keyed draws by dataset index.
     ``keep`` (default ``KEEP``, E3D_SAMPLE_KEEP): partial redesign -- a position list such as "0-3,7" or a callable
-    dataset index -> bool [L] (packing.keep_mask); those residues are held at the record's own ``ligand_seq``."""
+    dataset index -> bool [L] (packing.keep_mask); those residues are held at the record's own ``ligand_seq``.
+    Design controls (design.DesignControls; ``denoise``): ``temperature`` (E3D_SAMPLE_TEMPERATURE), ``omit`` -- residue
+    letters forbidden everywhere (E3D_SAMPLE_OMIT) -- and ``allow`` -- "3:LIV;7:DE", a dict or a callable dataset index ->
+    dict (E3D_SAMPLE_ALLOW).  ``scores``: the table gets a ``score`` column, the mean of -log p of the picked residues
+    over a ligand's designed positions (lower: the model likes the design better); without it the table is as before."""
     import pandas as pd
     seed = SEED if seed is None else seed
     keep = KEEP if keep is None else keep
@@ -391,15 +458,27 @@ def run(transition, diverse=True, seed=None, keep=None):
     model = get_model(len(loader))
     schedule = PredefinedNoiseScheduleDiscrete(CONFIG["noise_schedule"], CONFIG["timesteps"]).to(DEVICE)
     cols = ([], [], [], [])
+    score = []
     for idx, batch in enumerate(loader):
         print(f"Generating Batch {idx}")
         n = batch["ligand_seq"].shape[0]
-        ids = None if seed is None else list(range(idx * CONFIG["batch_size"], idx * CONFIG["batch_size"] + n))
-        known_mask = batch_keep_mask(keep, batch, idx * CONFIG["batch_size"])
+        first = idx * CONFIG["batch_size"]
+        ids = None if seed is None else list(range(first, first + n))
+        known_mask = batch_keep_mask(keep, batch, first)
+        design = {}
+        controls = batch_controls(batch, first, temperature, omit, allow)
+        if controls is not None:
+            design["controls"] = controls
+        if scores:
+            design["details"] = {}
         for acc, part in zip(cols, denoise(batch, model, schedule, transition, diverse, pack=PACK, seed=seed,
-                                           item_ids=ids, known_mask=known_mask)):
+                                           item_ids=ids, known_mask=known_mask, **design)):
             acc.extend(part)
+        if scores:
+            score.extend(design["details"]["score"].tolist())
     res = pd.DataFrame(zip(*cols), columns=["structure_ids", "true_sequence", "predict_sequence", "recovery_rate"])
+    if scores:
+        res["score"] = score
     res.to_pickle(OUTPUT_PATH)
     print(res)
     return res

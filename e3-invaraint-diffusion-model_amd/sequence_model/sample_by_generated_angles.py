@@ -56,8 +56,9 @@ def angles_from_trajectory(traj, ligand_mask):
 
 def denoise(batch, generated_angles, model, noise_schedule, transition, diverse, **kw):
     """reference lines 196-243: sample.denoise with the ligand angles replaced.  ``seed`` / ``item_ids`` (and every
-    other keyword of sample.denoise, ``pack`` and the partial redesign's ``known_mask`` among them) pass through: a seeded
-    joint run keys both stages by the same item ids, and holds the same positions in both."""
+    other keyword of sample.denoise, ``pack``, the partial redesign's ``known_mask`` and the design controls' ``controls`` /
+    ``details`` among them) pass through: a seeded joint run keys both stages by the same item ids, and holds the same
+    positions in both."""
     return _denoise(batch, model, noise_schedule, transition, diverse, generated_angles=generated_angles, **kw)
 
 
@@ -74,8 +75,9 @@ if __name__ == "__main__":
     for idx, batch in enumerate(loader):
         print(f"Generating Batch {idx}")
         known_mask = _sample.batch_keep_mask(_sample.KEEP, batch, idx * CONFIG["batch_size"])     # E3D_SAMPLE_KEEP
+        controls = _sample.batch_controls(batch, idx * CONFIG["batch_size"])    # E3D_SAMPLE_TEMPERATURE / _OMIT / _ALLOW
         for acc, part in zip(cols, denoise(batch, generated_angles[idx], model, schedule, transition, True,
-                                           known_mask=known_mask)):
+                                           known_mask=known_mask, **({} if controls is None else {"controls": controls}))):
             acc.extend(part)
     res = pd.DataFrame(zip(*cols), columns=["structure_ids", "true_sequence", "predict_sequence", "recovery_rate"])
     res.to_pickle(OUTPUT_PATH)

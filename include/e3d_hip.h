@@ -358,6 +358,41 @@ int e3d_keyed_discrete_known_compose(int32_t* idx, const int32_t* x0_idx, const 
                                      const int64_t* row_keys, uint64_t seed, const int64_t* s_dev, int B, int L,
                                      int C, void* stream);
 
+/* ------------------------------------------------------------------ sequence design controls
+ * Temperature, per-position residue bias and design scores of the sequence chain.  The controls shape the model's x0
+ * prediction: wherever the posterior kernel takes softmax(logits[n]) it takes softmax(z[n]) instead, with the
+ * EFFECTIVE LOGITS
+ *   z[n,c] = (logits[n,c] + bias[n,c]) * inv_temp        (fp32: one add, then one multiply, never fused)
+ * bias float [B*L, C] or NULL for zero; bias == -inf forbids class c at row n; inv_temp = 1 / temperature > 0, by
+ * value.  A forbidden class has probability exactly 0 in the x0 prediction, so it contributes nothing to the posterior.
+ * The intermediate states z_s are noisy by construction (the forward law Qsb spreads every class) and may pass through
+ * a forbidden class; the guarantee is on the chain's OUTPUT, which the final-pick entry point below takes as the argmax
+ * of z: it never holds a forbidden class.  The temperature therefore acts on the steps s > 0 only.  No new random
+ * stream: the keyed form draws stream 3 with the counters of the entry point it extends.  These entry points are
+ * additions to ABI v5; the two posterior entry points above share the kernel body and keep their results bit for bit. */
+
+/* The posterior of the reverse step over the effective logits; every other argument, the arithmetic and the launch
+ * shape are those of the entry point without controls.  A row whose classes are all forbidden takes an all-zero x0
+ * prediction and hence the zero-total rule (1e-5 per class, i.e. 1 / C after the normalisation): never NaN.
+ * C in [1, 32]; inv_temp must be positive and finite. */
+int e3d_discrete_posterior_sample_ctl(const int32_t* xt_idx, const float* logits, const float* bias, float inv_temp,
+                                      const float* Qsb, const float* Qtb, const float* u, int mode, int32_t* out_idx,
+                                      float* prob_out, int B, int L, int C, void* stream);
+
+/* The same in mode 1 with the uniforms of the keyed entry point: stream 3 at step s_dev[0] with key row_keys[n], the
+ * same counters; rows of no item draw u = 0. */
+int e3d_keyed_discrete_posterior_sample_ctl(const int32_t* xt_idx, const float* logits, const float* bias,
+                                            float inv_temp, const float* Qsb, const float* Qtb,
+                                            const int64_t* row_keys, uint64_t seed, const int64_t* s_dev,
+                                            int32_t* out_idx, int B, int L, int C, void* stream);
+
+/* The last step's pick, one thread per row of logits [rows, C]:
+ *   out_idx[n] = the first maximum of z[n];   logp[n] = log_softmax(z[n])[out_idx[n]];
+ *   entropy[n] = -sum_c p log p of p = softmax(z[n]), a forbidden class counting 0 (0 log 0 = 0).
+ * logp and entropy may each be NULL.  A row whose classes are all forbidden: out_idx = 0, logp = entropy = NaN. */
+int e3d_discrete_final_pick(const float* logits, const float* bias, float inv_temp, int32_t* out_idx, float* logp,
+                            float* entropy, int64_t rows, int C, void* stream);
+
 /* ------------------------------------------------------------------ keyed training and validation draws
  * The same generator and counter layout with the EPOCH in the step field (training epochs 0 .. 65534; 65535 is the
  * validation value) and streams 4 structure timestep, 5 structure forward noise, 6 sequence timestep, 7 sequence
