@@ -3,6 +3,7 @@
 // The keyed forms (seeded chains) generate their draws in-register from (seed, row key, step): e3d_philox.h.
 #include "e3d_common.h"
 #include "e3d_philox.h"
+#include <initializer_list>
 
 namespace {
 
@@ -23,40 +24,89 @@ __device__ __forceinline__ uint32_t keyed_epoch(const int64_t* __restrict__ epoc
     return (uint32_t)epoch_dev[0] & 0xFFFFu;
 }
 
+// ---------------------------------------------------------------- the draw source of the continuous updates
+// The DDPM update, the strided update and the known compose each have one body; where the four N(0,1) draws of float4
+// group i come from is the template parameter KEYED and this record, both chosen by the entry point:
+//   buffer (KEYED false): a load from ``noise`` (may be null: the kernel then asks for no draws)
+//   keyed  (KEYED true):  one Philox call on (seed, row key, stream, step, block) over a key table of rows x nb groups --
+//                         one thread per (row, block j of 4 features) gets the 4 normals of features 4j .. 4j+3
+// Same arithmetic per element either way, so a keyed launch equals the buffer form fed with the keyed normals.
+struct Draws {
+    const float* noise;
+    const int64_t* row_keys;
+    uint64_t seed;
+    int stream, nb;
+};
+
+__device__ __forceinline__ bool keyed_row(const int64_t* __restrict__ row_keys, int64_t row, uint64_t& item,
+                                          uint32_t& pos) {
+    const int64_t p = row_keys[2 * row + 1];
+    item = (uint64_t)row_keys[2 * row];
+    pos = (uint32_t)p;
+    return p >= 0;
+}
+
+// Does float4 group i belong to a row of an item (a buffer: always)?  ``want``: also fill z with the group's draws at ``step``.
+template <bool KEYED>
+__device__ __forceinline__ bool draws4(const Draws d, uint32_t step, int64_t i, bool want, float (&z)[4]) {
+    if (!KEYED) {
+        if (want) {
+            const f32x4 v = reinterpret_cast<const f32x4*>(d.noise)[i];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) z[j] = v[j];
+        }
+        return true;
+    }
+    const int64_t row = i / d.nb;
+    uint64_t item;
+    uint32_t pos;
+    if (!keyed_row(d.row_keys, row, item, pos)) return false;
+    if (want) e3d_keyed_normal4(e3d_keyed_words(d.seed, item, d.stream, step, pos, (uint32_t)(i - row * d.nb)), z);
+    return true;
+}
+
+// ---------------------------------------------------------------- DDPM ancestral update
+struct DdpmCoef { float sra, beta, s1m, sigma; };
+
+// ``z``: the element's draw, or null for the mean alone.  Taken by address so that a caller's load of the draw and this
+// add share one branch: the compiler's choice between a fused multiply-add and two rounded products for the noise term
+// (the n % 4 tail gets the former, the float4 loop the latter) hangs on that, and seeded results on the choice.
+__device__ __forceinline__ float ddpm_elem(const DdpmCoef c, float x, float e, const float* z, int wrap) {
+    float mean = c.sra * (x - c.beta * e / c.s1m);
+    if (z) mean = mean + c.sigma * *z;
+    return wrap ? wrap_pi(mean) : mean;
+}
+
+// ``out`` may be ``x``: every element is read before it is written, by the thread that writes it.
+// KEYED: always the table form, the draws from stream d.stream at step t_dev[0]; a row of no item gets the mean, and at
+// sigma == 0 there is no Philox call and the key table is not read.  A keyed launch has n == 4 * n4: no tail.
+template <bool KEYED>
 __global__ __launch_bounds__(256) void ddpm_step_wrap_kernel(
-    const float* __restrict__ x, const float* __restrict__ eps_hat, const float* __restrict__ noise,
-    float sra, float beta, float s1m, float sigma, const float* __restrict__ coef_table,
-    const int64_t* __restrict__ t_dev, int wrap, float* __restrict__ out, int64_t n4, int64_t n) {
-    if (coef_table) {   // graph-replayable form: the step index lives on the device, the coefficients in a [T,4] table
+    const float* x, const float* __restrict__ eps_hat, const Draws d, DdpmCoef c, const float* __restrict__ coef_table,
+    const int64_t* __restrict__ t_dev, int wrap, float* out, int64_t n4, int64_t n) {
+    bool noisy = KEYED || d.noise != nullptr;
+    uint32_t step = 0;
+    if (KEYED || coef_table) {   // graph-replayable form: the step index lives on the device, the coefficients in a [T,4] table
         const int64_t t = t_dev[0];
-        sra = coef_table[4 * t];
-        beta = coef_table[4 * t + 1];
-        s1m = coef_table[4 * t + 2];
-        sigma = coef_table[4 * t + 3];
-        if (sigma == 0.f) noise = nullptr;   // t == 0: the mean, exactly as the scalar form
+        c = DdpmCoef{coef_table[4 * t], coef_table[4 * t + 1], coef_table[4 * t + 2], coef_table[4 * t + 3]};
+        step = (uint32_t)t;
+        if (c.sigma == 0.f) noisy = false;   // t == 0: the mean, exactly as the scalar form
     }
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
         const f32x4 xv = reinterpret_cast<const f32x4*>(x)[i];
         const f32x4 ev = reinterpret_cast<const f32x4*>(eps_hat)[i];
-        f32x4 nv = {0.f, 0.f, 0.f, 0.f};
-        if (noise) nv = reinterpret_cast<const f32x4*>(noise)[i];
+        float z[4] = {0.f, 0.f, 0.f, 0.f};
+        const bool has = noisy && draws4<KEYED>(d, step, i, true, z);
         f32x4 o;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float mean = sra * (xv[j] - beta * ev[j] / s1m);
-            if (noise) mean = mean + sigma * nv[j];
-            o[j] = wrap ? wrap_pi(mean) : mean;
-        }
+        for (int j = 0; j < 4; ++j) o[j] = ddpm_elem(c, xv[j], ev[j], has ? &z[j] : nullptr, wrap);
         reinterpret_cast<f32x4*>(out)[i] = o;
     }
+    if (KEYED) return;
     // tail (n % 4)
-    const int64_t t = n4 * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < n) {
-        float mean = sra * (x[t] - beta * eps_hat[t] / s1m);
-        if (noise) mean = mean + sigma * noise[t];
-        out[t] = wrap ? wrap_pi(mean) : mean;
-    }
+    const int64_t r = n4 * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < n) out[r] = ddpm_elem(c, x[r], eps_hat[r], noisy ? d.noise + r : nullptr, wrap);
 }
 
 // ---------------------------------------------------------------- strided (DDIM / respaced-ancestral) update
@@ -64,7 +114,7 @@ __global__ __launch_bounds__(256) void ddpm_step_wrap_kernel(
 // wrap of the x0 estimate is nonlinear, so the update cannot be collapsed into one linear expression:
 //   x0 = (x - s1m e) rsa;  wrap_x0: x0 = wrap_pi(x0);  mean = a_s x0 + c_dir e;  out = mean (+ sigma z);  wrap: wrap_pi(out)
 // Row t of the [T,8] table (structure_model/utils.py, StridedTables) = (s1m, rsa, a_s, c_dir, sigma, 0, 0, 0).  The
-// multiply-adds are written as fmaf, so both kernels (and the tail) round alike whatever the compiler contracts.
+// multiply-adds are written as fmaf, so both instantiations (and the tail) round alike whatever the compiler contracts.
 struct StridedCoef { float s1m, rsa, a_s, c_dir, sigma; };
 
 __device__ __forceinline__ StridedCoef strided_row(const float* __restrict__ coef_table, int64_t t) {
@@ -91,28 +141,32 @@ __device__ __forceinline__ void strided_fill_nan(float* __restrict__ out, int64_
 }
 
 // ``out`` may be ``x``: every element is read before it is written, by the thread that writes it.
+// KEYED: the draws come from the ancestral keyed launch's stream at step t_dev[0], so a pocket's draw at timestep t is
+// the same under either update; a row of no item gets no noise term.  A keyed launch has n == 4 * n4: no tail.
+template <bool KEYED>
 __global__ __launch_bounds__(256) void strided_step_wrap_kernel(
-    const float* x, const float* __restrict__ eps_hat, const float* __restrict__ noise,
-    const float* __restrict__ coef_table, const int64_t* __restrict__ t_dev, int T, int wrap, int wrap_x0, float* out,
-    int64_t n4, int64_t n) {
+    const float* x, const float* __restrict__ eps_hat, const Draws d, const float* __restrict__ coef_table,
+    const int64_t* __restrict__ t_dev, int T, int wrap, int wrap_x0, float* out, int64_t n4, int64_t n) {
     const int64_t t = t_dev[0];
     if (t < 0 || t >= T) { strided_fill_nan(out, n4, n); return; }
     const StridedCoef c = strided_row(coef_table, t);
-    const bool noisy = noise != nullptr && c.sigma != 0.f;   // sigma == 0 (eta = 0, or the last step): nothing is read through noise
+    // sigma == 0 (eta = 0, or the last step): nothing is read through noise, no Philox call, the key table is not read
+    const bool noisy = (KEYED || d.noise != nullptr) && c.sigma != 0.f;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
         const f32x4 xv = reinterpret_cast<const f32x4*>(x)[i];
         const f32x4 ev = reinterpret_cast<const f32x4*>(eps_hat)[i];
-        f32x4 nv = {0.f, 0.f, 0.f, 0.f};
-        if (noisy) nv = reinterpret_cast<const f32x4*>(noise)[i];
+        float z[4] = {0.f, 0.f, 0.f, 0.f};
+        const bool has = noisy && draws4<KEYED>(d, (uint32_t)t, i, true, z);
         f32x4 o;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = strided_elem(c, xv[j], ev[j], nv[j], noisy, wrap, wrap_x0);
+        for (int j = 0; j < 4; ++j) o[j] = strided_elem(c, xv[j], ev[j], z[j], has, wrap, wrap_x0);
         reinterpret_cast<f32x4*>(out)[i] = o;
     }
+    if (KEYED) return;
     // tail (n % 4)
     const int64_t r = n4 * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r < n) out[r] = strided_elem(c, x[r], eps_hat[r], noisy ? noise[r] : 0.f, noisy, wrap, wrap_x0);
+    if (r < n) out[r] = strided_elem(c, x[r], eps_hat[r], noisy ? d.noise[r] : 0.f, noisy, wrap, wrap_x0);
 }
 
 // q(x_t | x_0) of one element: wrap(a_t x0 + s_t noise); shared by the buffer form and the keyed form
@@ -334,76 +388,6 @@ __global__ __launch_bounds__(256) void discrete_q_sample_kernel(
 }
 
 // ---------------------------------------------------------------- keyed (seeded) draws
-// One thread per (row, block j of 4 features): one Philox call gives the 4 normals of features 4j .. 4j+3.
-__device__ __forceinline__ bool keyed_row(const int64_t* __restrict__ row_keys, int64_t row, uint64_t& item,
-                                          uint32_t& pos) {
-    const int64_t p = row_keys[2 * row + 1];
-    item = (uint64_t)row_keys[2 * row];
-    pos = (uint32_t)p;
-    return p >= 0;
-}
-
-// ddpm_step_wrap_kernel's table form with the noise generated from stream 1 at step t_dev[0]; same arithmetic per
-// element, so the result equals the table form fed with these normals (rows of no item: no noise term).
-__global__ __launch_bounds__(256) void keyed_ddpm_step_wrap_kernel(
-    const float* __restrict__ x, const float* __restrict__ eps_hat, const float* __restrict__ coef_table,
-    const int64_t* __restrict__ t_dev, const int64_t* __restrict__ row_keys, uint64_t seed, int wrap,
-    float* __restrict__ out, int64_t n4, int nb) {
-    const int64_t t = t_dev[0];
-    const float sra = coef_table[4 * t], beta = coef_table[4 * t + 1], s1m = coef_table[4 * t + 2],
-                sigma = coef_table[4 * t + 3];
-    const bool noisy = sigma != 0.f;   // t == 0: the mean, exactly as the table form
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-        const f32x4 xv = reinterpret_cast<const f32x4*>(x)[i];
-        const f32x4 ev = reinterpret_cast<const f32x4*>(eps_hat)[i];
-        const int64_t row = i / nb;
-        uint64_t item;
-        uint32_t pos;
-        const bool has = noisy && keyed_row(row_keys, row, item, pos);
-        float nv[4] = {0.f, 0.f, 0.f, 0.f};
-        if (has) e3d_keyed_normal4(e3d_keyed_words(seed, item, E3D_STREAM_STRUCT_STEP, (uint32_t)t, pos,
-                                                   (uint32_t)(i - row * nb)), nv);
-        f32x4 o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float mean = sra * (xv[j] - beta * ev[j] / s1m);
-            if (has) mean = mean + sigma * nv[j];
-            o[j] = wrap ? wrap_pi(mean) : mean;
-        }
-        reinterpret_cast<f32x4*>(out)[i] = o;
-    }
-}
-
-// strided_step_wrap_kernel with the noise generated from stream 1 at step t_dev[0] -- the ancestral keyed kernel's
-// stream, so a pocket's draw at timestep t is the same under either update.  Same arithmetic per element: the result
-// equals the unkeyed form fed with these normals (rows of no item: no noise term; sigma == 0: no Philox call).
-__global__ __launch_bounds__(256) void keyed_strided_step_wrap_kernel(
-    const float* x, const float* __restrict__ eps_hat, const float* __restrict__ coef_table,
-    const int64_t* __restrict__ t_dev, int T, const int64_t* __restrict__ row_keys, uint64_t seed, int wrap, int wrap_x0,
-    float* out, int64_t n4, int nb) {
-    const int64_t t = t_dev[0];
-    if (t < 0 || t >= T) { strided_fill_nan(out, n4, n4 * 4); return; }
-    const StridedCoef c = strided_row(coef_table, t);
-    const bool noisy = c.sigma != 0.f;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-        const f32x4 xv = reinterpret_cast<const f32x4*>(x)[i];
-        const f32x4 ev = reinterpret_cast<const f32x4*>(eps_hat)[i];
-        const int64_t row = i / nb;
-        uint64_t item;
-        uint32_t pos;
-        const bool has = noisy && keyed_row(row_keys, row, item, pos);
-        float nv[4] = {0.f, 0.f, 0.f, 0.f};
-        if (has) e3d_keyed_normal4(e3d_keyed_words(seed, item, E3D_STREAM_STRUCT_STEP, (uint32_t)t, pos,
-                                                   (uint32_t)(i - row * nb)), nv);
-        f32x4 o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = strided_elem(c, xv[j], ev[j], nv[j], has, wrap, wrap_x0);
-        reinterpret_cast<f32x4*>(out)[i] = o;
-    }
-}
-
 // Raw keyed draws of one (stream, step) over a key table (rows of no item: zeros):
 //   kind 0: wrap ? wrap_pi(scale * z) : z, z the normals  -> float [rows, 4 nb]   (wrap + stream 0: keyed x_T)
 //   kind 1: uniforms from word 0 of block 0                -> float [rows]
@@ -518,54 +502,32 @@ __device__ __forceinline__ void known_store4(float* x, int64_t i, uint32_t m4, c
         if ((m4 >> (8 * j)) & 0xFFu) x[4 * i + j] = v[j];
 }
 
+// KEYED: z = the normals of (seed, item, stream d.stream, step t_dev[0], position, block), laid out as the update's
+// stream.  Rows of no item are left alone at every level; a float4 group with no held element makes no Philox call.  A
+// keyed launch has n == 4 * n4: no tail.
+template <bool KEYED>
 __global__ __launch_bounds__(256) void known_compose_wrap_kernel(
-    float* x, const float* __restrict__ x0, const uint8_t* __restrict__ mask, const float* __restrict__ noise,
+    float* x, const float* __restrict__ x0, const uint8_t* __restrict__ mask, const Draws d,
     const float* __restrict__ level_table, const int64_t* __restrict__ t_dev, int T, float scale, int64_t n4, int64_t n) {
-    const KnownLevel lv = known_level(level_table, t_dev, T, noise != nullptr);
+    const KnownLevel lv = known_level(level_table, t_dev, T, KEYED || d.noise != nullptr);
     const bool noisy = lv.kind == 1;
+    const uint32_t step = (uint32_t)t_dev[0];
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
         const uint32_t m4 = known_mask4(mask, i);
         if (m4 == 0u) continue;
+        float z[4] = {0.f, 0.f, 0.f, 0.f};
+        if (!draws4<KEYED>(d, step, i, noisy, z)) continue;
         const f32x4 kv = reinterpret_cast<const f32x4*>(x0)[i];
-        f32x4 nv = {0.f, 0.f, 0.f, 0.f};
-        if (noisy) nv = reinterpret_cast<const f32x4*>(noise)[i];
         f32x4 o;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = known_elem(lv, scale, kv[j], nv[j]);
+        for (int j = 0; j < 4; ++j) o[j] = known_elem(lv, scale, kv[j], z[j]);
         known_store4(x, i, m4, o);
     }
+    if (KEYED) return;
     // tail (n % 4)
     const int64_t r = n4 * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r < n && mask[r]) x[r] = known_elem(lv, scale, x0[r], noisy ? noise[r] : 0.f);
-}
-
-// The draws generated in-register: z = the normals of (seed, item, stream 10, step t_dev[0], position, block), laid out
-// as stream 1.  Same arithmetic per element, so the result equals the buffer form fed with these normals.  Rows of no
-// item are left alone; a float4 group with no held element makes no Philox call.
-__global__ __launch_bounds__(256) void keyed_known_compose_wrap_kernel(
-    float* x, const float* __restrict__ x0, const uint8_t* __restrict__ mask, const float* __restrict__ level_table,
-    const int64_t* __restrict__ t_dev, int T, float scale, const int64_t* __restrict__ row_keys, uint64_t seed, int64_t n4,
-    int nb) {
-    const KnownLevel lv = known_level(level_table, t_dev, T, true);
-    const uint32_t t = (uint32_t)t_dev[0];
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-        const uint32_t m4 = known_mask4(mask, i);
-        if (m4 == 0u) continue;
-        const int64_t row = i / nb;
-        uint64_t item;
-        uint32_t pos;
-        if (!keyed_row(row_keys, row, item, pos)) continue;
-        float nv[4] = {0.f, 0.f, 0.f, 0.f};
-        if (lv.kind == 1) e3d_keyed_normal4(e3d_keyed_words(seed, item, E3D_KNOWN_STREAM_STRUCT, t, pos,
-                                                            (uint32_t)(i - row * nb)), nv);
-        const f32x4 kv = reinterpret_cast<const f32x4*>(x0)[i];
-        f32x4 o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = known_elem(lv, scale, kv[j], nv[j]);
-        known_store4(x, i, m4, o);
-    }
+    if (r < n && mask[r]) x[r] = known_elem(lv, scale, x0[r], noisy ? d.noise[r] : 0.f);
 }
 
 // Sequence chain: the class index of a held row (mask != 0, x0 >= 0) is redrawn in place from column x0 of Qsb, the
@@ -602,18 +564,38 @@ __global__ __launch_bounds__(256) void discrete_known_compose_kernel(
 
 }  // namespace
 
+// ---------------------------------------------------------------- what the entry points share
+// 256-thread blocks: one thread per item, or -- a grid-stride sweep over n items -- at least one block and at most 2048
+static unsigned row_blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
+static unsigned sweep_blocks(int64_t n) { return n <= 0 ? 1u : (n > 2048 * 256 ? 2048u : row_blocks(n)); }
+
+static bool aligned16(std::initializer_list<const void*> ptrs) {   // a null pointer (an absent operand) passes
+    for (const void* p : ptrs)
+        if ((uintptr_t)p % 16) return false;
+    return true;
+}
+#define REQUIRE_ALIGNED16(name, ...) E3D_REQUIRE(aligned16({__VA_ARGS__}), name ": pointers must be 16B aligned")
+
+// A keyed row is at most 256 blocks of 4 features: the block is a byte of the Philox counter (e3d_philox.h)
+static bool keyed_width(int F) { return F > 0 && F % 4 == 0 && F / 4 <= 256; }
+#define REQUIRE_KEYED_WIDTH(name, F) \
+    E3D_REQUIRE(keyed_width(F), name ": F must be a multiple of 4 in [4, 1024] (F=%d)", F)
+// ... and the step is 16 bits of it: a table read by the step index has at most 65536 rows
+#define REQUIRE_KEYED_STEPS(name, T) E3D_REQUIRE(T <= 65536, name ": keyed streams hold steps up to 65535 (T=%d)", T)
+
+static Draws buffer_draws(const float* noise) { return Draws{noise, nullptr, 0ull, 0, 1}; }
+static Draws keyed_draws_of(const int64_t* row_keys, uint64_t seed, int stream, int F) {
+    return Draws{nullptr, row_keys, seed, stream, F / 4};
+}
+
 extern "C" int e3d_ddpm_step_wrap(const float* x, const float* eps_hat, const float* noise,
                                   float sqrt_recip_alpha, float beta, float sqrt_one_minus_ab,
                                   float sigma, int wrap, float* out, int64_t n, void* stream) {
     E3D_REQUIRE(x && eps_hat && out && n > 0, "ddpm_step_wrap: bad arguments");
-    E3D_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)eps_hat % 16) == 0 && ((uintptr_t)out % 16) == 0 &&
-                    ((uintptr_t)noise % 16) == 0, "ddpm_step_wrap: pointers must be 16B aligned");
-    const int64_t n4 = n / 4;
-    int64_t blocks = (n4 + 255) / 256;
-    blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
-    hipLaunchKernelGGL(ddpm_step_wrap_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, eps_hat,
-                       sigma != 0.f ? noise : nullptr, sqrt_recip_alpha, beta, sqrt_one_minus_ab, sigma, nullptr, nullptr, wrap,
-                       out, n4, n);
+    REQUIRE_ALIGNED16("ddpm_step_wrap", x, eps_hat, out, noise);
+    hipLaunchKernelGGL(ddpm_step_wrap_kernel<false>, dim3(sweep_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, x, eps_hat,
+                       buffer_draws(sigma != 0.f ? noise : nullptr), DdpmCoef{sqrt_recip_alpha, beta, sqrt_one_minus_ab, sigma},
+                       nullptr, nullptr, wrap, out, n / 4, n);
     return e3d_launch_status("e3d_ddpm_step_wrap");
 }
 
@@ -621,13 +603,9 @@ extern "C" int e3d_ddpm_step_wrap_table(const float* x, const float* eps_hat, co
                                         const float* coef_table, const int64_t* t_dev, int wrap, float* out,
                                         int64_t n, void* stream) {
     E3D_REQUIRE(x && eps_hat && noise && coef_table && t_dev && out && n > 0, "ddpm_step_wrap_table: bad arguments");
-    E3D_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)eps_hat % 16) == 0 && ((uintptr_t)out % 16) == 0 &&
-                    ((uintptr_t)noise % 16) == 0, "ddpm_step_wrap_table: pointers must be 16B aligned");
-    const int64_t n4 = n / 4;
-    int64_t blocks = (n4 + 255) / 256;
-    blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
-    hipLaunchKernelGGL(ddpm_step_wrap_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, eps_hat, noise,
-                       0.f, 0.f, 1.f, 0.f, coef_table, t_dev, wrap, out, n4, n);
+    REQUIRE_ALIGNED16("ddpm_step_wrap_table", x, eps_hat, out, noise);
+    hipLaunchKernelGGL(ddpm_step_wrap_kernel<false>, dim3(sweep_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, x, eps_hat,
+                       buffer_draws(noise), DdpmCoef{0.f, 0.f, 1.f, 0.f}, coef_table, t_dev, wrap, out, n / 4, n);
     return e3d_launch_status("e3d_ddpm_step_wrap_table");
 }
 
@@ -635,13 +613,9 @@ extern "C" int e3d_strided_step_wrap(const float* x, const float* eps_hat, const
                                      const int64_t* t_dev, int T, int wrap, int wrap_x0, float* out, int64_t n,
                                      void* stream) {
     E3D_REQUIRE(x && eps_hat && coef_table && t_dev && out && n > 0 && T > 0, "strided_step_wrap: bad arguments");
-    E3D_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)eps_hat % 16) == 0 && ((uintptr_t)out % 16) == 0 &&
-                    ((uintptr_t)noise % 16) == 0, "strided_step_wrap: pointers must be 16B aligned");
-    const int64_t n4 = n / 4;
-    int64_t blocks = (n4 + 255) / 256;
-    blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
-    hipLaunchKernelGGL(strided_step_wrap_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, eps_hat, noise,
-                       coef_table, t_dev, T, wrap, wrap_x0, out, n4, n);
+    REQUIRE_ALIGNED16("strided_step_wrap", x, eps_hat, out, noise);
+    hipLaunchKernelGGL(strided_step_wrap_kernel<false>, dim3(sweep_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, x,
+                       eps_hat, buffer_draws(noise), coef_table, t_dev, T, wrap, wrap_x0, out, n / 4, n);
     return e3d_launch_status("e3d_strided_step_wrap");
 }
 
@@ -650,9 +624,7 @@ extern "C" int e3d_q_sample_wrap(const float* x0, const float* noise, const int6
                                  int64_t per, void* stream) {
     E3D_REQUIRE(x0 && noise && t && sqrt_ab && sqrt_1mab && out && B > 0 && per > 0, "q_sample_wrap: bad arguments");
     const int64_t n = (int64_t)B * per;
-    int64_t blocks = (n + 255) / 256;
-    blocks = blocks > 2048 ? 2048 : blocks;
-    hipLaunchKernelGGL(q_sample_wrap_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x0, noise, t,
+    hipLaunchKernelGGL(q_sample_wrap_kernel, dim3(sweep_blocks(n)), dim3(256), 0, (hipStream_t)stream, x0, noise, t,
                        sqrt_ab, sqrt_1mab, out, per, n);
     return e3d_launch_status("e3d_q_sample_wrap");
 }
@@ -675,27 +647,22 @@ extern "C" int e3d_discrete_q_sample(const int32_t* x0_idx, const float* Qtb, co
     E3D_REQUIRE(C >= 2 && C <= CMAX, "discrete_q_sample: C must be in [2,%d] (C=%d)", CMAX, C);
     E3D_REQUIRE(mode == 0 || (mode == 1 && u), "discrete_q_sample: mode 1 needs uniforms");
     const int64_t n = (int64_t)B * L;
-    hipLaunchKernelGGL(discrete_q_sample_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+    hipLaunchKernelGGL(discrete_q_sample_kernel<false>, dim3(row_blocks(n)), dim3(256), 0,
                        (hipStream_t)stream, x0_idx, Qtb, u, mode, out_idx, L, C, n, nullptr, nullptr, 0ull);
     return e3d_launch_status("e3d_discrete_q_sample");
 }
 
 // ---------------------------------------------------------------- keyed (seeded) entry points
-static int keyed_blocks(int64_t n) {
-    int64_t blocks = (n + 255) / 256;
-    return (int)(blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks));
-}
-
 extern "C" int e3d_keyed_ddpm_step_wrap(const float* x, const float* eps_hat, const float* coef_table, const int64_t* t_dev,
                                         const int64_t* row_keys, uint64_t seed, int wrap, float* out, int64_t rows, int F,
                                         void* stream) {
     E3D_REQUIRE(x && eps_hat && coef_table && t_dev && row_keys && out && rows > 0, "keyed_ddpm_step_wrap: bad arguments");
-    E3D_REQUIRE(F > 0 && F % 4 == 0 && F / 4 <= 256, "keyed_ddpm_step_wrap: F must be a multiple of 4 in [4, 1024] (F=%d)", F);
-    E3D_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)eps_hat % 16) == 0 && ((uintptr_t)out % 16) == 0,
-                "keyed_ddpm_step_wrap: pointers must be 16B aligned");
+    REQUIRE_KEYED_WIDTH("keyed_ddpm_step_wrap", F);
+    REQUIRE_ALIGNED16("keyed_ddpm_step_wrap", x, eps_hat, out);
     const int64_t n4 = rows * (F / 4);
-    hipLaunchKernelGGL(keyed_ddpm_step_wrap_kernel, dim3(keyed_blocks(n4)), dim3(256), 0, (hipStream_t)stream, x, eps_hat,
-                       coef_table, t_dev, row_keys, seed, wrap, out, n4, F / 4);
+    hipLaunchKernelGGL(ddpm_step_wrap_kernel<true>, dim3(sweep_blocks(n4)), dim3(256), 0, (hipStream_t)stream, x, eps_hat,
+                       keyed_draws_of(row_keys, seed, E3D_STREAM_STRUCT_STEP, F), DdpmCoef{0.f, 0.f, 1.f, 0.f}, coef_table,
+                       t_dev, wrap, out, n4, 4 * n4);
     return e3d_launch_status("e3d_keyed_ddpm_step_wrap");
 }
 
@@ -704,13 +671,13 @@ extern "C" int e3d_keyed_strided_step_wrap(const float* x, const float* eps_hat,
                                            int wrap_x0, float* out, int64_t rows, int F, void* stream) {
     E3D_REQUIRE(x && eps_hat && coef_table && t_dev && row_keys && out && rows > 0 && T > 0,
                 "keyed_strided_step_wrap: bad arguments");
-    E3D_REQUIRE(F > 0 && F % 4 == 0 && F / 4 <= 256, "keyed_strided_step_wrap: F must be a multiple of 4 in [4, 1024] (F=%d)", F);
-    E3D_REQUIRE(T <= 65536, "keyed_strided_step_wrap: keyed streams hold steps up to 65535 (T=%d)", T);
-    E3D_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)eps_hat % 16) == 0 && ((uintptr_t)out % 16) == 0,
-                "keyed_strided_step_wrap: pointers must be 16B aligned");
+    REQUIRE_KEYED_WIDTH("keyed_strided_step_wrap", F);
+    REQUIRE_KEYED_STEPS("keyed_strided_step_wrap", T);
+    REQUIRE_ALIGNED16("keyed_strided_step_wrap", x, eps_hat, out);
     const int64_t n4 = rows * (F / 4);
-    hipLaunchKernelGGL(keyed_strided_step_wrap_kernel, dim3(keyed_blocks(n4)), dim3(256), 0, (hipStream_t)stream, x, eps_hat,
-                       coef_table, t_dev, T, row_keys, seed, wrap, wrap_x0, out, n4, F / 4);
+    hipLaunchKernelGGL(strided_step_wrap_kernel<true>, dim3(sweep_blocks(n4)), dim3(256), 0, (hipStream_t)stream, x, eps_hat,
+                       keyed_draws_of(row_keys, seed, E3D_STREAM_STRUCT_STEP, F), coef_table, t_dev, T, wrap, wrap_x0, out, n4,
+                       4 * n4);
     return e3d_launch_status("e3d_keyed_strided_step_wrap");
 }
 
@@ -733,12 +700,12 @@ extern "C" int e3d_keyed_draws(const int64_t* row_keys, uint64_t seed, int strea
                  stream_id == E3D_KNOWN_STREAM_SEQ) && t >= 0 && t <= 65535,
                 "keyed_draws: stream %d / step %d out of range", stream_id, t);
     E3D_REQUIRE(kind >= 0 && kind <= 3, "keyed_draws: kind %d", kind);
-    E3D_REQUIRE(kind != 0 || (width > 0 && width % 4 == 0 && width / 4 <= 256 && ((uintptr_t)out % 16) == 0),
+    E3D_REQUIRE(kind != 0 || (keyed_width(width) && aligned16({out})),
                 "keyed_draws: normals need F a multiple of 4 in [4, 1024] (F=%d) and a 16B aligned output", width);
     E3D_REQUIRE(kind < 2 || (width >= 2 && width <= 1 << 24), "keyed_draws: class count %d", width);
     const int nb = kind == 0 ? width / 4 : 1;
     const int64_t n = rows * nb;
-    hipLaunchKernelGGL(keyed_draws_kernel, dim3(keyed_blocks(n)), dim3(256), 0, (hipStream_t)stream, row_keys, seed,
+    hipLaunchKernelGGL(keyed_draws_kernel, dim3(sweep_blocks(n)), dim3(256), 0, (hipStream_t)stream, row_keys, seed,
                        stream_id, (uint32_t)t, kind, nb, width, wrap, scale, out, n);
     return e3d_launch_status("e3d_keyed_draws");
 }
@@ -750,7 +717,7 @@ extern "C" int e3d_keyed_timesteps(const int64_t* item_ids, const int64_t* epoch
     E3D_REQUIRE(stream_id == E3D_STREAM_TRAIN_STRUCT_T || stream_id == E3D_STREAM_TRAIN_SEQ_T,
                 "keyed_timesteps: stream %d is not a timestep stream", stream_id);
     E3D_REQUIRE(C >= 1 && C <= 1 << 24, "keyed_timesteps: class count %d", C);
-    hipLaunchKernelGGL(keyed_timesteps_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(keyed_timesteps_kernel, dim3(row_blocks(B)), dim3(256), 0, (hipStream_t)stream,
                        item_ids, epoch_dev, seed, stream_id, C, out, B);
     return e3d_launch_status("e3d_keyed_timesteps");
 }
@@ -762,11 +729,10 @@ extern "C" int e3d_keyed_q_sample_wrap(const float* x0, const int64_t* t, const 
     E3D_REQUIRE(x0 && t && sqrt_ab && sqrt_1mab && item_ids && epoch_dev && noise_out && xt_out && B > 0 && L > 0 && T > 0,
                 "keyed_q_sample_wrap: bad arguments");
     E3D_REQUIRE(L <= 1 << 24, "keyed_q_sample_wrap: positions must stay below 2^24 (L=%d)", L);
-    E3D_REQUIRE(F > 0 && F % 4 == 0 && F / 4 <= 256, "keyed_q_sample_wrap: F must be a multiple of 4 in [4, 1024] (F=%d)", F);
-    E3D_REQUIRE(((uintptr_t)x0 % 16) == 0 && ((uintptr_t)noise_out % 16) == 0 && ((uintptr_t)xt_out % 16) == 0,
-                "keyed_q_sample_wrap: pointers must be 16B aligned");
+    REQUIRE_KEYED_WIDTH("keyed_q_sample_wrap", F);
+    REQUIRE_ALIGNED16("keyed_q_sample_wrap", x0, noise_out, xt_out);
     const int64_t n4 = (int64_t)B * L * (F / 4);
-    hipLaunchKernelGGL(keyed_q_sample_wrap_kernel, dim3(keyed_blocks(n4)), dim3(256), 0, (hipStream_t)stream, x0, t, sqrt_ab,
+    hipLaunchKernelGGL(keyed_q_sample_wrap_kernel, dim3(sweep_blocks(n4)), dim3(256), 0, (hipStream_t)stream, x0, t, sqrt_ab,
                        sqrt_1mab, T, scale, item_ids, epoch_dev, seed, noise_out, xt_out, L, F / 4, n4);
     return e3d_launch_status("e3d_keyed_q_sample_wrap");
 }
@@ -778,7 +744,7 @@ extern "C" int e3d_keyed_discrete_q_sample(const int32_t* x0_idx, const float* Q
     E3D_REQUIRE(L <= 1 << 24, "keyed_discrete_q_sample: positions must stay below 2^24 (L=%d)", L);
     E3D_REQUIRE(C >= 2 && C <= CMAX, "keyed_discrete_q_sample: C must be in [2,%d] (C=%d)", CMAX, C);
     const int64_t n = (int64_t)B * L;
-    hipLaunchKernelGGL(discrete_q_sample_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+    hipLaunchKernelGGL(discrete_q_sample_kernel<true>, dim3(row_blocks(n)), dim3(256), 0,
                        (hipStream_t)stream, x0_idx, Qtb, nullptr, 1, out_idx, L, C, n, item_ids, epoch_dev, seed);
     return e3d_launch_status("e3d_keyed_discrete_q_sample");
 }
@@ -788,11 +754,10 @@ extern "C" int e3d_known_compose_wrap(float* x, const float* x0, const uint8_t* 
                                       const float* level_table, const int64_t* t_dev, int T, float scale, int64_t n,
                                       void* stream) {
     E3D_REQUIRE(x && x0 && mask && level_table && t_dev && n > 0 && T > 0, "known_compose_wrap: bad arguments");
-    E3D_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)x0 % 16) == 0 && ((uintptr_t)noise % 16) == 0 &&
-                    ((uintptr_t)mask % 4) == 0, "known_compose_wrap: x, x0, noise must be 16B and mask 4B aligned");
-    const int64_t n4 = n / 4;
-    hipLaunchKernelGGL(known_compose_wrap_kernel, dim3(keyed_blocks(n4)), dim3(256), 0, (hipStream_t)stream, x, x0, mask,
-                       noise, level_table, t_dev, T, scale, n4, n);
+    E3D_REQUIRE(aligned16({x, x0, noise}) && ((uintptr_t)mask % 4) == 0,
+                "known_compose_wrap: x, x0, noise must be 16B and mask 4B aligned");
+    hipLaunchKernelGGL(known_compose_wrap_kernel<false>, dim3(sweep_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, x, x0,
+                       mask, buffer_draws(noise), level_table, t_dev, T, scale, n / 4, n);
     return e3d_launch_status("e3d_known_compose_wrap");
 }
 
@@ -801,13 +766,13 @@ extern "C" int e3d_keyed_known_compose_wrap(float* x, const float* x0, const uin
                                             uint64_t seed, int64_t rows, int F, void* stream) {
     E3D_REQUIRE(x && x0 && mask && level_table && t_dev && row_keys && rows > 0 && T > 0,
                 "keyed_known_compose_wrap: bad arguments");
-    E3D_REQUIRE(F > 0 && F % 4 == 0 && F / 4 <= 256, "keyed_known_compose_wrap: F must be a multiple of 4 in [4, 1024] (F=%d)", F);
-    E3D_REQUIRE(T <= 65536, "keyed_known_compose_wrap: keyed streams hold steps up to 65535 (T=%d)", T);
-    E3D_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)x0 % 16) == 0 && ((uintptr_t)mask % 4) == 0,
+    REQUIRE_KEYED_WIDTH("keyed_known_compose_wrap", F);
+    REQUIRE_KEYED_STEPS("keyed_known_compose_wrap", T);
+    E3D_REQUIRE(aligned16({x, x0}) && ((uintptr_t)mask % 4) == 0,
                 "keyed_known_compose_wrap: x, x0 must be 16B and mask 4B aligned");
     const int64_t n4 = rows * (F / 4);
-    hipLaunchKernelGGL(keyed_known_compose_wrap_kernel, dim3(keyed_blocks(n4)), dim3(256), 0, (hipStream_t)stream, x, x0,
-                       mask, level_table, t_dev, T, scale, row_keys, seed, n4, F / 4);
+    hipLaunchKernelGGL(known_compose_wrap_kernel<true>, dim3(sweep_blocks(n4)), dim3(256), 0, (hipStream_t)stream, x, x0, mask,
+                       keyed_draws_of(row_keys, seed, E3D_KNOWN_STREAM_STRUCT, F), level_table, t_dev, T, scale, n4, 4 * n4);
     return e3d_launch_status("e3d_keyed_known_compose_wrap");
 }
 
@@ -817,7 +782,7 @@ extern "C" int e3d_discrete_known_compose(int32_t* idx, const int32_t* x0_idx, c
     E3D_REQUIRE(C >= 2 && C <= CMAX, "discrete_known_compose: C must be in [2,%d] (C=%d)", CMAX, C);
     E3D_REQUIRE(mode == 0 || (mode == 1 && u), "discrete_known_compose: mode 1 needs uniforms");
     const int64_t n = (int64_t)B * L;
-    hipLaunchKernelGGL(discrete_known_compose_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+    hipLaunchKernelGGL(discrete_known_compose_kernel<false>, dim3(row_blocks(n)), dim3(256), 0,
                        (hipStream_t)stream, idx, x0_idx, mask, Qsb, u, mode, L, C, n, nullptr, 0ull, nullptr);
     return e3d_launch_status("e3d_discrete_known_compose");
 }
@@ -829,7 +794,7 @@ extern "C" int e3d_keyed_discrete_known_compose(int32_t* idx, const int32_t* x0_
                 "keyed_discrete_known_compose: bad arguments");
     E3D_REQUIRE(C >= 2 && C <= CMAX, "keyed_discrete_known_compose: C must be in [2,%d] (C=%d)", CMAX, C);
     const int64_t n = (int64_t)B * L;
-    hipLaunchKernelGGL(discrete_known_compose_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+    hipLaunchKernelGGL(discrete_known_compose_kernel<true>, dim3(row_blocks(n)), dim3(256), 0,
                        (hipStream_t)stream, idx, x0_idx, mask, Qsb, nullptr, 1, L, C, n, row_keys, seed, s_dev);
     return e3d_launch_status("e3d_keyed_discrete_known_compose");
 }
@@ -873,7 +838,7 @@ extern "C" int e3d_discrete_final_pick(const float* logits, const float* bias, f
     E3D_REQUIRE(C >= 1 && C <= CMAX, "discrete_final_pick: C must be in [1,%d] (C=%d)", CMAX, C);
     E3D_REQUIRE(good_inv_temp(inv_temp), "discrete_final_pick: inv_temp must be positive and finite (inv_temp=%g)",
                 (double)inv_temp);
-    hipLaunchKernelGGL(discrete_final_pick_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(discrete_final_pick_kernel, dim3(row_blocks(rows)), dim3(256), 0, (hipStream_t)stream,
                        logits, bias, inv_temp, out_idx, logp, entropy, rows, C);
     return e3d_launch_status("e3d_discrete_final_pick");
 }

@@ -942,12 +942,20 @@ def head_linear(x, weight, bias):
     return out
 
 
+def _chk_update(name, x, eps_hat, noise, coef_table, width, t_dev, out):
+    """The operand checks the continuous updates share: the DDPM update (a [T, ``width`` 4] table; ``coef_table`` and
+    ``t_dev`` None in the scalar form) and the strided one (8).  Returns ``out``, allocated like ``x`` when None."""
+    for n, t in (("x", x), ("eps_hat", eps_hat), ("noise", noise), ("coef_table", coef_table)):
+        _chk(t, f"{name}.{n}")
+    _chk(t_dev, name + ".t_dev", torch.int64)
+    assert x.is_contiguous() and eps_hat.is_contiguous() and eps_hat.shape == x.shape
+    assert noise is None or (noise.is_contiguous() and noise.shape == x.shape)
+    assert coef_table is None or (coef_table.is_contiguous() and coef_table.dim() == 2 and coef_table.shape[1] == width)
+    return torch.empty_like(x) if out is None else out
+
+
 def ddpm_step_wrap(x, eps_hat, noise, sqrt_recip_alpha, beta, sqrt_one_minus_ab, sigma, wrap=True, out=None):
-    for n, t in (("x", x), ("eps_hat", eps_hat), ("noise", noise)):
-        _chk(t, "ddpm_step_wrap." + n)
-    assert x.is_contiguous() and eps_hat.is_contiguous() and (noise is None or noise.is_contiguous())
-    if out is None:
-        out = torch.empty_like(x)
+    out = _chk_update("ddpm_step_wrap", x, eps_hat, noise, None, 4, None, out)
     with _timed("ddpm_step_wrap"):
         hip.check(hip.lib().e3d_ddpm_step_wrap(_p(x), _p(eps_hat), _p(noise), sqrt_recip_alpha, beta,
                                                sqrt_one_minus_ab, sigma, int(wrap), _p(out), x.numel(), _stream()),
@@ -958,13 +966,7 @@ def ddpm_step_wrap(x, eps_hat, noise, sqrt_recip_alpha, beta, sqrt_one_minus_ab,
 def ddpm_step_wrap_table(x, eps_hat, noise, coef_table, t_dev, wrap=True, out=None):
     """ddpm_step_wrap with the step index on the device (``t_dev`` int64, first element) and the four
     coefficients in ``coef_table`` [T,4]: nothing host-side changes between steps (HIP-graph replay)."""
-    for n, t in (("x", x), ("eps_hat", eps_hat), ("noise", noise), ("coef_table", coef_table)):
-        _chk(t, "ddpm_step_wrap_table." + n)
-    _chk(t_dev, "ddpm_step_wrap_table.t_dev", torch.int64)
-    assert x.is_contiguous() and eps_hat.is_contiguous() and noise.is_contiguous() and coef_table.is_contiguous()
-    assert coef_table.dim() == 2 and coef_table.shape[1] == 4
-    if out is None:
-        out = torch.empty_like(x)
+    out = _chk_update("ddpm_step_wrap_table", x, eps_hat, noise, coef_table, 4, t_dev, out)
     with _timed("ddpm_step_wrap"):
         hip.check(hip.lib().e3d_ddpm_step_wrap_table(_p(x), _p(eps_hat), _p(noise), _p(coef_table), _p(t_dev), int(wrap),
                                                      _p(out), x.numel(), _stream()), "e3d_ddpm_step_wrap_table")
@@ -975,14 +977,7 @@ def strided_step_wrap(x, eps_hat, noise, coef_table, t_dev, wrap=True, wrap_x0=F
     """The strided (DDIM / respaced) update t -> successor(t): x0 form with the coefficients in row ``t_dev[0]`` of
     ``coef_table`` [T,8] (structure_model.utils.StridedTables.coef).  ``noise`` None: no noise term; a row with
     sigma == 0 reads nothing through ``noise``.  ``wrap_x0``: wrap the x0 estimate to [-pi, pi).  ``out`` may be ``x``."""
-    for n, t in (("x", x), ("eps_hat", eps_hat), ("noise", noise), ("coef_table", coef_table)):
-        _chk(t, "strided_step_wrap." + n)
-    _chk(t_dev, "strided_step_wrap.t_dev", torch.int64)
-    assert x.is_contiguous() and eps_hat.is_contiguous() and coef_table.is_contiguous() and eps_hat.shape == x.shape
-    assert noise is None or (noise.is_contiguous() and noise.shape == x.shape)
-    assert coef_table.dim() == 2 and coef_table.shape[1] == 8
-    if out is None:
-        out = torch.empty_like(x)
+    out = _chk_update("strided_step_wrap", x, eps_hat, noise, coef_table, 8, t_dev, out)
     with _timed("strided_step_wrap"):
         hip.check(hip.lib().e3d_strided_step_wrap(_p(x), _p(eps_hat), _p(noise), _p(coef_table), _p(t_dev),
                                                   coef_table.shape[0], int(wrap), int(wrap_x0), _p(out), x.numel(),
@@ -1002,13 +997,19 @@ def q_sample_wrap(x0, noise, t, sqrt_ab, sqrt_1mab):
     return out
 
 
-def discrete_posterior_sample(xt_idx, logits, qsb, qtb, u=None, want_prob=False):
-    """xt_idx int32 [B,L]; logits [B,L,C]; qsb/qtb [B,C,C]; u [B,L] uniforms or None (argmax)."""
-    _chk(xt_idx, "xt_idx", torch.int32); _chk(logits, "logits"); _chk(qsb, "qsb"); _chk(qtb, "qtb"); _chk(u, "u")
+def _chk_posterior(xt_idx, logits, qsb, qtb):
+    """The operand checks the four posterior launches share; returns B, L, C and the int32 [B,L] output."""
+    _chk(xt_idx, "xt_idx", torch.int32); _chk(logits, "logits"); _chk(qsb, "qsb"); _chk(qtb, "qtb")
     B, L, C = logits.shape
     assert xt_idx.is_contiguous() and logits.is_contiguous() and qsb.is_contiguous() and qtb.is_contiguous()
     assert qsb.shape == (B, C, C) and qtb.shape == (B, C, C) and xt_idx.shape == (B, L)
-    out = torch.empty((B, L), device=logits.device, dtype=torch.int32)
+    return B, L, C, torch.empty((B, L), device=logits.device, dtype=torch.int32)
+
+
+def discrete_posterior_sample(xt_idx, logits, qsb, qtb, u=None, want_prob=False):
+    """xt_idx int32 [B,L]; logits [B,L,C]; qsb/qtb [B,C,C]; u [B,L] uniforms or None (argmax)."""
+    B, L, C, out = _chk_posterior(xt_idx, logits, qsb, qtb)
+    _chk(u, "u")
     prob = torch.empty((B, L, C), device=logits.device, dtype=torch.float32) if want_prob else None
     with _timed("discrete_posterior"):
         hip.check(hip.lib().e3d_discrete_posterior_sample(
@@ -1039,23 +1040,24 @@ def _chk_keys(row_keys, rows, name):
         raise ValueError(f"{name}: row_keys must be a contiguous [{rows}, 2] table, got {tuple(row_keys.shape)}")
 
 
+def _keyed_rows(name, x, row_keys, table):
+    """The geometry of a keyed launch on ``x`` [.., F]: (rows, F) with rows = x.numel() // F, F % 4 == 0, one key per row;
+    ``table`` is read by the step index, which a keyed stream holds up to 65535."""
+    F = x.shape[-1]
+    if F % 4:
+        raise ValueError(f"{name}: the feature count must be a multiple of 4, got {F}")
+    rows = x.numel() // F
+    _chk_keys(row_keys, rows, name)
+    if table.shape[0] - 1 > 65535:
+        raise ValueError(f"{name}: keyed streams hold steps up to 65535, the table has {table.shape[0]}")
+    return rows, F
+
+
 def keyed_ddpm_step_wrap(x, eps_hat, coef_table, t_dev, row_keys, seed, wrap=True, out=None):
     """ddpm_step_wrap_table with the N(0,1) draw generated in the kernel from (seed, row key, stream 1, t_dev[0]):
     x / eps_hat [.., F] with rows = x.numel() // F, F % 4 == 0.  No noise buffer, no host sync: graph-capturable."""
-    for n, t in (("x", x), ("eps_hat", eps_hat), ("coef_table", coef_table)):
-        _chk(t, "keyed_ddpm_step_wrap." + n)
-    _chk(t_dev, "keyed_ddpm_step_wrap.t_dev", torch.int64)
-    F = x.shape[-1]
-    if F % 4:
-        raise ValueError(f"keyed_ddpm_step_wrap: the feature count must be a multiple of 4, got {F}")
-    rows = x.numel() // F
-    _chk_keys(row_keys, rows, "keyed_ddpm_step_wrap")
-    assert x.is_contiguous() and eps_hat.is_contiguous() and coef_table.is_contiguous() and eps_hat.shape == x.shape
-    assert coef_table.dim() == 2 and coef_table.shape[1] == 4
-    if coef_table.shape[0] - 1 > 65535:
-        raise ValueError(f"keyed_ddpm_step_wrap: keyed streams hold steps up to 65535, the table has {coef_table.shape[0]}")
-    if out is None:
-        out = torch.empty_like(x)
+    out = _chk_update("keyed_ddpm_step_wrap", x, eps_hat, None, coef_table, 4, t_dev, out)
+    rows, F = _keyed_rows("keyed_ddpm_step_wrap", x, row_keys, coef_table)
     with _timed("keyed_ddpm_step_wrap"):
         hip.check(hip.lib().e3d_keyed_ddpm_step_wrap(_p(x), _p(eps_hat), _p(coef_table), _p(t_dev), _p(row_keys),
                                                      keyed.check_seed(seed), int(wrap), _p(out), rows, F, _stream()),
@@ -1066,20 +1068,8 @@ def keyed_ddpm_step_wrap(x, eps_hat, coef_table, t_dev, row_keys, seed, wrap=Tru
 def keyed_strided_step_wrap(x, eps_hat, coef_table, t_dev, row_keys, seed, wrap=True, wrap_x0=False, out=None):
     """strided_step_wrap with the N(0,1) draw generated in the kernel from (seed, row key, stream 1, t_dev[0]) -- the
     draws of keyed_ddpm_step_wrap at the same step; x / eps_hat [.., F], rows = x.numel() // F, F % 4 == 0."""
-    for n, t in (("x", x), ("eps_hat", eps_hat), ("coef_table", coef_table)):
-        _chk(t, "keyed_strided_step_wrap." + n)
-    _chk(t_dev, "keyed_strided_step_wrap.t_dev", torch.int64)
-    F = x.shape[-1]
-    if F % 4:
-        raise ValueError(f"keyed_strided_step_wrap: the feature count must be a multiple of 4, got {F}")
-    rows = x.numel() // F
-    _chk_keys(row_keys, rows, "keyed_strided_step_wrap")
-    assert x.is_contiguous() and eps_hat.is_contiguous() and coef_table.is_contiguous() and eps_hat.shape == x.shape
-    assert coef_table.dim() == 2 and coef_table.shape[1] == 8
-    if coef_table.shape[0] - 1 > 65535:
-        raise ValueError(f"keyed_strided_step_wrap: keyed streams hold steps up to 65535, the table has {coef_table.shape[0]}")
-    if out is None:
-        out = torch.empty_like(x)
+    out = _chk_update("keyed_strided_step_wrap", x, eps_hat, None, coef_table, 8, t_dev, out)
+    rows, F = _keyed_rows("keyed_strided_step_wrap", x, row_keys, coef_table)
     with _timed("keyed_strided_step_wrap"):
         hip.check(hip.lib().e3d_keyed_strided_step_wrap(_p(x), _p(eps_hat), _p(coef_table), _p(t_dev), coef_table.shape[0],
                                                         _p(row_keys), keyed.check_seed(seed), int(wrap), int(wrap_x0),
@@ -1090,13 +1080,9 @@ def keyed_strided_step_wrap(x, eps_hat, coef_table, t_dev, row_keys, seed, wrap=
 def keyed_discrete_posterior_sample(xt_idx, logits, qsb, qtb, row_keys, seed, s_dev):
     """discrete_posterior_sample (categorical draw) with the uniforms from (seed, row key, stream 3, s_dev[0]);
     row_keys [B * L, 2]."""
-    _chk(xt_idx, "xt_idx", torch.int32); _chk(logits, "logits"); _chk(qsb, "qsb"); _chk(qtb, "qtb")
+    B, L, C, out = _chk_posterior(xt_idx, logits, qsb, qtb)
     _chk(s_dev, "s_dev", torch.int64)
-    B, L, C = logits.shape
     _chk_keys(row_keys, B * L, "keyed_discrete_posterior_sample")
-    assert xt_idx.is_contiguous() and logits.is_contiguous() and qsb.is_contiguous() and qtb.is_contiguous()
-    assert qsb.shape == (B, C, C) and qtb.shape == (B, C, C) and xt_idx.shape == (B, L)
-    out = torch.empty((B, L), device=logits.device, dtype=torch.int32)
     with _timed("discrete_posterior"):
         hip.check(hip.lib().e3d_keyed_discrete_posterior_sample(
             _p(xt_idx), _p(logits), _p(qsb), _p(qtb), _p(row_keys), keyed.check_seed(seed), _p(s_dev), _p(out), B, L, C,
@@ -1124,12 +1110,9 @@ def _chk_ctl(logits, bias, inv_temp, name):
 def discrete_posterior_sample_ctl(xt_idx, logits, bias, inv_temp, qsb, qtb, u=None, want_prob=False):
     """discrete_posterior_sample with the softmax over (logits + bias) * inv_temp: bias contiguous [B,L,C] (-inf forbids
     a class) or None for zero; inv_temp > 0."""
-    _chk(xt_idx, "xt_idx", torch.int32); _chk(qsb, "qsb"); _chk(qtb, "qtb"); _chk(u, "u")
     inv_temp = _chk_ctl(logits, bias, inv_temp, "discrete_posterior_sample_ctl")
-    B, L, C = logits.shape
-    assert xt_idx.is_contiguous() and qsb.is_contiguous() and qtb.is_contiguous()
-    assert qsb.shape == (B, C, C) and qtb.shape == (B, C, C) and xt_idx.shape == (B, L)
-    out = torch.empty((B, L), device=logits.device, dtype=torch.int32)
+    B, L, C, out = _chk_posterior(xt_idx, logits, qsb, qtb)
+    _chk(u, "u")
     prob = torch.empty((B, L, C), device=logits.device, dtype=torch.float32) if want_prob else None
     with _timed("discrete_posterior"):
         hip.check(hip.lib().e3d_discrete_posterior_sample_ctl(
@@ -1140,14 +1123,10 @@ def discrete_posterior_sample_ctl(xt_idx, logits, bias, inv_temp, qsb, qtb, u=No
 
 def keyed_discrete_posterior_sample_ctl(xt_idx, logits, bias, inv_temp, qsb, qtb, row_keys, seed, s_dev):
     """keyed_discrete_posterior_sample with the softmax over (logits + bias) * inv_temp; stream 3, the same counters."""
-    _chk(xt_idx, "xt_idx", torch.int32); _chk(qsb, "qsb"); _chk(qtb, "qtb")
-    _chk(s_dev, "s_dev", torch.int64)
     inv_temp = _chk_ctl(logits, bias, inv_temp, "keyed_discrete_posterior_sample_ctl")
-    B, L, C = logits.shape
+    B, L, C, out = _chk_posterior(xt_idx, logits, qsb, qtb)
+    _chk(s_dev, "s_dev", torch.int64)
     _chk_keys(row_keys, B * L, "keyed_discrete_posterior_sample_ctl")
-    assert xt_idx.is_contiguous() and qsb.is_contiguous() and qtb.is_contiguous()
-    assert qsb.shape == (B, C, C) and qtb.shape == (B, C, C) and xt_idx.shape == (B, L)
-    out = torch.empty((B, L), device=logits.device, dtype=torch.int32)
     with _timed("discrete_posterior"):
         hip.check(hip.lib().e3d_keyed_discrete_posterior_sample_ctl(
             _p(xt_idx), _p(logits), _p(bias), inv_temp, _p(qsb), _p(qtb), _p(row_keys), keyed.check_seed(seed), _p(s_dev),
@@ -1211,13 +1190,7 @@ def keyed_known_compose_wrap(x, x0, mask, level_table, t_dev, row_keys, seed, sc
     rows = x.numel() // F, F % 4 == 0.  Rows of no item are left alone."""
     _chk_known(x, x0, mask, "keyed_known_compose_wrap")
     _chk_levels(level_table, t_dev, "keyed_known_compose_wrap")
-    F = x.shape[-1]
-    if F % 4:
-        raise ValueError(f"keyed_known_compose_wrap: the feature count must be a multiple of 4, got {F}")
-    rows = x.numel() // F
-    _chk_keys(row_keys, rows, "keyed_known_compose_wrap")
-    if level_table.shape[0] - 1 > 65535:
-        raise ValueError(f"keyed_known_compose_wrap: keyed streams hold steps up to 65535, the table has {level_table.shape[0]}")
+    rows, F = _keyed_rows("keyed_known_compose_wrap", x, row_keys, level_table)
     with _timed("keyed_known_compose_wrap"):
         hip.check(hip.lib().e3d_keyed_known_compose_wrap(_p(x), _p(x0), _p(mask), _p(level_table), _p(t_dev),
                                                          level_table.shape[0], float(scale), _p(row_keys),

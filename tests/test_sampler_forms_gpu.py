@@ -3,33 +3,36 @@ statements and the exact fp32 rules of tests/sampler_ref.py (which tests/test_sa
 whose inputs it examines).  The branches are forced by operand properties only: n against 4 and against the 2048-block
 grid cap, L against the 256 threads of a block, C against the 32 classes the LDS arrays hold, null pointers, sigma == 0.
 
-One row per ``hipLaunchKernelGGL`` site of csrc/sampler.hip:
+One row per ``hipLaunchKernelGGL`` site of csrc/sampler.hip, by entry point and the instantiation it launches:
 
-=====  ====================================  ==========================================  ==========================================
-line   kernel                                forced by                                   test id
-=====  ====================================  ==========================================  ==========================================
-557    ddpm_step_wrap_kernel, scalars        e3d_ddpm_step_wrap; n % 4, n < 4, n4 >     test_ddpm_update[*], test_ddpm_without_noise,
-                                             2048 * 256, noise NULL, sigma == 0, out     test_ddpm_out_may_alias_x, test_wrap_pi_bit_exact,
-                                             == x, a pointer at +4 bytes                 test_ddpm_refuses_misaligned_pointers
-572    ddpm_step_wrap_kernel, table row      e3d_ddpm_step_wrap_table, the same sizes    test_ddpm_update[*], test_ddpm_out_may_alias_x,
-                                                                                         test_ddpm_refuses_misaligned_pointers
-586    strided_step_wrap_kernel              --                                          test_strided_gpu.py::test_kernel_against_the_float64_ref
-598    q_sample_wrap_kernel                  n against 2048 * 256, i / per               test_q_sample_wrap[*]
-610    discrete_posterior_kernel<false>      L against 256, C = 2 .. 32, tot == 0,       test_discrete_posterior[*],
-                                             prob_out NULL, both modes                   test_discrete_posterior_zero_total[*]
-621    discrete_q_sample_kernel<false>       B L against 256, C, padding rows            test_discrete_q_sample[*]
-640    keyed_ddpm_step_wrap_kernel           F = 4 | 1024, n4 > 2048 * 256               test_keyed_ddpm_step[*]
-655    keyed_strided_step_wrap_kernel        --                                          test_strided_gpu.py::test_keyed_form_equals_the_unkeyed_form_with_the_keyed_draws
-667    discrete_posterior_kernel<true>       L > 256, C = 32, rows of no item            test_keyed_discrete_posterior[*]
-684    keyed_draws_kernel                    kind 0 .. 3, F, n > 2048 * 256, step 65535  test_keyed_draws[*]
-696    keyed_timesteps_kernel                B against 256, C = 1                        test_keyed_timesteps[*]
-712    keyed_q_sample_wrap_kernel            F = 1024, n4 > 2048 * 256, t outside [0,T)  test_keyed_q_sample_wrap[*]
-724    discrete_q_sample_kernel<true>        B L = 257 | 900, ids above 2^63             test_discrete_q_sample[257-*|900-*]
-737    known_compose_wrap_kernel             --                                          test_known_gpu.py::test_compose_against_the_float64_ref
-752    keyed_known_compose_wrap_kernel       --                                          test_known_gpu.py::test_keyed_compose_equals_the_buffer_form_with_the_keyed_draws
-763    discrete_known_compose_kernel<false>  --                                          test_known_gpu.py::test_discrete_compose_equals_q_sample_and_where
-775    discrete_known_compose_kernel<true>   --                                          test_known_gpu.py::test_discrete_compose_equals_q_sample_and_where
-=====  ====================================  ==========================================  ==========================================
+=======================================  =======================================  ===========================================  ==========================================
+entry point                              kernel                                   forced by                                    test id
+=======================================  =======================================  ===========================================  ==========================================
+e3d_ddpm_step_wrap                       ddpm_step_wrap_kernel<false>, scalars    n % 4, n < 4, n4 > 2048 * 256, noise NULL,   test_ddpm_update[*], test_ddpm_without_noise,
+                                                                                  sigma == 0, out == x, a pointer at +4 bytes  test_ddpm_out_may_alias_x, test_wrap_pi_bit_exact,
+                                                                                                                               test_ddpm_refuses_misaligned_pointers
+e3d_ddpm_step_wrap_table                 ddpm_step_wrap_kernel<false>, table row  the same sizes                               test_ddpm_update[*], test_ddpm_out_may_alias_x,
+                                                                                                                               test_ddpm_refuses_misaligned_pointers
+e3d_strided_step_wrap                    strided_step_wrap_kernel<false>          --                                           test_strided_gpu.py::test_kernel_against_the_float64_ref
+e3d_q_sample_wrap                        q_sample_wrap_kernel                     n against 2048 * 256, i / per                test_q_sample_wrap[*]
+e3d_discrete_posterior_sample            discrete_posterior_kernel<false, false>  L against 256, C = 2 .. 32, tot == 0,        test_discrete_posterior[*],
+                                                                                  prob_out NULL, both modes                    test_discrete_posterior_zero_total[*]
+e3d_discrete_q_sample                    discrete_q_sample_kernel<false>          B L against 256, C, padding rows             test_discrete_q_sample[*]
+e3d_keyed_ddpm_step_wrap                 ddpm_step_wrap_kernel<true>              F = 4 | 1024, n4 > 2048 * 256                test_keyed_ddpm_step[*]
+e3d_keyed_strided_step_wrap              strided_step_wrap_kernel<true>           --                                           test_strided_gpu.py::test_keyed_form_equals_the_unkeyed_form_with_the_keyed_draws
+e3d_keyed_discrete_posterior_sample      discrete_posterior_kernel<true, false>   L > 256, C = 32, rows of no item             test_keyed_discrete_posterior[*]
+e3d_keyed_draws                          keyed_draws_kernel                       kind 0 .. 3, F, n > 2048 * 256, step 65535   test_keyed_draws[*]
+e3d_keyed_timesteps                      keyed_timesteps_kernel                   B against 256, C = 1                         test_keyed_timesteps[*]
+e3d_keyed_q_sample_wrap                  keyed_q_sample_wrap_kernel               F = 1024, n4 > 2048 * 256, t outside [0,T)   test_keyed_q_sample_wrap[*]
+e3d_keyed_discrete_q_sample              discrete_q_sample_kernel<true>           B L = 257 | 900, ids above 2^63              test_discrete_q_sample[257-*|900-*]
+e3d_known_compose_wrap                   known_compose_wrap_kernel<false>         --                                           test_known_gpu.py::test_compose_against_the_float64_ref
+e3d_keyed_known_compose_wrap             known_compose_wrap_kernel<true>          --                                           test_known_gpu.py::test_keyed_compose_equals_the_buffer_form_with_the_keyed_draws
+e3d_discrete_known_compose               discrete_known_compose_kernel<false>     --                                           test_known_gpu.py::test_discrete_compose_equals_q_sample_and_where
+e3d_keyed_discrete_known_compose         discrete_known_compose_kernel<true>      --                                           test_known_gpu.py::test_discrete_compose_equals_q_sample_and_where
+e3d_discrete_posterior_sample_ctl        discrete_posterior_kernel<false, true>   --                                           test_design_gpu.py::test_posterior_under_controls_against_float64
+e3d_keyed_discrete_posterior_sample_ctl  discrete_posterior_kernel<true, true>    --                                           test_design_gpu.py::test_keyed_ctl_form_equals_the_buffer_ctl_form_with_the_keyed_uniforms
+e3d_discrete_final_pick                  discrete_final_pick_kernel               --                                           test_design_gpu.py::test_final_pick
+=======================================  =======================================  ===========================================  ==========================================
 
 Conventions (those of tests/test_rowops_forms_gpu.py, whose plumbing this module uses).  Every output is a block in the
 middle of a sentinel-filled allocation, 16 guard words on each side, 16-byte aligned where the kernel stores float4; the

@@ -2,8 +2,8 @@
 """Strided (DDIM / respaced) structure sampling against the ancestral chain: one JSON line.
 
     python tools/bench_strided.py --kernels [--batch 256] [--seq-len 256] [--launches 200]
-        # the four update kernels (ancestral table form, keyed ancestral, strided, keyed strided) launched alternately on
-        # one [batch, seq-len, 8] state -- for ``rocprofv3 --kernel-trace --stats``: per-kernel times in one run
+        # the update kernels (ancestral table form, strided, known compose; each with buffer and keyed draws) launched
+        # alternately on one [batch, seq-len, 8] state -- for ``rocprofv3 --kernel-trace --stats``: per-kernel times in one run
     python tools/bench_strided.py --single [--steps 50]
         # tools/bench_single.py's chain (ONE 64-residue pocket) four times in one process: ancestral / strided, torch /
         # keyed draws, eager launches -- under rocprofv3 the same four kernels at that shape; without it ms per step
@@ -29,10 +29,10 @@ DEV = "cuda:0"
 
 
 def kernels(batch, seq_len, launches, eta=1.0):
-    """Alternate launches of the four update kernels on one state; wall time per launch by HIP events as a cross-check."""
+    """Alternate launches of the update kernels on one state; wall time per launch by HIP events as a cross-check."""
     from e3diff_amd import keyed
     from e3diff_amd.structure_model.sample import _coef_table
-    from e3diff_amd.structure_model.utils import CosineTables, StridedTables
+    from e3diff_amd.structure_model.utils import CosineTables, KnownLevels, StridedTables
     ops = pkg.ops
     tab = CosineTables(1000)
     coef4 = _coef_table(tab, DEV)
@@ -41,14 +41,20 @@ def kernels(batch, seq_len, launches, eta=1.0):
     x = (torch.rand(batch, seq_len, 8, device=DEV, generator=g) * 6.28 - 3.14).contiguous()
     e = torch.randn(batch, seq_len, 8, device=DEV, generator=g)
     z = torch.randn(batch, seq_len, 8, device=DEV, generator=g)
+    # the two compose legs hold half the positions (whole residues, as a chain's mask does), at level row 500
+    x0 = (torch.rand(batch, seq_len, 8, device=DEV, generator=g) * 6.28 - 3.14).contiguous()
+    mask = (torch.rand(batch, seq_len, 1, device=DEV, generator=g) < 0.5).expand_as(x).to(torch.uint8).contiguous()
+    levels = KnownLevels(tab, list(reversed(range(1000)))).levels.to(DEV)
     out = torch.empty_like(x)
-    keys = keyed.padded_keys(list(range(batch)), seq_len, DEV)
+    keys =keyed.padded_keys(list(range(batch)), seq_len, DEV)
     t = torch.full((1,), 500, device=DEV, dtype=torch.long)
     legs = {"ancestral": lambda: ops.ddpm_step_wrap_table(x, e, z, coef4, t, out=out),
             "keyed_ancestral": lambda: ops.keyed_ddpm_step_wrap(x, e, coef4, t, keys, 7, out=out),
             "strided": lambda: ops.strided_step_wrap(x, e, z, coef8, t, out=out),
             "strided_wrap_x0": lambda: ops.strided_step_wrap(x, e, z, coef8, t, wrap_x0=True, out=out),
-            "keyed_strided": lambda: ops.keyed_strided_step_wrap(x, e, coef8, t, keys, 7, out=out)}
+            "keyed_strided": lambda: ops.keyed_strided_step_wrap(x, e, coef8, t, keys, 7, out=out),
+            "known_compose": lambda: ops.known_compose_wrap(x, x0, mask, z, levels, t),
+            "keyed_known_compose": lambda: ops.keyed_known_compose_wrap(x, x0, mask, levels, t, keys, 7)}
     for f in legs.values():
         f()
     torch.cuda.synchronize()
