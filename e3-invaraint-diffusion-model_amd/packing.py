@@ -264,3 +264,23 @@ def capture_graph(capture, rows, steps, use_graph=None, what="the reverse step")
     except Exception as e:   # noqa: BLE001 -- any capture problem: eager launches are always correct
         warnings.warn(f"HIP-graph capture of {what} failed ({type(e).__name__}: {e}); using eager launches")
         return None
+
+
+def warm_up_and_capture(body, device, restore_rng=False):
+    """``body()`` once on a side stream, off the capture (first-launch attribute calls, caches, the allocator: one eager
+    step per chain), then captured into a HIP graph; returns (graph, what the captured ``body()`` returned).
+    ``restore_rng``: put the device generator back after the warm-up, so that a chain sees the same random numbers
+    whether its steps are replayed or launched one by one (a size threshold decides which)."""
+    side = torch.cuda.Stream(device=device)
+    side.wait_stream(torch.cuda.current_stream(device))
+    rng = torch.cuda.get_rng_state(device) if restore_rng else None
+    with torch.cuda.stream(side):
+        body()
+    torch.cuda.current_stream(device).wait_stream(side)
+    if restore_rng:
+        torch.cuda.synchronize(device)
+        torch.cuda.set_rng_state(rng, device)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        out = body()
+    return graph, out

@@ -173,6 +173,19 @@ def sample_p_zs_given_zt_discrete(t, s, noised_data, pred_noise, noise_schedule,
     return F.one_hot(idx.long(), num_classes=C).float()
 
 
+def _denoise_step(model, s, T, x, args, layouts, noise_schedule, transition, diverse, is_last_step, **draws):
+    """One reverse step z_t -> z_s at the step index ``s`` ([B,1] float on the device), eager or captured.  ``args`` =
+    (ligand angles, ligand mask, pocket sequence, pocket angles, pocket mask); with ``layouts`` the model runs packed and
+    reads no mask.  ``draws``: the ``u``, ``keyed_draw``, ``known`` and ``controls`` of ``sample_p_zs_given_zt_discrete``."""
+    ang, lmask, rseq, rang, rmask = args
+    if layouts is None:
+        logits = model.forward(s, x, ang, lmask, rseq, rang, rmask)
+    else:
+        logits = model.forward_packed(s, x, ang, rseq, rang, *layouts)[None]
+    return sample_p_zs_given_zt_discrete((s + 1) / T, s / T, x, logits, noise_schedule, transition, diverse, is_last_step,
+                                         **draws)
+
+
 class GraphedDenoiseStep:
     """One reverse step of the sequence chain -- ``model.forward`` + ``sample_p_zs_given_zt_discrete`` -- captured once
     into a HIP graph and replayed per step, as structure_model/sample.py::GraphedReverseStep does for the angle chain.
@@ -207,31 +220,13 @@ class GraphedDenoiseStep:
         self.u = torch.zeros(x_like.shape[:2], device=dev) if (inject_u and diverse) else None
         self.known_u = torch.zeros(x_like.shape[:2], device=dev) if (known is not None and self.u is not None) else None
         self.known = None if known is None else (known[0], known[1], self.known_u)
-        self.out = None
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        # the warm-up draws uniforms when the chain samples (diverse, no injected u): put the device generator back
-        # afterwards, so that a seeded chain sees the same random numbers whether its steps are replayed or launched one
-        # by one (which path runs is decided by a size threshold)
-        rng = torch.cuda.get_rng_state(dev)
-        with torch.cuda.stream(side):       # warm-up off the capture: first-launch attribute calls, caches, allocator
-            self._body()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
-        torch.cuda.set_rng_state(rng, dev)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self.out = self._body()
+        # the warm-up draws uniforms when the chain samples (diverse, no injected u): the device generator is put back
+        self.graph, self.out = packing.warm_up_and_capture(self._body, dev, restore_rng=True)
 
     def _body(self):
-        if self.layouts is None:
-            logits = self.model.forward(self.s, self.x, *self.args)
-        else:
-            ang, _, rseq, rang, _ = self.args
-            logits = self.model.forward_packed(self.s, self.x, ang, rseq, rang, *self.layouts)[None]
-        return sample_p_zs_given_zt_discrete((self.s + 1) / self.T, self.s / self.T, self.x, logits, self.schedule, self.transition,
-                                             self.diverse, is_last_step=False, u=self.u, keyed_draw=self.keyed_draw,
-                                             known=self.known, controls=self.controls)
+        return _denoise_step(self.model, self.s, self.T, self.x, self.args, self.layouts, self.schedule, self.transition,
+                             self.diverse, False, u=self.u, keyed_draw=self.keyed_draw, known=self.known,
+                             controls=self.controls)
 
     def step(self, s_int, x, u=None, known_u=None):
         """z_t -> z_s for the step index ``s_int`` (> 0); returns the graph's output buffer (overwritten by the next call)."""
@@ -375,14 +370,9 @@ def denoise(batch, model: PeptideDiff, noise_schedule, transition, diverse, x_T=
             x = graphed.step(s_int, x, u, ku if graphed.known_u is not None else None)
             continue
         s_array = torch.full((x.shape[0], 1), float(s_int), device=dev)     # [1, 1] packed: every item shares the step
-        if layouts is None:
-            logits = model.forward(s_array, x, ang, lmask, rseq, rang, rmask)
-        else:
-            logits = model.forward_packed(s_array, x, ang, rseq, rang, *layouts)[None]
-        x = sample_p_zs_given_zt_discrete((s_array + 1) / T, s_array / T, x, logits, noise_schedule, transition,
-                                          diverse, is_last_step=s_int == 0, u=u,
-                                          keyed_draw=_keyed_draw(row_keys, seed, s_int, dev),
-                                          known=None if known is None else known + (ku,), controls=controls)
+        x = _denoise_step(model, s_array, T, x, (ang, lmask, rseq, rang, rmask), layouts, noise_schedule, transition, diverse,
+                          s_int == 0, u=u, keyed_draw=_keyed_draw(row_keys, seed, s_int, dev),
+                          known=None if known is None else known + (ku,), controls=controls)
     logp = entropy = None
     if controls is not None or details is not None:      # x holds the last step's logits: pick on the device
         idx, logp, entropy = ops.discrete_final_pick(x.contiguous().float(), None if controls is None else controls.bias,

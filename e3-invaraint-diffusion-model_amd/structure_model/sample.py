@@ -23,6 +23,7 @@ if __package__ in (None, ""):  # executed as a script from inside this directory
 import os
 import pickle
 import warnings
+from dataclasses import dataclass
 
 import torch
 from torch import nn
@@ -115,38 +116,28 @@ def p_sample(model, ligand_mask, ligand_angle_noise, receptor_seq, receptor_mask
     the held positions of the result are overwritten with the forward-noised copy of ``known`` at the level the step lands
     on (``p_sample_loop``, "partial redesign"); ``known_noise`` injects its N(0,1) draw, a ``seed`` keys it (stream 10).
     """
-    held = _known_chain(known, known_mask, known_noise, seed, ligand_mask, ligand_angle_noise, None, "p_sample")
-    if held is not None:
-        if not isinstance(known_levels, KnownLevels):
-            raise ValueError("p_sample: held positions need known_levels=KnownLevels(tables, order of the chain)")
-        x0, m8, kn = held
-        held = (x0.contiguous(), m8.contiguous(), known_levels, known_levels.levels.to(x0.device), float(known_scale),
-                None if kn is None else kn.contiguous())
-    if strided is None and wrap_x0:
-        raise ValueError("p_sample: wrap_x0 belongs to the strided update; pass strided=StridedTables(...)")
-    keyed_step = None
+    x = ligand_angle_noise
+    x0, m8, kn = _known_chain(known, known_mask, known_noise, seed, ligand_mask, x, None, "p_sample")
+    row_keys = None
     if seed is not None:
         if noise is not None:
             raise ValueError("p_sample: pass either an injected noise or a seed, not both")
-        x = ligand_angle_noise
-        keyed_step = _keyed_step(seed, keyed.padded_keys(keyed.item_ids(item_ids, x.shape[0]), x.shape[1], x.device),
-                                 _tables(betas), x.device, strided is None)
+        row_keys = keyed.padded_keys(keyed.item_ids(item_ids, x.shape[0]), x.shape[1], x.device)
     elif item_ids is not None:
         raise ValueError("p_sample: item_ids key the seeded draws; pass a seed with them")
-    if strided is not None:
-        strided = _strided_step(strided, ligand_angle_noise.device, wrap_x0)
-    return _reverse_step(model, ligand_mask, ligand_angle_noise, receptor_seq, receptor_mask,
-                         receptor_angle, timestep, betas, noise, receptor_cache, out, wrap=wrap, keyed_step=keyed_step,
-                         strided=strided, known=held)
+    plan = step_plan(betas, x.device, strided=strided, wrap_x0=wrap_x0, row_keys=row_keys, seed=seed, known=x0,
+                     known_mask=m8, known_levels=known_levels, known_scale=known_scale)
+    return _reverse_step(model, ligand_mask, x, receptor_seq, receptor_mask, receptor_angle, timestep, betas, noise,
+                         receptor_cache, out, wrap=wrap, plan=plan, known_noise=kn)
 
 
 def _known_chain(known, known_mask, known_noises, seed, ligand_mask, x, steps, who):
-    """The held positions of a chain, checked: None (nothing held: the chain runs as without the arguments), or
-    (known float [B,L,F], mask uint8 [B,L,F] -- and-ed with the padding mask --, injected noises or None), padded frame."""
+    """The held positions of a chain, checked, in the padded frame: known float [B,L,F], mask uint8 [B,L,F] -- and-ed with
+    the padding mask --, injected noises or None; three Nones when nothing is held: the chain runs as without them."""
     if known is None and known_mask is None:
         if known_noises is not None:
             raise ValueError(f"{who}: known_noises are the draws of the held positions; pass known and known_mask")
-        return None
+        return None, None, None
     if known is None or known_mask is None:
         raise ValueError(f"{who}: known and known_mask go together")
     if known_noises is not None and seed is not None:
@@ -165,41 +156,121 @@ def _known_chain(known, known_mask, known_noises, seed, ligand_mask, x, steps, w
     m = known_mask.to(dev)
     m = (m if m.dim() == 3 else m[..., None]) & (ligand_mask.to(dev) != 0)[..., None]
     if not bool(m.any()):
-        return None
+        return None, None, None
     return (known.to(dev).float(), m.expand(shape).to(torch.uint8).contiguous(),
             None if known_noises is None else known_noises.to(dev).float())
 
 
-def _compose_known(x, t_dev, t_index, known, keyed_step):
-    """Overwrite the held positions of ``x`` (the update's result) in place for the step at ``t_index``."""
-    x0, m8, kl, levels, scale, noise = known
-    if keyed_step is not None:
-        return ops.keyed_known_compose_wrap(x, x0, m8, levels, t_dev, keyed_step[0], keyed_step[1], scale)
-    if float(kl.levels[t_index, 1]) == 0.0:       # the clean level: a copy, no draw
-        noise = None
-    elif noise is None:
-        noise = torch.randn_like(x)
-    return ops.known_compose_wrap(x, x0, m8, noise, levels, t_dev, scale)
+@dataclass(frozen=True)
+class StepPlan:
+    """What one reverse step of a chain is, decided once per chain or ``p_sample`` call (``step_plan``): the update rule,
+    the source of its draws and the held positions.  The eager step (``_reverse_step``) and the captured one
+    (``GraphedReverseStep``) both run ``update`` then ``compose`` and choose nothing themselves.
+    ``coef``: the device table the update reads by the step index -- [T,4] = (sqrt_recip_alpha, beta,
+    sqrt_one_minus_alphas_cumprod, sigma), or ``strided.coef`` [T,8]; None where no launch of the plan reads one (the
+    eager unkeyed ancestral step takes four scalars from ``tab``).  ``keyed`` = (row keys, seed): the draws are generated
+    inside the kernels (keyed.py); None: noise tensors.  ``known_x0`` / ``known_mask`` (uint8) / ``known_levels`` (a
+    KnownLevels; ``levels``: its table on the device) / ``known_scale``: the held positions; ``known_x0`` None: none."""
+    tab: CosineTables
+    coef: torch.Tensor = None
+    strided: StridedTables = None
+    wrap_x0: bool = False
+    keyed: tuple = None
+    known_x0: torch.Tensor = None
+    known_mask: torch.Tensor = None
+    known_levels: KnownLevels = None
+    levels: torch.Tensor = None
+    known_scale: float = 1.0
+
+    @property
+    def order(self):
+        """The timesteps a chain of this plan may visit, descending: the rows of its tables that are not NaN."""
+        if self.strided is not None:
+            return self.strided.order
+        if self.known_levels is not None:
+            return self.known_levels.order
+        return range(self.tab.betas.shape[0] - 1, -1, -1)
+
+    def update_draws(self, t_index):
+        """Whether the update at ``t_index`` reads a noise tensor: not keyed, not t = 0 (ancestral), not a strided sigma of 0."""
+        if self.keyed is not None:
+            return False
+        if self.strided is not None:
+            return float(self.strided.coef[t_index, 4]) != 0.0
+        return t_index != 0
+
+    def compose_draws(self, t_index):
+        """Whether ``compose`` at ``t_index`` reads a noise tensor: held positions, not keyed, not the clean level."""
+        return self.known_x0 is not None and self.keyed is None and float(self.known_levels.levels[t_index, 1]) != 0.0
+
+    def update(self, x, eps_hat, t_dev, noise, out, wrap, t_index=None):
+        """x_t -> x_{t-1} (``t_dev``: int64 on the device, the step index first).  With the host's ``t_index`` (eager) the
+        draw is settled here -- none where ``update_draws`` says so, else ``noise`` or a fresh ``torch.randn_like`` -- and
+        the unkeyed ancestral update is the scalar launch; without it (captured) ``noise`` is the graph's buffer or None."""
+        eps_hat = eps_hat.contiguous()
+        if t_index is not None:
+            noise = _eager_noise(x, noise, self.update_draws(t_index))
+        if self.strided is not None:      # t -> its successor in the table's order
+            if self.keyed is not None:
+                return ops.keyed_strided_step_wrap(x, eps_hat, self.coef, t_dev, *self.keyed, wrap=wrap,
+                                                   wrap_x0=self.wrap_x0, out=out)
+            return ops.strided_step_wrap(x, eps_hat, noise, self.coef, t_dev, wrap=wrap, wrap_x0=self.wrap_x0, out=out)
+        if self.keyed is not None:
+            return ops.keyed_ddpm_step_wrap(x, eps_hat, self.coef, t_dev, *self.keyed, wrap=wrap, out=out)
+        if t_index is None:
+            return ops.ddpm_step_wrap_table(x, eps_hat, noise, self.coef, t_dev, wrap=wrap, out=out)
+        sra, beta, s1m, sigma = (float(c[t_index]) for c in (self.tab.sqrt_recip_alphas, self.tab.betas,
+                                                             self.tab.sqrt_one_minus_alphas_cumprod, self.tab.sigma))
+        return ops.ddpm_step_wrap(x, eps_hat, noise, sra, beta, s1m, 0.0 if noise is None else sigma, wrap=wrap, out=out)
+
+    def compose(self, x, t_dev, noise, t_index=None):
+        """Overwrite the held positions of ``x`` (the update's result) in place with the forward-noised copy of
+        ``known_x0`` at the level the step landed on; returns ``x``.  ``noise`` / ``t_index`` as for ``update``."""
+        if self.known_x0 is None:
+            return x
+        if self.keyed is not None:
+            return ops.keyed_known_compose_wrap(x, self.known_x0, self.known_mask, self.levels, t_dev, *self.keyed,
+                                                self.known_scale)
+        if t_index is not None:
+            noise = _eager_noise(x, noise, self.compose_draws(t_index))
+        return ops.known_compose_wrap(x, self.known_x0, self.known_mask, noise, self.levels, t_dev, self.known_scale)
 
 
-def _coef_table(tab, dev):
-    """[T,4] = (sqrt_recip_alpha, beta, sqrt_one_minus_alphas_cumprod, sigma): the table the device-step kernels read."""
-    return torch.stack([tab.sqrt_recip_alphas, tab.betas, tab.sqrt_one_minus_alphas_cumprod, tab.sigma],
-                       dim=1).float().contiguous().to(dev)
+def _eager_noise(x, noise, draws):
+    """The noise tensor of an eager launch: None where the step draws nothing, else the injected one or a fresh draw."""
+    if not draws:
+        return None
+    return torch.randn_like(x) if noise is None else noise.contiguous()
 
 
-def _keyed_step(seed, row_keys, tab, dev, ancestral=True):
-    """What a keyed reverse step needs besides the state: (row keys, seed, coefficient table); a strided step brings its
-    own table (``ancestral=False``: None)."""
-    keyed.check_steps(tab.betas.shape[0])
-    return row_keys, keyed.check_seed(seed), _coef_table(tab, dev) if ancestral else None
-
-
-def _strided_step(st, dev, wrap_x0):
-    """What a strided reverse step needs besides the state: (StridedTables, its [T,8] table on the device, wrap_x0)."""
-    if not isinstance(st, StridedTables):
-        raise TypeError(f"strided: expected a StridedTables, got {type(st).__name__}")
-    return st, st.coef.contiguous().to(dev), bool(wrap_x0)
+def step_plan(betas, dev=None, table=False, strided=None, wrap_x0=False, row_keys=None, seed=None, known=None,
+              known_mask=None, known_levels=None, known_scale=1.0):
+    """The StepPlan of a chain, checked.  ``betas``: the schedule betas or a CosineTables; ``dev``: where its tables go.
+    ``table``: build the [T,4] table although the eager step would not read it (a GraphedReverseStep may run the plan); a
+    keyed ancestral plan has it anyway, a strided one has its own.  ``strided``: a StridedTables (+ ``wrap_x0``);
+    ``row_keys`` + ``seed``: keyed draws; ``known`` + ``known_mask`` (uint8; both like the state, in the chain's frame) +
+    ``known_levels`` (a KnownLevels of the chain's order) + ``known_scale``: held positions."""
+    tab = _tables(betas)
+    if strided is None and wrap_x0:
+        raise ValueError("step_plan: wrap_x0 belongs to the strided update; pass strided=StridedTables(...)")
+    if strided is not None and not isinstance(strided, StridedTables):
+        raise TypeError(f"step_plan: strided must be a StridedTables, got {type(strided).__name__}")
+    if (row_keys is None) != (seed is None):
+        raise ValueError("step_plan: keyed draws need both row_keys and a seed")
+    if known is not None and not isinstance(known_levels, KnownLevels):
+        raise ValueError("step_plan: held positions need known_levels=KnownLevels(tables, order of the chain)")
+    if seed is not None:
+        keyed.check_steps(tab.betas.shape[0])
+    coef = None
+    if strided is not None:
+        coef = strided.coef.contiguous().to(dev)
+    elif table or seed is not None:
+        coef = torch.stack([tab.sqrt_recip_alphas, tab.betas, tab.sqrt_one_minus_alphas_cumprod, tab.sigma],
+                           dim=1).float().contiguous().to(dev)
+    held = {} if known is None else dict(known_x0=known.contiguous(), known_mask=known_mask.contiguous(),
+                                         known_levels=known_levels, levels=known_levels.levels.to(dev),
+                                         known_scale=float(known_scale))
+    return StepPlan(tab, coef, strided, bool(wrap_x0), None if seed is None else (row_keys, keyed.check_seed(seed)), **held)
 
 
 def keyed_x_T(seed, item_ids, L, n_ft=8, scale=1.0, device=None):
@@ -212,150 +283,77 @@ def keyed_x_T(seed, item_ids, L, n_ft=8, scale=1.0, device=None):
 
 
 def _reverse_step(model, ligand_mask, x_t, receptor_seq, receptor_mask, receptor_angle, timestep,
-                  betas, noise, receptor_cache, out, wrap, mod=None, layout=None, keyed_step=None, strided=None,
-                  known=None):
-    if known is not None:      # the update as ever, then the held positions on top of its result, on the same stream
-        x = _reverse_step(model, ligand_mask, x_t, receptor_seq, receptor_mask, receptor_angle, timestep, betas, noise,
-                          receptor_cache, out, wrap, mod=mod, layout=layout, keyed_step=keyed_step, strided=strided)
-        if isinstance(timestep, int):
-            t_index, t_dev = timestep, torch.full((1,), timestep, device=x.device, dtype=torch.long)
-        else:
-            t_index, t_dev = int(timestep.reshape(-1)[0].item()), timestep.to(device=x.device, dtype=torch.long).contiguous()
-        return _compose_known(x, t_dev, t_index, known, keyed_step)
-    tab = _tables(betas)
+                  betas, noise, receptor_cache, out, wrap, mod=None, layout=None, plan=None, known_noise=None):
+    """The eager reverse step: decode, ``plan.update``, ``plan.compose``.  ``plan`` None: the plain ancestral step from
+    ``betas``.  ``noise`` / ``known_noise``: injected draws of the update / of the held positions."""
+    plan = step_plan(betas) if plan is None else plan
     if isinstance(timestep, int):
         t_index = timestep
-        timestep = torch.full((x_t.shape[0],), t_index, device=x_t.device, dtype=torch.long)
+        timestep = t_dev = torch.full((x_t.shape[0],), t_index, device=x_t.device, dtype=torch.long)
     else:
         t_unique = torch.unique(timestep)
         assert len(t_unique) == 1, f"Got multiple values for t: {t_unique}"
         t_index = int(t_unique.item())
+        t_dev = timestep.to(device=x_t.device, dtype=torch.long).contiguous()
     if receptor_cache is None:
         receptor_cache = model.encode_receptor(receptor_seq, receptor_angle, receptor_mask)
     eps_hat = model.decode(timestep, x_t, ligand_mask, receptor_cache, mod=mod, layout=layout)
-    sra = float(tab.sqrt_recip_alphas[t_index])
-    beta = float(tab.betas[t_index])
-    s1m = float(tab.sqrt_one_minus_alphas_cumprod[t_index])
-    x_c = x_t.contiguous().float()
-    if strided is not None:        # t -> its successor in the table's order; the row is read at the device step index
-        st, coef8, wrap_x0 = strided
-        t_dev = timestep.to(device=x_c.device, dtype=torch.long).contiguous()
-        if keyed_step is not None:
-            return ops.keyed_strided_step_wrap(x_c, eps_hat.contiguous(), coef8, t_dev, keyed_step[0], keyed_step[1],
-                                               wrap=wrap, wrap_x0=wrap_x0, out=out)
-        if float(st.coef[t_index, 4]) == 0.0:     # eta == 0, or the last visited step: no draw
-            noise = None
-        else:
-            noise = torch.randn_like(x_c) if noise is None else noise.contiguous()
-        return ops.strided_step_wrap(x_c, eps_hat.contiguous(), noise, coef8, t_dev, wrap=wrap, wrap_x0=wrap_x0, out=out)
-    if keyed_step is not None:     # the draw happens in the kernel, at the device step index
-        row_keys, seed, coef = keyed_step
-        t_dev = timestep.to(device=x_c.device, dtype=torch.long).contiguous()
-        return ops.keyed_ddpm_step_wrap(x_c, eps_hat.contiguous(), coef, t_dev, row_keys, seed, wrap=wrap, out=out)
-    if t_index == 0:
-        noise, sigma = None, 0.0
-    else:
-        sigma = float(tab.sigma[t_index])
-        noise = torch.randn_like(x_c) if noise is None else noise.contiguous()
-    return ops.ddpm_step_wrap(x_c, eps_hat.contiguous(), noise, sra, beta, s1m, sigma, wrap=wrap, out=out)
+    x = plan.update(x_t.contiguous().float(), eps_hat, t_dev, noise, out, wrap, t_index)
+    return plan.compose(x, t_dev, known_noise, t_index)
 
 
 class GraphedReverseStep:
-    """One reverse step (decoder forward + DDPM update + wrap) captured once into a HIP graph and replayed
-    per step.  Everything that varies between steps lives on the device: the step index (``self.t``,
-    also the row of the [T,4] coefficient table read by ``e3d_ddpm_step_wrap_table``), the state
-    ``self.x`` and the noise draw.  Results are bit-identical to the eager path for the same noise.
-    A keyed step (``row_keys`` and ``seed``) generates its draw inside the update kernel from the step index: no noise
-    buffer, and bit-identical to the eager keyed step.
-    A strided step (``strided``: a StridedTables) holds that table's [T,8] rows instead and runs
-    ``e3d_strided_step_wrap`` / its keyed form: bit-identical to the eager strided step for the same noise; eta == 0 has
-    no noise buffer and draws nothing.
-    Held positions (``known``) add one launch after the update, on the same stream -- ``e3d_known_compose_wrap`` or its
-    keyed form on ``self.out`` -- and, unseeded, a second noise buffer filled inside the graph; the captured step stays one
-    serial chain.
+    """One reverse step (decoder forward + ``StepPlan.update`` + ``StepPlan.compose``) captured once into a HIP graph and
+    replayed per step.  Everything that varies between steps lives on the device: the step index (``self.t``, also the
+    row of the plan's coefficient table that the update reads), the state ``self.x`` and the noise draw.  Results are
+    bit-identical to the eager path for the same noise, or the same keys.  A keyed plan generates its draws inside the
+    kernels from the step index and a strided one at eta == 0 draws nothing: no noise buffer.  Held positions add one
+    launch after the update, on the same stream and on ``self.out``, and, unseeded, a second noise buffer filled inside
+    the graph; the captured step stays one serial chain.
 
     Default for chains of at most packing.GRAPH_MAX_ROWS token rows (up to ~16 pockets of 64 residues),
     ``use_graph=True`` / E3D_SAMPLE_GRAPH=1 forces it, =0 turns it off.  Measured on MI355X, one 64-residue pocket
-    (tools/bench_single.py): round 1, 6-workgroup tiled GEMMs of ~29 us each: 3.9 ms per replayed step against 3.8 ms
-    eager -- the GPU was 100 % busy with dependent kernels, the graph had nothing to remove.  Round 2, K-sliced small-M
-    GEMMs of ~7 us per product (csrc/gemm_skinny.hip): eager launches are now host-bound at 2.4 ms per step, a replay
-    takes 1.5 ms."""
+    (tools/bench_single.py), with the K-sliced small-M GEMMs of ~7 us per product (csrc/gemm_skinny.hip): eager launches
+    are host-bound at 2.4 ms per step, a replay takes 1.5 ms."""
 
     def __init__(self, model, ligand_mask, cache, tab, x_like, wrap=True, draw=True, mod_table=None, layout=None,
                  row_keys=None, seed=None, strided=None, wrap_x0=False, known=None):
-        """``draw``: the graph draws its own N(0,1) noise each replay; False: ``step`` takes the draw (parity tests).
-        ``row_keys`` + ``seed`` (with ``draw``): the draw is the keyed stream of those rows (keyed.py).
+        """``tab``: the chain's StepPlan (``step_plan(..., table=True)``: the other plan arguments are then not read), or
+        its schedule -- the plan is then built here from ``row_keys`` + ``seed``, ``strided`` (+ ``wrap_x0``) and ``known``
+        = (x0, uint8 mask -- both like ``x_like`` --, KnownLevels, scale), as ``step_plan`` takes them.
+        ``draw``: the graph draws its own N(0,1) noise each replay; False: ``step`` takes the draws (parity tests) -- the
+        update's and, with held positions, theirs next to it.  A keyed plan draws inside its kernels and needs ``draw``.
         ``mod_table`` [T,6H]: row t = model.timestep_modulation(t), read on the device by the step index.
         ``layout``: the step runs on packed ligand rows (``x_like`` [rows,F]; a packed ``cache``); its segment and tile
-        tables are device tensors fixed for the chain, so the capture holds them like any other argument.
-        ``strided`` (+ ``wrap_x0``): the step is the strided update of that StridedTables; ``tab`` is then not read.
-        ``known`` = (x0, uint8 mask -- both like ``x_like`` --, KnownLevels, scale): the held positions; ``step`` then
-        takes their draw next to the update's when the graph was captured without draws of its own."""
+        tables are device tensors fixed for the chain, so the capture holds them like any other argument."""
         dev = x_like.device
-        self.model, self.mask, self.cache, self.wrap, self.mod_table = model, ligand_mask, cache, wrap, mod_table
-        self.layout = layout
-        if (row_keys is None) != (seed is None) or (seed is not None and not draw):
-            raise ValueError("a keyed graph needs row_keys and a seed, and draws its own noise")
-        self.keyed = None if seed is None else (row_keys, keyed.check_seed(seed))
-        self.x = torch.empty_like(x_like)
-        self.out = torch.empty_like(x_like)
-        self.strided = None if strided is None else _strided_step(strided, dev, wrap_x0)
-        if strided is None and wrap_x0:
-            raise ValueError("wrap_x0 belongs to the strided update")
-        noiseless = self.keyed is not None or (strided is not None and strided.eta == 0.0)
-        self.noise = None if noiseless else torch.zeros_like(x_like)
-        # a valid row for the warm-up and the capture (unvisited rows of a strided table are NaN)
-        self.t = torch.full((x_like.shape[0],), 0 if strided is None else strided.order[-1], device=dev, dtype=torch.long)
-        self.coef = _coef_table(tab, dev) if strided is None else self.strided[1]
-        self.draw = draw
-        self.known = self.known_noise = None
-        if known is not None:
-            x0, m8, kl, scale = known
-            self.known = (x0.contiguous(), m8.contiguous(), kl.levels.to(dev), float(scale))
-            self.known_noise = None if self.keyed is not None else torch.zeros_like(x_like)
-        self.x.copy_(x_like)
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):      # warm-up off the capture: first-launch attribute calls, allocator
-            self._body()                   # (one eager step: the chain pays for it once, ~2.4 ms at B=1, L=64)
-        torch.cuda.current_stream(dev).wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self._body()
+        plan = tab if isinstance(tab, StepPlan) else step_plan(tab, dev, True, strided, wrap_x0, row_keys, seed,
+                                                               *(known or (None, None, None, 1.0)))
+        if plan.keyed is not None and not draw:
+            raise ValueError("a keyed graph draws its own noise")
+        if plan.coef is None:
+            raise ValueError("a captured step reads its coefficients from the plan's table: step_plan(..., table=True)")
+        self.model, self.mask, self.cache, self.plan, self.wrap = model, ligand_mask, cache, plan, wrap
+        self.mod_table, self.layout, self.draw = mod_table, layout, draw
+        self.x, self.out = x_like.clone(), torch.empty_like(x_like)
+        # a noise buffer only where some step of the chain reads one (none: keyed draws, or strided at eta == 0)
+        self.noise = torch.zeros_like(x_like) if any(map(plan.update_draws, plan.order)) else None
+        self.known_noise = torch.zeros_like(x_like) if any(map(plan.compose_draws, plan.order)) else None
+        # a valid row for the warm-up and the capture (unvisited rows of a strided or level table are NaN)
+        self.t = torch.full((x_like.shape[0],), plan.order[-1], device=dev, dtype=torch.long)
+        # The warm-up step draws from torch's generator and its state is not put back (the sequence sampler's
+        # GraphedDenoiseStep does put it back): a self-drawing chain starts one step's draws further on when replayed.
+        self.graph, _ = packing.warm_up_and_capture(self._body, dev)
 
     def _body(self):
-        self._update()
-        if self.known is None:
-            return
-        x0, m8, levels, scale = self.known
-        if self.keyed is not None:
-            ops.keyed_known_compose_wrap(self.out, x0, m8, levels, self.t, *self.keyed, scale)
-            return
-        if self.draw:
-            self.known_noise.normal_()
-        ops.known_compose_wrap(self.out, x0, m8, self.known_noise, levels, self.t, scale)
-
-    def _update(self):
         mod = None if self.mod_table is None else self.mod_table.index_select(0, self.t[:1])
         eps_hat = self.model.decode(self.t, self.x, self.mask, self.cache, mod=mod, layout=self.layout)
-        if self.strided is not None:
-            wrap_x0 = self.strided[2]
-            if self.keyed is not None:
-                ops.keyed_strided_step_wrap(self.x, eps_hat.contiguous(), self.coef, self.t, *self.keyed, wrap=self.wrap,
-                                            wrap_x0=wrap_x0, out=self.out)
-                return
-            if self.draw and self.noise is not None:
-                self.noise.normal_()
-            ops.strided_step_wrap(self.x, eps_hat.contiguous(), self.noise, self.coef, self.t, wrap=self.wrap,
-                                  wrap_x0=wrap_x0, out=self.out)
-            return
-        if self.keyed is not None:
-            ops.keyed_ddpm_step_wrap(self.x, eps_hat.contiguous(), self.coef, self.t, *self.keyed, wrap=self.wrap,
-                                     out=self.out)
-            return
-        if self.draw:
+        if self.draw and self.noise is not None:
             self.noise.normal_()
-        ops.ddpm_step_wrap_table(self.x, eps_hat.contiguous(), self.noise, self.coef, self.t, wrap=self.wrap, out=self.out)
+        self.plan.update(self.x, eps_hat, self.t, self.noise, self.out, self.wrap)
+        if self.draw and self.known_noise is not None:
+            self.known_noise.normal_()
+        self.plan.compose(self.out, self.t, self.known_noise)
 
     def step(self, i, x, noise=None, known_noise=None):
         """x_t -> x_{t-1} for step index i; returns the graph's output buffer (overwritten by the next call)."""
@@ -435,18 +433,14 @@ def p_sample_loop(model: nn.Module, ligand_mask, ligand_angle_noise, receptor_se
     order = list(reversed(range(0, total_timesteps, step)))
     strided = StridedTables(tab, order, eta) if update == "strided" else None
     x = ligand_angle_noise.contiguous().float()
-    ids = None
-    held = _known_chain(known, known_mask, known_noises, seed, ligand_mask, x, len(order), "p_sample_loop")
-    if held is not None and (noises is None) != (held[2] is None) and seed is None:
+    x0, m8, known_noises = _known_chain(known, known_mask, known_noises, seed, ligand_mask, x, len(order), "p_sample_loop")
+    if x0 is not None and (noises is None) != (known_noises is None) and seed is None:
         raise ValueError("p_sample_loop: inject noises and known_noises together, or neither")
-    if seed is not None:
-        if noises is not None:
-            raise ValueError("p_sample_loop: pass either injected noises or a seed, not both")
-        ids = keyed.item_ids(item_ids, x.shape[0])
-        seed = keyed.check_seed(seed)
-        keyed.check_steps(total_timesteps)
-    elif item_ids is not None:
+    if seed is not None and noises is not None:
+        raise ValueError("p_sample_loop: pass either injected noises or a seed, not both")
+    if seed is None and item_ids is not None:
         raise ValueError("p_sample_loop: item_ids key the seeded draws; pass a seed with them")
+    ids = None if seed is None else keyed.item_ids(item_ids, x.shape[0])
     frame = packing.Frame(ligand_mask, receptor_mask, trim=trim_padding, pack=pack)
     layout, pocket_layout = frame.layouts or (None, None)
     if pocket_layout is None:
@@ -458,24 +452,19 @@ def p_sample_loop(model: nn.Module, ligand_mask, ligand_angle_noise, receptor_se
     mask = None if layout is not None else frame.ligand(ligand_mask).contiguous().float()   # a packed decode reads none
     if noises is not None:
         noises = frame.ligand(noises.to(x.device).float(), dim=1)
-    row_keys = None if seed is None else frame.row_keys(ids, x.device)
-    keyed_step = None if seed is None else _keyed_step(seed, row_keys, tab, x.device, strided is None)
-    strided_step = None if strided is None else _strided_step(strided, x.device, wrap_x0)
-    known_graph = known_step = known_noises = None
-    if held is not None:       # into the frame like the state; packed tails and trimmed-off rows hold nothing
-        kl = KnownLevels(tab, order)
-        x0, m8 = frame.ligand(held[0]).contiguous(), frame.ligand(held[1]).contiguous()
-        known_noises = None if held[2] is None else frame.ligand(held[2], dim=1)
-        known_graph = (x0, m8, kl, float(known_scale))
-        known_step = (x0, m8, kl, kl.levels.to(x.device), float(known_scale))
+    if x0 is not None:         # into the frame like the state; packed tails and trimmed-off rows hold nothing
+        x0, m8 = frame.ligand(x0), frame.ligand(m8)
+        known_noises = None if known_noises is None else frame.ligand(known_noises, dim=1)
+    plan = step_plan(tab, x.device, table=True, strided=strided, wrap_x0=wrap_x0,
+                     row_keys=None if seed is None else frame.row_keys(ids, x.device), seed=seed, known=x0, known_mask=m8,
+                     known_levels=None if x0 is None else KnownLevels(tab, order), known_scale=known_scale)
     traj = torch.empty((len(order),) + tuple(x.shape), device=x.device, dtype=torch.float32)
     # what depends on the timestep alone, for the whole chain at once: row t of the table = timestep_modulation(t)
     mod_rows = model.timestep_modulation(torch.tensor(order, device=x.device, dtype=torch.long))
     mod_table = torch.zeros((total_timesteps, mod_rows.shape[1]), device=x.device, dtype=torch.float32)
     mod_table[order] = mod_rows
     graphed = packing.capture_graph(
-        lambda: GraphedReverseStep(model, mask, cache, tab, x, draw=noises is None, mod_table=mod_table, layout=layout,
-                                   row_keys=row_keys, seed=seed, strided=strided, wrap_x0=wrap_x0, known=known_graph),
+        lambda: GraphedReverseStep(model, mask, cache, plan, x, draw=noises is None, mod_table=mod_table, layout=layout),
         frame.rows, len(order), use_graph)
     for n, i in enumerate(order):
         kn = None if known_noises is None else known_noises[n].contiguous()
@@ -484,8 +473,7 @@ def p_sample_loop(model: nn.Module, ligand_mask, ligand_angle_noise, receptor_se
             traj[n].copy_(x)
         else:
             x = _reverse_step(model, mask, x, None, None, None, i, tab, None if noises is None else noises[n], cache,
-                              traj[n], wrap=True, mod=mod_table[i:i + 1], layout=layout, keyed_step=keyed_step,
-                              strided=strided_step, known=None if known_step is None else known_step + (kn,))
+                              traj[n], wrap=True, mod=mod_table[i:i + 1], layout=layout, plan=plan, known_noise=kn)
     traj = frame.restore(traj, dim=1)                                     # [T/STEP, B, L, F], zeros outside the frame
     return traj if return_device else traj.cpu()
 

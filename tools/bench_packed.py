@@ -200,11 +200,15 @@ def main():
         """Key table of a frame's rows (--seed), or None."""
         return None if args.seed is None else frames[kind].row_keys(list(range(B)), device)
 
+    def plan_of(kind):
+        """The chain's StepPlan on one frame (--update, --eta, --wrap-x0, --seed)."""
+        keys = frame_keys(kind)
+        return S.step_plan(tab, device, table=True, strided=st, wrap_x0=args.wrap_x0, row_keys=keys,
+                           seed=None if keys is None else args.seed)
+
     def eager(kind, steps):
         mask, xa, cache, layout = frame(kind)
-        keys = frame_keys(kind)
-        ks = None if keys is None else S._keyed_step(args.seed, keys, tab, device)
-        ss = None if st is None else S._strided_step(st, device, args.wrap_x0)
+        plan = plan_of(kind)
         xb = torch.empty_like(xa)
         for k_steps in (args.warmup, steps):
             torch.cuda.synchronize()
@@ -212,7 +216,7 @@ def main():
             for j in range(k_steps):
                 i = 999 - j
                 y = S._reverse_step(model, mask, xa, None, None, None, i, tab, None, cache, xb, True,
-                                    mod=mod_table[i:i + 1], layout=layout, keyed_step=ks, strided=ss)
+                                    mod=mod_table[i:i + 1], layout=layout, plan=plan)
                 xa, xb = y, xa
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
@@ -220,10 +224,8 @@ def main():
 
     def graphed(kind, steps):
         mask, xa, cache, layout = frame(kind)
-        keys = frame_keys(kind)
-        g = S.GraphedReverseStep(model, None if mask is None else mask.contiguous().float(), cache, tab, xa,
-                                 mod_table=mod_table, layout=layout, row_keys=keys, seed=None if keys is None else args.seed,
-                                 strided=st, wrap_x0=args.wrap_x0)
+        g = S.GraphedReverseStep(model, None if mask is None else mask.contiguous().float(), cache, plan_of(kind), xa,
+                                 mod_table=mod_table, layout=layout)
         for k_steps in (args.warmup, steps):
             torch.cuda.synchronize()
             t0 = time.perf_counter()

@@ -31,11 +31,11 @@ DEV = "cuda:0"
 def kernels(batch, seq_len, launches, eta=1.0):
     """Alternate launches of the update kernels on one state; wall time per launch by HIP events as a cross-check."""
     from e3diff_amd import keyed
-    from e3diff_amd.structure_model.sample import _coef_table
+    from e3diff_amd.structure_model.sample import step_plan
     from e3diff_amd.structure_model.utils import CosineTables, KnownLevels, StridedTables
     ops = pkg.ops
     tab = CosineTables(1000)
-    coef4 = _coef_table(tab, DEV)
+    coef4 = step_plan(tab, DEV, table=True).coef
     coef8 = StridedTables(tab, list(reversed(range(1000))), eta).coef.to(DEV)
     g = torch.Generator(device=DEV).manual_seed(0)
     x = (torch.rand(batch, seq_len, 8, device=DEV, generator=g) * 6.28 - 3.14).contiguous()
