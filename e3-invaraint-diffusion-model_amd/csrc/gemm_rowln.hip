@@ -651,7 +651,7 @@ extern "C" int e3d_weight_planes_f32_split(const float* W, int N, int K, int ter
 }
 
 extern "C" int e3d_gemm_residual_layernorm_supported(int M, int N, int K, int64_t lda) {
-    return M >= 32 && M % 32 == 0 && N == RN && K >= 64 && K % 32 == 0 && lda >= K && lda % 4 == 0 && (int64_t)RBM * lda < (1ll << 31);
+    return M >= 32 && M % 32 == 0 && N == RN && K >= 64 && K % 32 == 0 && lda >= K && lda % 4 == 0 && (int64_t)RBM * lda < (1ll << 30);
 }
 
 extern "C" int e3d_gemm_residual_layernorm_f32_split(const float* A, int64_t lda, const void* w_planes, const float* bias,
@@ -660,10 +660,11 @@ extern "C" int e3d_gemm_residual_layernorm_f32_split(const float* A, int64_t lda
                                                      float out_scale, void* stream) {
     E3D_REQUIRE(A && w_planes && gamma && beta && out, "gemm_residual_layernorm: null pointer");
     E3D_REQUIRE(e3d_gemm_residual_layernorm_supported(M, N, K, lda),
-                "gemm_residual_layernorm: need M%%32==0, N==768, K%%32==0, K>=64 (M=%d N=%d K=%d lda=%lld)", M, N, K, (long long)lda);
+                "gemm_residual_layernorm: need M%%32==0, N==768, K%%32==0, K>=64, lda%%4==0, 96*lda < 2^30 (M=%d N=%d K=%d lda=%lld)", M, N, K,
+                (long long)lda);
     E3D_REQUIRE(((uintptr_t)A % 16) == 0 && ((uintptr_t)w_planes % 16) == 0 && ldo >= N, "gemm_residual_layernorm: alignment / ldo");
-    E3D_REQUIRE(!residual || (ldr >= N && ldr % 4 == 0 && ((uintptr_t)residual % 16) == 0 && 16 * ldr < (1ll << 31)),
-                "gemm_residual_layernorm: residual needs ldr >= N, ldr%%4==0, 16-byte alignment");
+    E3D_REQUIRE(!residual || (ldr >= N && ldr % 4 == 0 && ((uintptr_t)residual % 16) == 0 && 16 * ldr < (1ll << 30)),
+                "gemm_residual_layernorm: residual needs ldr >= N, ldr%%4==0, 16*ldr < 2^30, 16-byte alignment (ldr=%lld)", (long long)ldr);
     E3D_REQUIRE(terms == 3 || terms == E3D_TERMS_F16X3, "gemm_residual_layernorm: terms must be 3 or 19 (got %d)", terms);
     hipStream_t s = (hipStream_t)stream;
     if (terms == 3) return launch_rowln<__bf16>(A, lda, w_planes, bias, residual, ldr, gamma, beta, eps, out, ldo, M, K, out_scale, s);
@@ -697,8 +698,9 @@ extern "C" int e3d_gemm_residual_layernorm_planes_split(const void* a_planes, co
     E3D_REQUIRE(e3d_gemm_residual_layernorm_supported(M, N, K, K),
                 "gemm_residual_layernorm (planes): need M%%32==0, N==768, K%%32==0, K>=64 (M=%d N=%d K=%d)", M, N, K);
     E3D_REQUIRE(((uintptr_t)a_planes % 16) == 0 && ((uintptr_t)w_planes % 16) == 0 && ldo >= N, "gemm_residual_layernorm (planes): alignment / ldo");
-    E3D_REQUIRE(!residual || (ldr >= N && ldr % 4 == 0 && ((uintptr_t)residual % 16) == 0 && 16 * ldr < (1ll << 31)),
-                "gemm_residual_layernorm (planes): residual needs ldr >= N, ldr%%4==0, 16-byte alignment");
+    E3D_REQUIRE(!residual || (ldr >= N && ldr % 4 == 0 && ((uintptr_t)residual % 16) == 0 && 16 * ldr < (1ll << 30)),
+                "gemm_residual_layernorm (planes): residual needs ldr >= N, ldr%%4==0, 16*ldr < 2^30, 16-byte alignment (ldr=%lld)",
+                (long long)ldr);
     E3D_REQUIRE(terms == 3 || terms == E3D_TERMS_F16X3, "gemm_residual_layernorm (planes): terms must be 3 or 19 (got %d)", terms);
     hipStream_t s = (hipStream_t)stream;
     const float* A = reinterpret_cast<const float*>(a_planes);

@@ -617,7 +617,11 @@ int e3d_layernorm_bwd_ws(const float* dy, const float* s, const float* gamma, fl
  *     per weight version; e3d_weight_planes_bytes(N, K) = N K 4 bytes; for terms = 19 split the power-of-two-scaled weight
  *     and pass the inverse power as out_scale, exactly as for the *_ex GEMM entry points);
  *   residual may be NULL; A, residual and out are row-strided (lda, ldr, ldo in floats).
- * Shapes: N = 768, M % 32 == 0, K % 32 == 0, K >= 64 (e3d_gemm_residual_layernorm_supported). */
+ * Shapes: N = 768, M % 32 == 0, K % 32 == 0, K >= 64 (e3d_gemm_residual_layernorm_supported).
+ * Strides: lda >= K, ldr >= N, ldo >= N; lda % 4 == 0 and ldr % 4 == 0 (16-byte rows); 96 * lda < 2^30 and 16 * ldr < 2^30:
+ * the kernel addresses the rows of one tile (96 of A, 16 of the residual) by 32-bit BYTE offsets from the tile's first row,
+ * so the largest, (95 * lda + 28) * 4 + 16, must stay below 2^32.  The predicate refuses a larger lda, the entry points
+ * a larger ldr. */
 int64_t e3d_weight_planes_bytes(int N, int K);
 int e3d_weight_planes_f32_split(const float* W, int N, int K, int terms, void* planes, void* stream);
 int e3d_gemm_residual_layernorm_supported(int M, int N, int K, int64_t lda);
