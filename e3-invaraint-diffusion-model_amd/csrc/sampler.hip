@@ -1,5 +1,6 @@
 // Diffusion-process kernels: DDPM ancestral update + angular wrap, the strided (DDIM / respaced) update t -> s < t,
-// forward noising, and the discrete (BLOSUM / uniform transition) posterior + categorical draw.  All HBM-bound.
+// forward noising, the discrete (BLOSUM / uniform transition) posterior + categorical draw, and the score terms of a
+// supplied sequence under that posterior.  All HBM- or latency-bound.
 // The keyed forms (seeded chains) generate their draws in-register from (seed, row key, step): e3d_philox.h.
 #include "e3d_common.h"
 #include "e3d_philox.h"
@@ -562,6 +563,200 @@ __global__ __launch_bounds__(256) void discrete_known_compose_kernel(
     idx[n] = pick_class(p, C, tot, mode, un);
 }
 
+// ---------------------------------------------------------------- scoring supplied sequences
+// Forward noising of N = levels x items at once: row (n, l) is drawn from column x0 of Qtb[n], discrete_q_sample_kernel's
+// convention and arithmetic, with the uniform of stream 11 at the step field level_steps[n] -- the draw
+// discrete_known_compose_kernel<true> makes for a held row at that step.  A row of no item (x0 outside [0, C), a key
+// position outside [0, 2^24), a step outside [0, max_step]) gets class 0.
+__global__ __launch_bounds__(256) void discrete_forward_levels_kernel(
+    const int32_t* __restrict__ x0_idx, const float* __restrict__ Qtb, const int64_t* __restrict__ row_keys,
+    const int64_t* __restrict__ level_steps, int max_step, uint64_t seed, int32_t* __restrict__ out_idx, int L, int C,
+    int64_t n_rows) {
+    const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= n_rows) return;
+    const int x0 = x0_idx[n];
+    const int64_t pos = row_keys[2 * n + 1];
+    const int64_t step = level_steps[n / L];
+    if (x0 < 0 || x0 >= C || pos < 0 || pos >= ((int64_t)1 << 24) || step < 0 || step > max_step) {
+        out_idx[n] = 0;
+        return;
+    }
+    const float* q = Qtb + (n / L) * C * C;
+    float p[CMAX];
+    float tot = 0.f;
+#pragma unroll
+    for (int c = 0; c < CMAX; ++c) {
+        p[c] = c < C ? q[c * C + x0] : 0.f;
+        tot += p[c];
+    }
+    const float un = e3d_keyed_uniform(e3d_keyed_words(seed, (uint64_t)row_keys[2 * n], E3D_KNOWN_STREAM_SEQ, (uint32_t)step,
+                                                       (uint32_t)pos, 0).w[0]);
+    out_idx[n] = pick_class(p, C, tot, 1, un);
+}
+
+// The score terms of rows whose clean class x0 is known; one workgroup per item, its tables in LDS like
+// discrete_posterior_kernel, whose arithmetic for p is restated here expression by expression (p_out == its prob_out,
+// bit for bit).
+//   nll  = -log_softmax(logits)[x0] = lse - (logit[x0] - mx), lse = logf(se): the exponentials and their sum are the
+//          ones the x0 prediction pred = e / se is made of
+//   p    = the normalised posterior mixture under pred
+//   q    = the same expression under the one-hot of x0.  Only the x0 term of the mixture is non-zero there, and
+//          0 + 1 * v == v in fp32, fused or not, so the C - 1 zero terms are not computed
+//   term = KL(q || p) = sum_c q[c] * (logf(q[c]) - logf(p[c])) over the classes with q[c] > 0, in class order (0 log 0
+//          = 0).  A class with q > 0 and p == 0 adds +inf; no term is -inf or NaN, so the sum is finite or +inf.
+// is_final items (the chain's last step picks from the raw logits): term = nll, the tables are not read, p_out and
+// q_out get NaN.  A row with x0 or xt outside [0, C): NaN in every output.
+__global__ __launch_bounds__(256) void discrete_score_rows_kernel(
+    const int32_t* __restrict__ xt_idx, const int32_t* __restrict__ x0_idx, const float* __restrict__ logits,
+    const float* __restrict__ Qsb, const float* __restrict__ Qtb, const uint8_t* __restrict__ is_final,
+    float* __restrict__ term, float* __restrict__ nll, float* __restrict__ p_out, float* __restrict__ q_out, int L, int C) {
+    __shared__ float s_qsb[CMAX * CMAX], s_qtb[CMAX * CMAX], s_qt[CMAX * CMAX], s_rs[CMAX];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int CC = C * C;
+    const bool fin = is_final[b] != 0;      // one value per workgroup: the barriers below are met by all or by none
+    if (!fin) {
+        for (int i = tid; i < CC; i += blockDim.x) {
+            s_qsb[i] = Qsb[(int64_t)b * CC + i];
+            s_qtb[i] = Qtb[(int64_t)b * CC + i];
+        }
+        __syncthreads();
+        if (tid < C) {
+            float rs = 0.f;
+            for (int j = 0; j < C; ++j) rs += s_qsb[tid * C + j] / s_qtb[tid * C + j];
+            s_rs[tid] = rs;
+        }
+        __syncthreads();
+        for (int i = tid; i < CC; i += blockDim.x) s_qt[i] = (s_qsb[i] / s_qtb[i]) / s_rs[i / C];
+        __syncthreads();
+    }
+    const float nan = __builtin_nanf("");
+
+    for (int l = tid; l < L; l += blockDim.x) {
+        const int64_t n = (int64_t)b * L + l;
+        const int xt = xt_idx[n], x0 = x0_idx[n];
+        if (x0 < 0 || x0 >= C || xt < 0 || xt >= C) {
+            term[n] = nan;
+            nll[n] = nan;
+            for (int c = 0; c < C; ++c) {
+                if (p_out) p_out[n * C + c] = nan;
+                if (q_out) q_out[n * C + c] = nan;
+            }
+            continue;
+        }
+        const float* lg = logits + n * C;
+        float pred[CMAX], prob[CMAX];
+        float mx = -INFINITY, lg0 = 0.f;
+#pragma unroll
+        for (int c = 0; c < CMAX; ++c) {
+            pred[c] = c < C ? lg[c] : -INFINITY;
+            if (c == x0) lg0 = pred[c];
+            mx = fmaxf(mx, pred[c]);
+        }
+        float se = 0.f;
+#pragma unroll
+        for (int c = 0; c < CMAX; ++c) {
+            pred[c] = c < C ? expf(pred[c] - mx) : 0.f;
+            se += pred[c];
+        }
+        const float ce = logf(se) - (lg0 - mx);
+        nll[n] = ce;
+        if (fin) {
+            term[n] = ce;
+            for (int c = 0; c < C; ++c) {
+                if (p_out) p_out[n * C + c] = nan;
+                if (q_out) q_out[n * C + c] = nan;
+            }
+            continue;
+        }
+#pragma unroll
+        for (int c = 0; c < CMAX; ++c) { pred[c] = pred[c] / se; prob[c] = 0.f; }
+#pragma unroll 1
+        for (int k = 0; k < C; ++k) {
+            float den = s_qtb[k * C + xt];
+            if (den == 0.f) den = 1e-6f;
+            const float w = pred[k];
+#pragma unroll
+            for (int c = 0; c < CMAX; ++c)
+                if (c < C) prob[c] += w * ((s_qt[c * C + xt] * s_qsb[k * C + c]) / den);
+        }
+        float tot = 0.f;
+#pragma unroll
+        for (int c = 0; c < CMAX; ++c)
+            if (c < C) tot += prob[c];
+        if (tot == 0.f) {
+#pragma unroll
+            for (int c = 0; c < CMAX; ++c) prob[c] = c < C ? 1e-5f : 0.f;
+            tot = 0.f;
+#pragma unroll
+            for (int c = 0; c < CMAX; ++c)
+                if (c < C) tot += prob[c];
+        }
+#pragma unroll
+        for (int c = 0; c < CMAX; ++c) prob[c] = c < C ? prob[c] / tot : 0.f;
+        // q: the x0 term alone; pred is free now and holds it
+        float qden = s_qtb[x0 * C + xt];
+        if (qden == 0.f) qden = 1e-6f;
+        float qtot = 0.f;
+#pragma unroll
+        for (int c = 0; c < CMAX; ++c) {
+            pred[c] = c < C ? (s_qt[c * C + xt] * s_qsb[x0 * C + c]) / qden : 0.f;
+            qtot += pred[c];
+        }
+        if (qtot == 0.f) {
+            qtot = 0.f;
+#pragma unroll
+            for (int c = 0; c < CMAX; ++c) {
+                pred[c] = c < C ? 1e-5f : 0.f;
+                qtot += pred[c];
+            }
+        }
+        float kl = 0.f;
+#pragma unroll
+        for (int c = 0; c < CMAX; ++c) {
+            pred[c] = c < C ? pred[c] / qtot : 0.f;
+            if (pred[c] > 0.f) kl += prob[c] > 0.f ? pred[c] * (logf(pred[c]) - logf(prob[c])) : INFINITY;
+        }
+        term[n] = kl;
+        if (p_out) {
+#pragma unroll
+            for (int c = 0; c < CMAX; ++c)
+                if (c < C) p_out[n * C + c] = prob[c];
+        }
+        if (q_out) {
+#pragma unroll
+            for (int c = 0; c < CMAX; ++c)
+                if (c < C) q_out[n * C + c] = pred[c];
+        }
+    }
+}
+
+// Masked sums of the rows of values [N, L], one wave per item and no atomics: lane j adds positions j, j + 64, ... in
+// order, a masked-out position adding an exact +0, then the 64 lanes meet in a fixed xor butterfly (32, 16, .. 1).  The
+// result is a function of the item's (position, value) pairs alone: trailing masked-out positions add +0 to sums that
+// are never -0, so an item gives the same bits at L = 64 and L = 128, alone or in any batch.
+__global__ __launch_bounds__(64) void masked_item_sums_kernel(
+    const float* __restrict__ values, const uint8_t* __restrict__ mask, float* __restrict__ sums,
+    int32_t* __restrict__ counts, int L) {
+    const int64_t base = (int64_t)blockIdx.x * L;
+    const int lane = threadIdx.x;
+    float acc = 0.f;
+    int cnt = 0;
+    for (int l = lane; l < L; l += 64) {
+        const bool on = mask[base + l] != 0;
+        acc += on ? values[base + l] : 0.f;
+        cnt += on ? 1 : 0;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        acc += __shfl_xor(acc, off, 64);
+        cnt += __shfl_xor(cnt, off, 64);
+    }
+    if (lane == 0) {
+        sums[blockIdx.x] = acc;
+        counts[blockIdx.x] = cnt;
+    }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------- what the entry points share
@@ -841,4 +1036,38 @@ extern "C" int e3d_discrete_final_pick(const float* logits, const float* bias, f
     hipLaunchKernelGGL(discrete_final_pick_kernel, dim3(row_blocks(rows)), dim3(256), 0, (hipStream_t)stream,
                        logits, bias, inv_temp, out_idx, logp, entropy, rows, C);
     return e3d_launch_status("e3d_discrete_final_pick");
+}
+
+// ---------------------------------------------------------------- scoring supplied sequences (entry points)
+extern "C" int e3d_keyed_discrete_forward_levels(const int32_t* x0_idx, const float* Qtb, const int64_t* row_keys,
+                                                 const int64_t* level_steps, int max_step, uint64_t seed,
+                                                 int32_t* out_idx, int N, int L, int C, void* stream) {
+    E3D_REQUIRE(x0_idx && Qtb && row_keys && level_steps && out_idx && N > 0 && L > 0,
+                "keyed_discrete_forward_levels: bad arguments");
+    E3D_REQUIRE(max_step >= 0 && max_step <= 65535,
+                "keyed_discrete_forward_levels: keyed streams hold steps up to 65535 (max_step=%d)", max_step);
+    E3D_REQUIRE(L <= 1 << 24, "keyed_discrete_forward_levels: positions must stay below 2^24 (L=%d)", L);
+    E3D_REQUIRE(C >= 2 && C <= CMAX, "keyed_discrete_forward_levels: C must be in [2,%d] (C=%d)", CMAX, C);
+    const int64_t n = (int64_t)N * L;
+    hipLaunchKernelGGL(discrete_forward_levels_kernel, dim3(row_blocks(n)), dim3(256), 0, (hipStream_t)stream, x0_idx, Qtb,
+                       row_keys, level_steps, max_step, seed, out_idx, L, C, n);
+    return e3d_launch_status("e3d_keyed_discrete_forward_levels");
+}
+
+extern "C" int e3d_discrete_score_rows(const int32_t* xt_idx, const int32_t* x0_idx, const float* logits, const float* Qsb,
+                                       const float* Qtb, const uint8_t* is_final, float* term, float* nll, float* p_out,
+                                       float* q_out, int N, int L, int C, void* stream) {
+    E3D_REQUIRE(xt_idx && x0_idx && logits && Qsb && Qtb && is_final && term && nll && N > 0 && L > 0,
+                "discrete_score_rows: bad arguments");
+    E3D_REQUIRE(C >= 2 && C <= CMAX, "discrete_score_rows: C must be in [2,%d] (C=%d)", CMAX, C);
+    hipLaunchKernelGGL(discrete_score_rows_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, xt_idx, x0_idx, logits, Qsb,
+                       Qtb, is_final, term, nll, p_out, q_out, L, C);
+    return e3d_launch_status("e3d_discrete_score_rows");
+}
+
+extern "C" int e3d_masked_item_sums(const float* values, const uint8_t* mask, float* sums, int32_t* counts, int N, int L,
+                                    void* stream) {
+    E3D_REQUIRE(values && mask && sums && counts && N > 0 && L > 0, "masked_item_sums: bad arguments");
+    hipLaunchKernelGGL(masked_item_sums_kernel, dim3(N), dim3(64), 0, (hipStream_t)stream, values, mask, sums, counts, L);
+    return e3d_launch_status("e3d_masked_item_sums");
 }

@@ -132,6 +132,10 @@ _SIGNATURES = {
     "e3d_keyed_discrete_posterior_sample_ctl": (c_int, [_P, _P, _P, c_float, _P, _P, _P, c_uint64, _P, _P, c_int, c_int, c_int,
                                                         _P]),
     "e3d_discrete_final_pick": (c_int, [_P, _P, c_float, _P, _P, _P, c_int64, c_int, _P]),
+    # scoring supplied sequences: forward noising at per-item levels, per-row score terms, fixed-shape item sums
+    "e3d_keyed_discrete_forward_levels": (c_int, [_P, _P, _P, _P, c_int, c_uint64, _P, c_int, c_int, c_int, _P]),
+    "e3d_discrete_score_rows": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    "e3d_masked_item_sums": (c_int, [_P, _P, _P, _P, c_int, c_int, _P]),
     # keyed training and validation draws (ids and epoch read from device memory)
     "e3d_keyed_timesteps": (c_int, [_P, _P, c_uint64, c_int, c_int, _P, c_int, _P]),
     "e3d_keyed_q_sample_wrap": (c_int, [_P, _P, _P, _P, c_int, c_float, _P, _P, c_uint64, _P, _P, c_int, c_int, c_int, _P]),

@@ -32,7 +32,8 @@ MAX_EPOCH = VALIDATION_EPOCH - 1
 # position, block 0); an item's ligand position l and pocket position l must not share decisions, hence two streams
 DROP_LIGAND, DROP_POCKET = 8, 9
 # partial redesign (replacement conditioning): the forward-noised copies of the held ligand positions, drawn at the step
-# index of the chain; streams 1 and 3 stay as they are, so the free positions draw what they drew before
+# index of the chain; streams 1 and 3 stay as they are, so the free positions draw what they drew before.
+# sample.score_sequences noises a supplied sequence with KNOWN_SEQ too: the same law at the same step field
 KNOWN_STRUCT, KNOWN_SEQ = 10, 11
 
 

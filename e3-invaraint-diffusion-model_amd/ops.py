@@ -1240,6 +1240,77 @@ def keyed_discrete_known_compose(idx, x0_idx, mask, qsb, row_keys, seed, s_dev):
     return idx
 
 
+# ------------------------------------------------------------------------------------------ scoring supplied sequences
+# N = levels x items rows of tables per launch (sequence_model/sample.py::score_sequences).
+
+def keyed_discrete_forward_levels(x0_idx, qtb, row_keys, level_steps, seed, max_step):
+    """z_t int32 [N,L] of N items at their own levels: row (n, l) drawn from column x0_idx[n, l] (int32, -1 = padding row)
+    of ``qtb`` [N,C,C] with the uniform of (seed, row key, stream 11, level_steps[n]); ``level_steps`` int64 [N] on the
+    device, every entry in [0, max_step].  Rows of no item get class 0.  For equal steps this is
+    keyed_discrete_known_compose with a full mask."""
+    name = "keyed_discrete_forward_levels"
+    _chk(x0_idx, name + ".x0_idx", torch.int32); _chk(qtb, name + ".qtb"); _chk(level_steps, name + ".level_steps", torch.int64)
+    if x0_idx.dim() != 2:
+        raise ValueError(f"{name}: x0_idx must be [N, L], got {tuple(x0_idx.shape)}")
+    N, L = x0_idx.shape
+    C = qtb.shape[-1]
+    if qtb.shape != (N, C, C) or level_steps.shape != (N,):
+        raise ValueError(f"{name}: qtb must be [{N}, C, C] and level_steps [{N}], got {tuple(qtb.shape)} and "
+                         f"{tuple(level_steps.shape)}")
+    if not (x0_idx.is_contiguous() and qtb.is_contiguous() and level_steps.is_contiguous()):
+        raise ValueError(f"{name}: arguments must be contiguous")
+    if not 0 <= int(max_step) <= keyed.MAX_STEP:
+        raise ValueError(f"{name}: keyed streams hold steps up to {keyed.MAX_STEP}, got max_step={max_step}")
+    if L > keyed.MAX_POSITION:
+        raise ValueError(f"{name}: keyed streams hold positions below 2^24, got a frame of {L}")
+    _chk_keys(row_keys, N * L, name)
+    out = torch.empty((N, L), device=qtb.device, dtype=torch.int32)
+    with _timed("discrete_forward_levels"):
+        hip.check(hip.lib().e3d_keyed_discrete_forward_levels(_p(x0_idx), _p(qtb), _p(row_keys), _p(level_steps), int(max_step),
+                                                              keyed.check_seed(seed), _p(out), N, L, C, _stream()),
+                  "e3d_keyed_discrete_forward_levels")
+    return out
+
+
+def discrete_score_rows(xt_idx, x0_idx, logits, qsb, qtb, is_final, want_probs=False):
+    """(term, nll) float [N,L] of rows whose clean class is known: nll = -log_softmax(logits)[x0]; term = KL(q || p) in
+    nats with p the posterior of discrete_posterior_sample (want_prob) and q the same expression under the one-hot of
+    x0; items with ``is_final`` (uint8 [N]) set have term = nll and never read their tables.  Rows with x0_idx < 0: NaN.
+    ``want_probs``: (term, nll, p, q) with p, q [N,L,C]."""
+    name = "discrete_score_rows"
+    N, L, C, _ = _chk_posterior(xt_idx, logits, qsb, qtb)
+    _chk(x0_idx, name + ".x0_idx", torch.int32); _chk(is_final, name + ".is_final", torch.uint8)
+    if x0_idx.shape != (N, L) or is_final.shape != (N,) or not (x0_idx.is_contiguous() and is_final.is_contiguous()):
+        raise ValueError(f"{name}: x0_idx must be a contiguous [{N}, {L}] and is_final a contiguous [{N}], got "
+                         f"{tuple(x0_idx.shape)} and {tuple(is_final.shape)}")
+    term = torch.empty((N, L), device=logits.device, dtype=torch.float32)
+    nll = torch.empty_like(term)
+    p = torch.empty((N, L, C), device=logits.device, dtype=torch.float32) if want_probs else None
+    q = torch.empty_like(p) if want_probs else None
+    with _timed("discrete_score_rows"):
+        hip.check(hip.lib().e3d_discrete_score_rows(_p(xt_idx), _p(x0_idx), _p(logits), _p(qsb), _p(qtb), _p(is_final), _p(term),
+                                                    _p(nll), _p(p), _p(q), N, L, C, _stream()), "e3d_discrete_score_rows")
+    return (term, nll, p, q) if want_probs else (term, nll)
+
+
+def masked_item_sums(values, mask):
+    """(sums float [N], counts int32 [N]) of values [N,L] over mask (uint8 [N,L]) != 0, in a fixed reduction shape: the
+    same bits for an item whatever its padding or batch.  Masked-out values are not read into the sum (NaN allowed)."""
+    name = "masked_item_sums"
+    _chk(values, name + ".values"); _chk(mask, name + ".mask", torch.uint8)
+    if values.dim() != 2 or mask.shape != values.shape or not (values.is_contiguous() and mask.is_contiguous()):
+        raise ValueError(f"{name}: values and mask must be the same contiguous [N, L], got {tuple(values.shape)} and "
+                         f"{tuple(mask.shape)}")
+    N, L = values.shape
+    sums = torch.zeros((N,), device=values.device, dtype=torch.float32)
+    counts = torch.zeros((N,), device=values.device, dtype=torch.int32)
+    if N * L:
+        with _timed("masked_item_sums"):
+            hip.check(hip.lib().e3d_masked_item_sums(_p(values), _p(mask), _p(sums), _p(counts), N, L, _stream()),
+                      "e3d_masked_item_sums")
+    return sums, counts
+
+
 KEYED_NORMAL, KEYED_UNIFORM, KEYED_ONEHOT, KEYED_CLASS = 0, 1, 2, 3
 
 

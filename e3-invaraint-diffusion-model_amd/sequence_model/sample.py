@@ -408,6 +408,193 @@ def _keyed_draw(row_keys, seed, s_int, dev):
     return None if seed is None else (row_keys, seed, torch.full((1,), s_int, device=dev, dtype=torch.long))
 
 
+def score_levels(T, levels=None):
+    """The step indices ``score_sequences`` evaluates and the weight of their KL terms: ``levels=None`` -> every index
+    0 .. T-1 and w = 1; ``levels=k`` -> {0} and the multiples k, 2k, .. below T, w = (T - 1) / (their number), so that
+    w times their sum estimates the sum over all T - 1 indices s > 0 (w = 0 when there is none)."""
+    k = 1 if levels is None else int(levels)
+    if k < 1:
+        raise ValueError(f"score_sequences: levels must be a positive stride, got {levels!r}")
+    S = [0] + list(range(k, T, k))
+    return S, ((T - 1) / (len(S) - 1) if len(S) > 1 else 0.0)
+
+
+def sequence_indices(sequences, ligand_mask, num_classes=20):
+    """Class indices int32 [B, L] of B strings over ``AA_VOCAB``, written to the valid positions of ``ligand_mask``
+    [B, L] in order, -1 elsewhere.  A string of another length than its item's ligand, or a letter outside the
+    vocabulary, raises ``ValueError``."""
+    valid = ligand_mask.cpu() != 0
+    B, L = valid.shape
+    if isinstance(sequences, str) or len(sequences) != B:
+        raise ValueError(f"score_sequences: sequences must be a list of {B} strings, one per item")
+    letters = {a: i for i, a in enumerate(AA_VOCAB[:num_classes])}
+    idx = torch.full((B, L), -1, dtype=torch.int32)
+    for b, seq in enumerate(sequences):
+        n = int(valid[b].sum())
+        if not isinstance(seq, str) or len(seq) != n:
+            raise ValueError(f"score_sequences: item {b} has a ligand of {n} residues, its sequence "
+                             f"{len(seq) if isinstance(seq, str) else type(seq).__name__}")
+        bad = sorted(set(seq) - set(letters))
+        if bad:
+            raise ValueError(f"score_sequences: item {b}: letters {''.join(bad)!r} are outside the vocabulary {''.join(letters)}")
+        idx[b, valid[b]] = torch.tensor([letters[a] for a in seq], dtype=torch.int32)
+    return idx
+
+
+def prior_terms(q_top, x0):
+    """float64 [B, L]: KL(q(z_T | x0) || uniform) = sum_c p[c] log(C p[c]) with p the normalised column x0 of the table
+    at level 1 (``q_top`` [C, C]), 0 log 0 = 0; 0 where x0 < 0.  Host arithmetic."""
+    q = q_top.detach().double().cpu()
+    C = q.shape[0]
+    p = q / q.sum(dim=0, keepdim=True)
+    per_class = torch.where(p > 0, p * torch.log(C * p.clamp_min(1e-300)), torch.zeros((), dtype=torch.float64)).sum(dim=0)
+    return torch.where(x0 >= 0, per_class[x0.clamp_min(0).long()], torch.zeros((), dtype=torch.float64))
+
+
+@torch.no_grad()
+def score_sequences(batch, model, noise_schedule, transition, sequences=None, *, levels=None, seed=None, item_ids=None,
+                    us=None, generated_angles=None, score_mask=None, trim_padding=False, timesteps=None,
+                    levels_per_launch=None, details=None):
+    """How much the model likes given sequences: the variational score of the sampler's own reverse law, in nats per
+    residue (lower: the model likes the sequence better -- the sense of ``denoise``'s ``details["score"]``, but for any
+    sequence, on one scale).
+
+    ``sequences``: B strings over ``AA_VOCAB``, item b's as long as its ligand; None scores the batch's own ``ligand_seq``.
+    With the sampler's indexing -- step index s in 0 .. T-1 reads a state at level (s + 1) / T, feeds the model the
+    timestep s and lands on level s / T -- an item with sequence x0 gets, per ligand position,
+
+      * z_t ~ q(. | x0) at level (s + 1) / T, p[c] = Qtb[c][x0] (``apply_aa_noise``'s law; every position is noised);
+      * logits = model.forward(s, onehot(z_t), ...), the call the sampler makes;
+      * s > 0: term = KL(q_post(. | z_t, x0) || p_theta(. | z_t)), p_theta the normalised posterior the sampler draws
+        from (``e3d_discrete_posterior_sample``'s prob_out, its zero rules included) and q_post the same expression with
+        the x0 prediction replaced by the one-hot of x0; 0 log 0 = 0, and +inf (never NaN) where q_post > 0 meets
+        p_theta == 0, which takes an fp32 softmax underflow (a logit gap above about 100);
+        s == 0: term = -log_softmax(logits)[x0] (the chain's last step picks from the raw logits);
+        at every level nll = -log_softmax(logits)[x0], the denoising cross-entropy;
+      * prior = sum_c p[c] log(C p[c]), p the normalised column x0 of the table at level 1 (float64, on the host).
+
+    Over a set S of step indices that contains 0, bound = prior + term_0 + w * sum_{s in S, s > 0} term_s summed over the
+    scored positions, w = (T - 1) / |S \\ {0}|, and score = bound / (number of scored positions).  ``levels=None``: all T
+    indices (w = 1, the sum is exact); ``levels=k``: {0} and k, 2k, ...  (``score_levels``).
+
+    What this number is: zero exactly when the reverse law given the model's prediction equals the reverse law given
+    the true residue, at every level drawn.  The posterior's one-step matrix is a row-normalised Qsb / Qtb (as in the
+    reference sampler), not the forward process's own, so this is NOT a certified bound on a log-likelihood of the
+    forward process.  No trained checkpoint ships with the tree: nothing about its ranking quality has been measured.
+
+    Draws.  ``seed``: an int or a sequence of ints; each seed gives one keyed draw per (item, level, position) -- stream
+    11, "the forward-noised copy of a known residue", at the step field s -- so an item's score depends on (seed,
+    ``item_ids[b]``, its sequence, its inputs) alone; terms are averaged over the seeds and ``stderr`` is the standard
+    error of ``score`` over them (NaN for one seed).  ``item_ids`` default to 0 .. B-1 and need a seed.  ``seed=None``:
+    uniforms from torch's generator, or injected through ``us`` [S, B, L]; a seed and ``us`` together raise.
+
+    Levels are folded into the batch: a launch scores ``levels_per_launch`` levels x B items as one padded batch with a
+    per-item timestep (default: as many as keep it at about 64 items).  ``trim_padding`` runs the trimmed frame
+    (packing.Frame); packed frames share one timestep and are not offered.  ``score_mask`` bool [B, L] names the
+    positions that are summed (and-ed with the padding mask; an item with none gets a NaN score).  ``generated_angles``
+    replace the ligand angles as in ``denoise``.
+
+    Returns CPU tensors: ``bound``, ``score``, ``prior``, ``stderr`` float64 [B], ``n`` int32 [B], ``terms`` and ``nll``
+    float64 [S, B] (summed over the scored positions with a fixed reduction shape, ``e3d_masked_item_sums``; mean over
+    seeds), ``levels`` (the list S) and ``per_residue`` float64 [B, L], combined like ``bound``, NaN off the ligand.
+    ``details``: a dict that receives ``z_t`` int32 [S, B, L] and ``logits`` [S, B, L, C] in the padded frame (one seed
+    only)."""
+    T = CONFIG["timesteps"] if timesteps is None else timesteps
+    B, max_len, C = batch["ligand_seq"].shape
+    if details is not None and not isinstance(details, dict):
+        raise ValueError(f"score_sequences: details must be a dict to fill, got {type(details).__name__}")
+    valid = batch["ligand_attn_mask"].cpu() != 0
+    if sequences is None:
+        x0 = torch.where(valid, onehot_to_index(batch["ligand_seq"].cpu()), torch.full((), -1, dtype=torch.int32))
+    else:
+        x0 = sequence_indices(sequences, batch["ligand_attn_mask"], C)
+    if seed is None and item_ids is not None:
+        raise ValueError("score_sequences: item_ids key the seeded draws; pass a seed with them")
+    if seed is not None and us is not None:
+        raise ValueError("score_sequences: pass either injected us or a seed, not both")
+    seeds = [None]
+    if seed is not None:
+        seeds = [keyed.check_seed(v) for v in (seed if isinstance(seed, (list, tuple)) else [seed])]
+        if not seeds:
+            raise ValueError("score_sequences: an empty list of seeds")
+        keyed.check_steps(T)
+    if details is not None and len(seeds) > 1:
+        raise ValueError("score_sequences: details hold the draws of one seed; pass a single seed with them")
+    S, w = score_levels(T, levels)
+    if us is not None and (not torch.is_tensor(us) or tuple(us.shape) != (len(S), B, max_len)):
+        raise ValueError(f"score_sequences: us must be a tensor of {(len(S), B, max_len)}, one [B, L] per level")
+    scored = valid & (x0 >= 0)
+    if score_mask is not None:
+        if not torch.is_tensor(score_mask) or score_mask.dtype != torch.bool or tuple(score_mask.shape) != (B, max_len):
+            raise ValueError(f"score_sequences: score_mask must be a bool tensor of {(B, max_len)}")
+        scored = scored & score_mask.cpu()
+    chunk = max(1, 64 // B) if levels_per_launch is None else int(levels_per_launch)
+    if chunk < 1:
+        raise ValueError(f"score_sequences: levels_per_launch must be positive, got {levels_per_launch!r}")
+
+    dev = next(model.parameters()).device
+    ids = None if seed is None else keyed.item_ids(item_ids, B)
+    ligand_mask = batch["ligand_attn_mask"].to(dev)
+    receptor_mask = batch["receptor_attn_mask"].to(dev)
+    frame = packing.Frame(ligand_mask, receptor_mask, trim=trim_padding)
+    ang = frame.ligand((batch["ligand_angles"] if generated_angles is None else generated_angles).to(dev).float()).contiguous()
+    rseq, rang = frame.pocket(batch["receptor_seq"].to(dev).float()), frame.pocket(batch["receptor_angles"].to(dev).float())
+    lmask, rmask = frame.ligand(ligand_mask), frame.pocket(receptor_mask)
+    x0_f = frame.ligand(x0.to(dev)).contiguous()
+    keys = None if seed is None else frame.row_keys(ids, dev)
+    scored_d = scored.to(dev).to(torch.uint8)
+    if seed is None:
+        us = torch.rand(len(S), B, max_len, device=dev) if us is None else us.to(dev).float()
+        us = frame.ligand(us, dim=1)
+
+    def launch(first, n, one_seed):
+        """Levels S[first : first + n] x the B items as one batch of N = n B items, level-major."""
+        steps = torch.tensor(S[first:first + n], device=dev, dtype=torch.long).repeat_interleave(B)
+        s = steps.float().reshape(n * B, 1)
+        qtb = transition.get_Qt_bar(noise_schedule.get_alpha_bar(t_normalized=(s + 1) / T), dev).contiguous()
+        qsb = transition.get_Qt_bar(noise_schedule.get_alpha_bar(t_normalized=s / T), dev).contiguous()
+        x0_n = x0_f.repeat(n, 1)
+        if one_seed is None:
+            z = ops.discrete_q_sample(x0_n, qtb, us[first:first + n].reshape(n * B, -1).contiguous())
+        else:
+            z = ops.keyed_discrete_forward_levels(x0_n, qtb, keys.repeat(n, 1), steps, one_seed, T - 1)
+        logits = model.forward(s, F.one_hot(z.long(), num_classes=C).float(), ang.repeat(n, 1, 1), lmask.repeat(n, 1),
+                               rseq.repeat(n, 1, 1), rang.repeat(n, 1, 1), rmask.repeat(n, 1)).contiguous().float()
+        term, nll = ops.discrete_score_rows(z, x0_n, logits, qsb, qtb, (steps == 0).to(torch.uint8))
+        # back to the padded frame, then the fixed-shape sums over the scored positions
+        z, logits, term, nll = (frame.restore(t.reshape(n, B, *t.shape[1:]), dim=1) for t in (z, logits, term, nll))
+        mask = scored_d.repeat(n, 1)
+        sums = [ops.masked_item_sums(t.reshape(n * B, max_len).contiguous(), mask) for t in (term, nll)]
+        return z, logits, term, sums[0][0].reshape(n, B), sums[1][0].reshape(n, B), sums[0][1][:B]
+
+    per_seed = []
+    for one_seed in seeds:
+        parts = [launch(first, min(chunk, len(S) - first), one_seed) for first in range(0, len(S), chunk)]
+        z, logits, term, term_sums, nll_sums = (torch.cat([p[i] for p in parts]) for i in range(5))
+        per_seed.append((term.double().cpu(), term_sums.double().cpu(), nll_sums.double().cpu()))
+        counts = parts[0][5].cpu()
+        if details is not None:
+            details["z_t"], details["logits"] = z.cpu(), logits.cpu()
+
+    def combine(v):
+        """term_0 + w * the sum of the other levels, of per-level values v [S, ..] (float64, on the host)."""
+        return v[0] + (w * v[1:].sum(dim=0) if len(S) > 1 else 0.0)
+
+    prior_pos = prior_terms(transition.get_Qt_bar(noise_schedule.get_alpha_bar(t_normalized=torch.ones(1, 1, device=dev)), dev)[0], x0)
+    prior = torch.where(scored, prior_pos, torch.zeros((), dtype=torch.float64)).sum(dim=1)
+    bound_seeds = torch.stack([prior + combine(ts) for _, ts, _ in per_seed])            # [seeds, B]
+    n = counts.to(torch.int32)
+    per_item = torch.where(n > 0, 1.0 / n.double().clamp_min(1), torch.full((), float("nan"), dtype=torch.float64))
+    score_seeds = bound_seeds * per_item
+    nan_b = torch.full((B,), float("nan"), dtype=torch.float64)
+    stderr = score_seeds.std(dim=0, unbiased=True) / len(seeds) ** 0.5 if len(seeds) > 1 else nan_b
+    per_residue = prior_pos + combine(torch.stack([t for t, _, _ in per_seed]).mean(dim=0))
+    return {"bound": bound_seeds.mean(dim=0), "score": score_seeds.mean(dim=0), "prior": prior, "n": n, "stderr": stderr,
+            "terms": torch.stack([ts for _, ts, _ in per_seed]).mean(dim=0),
+            "nll": torch.stack([ns for _, _, ns in per_seed]).mean(dim=0), "levels": list(S),
+            "per_residue": torch.where(valid, per_residue, torch.full((), float("nan"), dtype=torch.float64))}
+
+
 def batch_keep_mask(keep, batch, first_index):
     """``known_mask`` [B, L] of a loader batch whose first item has dataset index ``first_index`` (packing.keep_mask per
     item, cut at the ligand's length); None when ``keep`` names nothing."""

@@ -62,6 +62,13 @@ def denoise(batch, generated_angles, model, noise_schedule, transition, diverse,
     return _denoise(batch, model, noise_schedule, transition, diverse, generated_angles=generated_angles, **kw)
 
 
+def score_sequences(batch, generated_angles, model, noise_schedule, transition, sequences=None, **kw):
+    """sample.score_sequences with the ligand angles replaced: the score of ``sequences`` on the backbone the structure
+    model generated.  Every keyword passes through."""
+    return _sample.score_sequences(batch, model, noise_schedule, transition, sequences, generated_angles=generated_angles,
+                                   **kw)
+
+
 if __name__ == "__main__":
     import pandas as pd
     torch.cuda.set_device(GPU_ID)

@@ -393,6 +393,39 @@ int e3d_keyed_discrete_posterior_sample_ctl(const int32_t* xt_idx, const float* 
 int e3d_discrete_final_pick(const float* logits, const float* bias, float inv_temp, int32_t* out_idx, float* logp,
                             float* entropy, int64_t rows, int C, void* stream);
 
+/* ------------------------------------------------------------------ scoring supplied sequences
+ * The variational score of the sampler's own reverse law for a sequence x0 the chain did not sample
+ * (sequence_model/sample.py::score_sequences; DESIGN.md, "Scoring sequences").  Levels do not depend on one another, so
+ * N = levels x items rows of tables go through one launch each.  Additions to ABI v5.
+ *
+ * Forward noising of N items at their own levels: row (n, l) of out_idx [N*L] is drawn from
+ * prob[c] = Qtb[n][c][x0_idx[n*L + l]], e3d_discrete_q_sample's convention and arithmetic, with the uniform of word 0
+ * of stream 11 at the step field level_steps[n] (int64 [N], DEVICE memory) with key row_keys[n*L + l] -- for equal
+ * steps, e3d_keyed_discrete_known_compose with a full mask, bit for bit.  max_step <= 65535 is the caller's bound on
+ * level_steps.  Class 0 for a row of no item: x0 outside [0, C), a key position outside [0, 2^24), a step outside
+ * [0, max_step]. */
+int e3d_keyed_discrete_forward_levels(const int32_t* x0_idx, const float* Qtb, const int64_t* row_keys,
+                                      const int64_t* level_steps, int max_step, uint64_t seed, int32_t* out_idx, int N,
+                                      int L, int C, void* stream);
+
+/* Per-row score terms, one workgroup per item n with Qsb[n], Qtb[n] [C, C] in LDS:
+ *   nll[n,l]  = -log_softmax(logits[n,l])[x0]
+ *   p         = prob_out of e3d_discrete_posterior_sample on the same inputs, bit for bit
+ *   q         = the same expression with the x0 prediction replaced by the one-hot of x0
+ *   term[n,l] = KL(q || p) in nats, 0 log 0 = 0; +inf when a class has q > 0 and p == 0; never NaN for a valid row
+ * is_final[n] != 0 (uint8 [N]): term = nll, bit for bit, Qsb and Qtb are not read and p_out / q_out get NaN.
+ * p_out, q_out [N*L, C] may each be NULL.  A row with x0 or xt outside [0, C): NaN in every output. */
+int e3d_discrete_score_rows(const int32_t* xt_idx, const int32_t* x0_idx, const float* logits, const float* Qsb,
+                            const float* Qtb, const uint8_t* is_final, float* term, float* nll, float* p_out,
+                            float* q_out, int N, int L, int C, void* stream);
+
+/* sums[n] = the sum of values[n, l] over mask[n, l] != 0 and counts[n] their number, one wave per item: lane j adds
+ * positions j, j + 64, ... in order (a masked-out position adds an exact +0, whatever its value), then a fixed xor
+ * butterfly over the 64 lanes.  No atomics; the result is a function of the item's (position, value) pairs alone, the
+ * same bits for any L >= the last set position and in any batch. */
+int e3d_masked_item_sums(const float* values, const uint8_t* mask, float* sums, int32_t* counts, int N, int L,
+                         void* stream);
+
 /* ------------------------------------------------------------------ keyed training and validation draws
  * The same generator and counter layout with the EPOCH in the step field (training epochs 0 .. 65534; 65535 is the
  * validation value) and streams 4 structure timestep, 5 structure forward noise, 6 sequence timestep, 7 sequence
