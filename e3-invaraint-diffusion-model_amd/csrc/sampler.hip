@@ -218,27 +218,46 @@ __device__ __forceinline__ float effective_logit(float logit, float bias, float 
     return sum * inv_temp;
 }
 
-// One workgroup per batch item: the three CxC matrices of the item live in LDS, each thread
-// walks rows l = tid, tid+256, ...
-// KEYED: the uniform of row n = b * L + l is drawn from stream 3 at step s_dev[0] with the row's key (row_keys[n]);
-// rows of no item draw u = 0.
-// CTL: the softmax runs over the effective logits (bias [B*L, C] or NULL for zero, inv_temp > 0); a forbidden class
-// has pred == 0 exactly, a row with every class forbidden has pred == 0 everywhere and takes the zero-total rule below.
-template <bool KEYED, bool CTL>
-__global__ __launch_bounds__(256) void discrete_posterior_kernel(
-    const int32_t* __restrict__ xt_idx, const float* __restrict__ logits, const float* __restrict__ Qsb,
-    const float* __restrict__ Qtb, const float* __restrict__ u, int mode, int32_t* __restrict__ out_idx,
-    float* __restrict__ prob_out, int L, int C, const int64_t* __restrict__ row_keys, uint64_t seed,
-    const int64_t* __restrict__ s_dev, const float* __restrict__ bias, float inv_temp) {
-    __shared__ float s_qsb[CMAX * CMAX], s_qtb[CMAX * CMAX], s_qt[CMAX * CMAX], s_rs[CMAX];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int CC = C * C;
+// ---------------------------------------------------------------- what the discrete kernels share
+// Column x0 of a CxC table in registers, p[c] = q[c][x0] = (q @ onehot(x0))[c]: the forward law of a row whose clean
+// class is x0 (model.py:305-308).  Returns the column's sum.
+__device__ __forceinline__ float table_column(const float* __restrict__ q, int x0, int C, float (&p)[CMAX]) {
+    float tot = 0.f;
+#pragma unroll
+    for (int c = 0; c < CMAX; ++c) {
+        p[c] = c < C ? q[c * C + x0] : 0.f;
+        tot += p[c];
+    }
+    return tot;
+}
+
+// The uniform of a keyed draw: word 0 of block 0 of (seed, item, stream, step, position).
+__device__ __forceinline__ float keyed_uniform_at(uint64_t seed, uint64_t item, int stream, uint32_t step, uint32_t pos) {
+    return e3d_keyed_uniform(e3d_keyed_words(seed, item, stream, step, pos, 0).w[0]);
+}
+
+// ... of row n of a key table.  False, and ``un`` as it was, for a row of no item: what such a row gets is its kernel's rule.
+__device__ __forceinline__ bool keyed_row_uniform(const int64_t* __restrict__ row_keys, int64_t n, uint64_t seed, int stream,
+                                                  uint32_t step, float& un) {
+    uint64_t item;
+    uint32_t pos;
+    if (!keyed_row(row_keys, n, item, pos)) return false;
+    un = keyed_uniform_at(seed, item, stream, step, pos);
+    return true;
+}
+
+// The three CxC tables of a workgroup's item in LDS, what p(z_s | z_t) is made of: Qsb, Qtb and
+// Qt = (Qsb/Qtb) / rowsum(Qsb/Qtb)   (sequence_model/sample.py:160), filled for item b; s_rs holds the C row sums.  Three
+// barriers: all threads of the workgroup come here, or none.
+__device__ __forceinline__ void load_posterior_tables(float* s_qsb, float* s_qtb, float* s_qt, float* s_rs,
+                                                      const float* __restrict__ Qsb, const float* __restrict__ Qtb, int b,
+                                                      int C) {
+    const int tid = threadIdx.x, CC = C * C;
     for (int i = tid; i < CC; i += blockDim.x) {
         s_qsb[i] = Qsb[(int64_t)b * CC + i];
         s_qtb[i] = Qtb[(int64_t)b * CC + i];
     }
     __syncthreads();
-    // Qt = (Qsb/Qtb) / rowsum(Qsb/Qtb)   (sequence_model/sample.py:160)
     if (tid < C) {
         float rs = 0.f;
         for (int j = 0; j < C; ++j) rs += s_qsb[tid * C + j] / s_qtb[tid * C + j];
@@ -247,70 +266,103 @@ __global__ __launch_bounds__(256) void discrete_posterior_kernel(
     __syncthreads();
     for (int i = tid; i < CC; i += blockDim.x) s_qt[i] = (s_qsb[i] / s_qtb[i]) / s_rs[i / C];
     __syncthreads();
+}
 
-    for (int l = tid; l < L; l += blockDim.x) {
+// Qtb[x0][xt], the denominator of the x0 term of the posterior; 0 -> 1e-6   (sample.py:128)
+__device__ __forceinline__ float posterior_den(const float* s_qtb, int x0, int xt, int C) {
+    const float den = s_qtb[x0 * C + xt];
+    return den == 0.f ? 1e-6f : den;
+}
+
+// The posterior of a row, stated once for discrete_posterior_kernel and discrete_score_rows_kernel -- as macros: as
+// functions, in every form measured, these steps changed the compiled posterior kernel with controls (slower per launch,
+// or fewer waves per SIMD), while a macro leaves each kernel the code of the expression written out in it.
+#define UNROLL _Pragma("unroll")
+
+// p[c] / sum(p) over the C classes, zero beyond them; a row that sums to zero is 1e-5 everywhere first (sample.py:166).
+// ntot: the sum of the result.
+#define NORMALISE_ROW(p_, C_, ntot_)                                                         \
+    do {                                                                                     \
+        float tot_ = 0.f;                                                                    \
+        UNROLL for (int c = 0; c < CMAX; ++c)                                                \
+            if (c < C_) tot_ += p_[c];                                                       \
+        if (tot_ == 0.f) {                                                                   \
+            UNROLL for (int c = 0; c < CMAX; ++c) p_[c] = c < C_ ? 1e-5f : 0.f;              \
+            tot_ = 0.f;                                                                      \
+            UNROLL for (int c = 0; c < CMAX; ++c)                                            \
+                if (c < C_) tot_ += p_[c];                                                   \
+        }                                                                                    \
+        ntot_ = 0.f;                                                                         \
+        UNROLL for (int c = 0; c < CMAX; ++c) {                                              \
+            p_[c] = c < C_ ? p_[c] / tot_ : 0.f;                                             \
+            ntot_ += p_[c];                                                                  \
+        }                                                                                    \
+    } while (0)
+
+// pred = exp(z - mx) and se its sum, z the C logits at lg (CTL: the effective logits, bias [rows, C] or NULL for zero)
+// and mx their maximum.  none: every class forbidden -- -inf - -inf is NaN, so no exponential is taken: pred = 0, se = 0.
+#define POSTERIOR_SOFTMAX(CTL_, lg_, bias_, inv_temp_, n_, C_, pred_, mx_, none_, se_)                                \
+    do {                                                                                                               \
+        mx_ = -INFINITY;                                                                                               \
+        UNROLL for (int c = 0; c < CMAX; ++c) {                                                                        \
+            if (CTL_) pred_[c] = c < C_ ? effective_logit(lg_[c], bias_ ? bias_[n_ * C_ + c] : 0.f, inv_temp_) : -INFINITY; \
+            else pred_[c] = c < C_ ? lg_[c] : -INFINITY;                                                               \
+            mx_ = fmaxf(mx_, pred_[c]);                                                                                \
+        }                                                                                                              \
+        none_ = CTL_ && mx_ == -INFINITY;                                                                              \
+        se_ = 0.f;                                                                                                     \
+        UNROLL for (int c = 0; c < CMAX; ++c) {                                                                        \
+            pred_[c] = (c < C_ && !none_) ? expf(pred_[c] - mx_) : 0.f;                                                \
+            se_ += pred_[c];                                                                                           \
+        }                                                                                                              \
+    } while (0)
+
+// The x0 prediction pred / se (zero when none; pred holds it afterwards) mixed over x0 at class xt,
+//   prob[c] = sum_x0 pred[x0] * (Qt[c][xt] * Qsb[x0][c]) / Qtb[x0][xt]   (sample.py:129-139,162-165)
+// then NORMALISE_ROW: a forbidden class has pred == 0 exactly, a row with every class forbidden takes the zero-total rule.
+#define POSTERIOR_MIXTURE(pred_, se_, none_, xt_, C_, s_qsb_, s_qtb_, s_qt_, prob_, ntot_)                   \
+    do {                                                                                                      \
+        UNROLL for (int c = 0; c < CMAX; ++c) { pred_[c] = none_ ? 0.f : pred_[c] / se_; prob_[c] = 0.f; }    \
+        _Pragma("unroll 1") for (int k_ = 0; k_ < C_; ++k_) {                                                 \
+            const float den_ = posterior_den(s_qtb_, k_, xt_, C_);                                            \
+            const float w_ = pred_[k_];                                                                       \
+            UNROLL for (int c = 0; c < CMAX; ++c)                                                             \
+                if (c < C_) prob_[c] += w_ * ((s_qt_[c * C_ + xt_] * s_qsb_[k_ * C_ + c]) / den_);            \
+        }                                                                                                     \
+        NORMALISE_ROW(prob_, C_, ntot_);                                                                      \
+    } while (0)
+
+// One workgroup per batch item, its tables in LDS; each thread walks rows l = tid, tid+256, ...
+// KEYED: the uniform of row n = b * L + l is drawn from stream 3 at step s_dev[0] with the row's key (row_keys[n]);
+// rows of no item draw u = 0.
+// CTL: the softmax runs over the effective logits (bias [B*L, C] or NULL for zero, inv_temp > 0).
+template <bool KEYED, bool CTL>
+__global__ __launch_bounds__(256) void discrete_posterior_kernel(
+    const int32_t* __restrict__ xt_idx, const float* __restrict__ logits, const float* __restrict__ Qsb,
+    const float* __restrict__ Qtb, const float* __restrict__ u, int mode, int32_t* __restrict__ out_idx,
+    float* __restrict__ prob_out, int L, int C, const int64_t* __restrict__ row_keys, uint64_t seed,
+    const int64_t* __restrict__ s_dev, const float* __restrict__ bias, float inv_temp) {
+    __shared__ float s_qsb[CMAX * CMAX], s_qtb[CMAX * CMAX], s_qt[CMAX * CMAX], s_rs[CMAX];
+    const int b = blockIdx.x;
+    load_posterior_tables(s_qsb, s_qtb, s_qt, s_rs, Qsb, Qtb, b, C);
+
+    for (int l = threadIdx.x; l < L; l += blockDim.x) {
         const int64_t n = (int64_t)b * L + l;
         const int xt = xt_idx[n];
-        const float* lg = logits + n * C;
         float pred[CMAX], prob[CMAX];
-        float mx = -INFINITY;
-#pragma unroll
-        for (int c = 0; c < CMAX; ++c) {
-            if (CTL) pred[c] = c < C ? effective_logit(lg[c], bias ? bias[n * C + c] : 0.f, inv_temp) : -INFINITY;
-            else pred[c] = c < C ? lg[c] : -INFINITY;
-            mx = fmaxf(mx, pred[c]);
-        }
-        const bool none = CTL && mx == -INFINITY;   // every class forbidden: -inf - -inf is NaN, so no exponential is taken
-        float se = 0.f;
-#pragma unroll
-        for (int c = 0; c < CMAX; ++c) {
-            pred[c] = (c < C && !none) ? expf(pred[c] - mx) : 0.f;
-            se += pred[c];
-        }
-#pragma unroll
-        for (int c = 0; c < CMAX; ++c) { pred[c] = none ? 0.f : pred[c] / se; prob[c] = 0.f; }
-        // prob[c] = sum_x0 pred[x0] * (Qt[c][xt] * Qsb[x0][c]) / Qtb[x0][xt]   (sample.py:129-139,162-165)
-#pragma unroll 1
-        for (int x0 = 0; x0 < C; ++x0) {
-            float den = s_qtb[x0 * C + xt];
-            if (den == 0.f) den = 1e-6f;
-            const float w = pred[x0];
-#pragma unroll
-            for (int c = 0; c < CMAX; ++c)
-                if (c < C) prob[c] += w * ((s_qt[c * C + xt] * s_qsb[x0 * C + c]) / den);
-        }
-        float tot = 0.f;
-#pragma unroll
-        for (int c = 0; c < CMAX; ++c)
-            if (c < C) tot += prob[c];
-        if (tot == 0.f) {  // sample.py:166
-#pragma unroll
-            for (int c = 0; c < CMAX; ++c) prob[c] = c < C ? 1e-5f : 0.f;
-            tot = 0.f;
-#pragma unroll
-            for (int c = 0; c < CMAX; ++c)
-                if (c < C) tot += prob[c];
-        }
-        float ntot = 0.f;
-#pragma unroll
-        for (int c = 0; c < CMAX; ++c) {
-            prob[c] = c < C ? prob[c] / tot : 0.f;
-            ntot += prob[c];
-        }
+        const float* lg = logits + n * C;
+        float mx, se, ntot;
+        bool none;
+        POSTERIOR_SOFTMAX(CTL, lg, bias, inv_temp, n, C, pred, mx, none, se);
+        POSTERIOR_MIXTURE(pred, se, none, xt, C, s_qsb, s_qtb, s_qt, prob, ntot);
         if (prob_out) {
 #pragma unroll
             for (int c = 0; c < CMAX; ++c)
                 if (c < C) prob_out[n * C + c] = prob[c];
         }
         float un = 0.f;
-        if (KEYED) {
-            const int64_t pos = row_keys[2 * n + 1];
-            if (pos >= 0)
-                un = e3d_keyed_uniform(e3d_keyed_words(seed, (uint64_t)row_keys[2 * n], E3D_STREAM_SEQ_U,
-                                                       (uint32_t)s_dev[0], (uint32_t)pos, 0).w[0]);
-        } else if (u) {
-            un = u[n];
-        }
+        if (KEYED) keyed_row_uniform(row_keys, n, seed, E3D_STREAM_SEQ_U, (uint32_t)s_dev[0], un);
+        else if (u) un = u[n];
         out_idx[n] = pick_class(prob, C, ntot, mode, un);
     }
 }
@@ -369,22 +421,13 @@ __global__ __launch_bounds__(256) void discrete_q_sample_kernel(
     if (n >= n_rows) return;
     const int x0 = x0_idx[n];
     if (x0 < 0) { out_idx[n] = 0; return; }  // all-zero (padding) row -> class 0, model.py:305-308
-    const float* q = Qtb + (n / L) * C * C;
+    const int64_t b = n / L;
     float p[CMAX];
-    float tot = 0.f;
-#pragma unroll
-    for (int c = 0; c < CMAX; ++c) {
-        p[c] = c < C ? q[c * C + x0] : 0.f;  // (Qtb @ onehot)[c] = Qtb[c][x0]
-        tot += p[c];
-    }
+    const float tot = table_column(Qtb + b * C * C, x0, C, p);
     float un = 0.f;
-    if (KEYED) {
-        const int64_t b = n / L;
-        un = e3d_keyed_uniform(e3d_keyed_words(seed, (uint64_t)item_ids[b], E3D_STREAM_TRAIN_SEQ_U, keyed_epoch(epoch_dev),
-                                               (uint32_t)(n - b * L), 0).w[0]);
-    } else if (u) {
-        un = u[n];
-    }
+    if (KEYED)
+        un = keyed_uniform_at(seed, (uint64_t)item_ids[b], E3D_STREAM_TRAIN_SEQ_U, keyed_epoch(epoch_dev), (uint32_t)(n - b * L));
+    else if (u) un = u[n];
     out_idx[n] = pick_class(p, C, tot, mode, un);
 }
 
@@ -543,23 +586,11 @@ __global__ __launch_bounds__(256) void discrete_known_compose_kernel(
     if (n >= n_rows || mask[n] == 0) return;
     const int x0 = x0_idx[n];
     if (x0 < 0 || x0 >= C) return;
-    const float* q = Qsb + (n / L) * C * C;
     float p[CMAX];
-    float tot = 0.f;
-#pragma unroll
-    for (int c = 0; c < CMAX; ++c) {
-        p[c] = c < C ? q[c * C + x0] : 0.f;
-        tot += p[c];
-    }
+    const float tot = table_column(Qsb + (n / L) * C * C, x0, C, p);
     float un = 0.f;
-    if (KEYED) {
-        const int64_t pos = row_keys[2 * n + 1];
-        if (pos < 0) return;
-        un = e3d_keyed_uniform(e3d_keyed_words(seed, (uint64_t)row_keys[2 * n], E3D_KNOWN_STREAM_SEQ, (uint32_t)s_dev[0],
-                                               (uint32_t)pos, 0).w[0]);
-    } else if (u) {
-        un = u[n];
-    }
+    if (KEYED && !keyed_row_uniform(row_keys, n, seed, E3D_KNOWN_STREAM_SEQ, (uint32_t)s_dev[0], un)) return;
+    if (!KEYED && u) un = u[n];
     idx[n] = pick_class(p, C, tot, mode, un);
 }
 
@@ -581,27 +612,20 @@ __global__ __launch_bounds__(256) void discrete_forward_levels_kernel(
         out_idx[n] = 0;
         return;
     }
-    const float* q = Qtb + (n / L) * C * C;
     float p[CMAX];
-    float tot = 0.f;
-#pragma unroll
-    for (int c = 0; c < CMAX; ++c) {
-        p[c] = c < C ? q[c * C + x0] : 0.f;
-        tot += p[c];
-    }
-    const float un = e3d_keyed_uniform(e3d_keyed_words(seed, (uint64_t)row_keys[2 * n], E3D_KNOWN_STREAM_SEQ, (uint32_t)step,
-                                                       (uint32_t)pos, 0).w[0]);
+    const float tot = table_column(Qtb + (n / L) * C * C, x0, C, p);
+    const float un = keyed_uniform_at(seed, (uint64_t)row_keys[2 * n], E3D_KNOWN_STREAM_SEQ, (uint32_t)step, (uint32_t)pos);
     out_idx[n] = pick_class(p, C, tot, 1, un);
 }
 
-// The score terms of rows whose clean class x0 is known; one workgroup per item, its tables in LDS like
-// discrete_posterior_kernel, whose arithmetic for p is restated here expression by expression (p_out == its prob_out,
-// bit for bit).
-//   nll  = -log_softmax(logits)[x0] = lse - (logit[x0] - mx), lse = logf(se): the exponentials and their sum are the
-//          ones the x0 prediction pred = e / se is made of
-//   p    = the normalised posterior mixture under pred
+// The score terms of rows whose clean class x0 is known; one workgroup per item, its tables in LDS.  p is
+// discrete_posterior_kernel's prob by construction: both kernels are load_posterior_tables, POSTERIOR_SOFTMAX and
+// POSTERIOR_MIXTURE, so p_out == its prob_out, bit for bit.
+//   nll  = -log_softmax(logits)[x0] = lse - (logit[x0] - mx), lse = logf(se): mx and se are POSTERIOR_SOFTMAX's
+//   p    = POSTERIOR_MIXTURE under that prediction
 //   q    = the same expression under the one-hot of x0.  Only the x0 term of the mixture is non-zero there, and
-//          0 + 1 * v == v in fp32, fused or not, so the C - 1 zero terms are not computed
+//          0 + 1 * v == v in fp32, fused or not, so the C - 1 zero terms are not computed: the x0 term with
+//          posterior_den's guard, then NORMALISE_ROW
 //   term = KL(q || p) = sum_c q[c] * (logf(q[c]) - logf(p[c])) over the classes with q[c] > 0, in class order (0 log 0
 //          = 0).  A class with q > 0 and p == 0 adds +inf; no term is -inf or NaN, so the sum is finite or +inf.
 // is_final items (the chain's last step picks from the raw logits): term = nll, the tables are not read, p_out and
@@ -611,56 +635,25 @@ __global__ __launch_bounds__(256) void discrete_score_rows_kernel(
     const float* __restrict__ Qsb, const float* __restrict__ Qtb, const uint8_t* __restrict__ is_final,
     float* __restrict__ term, float* __restrict__ nll, float* __restrict__ p_out, float* __restrict__ q_out, int L, int C) {
     __shared__ float s_qsb[CMAX * CMAX], s_qtb[CMAX * CMAX], s_qt[CMAX * CMAX], s_rs[CMAX];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int CC = C * C;
+    const int b = blockIdx.x;
     const bool fin = is_final[b] != 0;      // one value per workgroup: the barriers below are met by all or by none
-    if (!fin) {
-        for (int i = tid; i < CC; i += blockDim.x) {
-            s_qsb[i] = Qsb[(int64_t)b * CC + i];
-            s_qtb[i] = Qtb[(int64_t)b * CC + i];
-        }
-        __syncthreads();
-        if (tid < C) {
-            float rs = 0.f;
-            for (int j = 0; j < C; ++j) rs += s_qsb[tid * C + j] / s_qtb[tid * C + j];
-            s_rs[tid] = rs;
-        }
-        __syncthreads();
-        for (int i = tid; i < CC; i += blockDim.x) s_qt[i] = (s_qsb[i] / s_qtb[i]) / s_rs[i / C];
-        __syncthreads();
-    }
+    if (!fin) load_posterior_tables(s_qsb, s_qtb, s_qt, s_rs, Qsb, Qtb, b, C);
     const float nan = __builtin_nanf("");
 
-    for (int l = tid; l < L; l += blockDim.x) {
+    for (int l = threadIdx.x; l < L; l += blockDim.x) {
         const int64_t n = (int64_t)b * L + l;
         const int xt = xt_idx[n], x0 = x0_idx[n];
-        if (x0 < 0 || x0 >= C || xt < 0 || xt >= C) {
-            term[n] = nan;
-            nll[n] = nan;
-            for (int c = 0; c < C; ++c) {
-                if (p_out) p_out[n * C + c] = nan;
-                if (q_out) q_out[n * C + c] = nan;
-            }
-            continue;
-        }
-        const float* lg = logits + n * C;
+        const bool row = x0 >= 0 && x0 < C && xt >= 0 && xt < C;
         float pred[CMAX], prob[CMAX];
-        float mx = -INFINITY, lg0 = 0.f;
-#pragma unroll
-        for (int c = 0; c < CMAX; ++c) {
-            pred[c] = c < C ? lg[c] : -INFINITY;
-            if (c == x0) lg0 = pred[c];
-            mx = fmaxf(mx, pred[c]);
+        float mx, se, ntot, ce = nan;
+        bool none = false;
+        if (row) {
+            const float* lg = logits + n * C;
+            POSTERIOR_SOFTMAX(false, lg, ((const float*)nullptr), 1.f, n, C, pred, mx, none, se);
+            ce = logf(se) - (lg[x0] - mx);
         }
-        float se = 0.f;
-#pragma unroll
-        for (int c = 0; c < CMAX; ++c) {
-            pred[c] = c < C ? expf(pred[c] - mx) : 0.f;
-            se += pred[c];
-        }
-        const float ce = logf(se) - (lg0 - mx);
         nll[n] = ce;
-        if (fin) {
+        if (!row || fin) {
             term[n] = ce;
             for (int c = 0; c < C; ++c) {
                 if (p_out) p_out[n * C + c] = nan;
@@ -668,54 +661,16 @@ __global__ __launch_bounds__(256) void discrete_score_rows_kernel(
             }
             continue;
         }
-#pragma unroll
-        for (int c = 0; c < CMAX; ++c) { pred[c] = pred[c] / se; prob[c] = 0.f; }
-#pragma unroll 1
-        for (int k = 0; k < C; ++k) {
-            float den = s_qtb[k * C + xt];
-            if (den == 0.f) den = 1e-6f;
-            const float w = pred[k];
-#pragma unroll
-            for (int c = 0; c < CMAX; ++c)
-                if (c < C) prob[c] += w * ((s_qt[c * C + xt] * s_qsb[k * C + c]) / den);
-        }
-        float tot = 0.f;
-#pragma unroll
-        for (int c = 0; c < CMAX; ++c)
-            if (c < C) tot += prob[c];
-        if (tot == 0.f) {
-#pragma unroll
-            for (int c = 0; c < CMAX; ++c) prob[c] = c < C ? 1e-5f : 0.f;
-            tot = 0.f;
-#pragma unroll
-            for (int c = 0; c < CMAX; ++c)
-                if (c < C) tot += prob[c];
-        }
-#pragma unroll
-        for (int c = 0; c < CMAX; ++c) prob[c] = c < C ? prob[c] / tot : 0.f;
+        POSTERIOR_MIXTURE(pred, se, none, xt, C, s_qsb, s_qtb, s_qt, prob, ntot);
         // q: the x0 term alone; pred is free now and holds it
-        float qden = s_qtb[x0 * C + xt];
-        if (qden == 0.f) qden = 1e-6f;
-        float qtot = 0.f;
+        const float qden = posterior_den(s_qtb, x0, xt, C);
 #pragma unroll
-        for (int c = 0; c < CMAX; ++c) {
-            pred[c] = c < C ? (s_qt[c * C + xt] * s_qsb[x0 * C + c]) / qden : 0.f;
-            qtot += pred[c];
-        }
-        if (qtot == 0.f) {
-            qtot = 0.f;
-#pragma unroll
-            for (int c = 0; c < CMAX; ++c) {
-                pred[c] = c < C ? 1e-5f : 0.f;
-                qtot += pred[c];
-            }
-        }
+        for (int c = 0; c < CMAX; ++c) pred[c] = c < C ? (s_qt[c * C + xt] * s_qsb[x0 * C + c]) / qden : 0.f;
+        NORMALISE_ROW(pred, C, ntot);
         float kl = 0.f;
 #pragma unroll
-        for (int c = 0; c < CMAX; ++c) {
-            pred[c] = c < C ? pred[c] / qtot : 0.f;
+        for (int c = 0; c < CMAX; ++c)
             if (pred[c] > 0.f) kl += prob[c] > 0.f ? pred[c] * (logf(pred[c]) - logf(prob[c])) : INFINITY;
-        }
         term[n] = kl;
         if (p_out) {
 #pragma unroll
@@ -778,6 +733,10 @@ static bool keyed_width(int F) { return F > 0 && F % 4 == 0 && F / 4 <= 256; }
 // ... and the step is 16 bits of it: a table read by the step index has at most 65536 rows
 #define REQUIRE_KEYED_STEPS(name, T) E3D_REQUIRE(T <= 65536, name ": keyed streams hold steps up to 65535 (T=%d)", T)
 
+// The discrete kernels hold a row's classes in CMAX registers; mode 0 is argmax, 1 the categorical draw from uniforms u
+#define REQUIRE_CLASSES(name, lo, C) E3D_REQUIRE(C >= lo && C <= CMAX, name ": C must be in [" #lo ",%d] (C=%d)", CMAX, C)
+#define REQUIRE_MODE(name, mode, u) E3D_REQUIRE(mode == 0 || (mode == 1 && u), name ": mode 1 needs uniforms")
+
 static Draws buffer_draws(const float* noise) { return Draws{noise, nullptr, 0ull, 0, 1}; }
 static Draws keyed_draws_of(const int64_t* row_keys, uint64_t seed, int stream, int F) {
     return Draws{nullptr, row_keys, seed, stream, F / 4};
@@ -829,8 +788,8 @@ extern "C" int e3d_discrete_posterior_sample(const int32_t* xt_idx, const float*
                                              int mode, int32_t* out_idx, float* prob_out, int B,
                                              int L, int C, void* stream) {
     E3D_REQUIRE(xt_idx && logits && Qsb && Qtb && out_idx && B > 0 && L > 0, "discrete_posterior: bad arguments");
-    E3D_REQUIRE(C >= 2 && C <= CMAX, "discrete_posterior: C must be in [2,%d] (C=%d)", CMAX, C);
-    E3D_REQUIRE(mode == 0 || (mode == 1 && u), "discrete_posterior: mode 1 needs uniforms");
+    REQUIRE_CLASSES("discrete_posterior", 2, C);
+    REQUIRE_MODE("discrete_posterior", mode, u);
     hipLaunchKernelGGL((discrete_posterior_kernel<false, false>), dim3(B), dim3(256), 0, (hipStream_t)stream, xt_idx, logits,
                        Qsb, Qtb, u, mode, out_idx, prob_out, L, C, nullptr, 0ull, nullptr, nullptr, 1.f);
     return e3d_launch_status("e3d_discrete_posterior_sample");
@@ -839,8 +798,8 @@ extern "C" int e3d_discrete_posterior_sample(const int32_t* xt_idx, const float*
 extern "C" int e3d_discrete_q_sample(const int32_t* x0_idx, const float* Qtb, const float* u, int mode,
                                      int32_t* out_idx, int B, int L, int C, void* stream) {
     E3D_REQUIRE(x0_idx && Qtb && out_idx && B > 0 && L > 0, "discrete_q_sample: bad arguments");
-    E3D_REQUIRE(C >= 2 && C <= CMAX, "discrete_q_sample: C must be in [2,%d] (C=%d)", CMAX, C);
-    E3D_REQUIRE(mode == 0 || (mode == 1 && u), "discrete_q_sample: mode 1 needs uniforms");
+    REQUIRE_CLASSES("discrete_q_sample", 2, C);
+    REQUIRE_MODE("discrete_q_sample", mode, u);
     const int64_t n = (int64_t)B * L;
     hipLaunchKernelGGL(discrete_q_sample_kernel<false>, dim3(row_blocks(n)), dim3(256), 0,
                        (hipStream_t)stream, x0_idx, Qtb, u, mode, out_idx, L, C, n, nullptr, nullptr, 0ull);
@@ -882,7 +841,7 @@ extern "C" int e3d_keyed_discrete_posterior_sample(const int32_t* xt_idx, const 
                                                    void* stream) {
     E3D_REQUIRE(xt_idx && logits && Qsb && Qtb && row_keys && s_dev && out_idx && B > 0 && L > 0,
                 "keyed_discrete_posterior: bad arguments");
-    E3D_REQUIRE(C >= 2 && C <= CMAX, "keyed_discrete_posterior: C must be in [2,%d] (C=%d)", CMAX, C);
+    REQUIRE_CLASSES("keyed_discrete_posterior", 2, C);
     hipLaunchKernelGGL((discrete_posterior_kernel<true, false>), dim3(B), dim3(256), 0, (hipStream_t)stream, xt_idx, logits,
                        Qsb, Qtb, nullptr, 1, out_idx, nullptr, L, C, row_keys, seed, s_dev, nullptr, 1.f);
     return e3d_launch_status("e3d_keyed_discrete_posterior_sample");
@@ -937,7 +896,7 @@ extern "C" int e3d_keyed_discrete_q_sample(const int32_t* x0_idx, const float* Q
                                            void* stream) {
     E3D_REQUIRE(x0_idx && Qtb && item_ids && epoch_dev && out_idx && B > 0 && L > 0, "keyed_discrete_q_sample: bad arguments");
     E3D_REQUIRE(L <= 1 << 24, "keyed_discrete_q_sample: positions must stay below 2^24 (L=%d)", L);
-    E3D_REQUIRE(C >= 2 && C <= CMAX, "keyed_discrete_q_sample: C must be in [2,%d] (C=%d)", CMAX, C);
+    REQUIRE_CLASSES("keyed_discrete_q_sample", 2, C);
     const int64_t n = (int64_t)B * L;
     hipLaunchKernelGGL(discrete_q_sample_kernel<true>, dim3(row_blocks(n)), dim3(256), 0,
                        (hipStream_t)stream, x0_idx, Qtb, nullptr, 1, out_idx, L, C, n, item_ids, epoch_dev, seed);
@@ -974,8 +933,8 @@ extern "C" int e3d_keyed_known_compose_wrap(float* x, const float* x0, const uin
 extern "C" int e3d_discrete_known_compose(int32_t* idx, const int32_t* x0_idx, const uint8_t* mask, const float* Qsb,
                                           const float* u, int mode, int B, int L, int C, void* stream) {
     E3D_REQUIRE(idx && x0_idx && mask && Qsb && B > 0 && L > 0, "discrete_known_compose: bad arguments");
-    E3D_REQUIRE(C >= 2 && C <= CMAX, "discrete_known_compose: C must be in [2,%d] (C=%d)", CMAX, C);
-    E3D_REQUIRE(mode == 0 || (mode == 1 && u), "discrete_known_compose: mode 1 needs uniforms");
+    REQUIRE_CLASSES("discrete_known_compose", 2, C);
+    REQUIRE_MODE("discrete_known_compose", mode, u);
     const int64_t n = (int64_t)B * L;
     hipLaunchKernelGGL(discrete_known_compose_kernel<false>, dim3(row_blocks(n)), dim3(256), 0,
                        (hipStream_t)stream, idx, x0_idx, mask, Qsb, u, mode, L, C, n, nullptr, 0ull, nullptr);
@@ -987,7 +946,7 @@ extern "C" int e3d_keyed_discrete_known_compose(int32_t* idx, const int32_t* x0_
                                                 const int64_t* s_dev, int B, int L, int C, void* stream) {
     E3D_REQUIRE(idx && x0_idx && mask && Qsb && row_keys && s_dev && B > 0 && L > 0,
                 "keyed_discrete_known_compose: bad arguments");
-    E3D_REQUIRE(C >= 2 && C <= CMAX, "keyed_discrete_known_compose: C must be in [2,%d] (C=%d)", CMAX, C);
+    REQUIRE_CLASSES("keyed_discrete_known_compose", 2, C);
     const int64_t n = (int64_t)B * L;
     hipLaunchKernelGGL(discrete_known_compose_kernel<true>, dim3(row_blocks(n)), dim3(256), 0,
                        (hipStream_t)stream, idx, x0_idx, mask, Qsb, nullptr, 1, L, C, n, row_keys, seed, s_dev);
@@ -1003,10 +962,10 @@ extern "C" int e3d_discrete_posterior_sample_ctl(const int32_t* xt_idx, const fl
                                                  int mode, int32_t* out_idx, float* prob_out, int B, int L, int C,
                                                  void* stream) {
     E3D_REQUIRE(xt_idx && logits && Qsb && Qtb && out_idx && B > 0 && L > 0, "discrete_posterior_ctl: bad arguments");
-    E3D_REQUIRE(C >= 1 && C <= CMAX, "discrete_posterior_ctl: C must be in [1,%d] (C=%d)", CMAX, C);
+    REQUIRE_CLASSES("discrete_posterior_ctl", 1, C);
     E3D_REQUIRE(good_inv_temp(inv_temp), "discrete_posterior_ctl: inv_temp must be positive and finite (inv_temp=%g)",
                 (double)inv_temp);
-    E3D_REQUIRE(mode == 0 || (mode == 1 && u), "discrete_posterior_ctl: mode 1 needs uniforms");
+    REQUIRE_MODE("discrete_posterior_ctl", mode, u);
     hipLaunchKernelGGL((discrete_posterior_kernel<false, true>), dim3(B), dim3(256), 0, (hipStream_t)stream, xt_idx, logits,
                        Qsb, Qtb, u, mode, out_idx, prob_out, L, C, nullptr, 0ull, nullptr, bias, inv_temp);
     return e3d_launch_status("e3d_discrete_posterior_sample_ctl");
@@ -1018,7 +977,7 @@ extern "C" int e3d_keyed_discrete_posterior_sample_ctl(const int32_t* xt_idx, co
                                                        int32_t* out_idx, int B, int L, int C, void* stream) {
     E3D_REQUIRE(xt_idx && logits && Qsb && Qtb && row_keys && s_dev && out_idx && B > 0 && L > 0,
                 "keyed_discrete_posterior_ctl: bad arguments");
-    E3D_REQUIRE(C >= 1 && C <= CMAX, "keyed_discrete_posterior_ctl: C must be in [1,%d] (C=%d)", CMAX, C);
+    REQUIRE_CLASSES("keyed_discrete_posterior_ctl", 1, C);
     E3D_REQUIRE(good_inv_temp(inv_temp), "keyed_discrete_posterior_ctl: inv_temp must be positive and finite (inv_temp=%g)",
                 (double)inv_temp);
     hipLaunchKernelGGL((discrete_posterior_kernel<true, true>), dim3(B), dim3(256), 0, (hipStream_t)stream, xt_idx, logits,
@@ -1030,7 +989,7 @@ extern "C" int e3d_discrete_final_pick(const float* logits, const float* bias, f
                                        float* logp, float* entropy, int64_t rows, int C, void* stream) {
     E3D_REQUIRE(logits && out_idx && rows > 0, "discrete_final_pick: bad arguments");
     E3D_REQUIRE(rows <= (int64_t)2147483647 * 256,"discrete_final_pick: too many rows (rows=%lld)", (long long)rows);
-    E3D_REQUIRE(C >= 1 && C <= CMAX, "discrete_final_pick: C must be in [1,%d] (C=%d)", CMAX, C);
+    REQUIRE_CLASSES("discrete_final_pick", 1, C);
     E3D_REQUIRE(good_inv_temp(inv_temp), "discrete_final_pick: inv_temp must be positive and finite (inv_temp=%g)",
                 (double)inv_temp);
     hipLaunchKernelGGL(discrete_final_pick_kernel, dim3(row_blocks(rows)), dim3(256), 0, (hipStream_t)stream,
@@ -1047,7 +1006,7 @@ extern "C" int e3d_keyed_discrete_forward_levels(const int32_t* x0_idx, const fl
     E3D_REQUIRE(max_step >= 0 && max_step <= 65535,
                 "keyed_discrete_forward_levels: keyed streams hold steps up to 65535 (max_step=%d)", max_step);
     E3D_REQUIRE(L <= 1 << 24, "keyed_discrete_forward_levels: positions must stay below 2^24 (L=%d)", L);
-    E3D_REQUIRE(C >= 2 && C <= CMAX, "keyed_discrete_forward_levels: C must be in [2,%d] (C=%d)", CMAX, C);
+    REQUIRE_CLASSES("keyed_discrete_forward_levels", 2, C);
     const int64_t n = (int64_t)N * L;
     hipLaunchKernelGGL(discrete_forward_levels_kernel, dim3(row_blocks(n)), dim3(256), 0, (hipStream_t)stream, x0_idx, Qtb,
                        row_keys, level_steps, max_step, seed, out_idx, L, C, n);
@@ -1059,7 +1018,7 @@ extern "C" int e3d_discrete_score_rows(const int32_t* xt_idx, const int32_t* x0_
                                        float* q_out, int N, int L, int C, void* stream) {
     E3D_REQUIRE(xt_idx && x0_idx && logits && Qsb && Qtb && is_final && term && nll && N > 0 && L > 0,
                 "discrete_score_rows: bad arguments");
-    E3D_REQUIRE(C >= 2 && C <= CMAX, "discrete_score_rows: C must be in [2,%d] (C=%d)", CMAX, C);
+    REQUIRE_CLASSES("discrete_score_rows", 2, C);
     hipLaunchKernelGGL(discrete_score_rows_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, xt_idx, x0_idx, logits, Qsb,
                        Qtb, is_final, term, nll, p_out, q_out, L, C);
     return e3d_launch_status("e3d_discrete_score_rows");

@@ -1006,16 +1006,38 @@ def _chk_posterior(xt_idx, logits, qsb, qtb):
     return B, L, C, torch.empty((B, L), device=logits.device, dtype=torch.int32)
 
 
+_POSTERIOR_ENTRIES = {(False, False): "e3d_discrete_posterior_sample", (True, False): "e3d_keyed_discrete_posterior_sample",
+                      (False, True): "e3d_discrete_posterior_sample_ctl",
+                      (True, True): "e3d_keyed_discrete_posterior_sample_ctl"}      # (keyed?, controls?)
+
+
+def _posterior(name, xt_idx, logits, qsb, qtb, u=None, want_prob=False, keyed_draw=None, ctl=None):
+    """The launch behind the four posterior wrappers, ``name`` the caller's.  ``keyed_draw`` = (row_keys, seed, s_dev):
+    the keyed entry point (a categorical draw, no ``prob``), else the one that reads ``u``; ``ctl`` = (bias, inv_temp):
+    the design-control form of either."""
+    if ctl is not None:      # the check first: it speaks for a bias that is no tensor
+        inv_temp = _chk_ctl(logits, *ctl, name)
+        ctl = (_p(ctl[0]), inv_temp)
+    B, L, C, out = _chk_posterior(xt_idx, logits, qsb, qtb)
+    prob = torch.empty((B, L, C), device=logits.device, dtype=torch.float32) if want_prob else None
+    if keyed_draw is None:
+        _chk(u, "u")
+        draw = (_p(u), 0 if u is None else 1, _p(out), _p(prob))
+    else:
+        row_keys, seed, s_dev = keyed_draw
+        _chk(s_dev, "s_dev", torch.int64)
+        _chk_keys(row_keys, B * L, name)
+        draw = (_p(row_keys), keyed.check_seed(seed), _p(s_dev), _p(out))
+    entry = _POSTERIOR_ENTRIES[keyed_draw is not None, ctl is not None]
+    with _timed("discrete_posterior"):
+        hip.check(getattr(hip.lib(), entry)(_p(xt_idx), _p(logits), *(ctl or ()), _p(qsb), _p(qtb), *draw, B, L, C,
+                                            _stream()), entry)
+    return (out, prob) if want_prob else out
+
+
 def discrete_posterior_sample(xt_idx, logits, qsb, qtb, u=None, want_prob=False):
     """xt_idx int32 [B,L]; logits [B,L,C]; qsb/qtb [B,C,C]; u [B,L] uniforms or None (argmax)."""
-    B, L, C, out = _chk_posterior(xt_idx, logits, qsb, qtb)
-    _chk(u, "u")
-    prob = torch.empty((B, L, C), device=logits.device, dtype=torch.float32) if want_prob else None
-    with _timed("discrete_posterior"):
-        hip.check(hip.lib().e3d_discrete_posterior_sample(
-            _p(xt_idx), _p(logits), _p(qsb), _p(qtb), _p(u), 0 if u is None else 1, _p(out), _p(prob),
-            B, L, C, _stream()), "e3d_discrete_posterior_sample")
-    return (out, prob) if want_prob else out
+    return _posterior("discrete_posterior_sample", xt_idx, logits, qsb, qtb, u, want_prob)
 
 
 def discrete_q_sample(x0_idx, qtb, u=None):
@@ -1080,14 +1102,7 @@ def keyed_strided_step_wrap(x, eps_hat, coef_table, t_dev, row_keys, seed, wrap=
 def keyed_discrete_posterior_sample(xt_idx, logits, qsb, qtb, row_keys, seed, s_dev):
     """discrete_posterior_sample (categorical draw) with the uniforms from (seed, row key, stream 3, s_dev[0]);
     row_keys [B * L, 2]."""
-    B, L, C, out = _chk_posterior(xt_idx, logits, qsb, qtb)
-    _chk(s_dev, "s_dev", torch.int64)
-    _chk_keys(row_keys, B * L, "keyed_discrete_posterior_sample")
-    with _timed("discrete_posterior"):
-        hip.check(hip.lib().e3d_keyed_discrete_posterior_sample(
-            _p(xt_idx), _p(logits), _p(qsb), _p(qtb), _p(row_keys), keyed.check_seed(seed), _p(s_dev), _p(out), B, L, C,
-            _stream()), "e3d_keyed_discrete_posterior_sample")
-    return out
+    return _posterior("keyed_discrete_posterior_sample", xt_idx, logits, qsb, qtb, keyed_draw=(row_keys, seed, s_dev))
 
 
 # ------------------------------------------------------------------------------------------ sequence design controls
@@ -1110,28 +1125,13 @@ def _chk_ctl(logits, bias, inv_temp, name):
 def discrete_posterior_sample_ctl(xt_idx, logits, bias, inv_temp, qsb, qtb, u=None, want_prob=False):
     """discrete_posterior_sample with the softmax over (logits + bias) * inv_temp: bias contiguous [B,L,C] (-inf forbids
     a class) or None for zero; inv_temp > 0."""
-    inv_temp = _chk_ctl(logits, bias, inv_temp, "discrete_posterior_sample_ctl")
-    B, L, C, out = _chk_posterior(xt_idx, logits, qsb, qtb)
-    _chk(u, "u")
-    prob = torch.empty((B, L, C), device=logits.device, dtype=torch.float32) if want_prob else None
-    with _timed("discrete_posterior"):
-        hip.check(hip.lib().e3d_discrete_posterior_sample_ctl(
-            _p(xt_idx), _p(logits), _p(bias), inv_temp, _p(qsb), _p(qtb), _p(u), 0 if u is None else 1, _p(out), _p(prob),
-            B, L, C, _stream()), "e3d_discrete_posterior_sample_ctl")
-    return (out, prob) if want_prob else out
+    return _posterior("discrete_posterior_sample_ctl", xt_idx, logits, qsb, qtb, u, want_prob, ctl=(bias, inv_temp))
 
 
 def keyed_discrete_posterior_sample_ctl(xt_idx, logits, bias, inv_temp, qsb, qtb, row_keys, seed, s_dev):
     """keyed_discrete_posterior_sample with the softmax over (logits + bias) * inv_temp; stream 3, the same counters."""
-    inv_temp = _chk_ctl(logits, bias, inv_temp, "keyed_discrete_posterior_sample_ctl")
-    B, L, C, out = _chk_posterior(xt_idx, logits, qsb, qtb)
-    _chk(s_dev, "s_dev", torch.int64)
-    _chk_keys(row_keys, B * L, "keyed_discrete_posterior_sample_ctl")
-    with _timed("discrete_posterior"):
-        hip.check(hip.lib().e3d_keyed_discrete_posterior_sample_ctl(
-            _p(xt_idx), _p(logits), _p(bias), inv_temp, _p(qsb), _p(qtb), _p(row_keys), keyed.check_seed(seed), _p(s_dev),
-            _p(out), B, L, C, _stream()), "e3d_keyed_discrete_posterior_sample_ctl")
-    return out
+    return _posterior("keyed_discrete_posterior_sample_ctl", xt_idx, logits, qsb, qtb, keyed_draw=(row_keys, seed, s_dev),
+                      ctl=(bias, inv_temp))
 
 
 def discrete_final_pick(logits, bias=None, inv_temp=1.0, want_scores=True):
@@ -1199,7 +1199,9 @@ def keyed_known_compose_wrap(x, x0, mask, level_table, t_dev, row_keys, seed, sc
     return x
 
 
-def _chk_discrete_known(idx, x0_idx, mask, qsb, name):
+def _discrete_known_compose(name, idx, x0_idx, mask, qsb, u=None, keyed_draw=None):
+    """The launch behind the two wrappers, ``name`` the caller's: ``keyed_draw`` = (row_keys, seed, s_dev) takes the keyed
+    entry point, else the one that reads ``u``."""
     _chk(idx, name + ".idx", torch.int32); _chk(x0_idx, name + ".x0_idx", torch.int32)
     _chk(mask, name + ".mask", torch.uint8); _chk(qsb, name + ".qsb")
     if idx.dim() != 2 or x0_idx.shape != idx.shape or mask.shape != idx.shape:
@@ -1211,33 +1213,32 @@ def _chk_discrete_known(idx, x0_idx, mask, qsb, name):
         raise ValueError(f"{name}: qsb must be [{B}, C, C], got {tuple(qsb.shape)}")
     if not (idx.is_contiguous() and x0_idx.is_contiguous() and mask.is_contiguous() and qsb.is_contiguous()):
         raise ValueError(f"{name}: arguments must be contiguous")
-    return B, L, C
+    if keyed_draw is None:
+        _chk(u, name + ".u")
+        if u is not None and not (u.is_contiguous() and u.numel() == B * L):
+            raise ValueError(f"{name}: u must be contiguous [B, L]")
+        entry, draw = "e3d_discrete_known_compose", (_p(u), 0 if u is None else 1)
+    else:
+        row_keys, seed, s_dev = keyed_draw
+        _chk(s_dev, name + ".s_dev", torch.int64)
+        _chk_keys(row_keys, B * L, name)
+        entry, draw = "e3d_keyed_discrete_known_compose", (_p(row_keys), keyed.check_seed(seed), _p(s_dev))
+    with _timed("discrete_known_compose"):
+        hip.check(getattr(hip.lib(), entry)(_p(idx), _p(x0_idx), _p(mask), _p(qsb), *draw, B, L, C, _stream()), entry)
+    return idx
 
 
 def discrete_known_compose(idx, x0_idx, mask, qsb, u=None):
     """In place on ``idx`` int32 [B,L]: a row with ``mask`` (uint8) set and x0_idx >= 0 is redrawn from column x0_idx of
     ``qsb`` [B,C,C] -- discrete_q_sample's law; u [B,L] uniforms or None (argmax).  Returns ``idx``."""
-    B, L, C = _chk_discrete_known(idx, x0_idx, mask, qsb, "discrete_known_compose")
-    _chk(u, "discrete_known_compose.u")
-    if u is not None and not (u.is_contiguous() and u.numel() == B * L):
-        raise ValueError("discrete_known_compose: u must be contiguous [B, L]")
-    with _timed("discrete_known_compose"):
-        hip.check(hip.lib().e3d_discrete_known_compose(_p(idx), _p(x0_idx), _p(mask), _p(qsb), _p(u), 0 if u is None else 1,
-                                                       B, L, C, _stream()), "e3d_discrete_known_compose")
-    return idx
+    return _discrete_known_compose("discrete_known_compose", idx, x0_idx, mask, qsb, u)
 
 
 def keyed_discrete_known_compose(idx, x0_idx, mask, qsb, row_keys, seed, s_dev):
     """discrete_known_compose (categorical draw) with the uniforms from (seed, row key, stream 11, s_dev[0]);
     row_keys [B * L, 2]."""
-    B, L, C = _chk_discrete_known(idx, x0_idx, mask, qsb, "keyed_discrete_known_compose")
-    _chk(s_dev, "keyed_discrete_known_compose.s_dev", torch.int64)
-    _chk_keys(row_keys, B * L, "keyed_discrete_known_compose")
-    with _timed("discrete_known_compose"):
-        hip.check(hip.lib().e3d_keyed_discrete_known_compose(_p(idx), _p(x0_idx), _p(mask), _p(qsb), _p(row_keys),
-                                                             keyed.check_seed(seed), _p(s_dev), B, L, C, _stream()),
-                  "e3d_keyed_discrete_known_compose")
-    return idx
+    return _discrete_known_compose("keyed_discrete_known_compose", idx, x0_idx, mask, qsb,
+                                   keyed_draw=(row_keys, seed, s_dev))
 
 
 # ------------------------------------------------------------------------------------------ scoring supplied sequences

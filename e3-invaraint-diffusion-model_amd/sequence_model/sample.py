@@ -13,6 +13,7 @@ if __package__ in (None, ""):  # executed as a script from inside this directory
     __package__ = "e3diff_amd.sequence_model"
 
 import os
+from dataclasses import dataclass
 
 import torch
 from torch.nn import functional as F
@@ -129,61 +130,93 @@ def compute_batched_over0_posterior_distribution(X_t, Q_t, Qsb, Qtb, batch):
     return left * Qsb[batch] / den
 
 
+@dataclass(frozen=True)
+class DrawPlan:
+    """How a chain draws z_s from the posterior, decided and checked once per chain (``draw_plan``), as
+    structure_model/sample.py::StepPlan is for the angle chain; ``step`` is the one place the sampler calls the four
+    posterior and the two compose launches from.  ``diverse``: categorical draws, else argmax (which reads no uniforms).
+    ``keyed`` = (row keys [B*L, 2], seed): the uniforms are generated inside the kernels at the step ``s_dev`` (int64 on
+    the device), stream 3 for the posterior and 11 for the held rows (keyed.py); None: uniforms [B,L], injected or
+    torch.rand on the device.  ``known_x0`` (class indices int32 [B,L]) + ``known_mask`` (uint8 [B,L]): the held rows,
+    redrawn from q(z_s | x0) -- column x0 of Qsb, ``PeptideDiff.apply_aa_noise``'s law at the level the step lands on.
+    ``controls``: an active design.DesignControls whose bias, if any, has the logits' shape: the x0 prediction is
+    softmax((logits + bias) * inv_temp)."""
+    diverse: bool
+    keyed: tuple = None
+    known_x0: torch.Tensor = None
+    known_mask: torch.Tensor = None
+    controls: object = None
+
+    def _uniforms(self, rows, u):      # of an unkeyed launch: None for argmax, else the injected ones or a fresh draw
+        if not self.diverse:
+            return None
+        return torch.rand(rows.shape, device=rows.device) if u is None else u.contiguous().float()
+
+    def posterior(self, xt_idx, logits, qsb, qtb, s_dev=None, u=None):
+        """Class indices int32 [B,L] of z_s given z_t = ``xt_idx`` and the model's ``logits``."""
+        c = self.controls
+        if self.diverse and self.keyed is not None:
+            if u is not None:      # here, not in draw_plan: the uniforms are a step's operand, not the chain's
+                raise ValueError("sample_p_zs_given_zt_discrete: pass either uniforms or a keyed draw, not both")
+            if c is None:
+                return ops.keyed_discrete_posterior_sample(xt_idx, logits, qsb, qtb, *self.keyed, s_dev)
+            return ops.keyed_discrete_posterior_sample_ctl(xt_idx, logits, c.bias, c.inv_temp, qsb, qtb, *self.keyed, s_dev)
+        u = self._uniforms(xt_idx, u)
+        if c is None:
+            return ops.discrete_posterior_sample(xt_idx, logits, qsb, qtb, u)
+        return ops.discrete_posterior_sample_ctl(xt_idx, logits, c.bias, c.inv_temp, qsb, qtb, u)
+
+    def compose(self, idx, qsb, s_dev=None, u=None):
+        """Redraw the held rows of ``idx`` in place; returns ``idx``."""
+        if self.known_x0 is None:
+            return idx
+        if self.diverse and self.keyed is not None:
+            return ops.keyed_discrete_known_compose(idx, self.known_x0, self.known_mask, qsb, *self.keyed, s_dev)
+        return ops.discrete_known_compose(idx, self.known_x0, self.known_mask, qsb, self._uniforms(idx, u))
+
+    def step(self, t, s, x, logits, noise_schedule, transition, s_dev=None, u=None, known_u=None):
+        """One-hot z_s [B,L,C] from z_t = ``x`` at the normalised times t -> s: the two tables, ``posterior``, ``compose``."""
+        qtb = transition.get_Qt_bar(noise_schedule.get_alpha_bar(t_normalized=t), x.device).contiguous()
+        qsb = transition.get_Qt_bar(noise_schedule.get_alpha_bar(t_normalized=s), x.device).contiguous()
+        idx = self.posterior(x.argmax(dim=-1).to(torch.int32).contiguous(), logits.contiguous().float(), qsb, qtb, s_dev, u)
+        return F.one_hot(self.compose(idx, qsb, s_dev, known_u).long(), num_classes=x.shape[-1]).float()
+
+
+def draw_plan(diverse, row_keys=None, seed=None, known_x0=None, known_mask=None, controls=None):
+    """The DrawPlan of a chain, checked; its operands are in the chain's frame.  Controls with nothing set count as None."""
+    if (row_keys is None) != (seed is None):
+        raise ValueError("draw_plan: keyed draws need both row_keys and a seed")
+    return DrawPlan(bool(diverse), None if seed is None else (row_keys, keyed.check_seed(seed)), known_x0, known_mask,
+                    None if controls is None or not controls.active else controls)
+
+
 def sample_p_zs_given_zt_discrete(t, s, noised_data, pred_noise, noise_schedule, transition, diverse,
                                   is_last_step, u=None, keyed_draw=None, known=None, controls=None):
-    """z_s ~ p(z_s | z_t) for every residue (reference sample.py:141-179).  ``diverse`` draws
-    from the categorical (inverse CDF with uniforms ``u`` [B,L], default torch.rand on device),
-    otherwise argmax; the last step returns the raw logits, as the reference does.
-    ``keyed_draw`` = (row keys [B*L, 2], seed, int64 step on the device): the uniforms are the keyed stream 3 of those
-    rows at that step, generated inside the posterior kernel (keyed.py); exclusive with ``u``.
-    ``known`` = (x0 class indices int32 [B,L], uint8 mask [B,L], uniforms [B,L] or None): the held rows of z_s are redrawn
-    from q(z_s | x0) -- column x0 of Qsb, ``PeptideDiff.apply_aa_noise``'s law at level ``s`` -- on the class indices,
-    before the one-hot (``e3d_discrete_known_compose``; with ``keyed_draw`` its uniforms are keyed stream 11).  The last
-    step returns the logits untouched: ``denoise`` puts the held residues there itself, once per chain.
-    ``controls``: a design.DesignControls whose bias, if any, has ``pred_noise``'s shape (``DesignControls.in_frame``).
-    When active, the x0 prediction inside the posterior is softmax((pred_noise + bias) * inv_temp)
-    (``e3d_discrete_posterior_sample_ctl`` and its keyed form, same draws); None or inactive: the launches above.  The
-    last step returns the raw logits either way: ``denoise`` picks from them under the controls."""
+    """z_s ~ p(z_s | z_t) for every residue (reference sample.py:141-179).  ``diverse`` draws from the categorical
+    (inverse CDF with uniforms ``u`` [B,L], default torch.rand on device), otherwise argmax; the last step returns the raw
+    logits, as the reference does (``denoise`` puts the held residues there and picks under the controls, once per chain).
+    One step of a DrawPlan made of the keywords: ``keyed_draw`` = (row keys, seed, int64 step on the device), exclusive
+    with ``u``; ``known`` = (x0 class indices, uint8 mask, uniforms of the held rows or None); ``controls``."""
     if is_last_step:
         return pred_noise
-    B, L, C = noised_data.shape
-    dev = noised_data.device
-    ctl = () if controls is None or not controls.active else (controls.bias, controls.inv_temp)
-    qtb = transition.get_Qt_bar(noise_schedule.get_alpha_bar(t_normalized=t), dev).contiguous()
-    qsb = transition.get_Qt_bar(noise_schedule.get_alpha_bar(t_normalized=s), dev).contiguous()
-    if diverse and keyed_draw is not None:
-        if u is not None:
-            raise ValueError("sample_p_zs_given_zt_discrete: pass either uniforms or a keyed draw, not both")
-        post = ops.keyed_discrete_posterior_sample_ctl if ctl else ops.keyed_discrete_posterior_sample
-        idx = post(noised_data.argmax(dim=-1).to(torch.int32).contiguous(), pred_noise.contiguous().float(), *ctl, qsb, qtb,
-                   *keyed_draw)
-        if known is not None:
-            ops.keyed_discrete_known_compose(idx, known[0], known[1], qsb, *keyed_draw)
-        return F.one_hot(idx.long(), num_classes=C).float()
-    if diverse and u is None:
-        u = torch.rand(B, L, device=dev)
-    post = ops.discrete_posterior_sample_ctl if ctl else ops.discrete_posterior_sample
-    idx = post(noised_data.argmax(dim=-1).to(torch.int32).contiguous(), pred_noise.contiguous().float(), *ctl, qsb, qtb,
-               u.contiguous().float() if diverse else None)
-    if known is not None:
-        ku = None
-        if diverse:
-            ku = torch.rand(B, L, device=dev) if known[2] is None else known[2].contiguous().float()
-        ops.discrete_known_compose(idx, known[0], known[1], qsb, ku)
-    return F.one_hot(idx.long(), num_classes=C).float()
+    row_keys, seed, s_dev = keyed_draw or (None, None, None)
+    known_x0, known_mask, known_u = (*(known or (None, None)), None)[:3]
+    return draw_plan(diverse, row_keys, seed, known_x0, known_mask, controls).step(
+        t, s, noised_data, pred_noise, noise_schedule, transition, s_dev, u, known_u)
 
 
-def _denoise_step(model, s, T, x, args, layouts, noise_schedule, transition, diverse, is_last_step, **draws):
+def _denoise_step(model, s, T, x, args, layouts, noise_schedule, transition, plan, is_last_step, s_dev=None, u=None,
+                  known_u=None):
     """One reverse step z_t -> z_s at the step index ``s`` ([B,1] float on the device), eager or captured.  ``args`` =
     (ligand angles, ligand mask, pocket sequence, pocket angles, pocket mask); with ``layouts`` the model runs packed and
-    reads no mask.  ``draws``: the ``u``, ``keyed_draw``, ``known`` and ``controls`` of ``sample_p_zs_given_zt_discrete``."""
+    reads no mask.  ``plan``: the chain's DrawPlan; ``s_dev``, ``u``, ``known_u``: this step's operands of ``plan.step``.
+    The last step returns the raw logits."""
     ang, lmask, rseq, rang, rmask = args
     if layouts is None:
         logits = model.forward(s, x, ang, lmask, rseq, rang, rmask)
     else:
         logits = model.forward_packed(s, x, ang, rseq, rang, *layouts)[None]
-    return sample_p_zs_given_zt_discrete((s + 1) / T, s / T, x, logits, noise_schedule, transition, diverse, is_last_step,
-                                         **draws)
+    return logits if is_last_step else plan.step((s + 1) / T, s / T, x, logits, noise_schedule, transition, s_dev, u, known_u)
 
 
 class GraphedDenoiseStep:
@@ -197,7 +230,8 @@ class GraphedDenoiseStep:
     E3D_SAMPLE_GRAPH override."""
 
     def __init__(self, model, x_like, ligand_angles, ligand_mask, receptor_seq, receptor_angles, receptor_mask, noise_schedule,
-                 transition, diverse, T, inject_u=False, layouts=None, row_keys=None, seed=None, known=None, controls=None):
+                 transition, diverse, T, inject_u=False, layouts=None, row_keys=None, seed=None, known=None, controls=None,
+                 plan=None):
         """``layouts`` = (ligand, pocket) packing.PackedLayout: the step runs ``model.forward_packed`` on packed rows
         (``x_like`` [1, rows, C], packed angles and pocket inputs; the masks are not read).  The layouts' device tables
         are fixed for the chain, so the capture holds them like any other argument.
@@ -205,28 +239,28 @@ class GraphedDenoiseStep:
         ``known`` = (x0 class indices, uint8 mask), both like ``x_like``'s first two dimensions: the held rows are composed
         inside the body; with ``inject_u`` their uniforms are injected too (``self.known_u``).
         ``controls``: a design.DesignControls in the frame of ``x_like``; its bias is copied into a buffer the capture
-        holds, like the state."""
+        holds, like the state.  ``plan``: the chain's DrawPlan, in place of ``diverse`` and those four keywords."""
         dev = x_like.device
-        self.controls = None if controls is None or not controls.active else controls.in_frame(torch.clone, dev)
-        if (row_keys is None) != (seed is None) or (seed is not None and inject_u):
+        if (row_keys is None) != (seed is None) or (inject_u and (seed if plan is None else plan.keyed) is not None):
             raise ValueError("a keyed graph needs row_keys and a seed, and no injected uniforms")
+        if plan is None:
+            controls = None if controls is None or not controls.active else controls.in_frame(torch.clone, dev)
+            plan = draw_plan(diverse, row_keys, seed, *(known or ()), controls=controls)
+        self.plan, self.controls, diverse, known = plan, plan.controls, plan.diverse, plan.known_x0
         self.s_idx = torch.zeros((1,), device=dev, dtype=torch.long)
-        self.keyed_draw = None if seed is None else (row_keys, keyed.check_seed(seed), self.s_idx)
         self.args = (ligand_angles, ligand_mask, receptor_seq, receptor_angles, receptor_mask)
         self.layouts = layouts
-        self.model, self.schedule, self.transition, self.diverse, self.T = model, noise_schedule, transition, diverse, T
+        self.model, self.schedule, self.transition, self.T = model, noise_schedule, transition, T
         self.x = x_like.clone()
         self.s = torch.zeros((x_like.shape[0], 1), device=dev)
         self.u = torch.zeros(x_like.shape[:2], device=dev) if (inject_u and diverse) else None
         self.known_u = torch.zeros(x_like.shape[:2], device=dev) if (known is not None and self.u is not None) else None
-        self.known = None if known is None else (known[0], known[1], self.known_u)
         # the warm-up draws uniforms when the chain samples (diverse, no injected u): the device generator is put back
         self.graph, self.out = packing.warm_up_and_capture(self._body, dev, restore_rng=True)
 
     def _body(self):
         return _denoise_step(self.model, self.s, self.T, self.x, self.args, self.layouts, self.schedule, self.transition,
-                             self.diverse, False, u=self.u, keyed_draw=self.keyed_draw, known=self.known,
-                             controls=self.controls)
+                             self.plan, False, self.s_idx, self.u, self.known_u)
 
     def step(self, s_int, x, u=None, known_u=None):
         """z_t -> z_s for the step index ``s_int`` (> 0); returns the graph's output buffer (overwritten by the next call)."""
@@ -358,10 +392,10 @@ def denoise(batch, model: PeptideDiff, noise_schedule, transition, diverse, x_T=
             known_us = [state(u.to(dev)).contiguous() if u is not None else u for u in known_us]
     else:
         known_us = None
+    plan = draw_plan(diverse, row_keys, seed, *(known or ()), controls=controls)
     graphed = packing.capture_graph(
         lambda: GraphedDenoiseStep(model, x, ang, lmask, rseq, rang, rmask, noise_schedule, transition, diverse, T,
-                                   inject_u=us is not None, layouts=layouts, row_keys=row_keys, seed=seed, known=known,
-                                   controls=controls),
+                                   inject_u=us is not None, layouts=layouts, plan=plan),
         frame.rows, T, use_graph, "the sequence reverse step")
     for n, s_int in enumerate(reversed(range(T))):
         u = None if us is None else us[n]
@@ -370,9 +404,9 @@ def denoise(batch, model: PeptideDiff, noise_schedule, transition, diverse, x_T=
             x = graphed.step(s_int, x, u, ku if graphed.known_u is not None else None)
             continue
         s_array = torch.full((x.shape[0], 1), float(s_int), device=dev)     # [1, 1] packed: every item shares the step
-        x = _denoise_step(model, s_array, T, x, (ang, lmask, rseq, rang, rmask), layouts, noise_schedule, transition, diverse,
-                          s_int == 0, u=u, keyed_draw=_keyed_draw(row_keys, seed, s_int, dev),
-                          known=None if known is None else known + (ku,), controls=controls)
+        s_dev = None if plan.keyed is None else torch.full((1,), s_int, device=dev, dtype=torch.long)     # as in the graph
+        x = _denoise_step(model, s_array, T, x, (ang, lmask, rseq, rang, rmask), layouts, noise_schedule, transition, plan,
+                          s_int == 0, s_dev, u, ku)
     logp = entropy = None
     if controls is not None or details is not None:      # x holds the last step's logits: pick on the device
         idx, logp, entropy = ops.discrete_final_pick(x.contiguous().float(), None if controls is None else controls.bias,
@@ -401,11 +435,6 @@ def denoise(batch, model: PeptideDiff, noise_schedule, transition, diverse, x_T=
         ids.append(f'{sid["pdb_id"][i]}_{sid["ligand_chain"][i]}' if sid is not None else str(i))
     print(sum(recovery_rates) / len(recovery_rates))
     return ids, true_sequences, pred_sequences, recovery_rates
-
-
-def _keyed_draw(row_keys, seed, s_int, dev):
-    """The keyed_draw argument of one eager step (the step index goes to the device, as in the graph)."""
-    return None if seed is None else (row_keys, seed, torch.full((1,), s_int, device=dev, dtype=torch.long))
 
 
 def score_levels(T, levels=None):

@@ -208,6 +208,39 @@ def test_discrete_compose_equals_q_sample_and_where(pkg, hip, trans_name, B, L):
         assert torch.equal(got, want), (s_int, "keyed")
 
 
+@pytest.mark.parametrize("C", [2, 20, 32])
+def test_the_three_column_draws_agree(pkg, hip, C):
+    """discrete_q_sample, discrete_known_compose (full mask) and keyed_discrete_forward_levels draw a row from column x0 of
+    its item's table: fed the same tables, x0 and uniforms -- the keyed stream 11 of one step -- they return the same
+    classes wherever a row has a clean class and an item.  B = 2 items with tables of their own (some entries zero),
+    L = 257: one row past a 256-thread block.  Elsewhere each keeps its own rule: a padding row (x0 = -1) is class 0 for
+    q_sample and forward_levels and left alone by the compose; a row of no item (key position < 0) is class 0 for
+    forward_levels, while the two buffer forms know no keys and draw with the u = 0 that keyed_draws gives such a row."""
+    from e3diff_amd import keyed
+    ops, B, L, seed, step, base = pkg.ops, 2, 257, 21, 17, 99
+    g = torch.Generator().manual_seed(C)
+    q = torch.rand(B, C, C, generator=g)
+    q[q < 0.25] = 0.0
+    x0 = torch.randint(0, C, (B, L), generator=g).int()
+    x0[:, 3::11] = -1
+    keys = keyed.padded_keys([5, (1 << 40) + 3], L, "cpu").clone()
+    keys[7::13, 1] = -1
+    q, x0, keys = q.to(DEV).contiguous(), x0.to(DEV), keys.to(DEV)
+    item, clean = (keys[:, 1] >= 0).reshape(B, L), x0 >= 0
+    assert bool((~item & clean).any()) and bool((item & ~clean).any()) and bool((~item & ~clean).any())
+    u = ops.keyed_draws(keys, seed, 11, step, ops.KEYED_UNIFORM).reshape(B, L)
+    assert bool((u[~item] == 0).all())
+    drawn = ops.discrete_q_sample(x0, q, u)
+    composed = ops.discrete_known_compose(torch.full((B, L), base, dtype=torch.int32, device=DEV), x0,
+                                          torch.ones(B, L, dtype=torch.uint8, device=DEV), q, u)
+    forward = ops.keyed_discrete_forward_levels(x0, q, keys, torch.full((B,), step, dtype=torch.long, device=DEV), seed, 49)
+    both = item & clean
+    assert torch.equal(drawn[both], composed[both]) and torch.equal(drawn[both], forward[both])
+    assert len(torch.unique(drawn[both])) > 1 and not torch.equal(drawn[0], drawn[1])
+    assert bool((drawn[~clean] == 0).all()) and bool((forward[~clean] == 0).all()) and bool((composed[~clean] == base).all())
+    assert bool((forward[~item] == 0).all()) and torch.equal(drawn[~item & clean], composed[~item & clean])
+
+
 # ------------------------------------------------------------------------------------------------ structure chains
 T_CHAIN, B_CHAIN, L_CHAIN = 6, 4, 128
 IDS = [11, (1 << 35) + 2, 7, 123456]
