@@ -7,6 +7,7 @@ but none of that package's code runs: the nn.Modules below only own parameters, 
 execute the math as fused gfx950 kernels on [B*L, H] row-major activations.
 """
 from dataclasses import dataclass
+from typing import NamedTuple
 
 import os
 
@@ -200,53 +201,57 @@ def kv_weights(sa):
     return _packed(sa, "kv", [sa.key.weight, sa.value.weight], [sa.key.bias, sa.value.bias])
 
 
-def dropout_rates(module):
-    """(hidden_dropout_prob, attention_probs_dropout_prob) in training mode, (0, 0) in eval -- where
-    transformers 4.38.2 applies ``nn.Dropout``: after the self/cross-attention softmax, after
-    ``BertSelfOutput.dense`` and after ``BertOutput.dense``."""
-    if not module.training:
-        return 0.0, 0.0
-    cfg = module.config
-    return float(getattr(cfg, "hidden_dropout_prob", 0.0)), float(getattr(cfg, "attention_probs_dropout_prob", 0.0))
+class Drop(NamedTuple):
+    """The dropout of one model-layer call: the rates after ``BertSelfOutput.dense`` / ``BertOutput.dense`` and after the
+    self/cross-attention softmax (where transformers 4.38.2 applies ``nn.Dropout``) and, keyed dropout, the key table of
+    the rows of x -- the query rows of both attentions (``ops.KeyedDropout.row_keys``) -- or None."""
+    hidden: float
+    attention: float
+    row_keys: object = None
+
+    @property
+    def off(self):
+        return self.hidden == 0 and self.attention == 0
+
+    @classmethod
+    def of(cls, module, rows):
+        """For ``module`` (a BertEncoder or BertAttention) on ``rows`` (packing.Rows): its config's rates in training mode, zeros in eval."""
+        cfg = module.config if module.training else None      # (eval: no config to read, both rates default to zero)
+        drop = cls(float(getattr(cfg, "hidden_dropout_prob", 0.0)), float(getattr(cfg, "attention_probs_dropout_prob", 0.0)),
+                   rows.row_keys)
+        if rows.packed and not drop.off:
+            raise RuntimeError("packed layouts are inference-only: put the model in eval mode")
+        return drop
 
 
 # ----------------------------------------------------------------------------- executors
-def _attention_output(att, ctx, x, p_hidden=0.0, row_keys=None):
+def _attention_output(att, ctx, x, drop):
     return F.linear_residual_layernorm(ctx, att.output.dense.weight, att.output.dense.bias, x, att.output.LayerNorm.weight,
-                                       att.output.LayerNorm.bias, att.eps, p_hidden, row_keys)
+                                       att.output.LayerNorm.bias, att.eps, drop.hidden, drop.row_keys)
 
 
 def _planes_for(att, x, drop):
     """The consumer of an attention context, for ``F.attention(planes_for=)``: without dropout (inference) the context's only
     reader is ``_attention_output`` -- out-projection + residual x + LayerNorm -- which may take it as activation planes."""
-    return (att.output.dense.weight, x) if drop[0] == 0 and drop[1] == 0 else None
+    return (att.output.dense.weight, x) if drop.off else None
 
 
-def drop_keys(drop):
-    """The row-key table of a ``drop`` value -- (hidden rate, attention rate) or, in a seeded step with keyed dropout,
-    (hidden rate, attention rate, key table of the rows being processed: ``ops.KeyedDropout.row_keys``) -- or None."""
-    return drop[2] if len(drop) > 2 else None
-
-
-def run_self_attention(att, x, mask, B, L, drop=(0.0, 0.0), layout=None):
-    """BertAttention on x [B*L,H] with key padding mask [B,L] (1/0): fused QKV GEMM ->
-    fused relative-key attention -> out-proj GEMM -> residual + LayerNorm.  ``layout`` (packing.PackedLayout,
-    inference): x holds the packed rows [layout.rows, H] and ``mask``, ``B``, ``L`` are not read."""
+def run_self_attention(att, x, rows, drop):
+    """BertAttention on x [rows.rows, H] (``rows``: packing.Rows): fused QKV GEMM -> fused relative-key attention over
+    the padded frame and its key mask, or over the segments of packed rows -> out-proj GEMM -> residual + LayerNorm."""
     sa = att.self
     w, b = qkv_weights(sa)
     qkv = F.linear(x, w, b, absmax=ops.absmax_slot(sa, "qkv", x.device))
-    relkey = sa.position_embedding_type == "relative_key"
-    if layout is not None:
+    dist_emb = sa.distance_embedding.weight if sa.position_embedding_type == "relative_key" else None
+    if rows.packed:
         H = att.num_heads * 64
-        ctx = ops.attention_varlen(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], layout, layout, att.num_heads,
-                                   dist_emb=sa.distance_embedding.weight if relkey else None,
-                                   max_pos=sa.max_position_embeddings)
-        return _attention_output(att, ctx, x)
-    ctx = F.attention(qkv, None, B, att.num_heads, L, L, key_mask=mask,
-                      dist_emb=sa.distance_embedding.weight if relkey else None,
-                      max_pos=sa.max_position_embeddings, drop_p=drop[1], row_keys=drop_keys(drop),
-                      planes_for=_planes_for(att, x, drop))
-    return _attention_output(att, ctx, x, drop[0], drop_keys(drop))
+        ctx = ops.attention_varlen(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], rows.layout, rows.layout, att.num_heads,
+                                   dist_emb=dist_emb, max_pos=sa.max_position_embeddings)
+    else:
+        ctx = F.attention(qkv, None, rows.B, att.num_heads, rows.L, rows.L, key_mask=rows.mask, dist_emb=dist_emb,
+                          max_pos=sa.max_position_embeddings, drop_p=drop.attention, row_keys=drop.row_keys,
+                          planes_for=_planes_for(att, x, drop))
+    return _attention_output(att, ctx, x, drop)
 
 
 def project_cross_kv(att, enc):
@@ -257,52 +262,42 @@ def project_cross_kv(att, enc):
     return F.linear(enc, w, b, absmax=torch.zeros(1, device=enc.device, dtype=torch.float32))
 
 
-def run_cross_attention(att, x, kv, enc_mask, B, Lq, Lk, drop=(0.0, 0.0), layout=None, enc_layout=None):
-    """``layout`` / ``enc_layout`` (inference): segments of the packed query rows x and of the key rows kv -- packed too,
-    or a padded cache (``enc_layout.padded_frame``); ``enc_mask``, ``B``, ``Lq``, ``Lk`` are then not read."""
+def run_cross_attention(att, x, rows, kv, kv_rows, drop):
+    """Queries x (``rows``) against the projected encoder states kv (``kv_rows``).  Packed query rows take key rows that
+    are packed too or a padded cache (``PackedLayout.padded_frame``)."""
     q = F.linear(x, att.self.query.weight, att.self.query.bias, absmax=ops.absmax_slot(att.self, "q", x.device))
-    if layout is not None:
+    if rows.packed:
         H = att.num_heads * 64
-        ctx = ops.attention_varlen(q, kv[:, :H], kv[:, H:], layout, enc_layout, att.num_heads)
-        return _attention_output(att, ctx, x)
-    ctx = F.attention(q, kv, B, att.num_heads, Lq, Lk, key_mask=enc_mask, drop_p=drop[1], row_keys=drop_keys(drop),
-                      planes_for=_planes_for(att, x, drop))
-    return _attention_output(att, ctx, x, drop[0], drop_keys(drop))
+        ctx = ops.attention_varlen(q, kv[:, :H], kv[:, H:], rows.layout, kv_rows.layout, att.num_heads)
+    else:
+        ctx = F.attention(q, kv, rows.B, att.num_heads, rows.L, kv_rows.L, key_mask=kv_rows.mask, drop_p=drop.attention,
+                          row_keys=drop.row_keys, planes_for=_planes_for(att, x, drop))
+    return _attention_output(att, ctx, x, drop)
 
 
-def run_layer(layer, x, mask, B, L, cross_kv=None, enc_mask=None, Lk=None, drop=(0.0, 0.0), layout=None,
-              enc_layout=None):
-    """``drop`` = (hidden, attention-probability) dropout rates of this call (training only), plus -- keyed dropout -- the
-    key table of the rows of x (the query rows of both attentions).  ``layout`` / ``enc_layout``: packed rows
-    (run_self_attention, run_cross_attention)."""
-    x = run_self_attention(layer.attention, x, mask, B, L, drop, layout=layout)
+def run_layer(layer, x, rows, drop, cross_kv=None, kv_rows=None):
+    """One BertLayer on x (``rows``); ``cross_kv`` (``kv_rows``): the projected encoder states of a decoder layer."""
+    x = run_self_attention(layer.attention, x, rows, drop)
     if hasattr(layer, "crossattention"):
         if cross_kv is None:
             raise ValueError("decoder layer needs encoder states")
-        x = run_cross_attention(layer.crossattention, x, cross_kv, enc_mask, B, L, Lk, drop, layout=layout,
-                                enc_layout=enc_layout)
+        x = run_cross_attention(layer.crossattention, x, rows, cross_kv, kv_rows, drop)
     # (without dropout -- inference -- the intermediate's only reader is the BertOutput below: it may leave as activation planes)
     inter = F.linear(x, layer.intermediate.dense.weight, layer.intermediate.dense.bias, ops.ACT_GELU,
-                     planes_for=(layer.output.dense.weight, x) if drop[0] == 0 and drop[1] == 0 else None)
+                     planes_for=(layer.output.dense.weight, x) if drop.off else None)
     return F.linear_residual_layernorm(inter, layer.output.dense.weight, layer.output.dense.bias, x,
-                                       layer.output.LayerNorm.weight, layer.output.LayerNorm.bias, layer.eps, drop[0],
-                                       drop_keys(drop))
+                                       layer.output.LayerNorm.weight, layer.output.LayerNorm.bias, layer.eps, drop.hidden,
+                                       drop.row_keys)
 
 
-def run_encoder(encoder, x, mask, B, L, enc=None, enc_mask=None, Lk=None, cross_kv=None, layout=None, enc_layout=None,
-                row_keys=None):
-    """BertEncoder(...).last_hidden_state on flat activations.  ``cross_kv`` (list, one per
-    layer) short-cuts the per-layer K/V projection of ``enc``.  ``layout`` / ``enc_layout`` (packing.PackedLayout,
-    inference): x (and enc) hold packed rows; the masks, B, L and Lk are then not read.  ``row_keys`` (keyed dropout):
-    the key table of the rows of x."""
-    drop = dropout_rates(encoder)
-    if layout is not None and drop != (0.0, 0.0):
-        raise RuntimeError("packed layouts are inference-only: put the model in eval mode")
-    if row_keys is not None:
-        drop = drop + (row_keys,)
+def run_encoder(encoder, x, rows, enc=None, enc_rows=None, cross_kv=None):
+    """BertEncoder(...).last_hidden_state on flat activations x (``rows``: packing.Rows).  ``enc`` (``enc_rows``): the
+    encoder states a decoder's cross-attention reads; ``cross_kv`` (list, one per layer) short-cuts their per-layer K/V
+    projection."""
+    drop = Drop.of(encoder, rows)
     for i, layer in enumerate(encoder.layer):
         kv = None
         if hasattr(layer, "crossattention"):
             kv = cross_kv[i] if cross_kv is not None else project_cross_kv(layer.crossattention, enc)
-        x = run_layer(layer, x, mask, B, L, kv, enc_mask, Lk, drop, layout=layout, enc_layout=enc_layout)
+        x = run_layer(layer, x, rows, drop, kv, enc_rows)
     return x

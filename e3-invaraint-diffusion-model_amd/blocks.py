@@ -11,6 +11,7 @@ import os
 
 from . import bert, keyed, ops
 from .autograd import functional as F
+from .packing import Rows
 
 # SELayer conditioning on one-hot rows (the pocket's residue types): modulation rows from a table of the distinct rows
 # (``onehot_modulation``).  0 = always the dense [M, 6H] launches (A/B runs, tests).
@@ -89,33 +90,25 @@ class SELayer(nn.Module):
         m0, m2 = self.adaLN_modulation[0], self.adaLN_modulation[2]
         return F.linear(F.linear(c, m0.weight, m0.bias, ops.ACT_SILU), m2.weight, m2.bias)
 
-    def run(self, x, c, mask, B, L, mod=None, layout=None, row_keys=None):
-        """x [B*L,H]; c [B*L,H] (per token) or [B,H] (one conditioning row per item).  ``mod``: the rows
-        ``modulation(c)`` would give, computed by the caller ([B*L,6H], [B,6H], or ONE row [1,6H] shared by every
-        item: samplers precompute it per timestep), or an ``IndexedModulation`` (per token) -- ``c`` is then not read.  ``layout`` (packing.PackedLayout,
-        inference): x holds packed rows [layout.rows, H] (pass B = 1, L = layout.rows) and the conditioning is per
-        token ([rows,H]) or ONE row shared by every item (a sampler's single timestep); ``mask`` is not read.
-        ``row_keys`` (keyed dropout, training): the key table of the rows of x."""
+    def run(self, x, c, rows, mod=None):
+        """x [rows.rows,H] (``rows``: packing.Rows); c [rows.rows,H] (per token), [B,H] (one conditioning row per item of a
+        padded frame) or ONE row shared by every item.  ``mod``: the rows ``modulation(c)`` would give, computed by the
+        caller in one of those forms (one row [1,6H]: samplers precompute it per timestep), or an ``IndexedModulation``
+        (per token); it takes the place of ``c``."""
         if mod is None:
             mod = self.modulation(c)
-        if layout is not None:
-            assert mod.shape[0] in (1, x.shape[0]), ("a packed batch takes per-token conditioning or one shared row",
-                                                     tuple(mod.shape))
-            assert bert.dropout_rates(self.attn) == (0.0, 0.0), "packed layouts are inference-only"
         rows_per_cond = x.shape[0] // mod.shape[0]
-        assert rows_per_cond in (1, L, B * L) and rows_per_cond * mod.shape[0] == x.shape[0], (x.shape, mod.shape)
-        drop = bert.dropout_rates(self.attn)   # (hidden, attention) rates in training, zeros in eval
-        if row_keys is not None:
-            drop = drop + (row_keys,)
-        att = bert.run_self_attention(self.attn, x, mask, B, L, drop, layout=layout)
+        assert rows_per_cond in (1, rows.L, rows.rows) and rows_per_cond * mod.shape[0] == x.shape[0], (x.shape, mod.shape)
+        drop = bert.Drop.of(self.attn, rows)
+        att = bert.run_self_attention(self.attn, x, rows, drop)
         if isinstance(mod, IndexedModulation):
             assert rows_per_cond == 1
             gate = lambda a, y, branch: ops.adaln_gate_indexed(a, y, mod.idx, mod.table, mod.mod, branch)   # noqa: E731
         else:
             gate = lambda a, y, branch: F.adaln_gate(a, y, mod, branch, rows_per_cond)   # noqa: E731
         x = gate(x, att, 0)
-        h = F.dropout(F.linear(x, self.mlp[0].weight, self.mlp[0].bias, ops.ACT_GELU), self.mlp[2].p, self.training, row_keys)
-        h = F.dropout(F.linear(h, self.mlp[3].weight, self.mlp[3].bias), self.mlp[4].p, self.training, row_keys)
+        h = F.dropout(F.linear(x, self.mlp[0].weight, self.mlp[0].bias, ops.ACT_GELU), self.mlp[2].p, self.training, drop.row_keys)
+        h = F.dropout(F.linear(h, self.mlp[3].weight, self.mlp[3].bias), self.mlp[4].p, self.training, drop.row_keys)
         return gate(x, h, 1)
 
 
@@ -148,14 +141,14 @@ class BertEmbeddings(nn.Module):
         self.LayerNorm = nn.LayerNorm(bert_config.hidden_size, eps=bert_config.layer_norm_eps)
         self.dropout = nn.Dropout(bert_config.hidden_dropout_prob)
 
-    def run(self, x2d, post_add=None, rows_per_add=1, row_keys=None):
-        """``post_add`` [M / rows_per_add, H] is what the caller adds to the embedding afterwards (the sequence
-        model's timestep term): fused into the kernel, except in training with dropout, which sits between.
-        ``row_keys`` (keyed dropout, training): the key table of the rows of x2d."""
+    def run(self, x2d, rows, post_add=None, rows_per_add=1):
+        """x2d [rows.rows, F] (``rows``: packing.Rows).  ``post_add`` [M / rows_per_add, H] is what the caller adds to the
+        embedding afterwards (the sequence model's timestep term): fused into the kernel, except in training with
+        dropout, which sits between."""
         if self.training and self.dropout.p > 0:
             e = F.embed_layernorm(x2d, self.linear.weight, self.linear.bias, self.LayerNorm.weight,
                                   self.LayerNorm.bias, self.LayerNorm.eps, None, 1)
-            e = F.dropout(e, self.dropout.p, row_keys=row_keys)
+            e = F.dropout(e, self.dropout.p, row_keys=rows.row_keys)
             if post_add is not None:
                 e = (e.view(-1, rows_per_add, e.shape[1]) + post_add[:, None, :]).view_as(e)
             return e
@@ -211,11 +204,11 @@ class KeyedDropoutSwitch:
         return ops.keyed_dropout(seed, epoch, keyed.batch_item_ids(batch, batch["ligand_attn_mask"].shape[0]))
 
 
-def drop_row_keys(stream, L):
-    """Inside ``ops.keyed_dropout``: the row-key table of the batch's [B, L] frame on ``stream`` (keyed.DROP_LIGAND /
-    keyed.DROP_POCKET), built once per step and frame; else None."""
+def frame_rows(mask, stream):
+    """The ``packing.Rows`` of a batch's padded frame from its float key mask [B, L]; inside ``ops.keyed_dropout`` with the
+    row-key table of that frame on ``stream`` (keyed.DROP_LIGAND / keyed.DROP_POCKET), built once per step and frame."""
     kd = ops.keyed_dropout_state()
-    return None if kd is None else kd.row_keys(stream, L)
+    return Rows.from_mask(mask, None if kd is None else kd.row_keys(stream, mask.shape[1]))
 
 
 def flat2d(x):

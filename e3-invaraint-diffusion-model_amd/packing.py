@@ -6,8 +6,8 @@ It holds the segment table the varlen attention kernel reads (``ops.attention_va
 buffers have ``rows`` rows: the valid rows of all items, then a zero tail up to a multiple of 32, so that every GEMM and
 row kernel keeps the shapes it is tested on; the attention kernel writes zeros into the tail's output rows.
 
-Every op of the BERT stacks except attention is row-wise, so a packed forward runs the padded-frame executors on
-[rows, H] activations (B = 1, L = rows) with the attention calls replaced by the varlen kernel.  Inference only.
+Every op of the BERT stacks except attention is row-wise, so a packed forward runs the executors of the padded frame on
+[rows, H] activations; a ``Rows`` record tells the two attention executors which kernel to call.  Inference only.
 
 A ``Frame`` is the choice both samplers make once per chain between the padded, the trimmed and the packed rows.
 """
@@ -124,6 +124,27 @@ class PackedLayout:
 
     def same_segments(self, other):
         return self.lengths == other.lengths
+
+
+class Rows:
+    """The rows of one activation matrix x [rows, H], as the model layer's executors (``bert.run_*``, ``SELayer.run``)
+    take them.  Padded (``from_mask``): the [B, L] frame, its float key mask [B, L] and, in a keyed training step, the
+    key table of its rows (``row_keys``; else None).  Packed (``from_layout``): the segments of a ``PackedLayout`` -- a
+    ``padded_frame`` one, e.g. a pocket cache kept in its frame, included.  The fields of the other form are None.
+    A record of references: nothing is allocated, launched or read back from the device."""
+
+    def __init__(self, rows, B=None, L=None, mask=None, row_keys=None, layout=None):
+        self.rows, self.B, self.L, self.mask, self.row_keys, self.layout = rows, B, L, mask, row_keys, layout
+        self.packed = layout is not None
+
+    @classmethod
+    def from_mask(cls, mask, row_keys=None):
+        B, L = mask.shape
+        return cls(B * L, B, L, mask, row_keys)
+
+    @classmethod
+    def from_layout(cls, layout):
+        return cls(layout.rows, layout=layout)
 
 
 def check_cross(q_layout, k_layout):

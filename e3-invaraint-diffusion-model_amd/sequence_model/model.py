@@ -15,8 +15,9 @@ from torch import nn
 from torch.nn import functional as F
 
 from .. import bert, keyed, ops
-from ..blocks import (BertEmbeddings, GaussianFourierProjection, KeyedDropoutSwitch, Predictor, SELayer, drop_row_keys,
-                      flat2d, require_gpu)
+from ..blocks import (BertEmbeddings, GaussianFourierProjection, KeyedDropoutSwitch, Predictor, SELayer, flat2d,
+                      frame_rows, require_gpu)
+from ..packing import Rows
 from ..training import adamw
 from .utils import BlosumTransition, PredefinedNoiseScheduleDiscrete, elbo_loss
 
@@ -66,24 +67,13 @@ class ConditionalBertForDiffusionBase(nn.Module):
         """Logits [B,L,20] (reference model.py:200-237)."""
         require_gpu(timestep, noised_ligand_seq, ligand_angle, ligand_attention_masks, receptor_seq,
                     receptor_angle, receptor_attention_masks)
-        B, L = noised_ligand_seq.shape[:2]
-        Lr = receptor_seq.shape[1]
         ops.reset_absmax(noised_ligand_seq.device)   # |Q|, |K| bounds of the attention calls: fresh per forward
         lig_mask = ligand_attention_masks.contiguous().float()
         rec_mask = receptor_attention_masks.contiguous().float()
         temb = self.timestep_projector(timestep.squeeze(dim=-1)).contiguous()            # [B,H]
-        # keyed dropout: the key tables of the ligand rows and of the pocket rows
-        lk, rk = drop_row_keys(keyed.DROP_LIGAND, L), drop_row_keys(keyed.DROP_POCKET, Lr)
-        lig_seq = self.ligand_seq_embedding.run(flat2d(noised_ligand_seq), row_keys=lk)
-        lig_ang = self.ligand_angle_embedding.run(flat2d(ligand_angle), post_add=temb, rows_per_add=L, row_keys=lk)
-        lig = self.ligand_feature_emb.run(lig_seq, lig_ang, lig_mask, B, L, row_keys=lk)
-        rec_seq = self.receptor_seq_embedding.run(flat2d(receptor_seq), row_keys=rk)
-        rec_ang = self.receptor_angle_embedding.run(flat2d(receptor_angle), post_add=temb, rows_per_add=Lr, row_keys=rk)
-        rec = self.ligand_feature_emb.run(rec_seq, rec_ang, rec_mask, B, Lr, row_keys=rk)
-        x = bert.run_encoder(self.decoder, lig, lig_mask, B, L, enc=rec, enc_mask=rec_mask, Lk=Lr, row_keys=lk)
-        x = self.decoder_normalize.run(x, temb, lig_mask, B, L, row_keys=lk)
-        return self.amino_acid_predictor.run(x).view(B, L, -1)
-
+        lig, rec = frame_rows(lig_mask, keyed.DROP_LIGAND), frame_rows(rec_mask, keyed.DROP_POCKET)
+        logits = self._denoise(temb, noised_ligand_seq, ligand_angle, receptor_seq, receptor_angle, lig, rec)
+        return logits.view(lig.B, lig.L, -1)
 
     def forward_packed(self, timestep, noised_ligand_seq, ligand_angle, receptor_seq, receptor_angle, layout,
                        receptor_layout):
@@ -95,17 +85,23 @@ class ConditionalBertForDiffusionBase(nn.Module):
         require_gpu(timestep, noised_ligand_seq, ligand_angle, receptor_seq, receptor_angle)
         if timestep.numel() != 1:
             raise ValueError(f"a packed batch shares one timestep: got {timestep.numel()} values")
-        rows, rows_r = layout.rows, receptor_layout.rows
         ops.reset_absmax(noised_ligand_seq.device)
         temb = self.timestep_projector(timestep.reshape(-1)).contiguous()                 # [1,H]
-        lig_seq = self.ligand_seq_embedding.run(flat2d(noised_ligand_seq))
-        lig_ang = self.ligand_angle_embedding.run(flat2d(ligand_angle), post_add=temb, rows_per_add=rows)
-        lig = self.ligand_feature_emb.run(lig_seq, lig_ang, None, 1, rows, layout=layout)
-        rec_seq = self.receptor_seq_embedding.run(flat2d(receptor_seq))
-        rec_ang = self.receptor_angle_embedding.run(flat2d(receptor_angle), post_add=temb, rows_per_add=rows_r)
-        rec = self.ligand_feature_emb.run(rec_seq, rec_ang, None, 1, rows_r, layout=receptor_layout)
-        x = bert.run_encoder(self.decoder, lig, None, 1, rows, enc=rec, layout=layout, enc_layout=receptor_layout)
-        x = self.decoder_normalize.run(x, temb, None, 1, rows, layout=layout)
+        return self._denoise(temb, noised_ligand_seq, ligand_angle, receptor_seq, receptor_angle,
+                             Rows.from_layout(layout), Rows.from_layout(receptor_layout))
+
+    def _denoise(self, temb, noised_ligand_seq, ligand_angle, receptor_seq, receptor_angle, lig, rec):
+        """reference model.py:200-237 on the ligand rows ``lig`` and the pocket rows ``rec`` (packing.Rows); ``temb``
+        [n,H]: one timestep row per item of the padded frame, or one row shared by all rows.  -> logits [lig.rows, 20]."""
+        n = temb.shape[0]
+        lig_seq = self.ligand_seq_embedding.run(flat2d(noised_ligand_seq), lig)
+        lig_ang = self.ligand_angle_embedding.run(flat2d(ligand_angle), lig, post_add=temb, rows_per_add=lig.rows // n)
+        x_lig = self.ligand_feature_emb.run(lig_seq, lig_ang, lig)
+        rec_seq = self.receptor_seq_embedding.run(flat2d(receptor_seq), rec)
+        rec_ang = self.receptor_angle_embedding.run(flat2d(receptor_angle), rec, post_add=temb, rows_per_add=rec.rows // n)
+        x_rec = self.ligand_feature_emb.run(rec_seq, rec_ang, rec)
+        x = bert.run_encoder(self.decoder, x_lig, lig, enc=x_rec, enc_rows=rec)
+        x = self.decoder_normalize.run(x, temb, lig)
         return self.amino_acid_predictor.run(x)
 
 

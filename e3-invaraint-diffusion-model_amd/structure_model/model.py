@@ -10,8 +10,9 @@ import torch
 from torch import nn
 
 from .. import bert, keyed, ops
-from ..blocks import (BertEmbeddings, GaussianFourierProjection, KeyedDropoutSwitch, Predictor, SELayer, drop_row_keys,
-                      flat2d, onehot_modulation, require_gpu)
+from ..blocks import (BertEmbeddings, GaussianFourierProjection, KeyedDropoutSwitch, Predictor, SELayer, flat2d,
+                      frame_rows, onehot_modulation, require_gpu)
+from ..packing import Rows
 from ..training import adamw
 import os
 
@@ -25,9 +26,10 @@ class ReceptorCache:
     noised ligand (reference model.py:191-200), so a sampler computes it once per batch instead
     of once per reverse step (41 % of per-step FLOPs + the cross K/V projections)."""
 
-    def __init__(self, encoder_states, cross_kv, mask, B, L, layout=None):
-        self.encoder_states, self.cross_kv, self.mask, self.B, self.L = encoder_states, cross_kv, mask, B, L
-        self.layout = layout   # packing.PackedLayout of the pocket rows, or None (padded frame)
+    def __init__(self, encoder_states, cross_kv, rows, B, L):
+        self.encoder_states, self.cross_kv, self.rows, self.B, self.L = encoder_states, cross_kv, rows, B, L
+        # the float key mask of the padded [B, L] frame, or the packing.PackedLayout of the pocket rows; the other is None
+        self.mask, self.layout = rows.mask, rows.layout
 
 
 class ConditionalBertForDiffusionBase(nn.Module):
@@ -56,27 +58,20 @@ class ConditionalBertForDiffusionBase(nn.Module):
         require_gpu(receptor_seq, receptor_angles, receptor_attention_masks)
         B, L = receptor_angles.shape[:2]
         ops.reset_absmax(receptor_angles.device)   # |Q|, |K| bounds of the attention calls: fresh per batch / chain
-        if layout is not None:
-            ang = self.receptor_angle_emb.run(flat2d(layout.pack(receptor_angles)))
-            seq2d = flat2d(layout.pack(receptor_seq))
-            mod = onehot_modulation(self.receptor_emb, self.receptor_seq_emb, seq2d)   # residue types: one-hot rows
-            seq = self.receptor_seq_emb.run(seq2d) if mod is None else None
-            x = self.receptor_emb.run(ang, seq, None, 1, layout.rows, mod=mod, layout=layout)
-            x = bert.run_encoder(self.encoder, x, None, 1, layout.rows, layout=layout)
-            kv = [bert.project_cross_kv(layer.crossattention, x) for layer in self.decoder.layer] if project_cross_kv else None
-            return ReceptorCache(x, kv, None, B, L, layout=layout)
-        mask = receptor_attention_masks.contiguous().float()
-        rk = drop_row_keys(keyed.DROP_POCKET, L)     # keyed dropout: the key table of the pocket rows
-        ang = self.receptor_angle_emb.run(flat2d(receptor_angles), row_keys=rk)
-        seq2d = flat2d(receptor_seq)
+        if layout is None:
+            rows = frame_rows(receptor_attention_masks.contiguous().float(), keyed.DROP_POCKET)
+            into = flat2d
+        else:
+            rows = Rows.from_layout(layout)
+            into = lambda t: flat2d(layout.pack(t))   # noqa: E731
+        ang = self.receptor_angle_emb.run(into(receptor_angles), rows)
+        seq2d = into(receptor_seq)
         mod = onehot_modulation(self.receptor_emb, self.receptor_seq_emb, seq2d)   # residue types: one-hot rows (inference)
-        seq = self.receptor_seq_emb.run(seq2d, row_keys=rk) if mod is None else None
-        x = self.receptor_emb.run(ang, seq, mask, B, L, mod=mod, row_keys=rk)
-        x = bert.run_encoder(self.encoder, x, mask, B, L, row_keys=rk)
-        kv = None
-        if project_cross_kv:
-            kv = [bert.project_cross_kv(layer.crossattention, x) for layer in self.decoder.layer]
-        return ReceptorCache(x, kv, mask, B, L)
+        seq = self.receptor_seq_emb.run(seq2d, rows) if mod is None else None
+        x = self.receptor_emb.run(ang, seq, rows, mod=mod)
+        x = bert.run_encoder(self.encoder, x, rows)
+        kv = [bert.project_cross_kv(layer.crossattention, x) for layer in self.decoder.layer] if project_cross_kv else None
+        return ReceptorCache(x, kv, rows, B, L)
 
     def timestep_modulation(self, timesteps):
         """The part of the decoder that depends on the timestep alone (reference model.py:205-207: Fourier features ->
@@ -88,39 +83,33 @@ class ConditionalBertForDiffusionBase(nn.Module):
     def decode(self, timestep, noised_ligand_angles, ligand_attention_masks, receptor: ReceptorCache, mod=None,
                layout=None):
         """reference model.py:202-214.  ``mod`` ([1,6H] or [B,6H]): ``timestep_modulation`` of this step's timestep,
-        if the caller has it already (``timestep`` is then not read).
+        if the caller has it already (it takes the place of ``timestep``).
         ``layout`` (packing.PackedLayout of the ligand mask, inference): ``noised_ligand_angles`` are the packed rows
         [layout.rows, F], the receptor cache must be packed too (``encode_receptor(..., layout=)``), every item shares
-        one timestep (``mod`` [1,6H]) and the result is packed [layout.rows, F]; ``ligand_attention_masks`` is not read."""
-        if layout is not None:
-            return self._decode_packed(timestep, noised_ligand_angles, receptor, mod, layout)
-        require_gpu(timestep, noised_ligand_angles, ligand_attention_masks)
-        B, L = noised_ligand_angles.shape[:2]
-        mask = ligand_attention_masks.contiguous().float()
-        lk = drop_row_keys(keyed.DROP_LIGAND, L)     # keyed dropout: the key table of the ligand rows
-        x = self.ligand_angle_emb.run(flat2d(noised_ligand_angles), row_keys=lk)
+        one timestep (``mod`` [1,6H]) and the result is packed [layout.rows, F]; no ligand mask is needed."""
+        if layout is None:
+            require_gpu(timestep, noised_ligand_angles, ligand_attention_masks)
+            rows = frame_rows(ligand_attention_masks.contiguous().float(), keyed.DROP_LIGAND)
+            x2d = flat2d(noised_ligand_angles)
+        else:
+            require_gpu(noised_ligand_angles)
+            if receptor.layout is None:
+                raise ValueError("a packed decode needs the pocket packed as well: encode_receptor(..., layout=)")
+            assert tuple(noised_ligand_angles.shape[:-1]) == (layout.rows,), (tuple(noised_ligand_angles.shape), layout.rows)
+            if mod is None:
+                t = timestep.reshape(-1)
+                assert bool((t == t[0]).all()), "a packed batch shares one timestep"
+                mod = self.timestep_modulation(t[:1])
+            assert mod.shape[0] == 1, "a packed batch shares one timestep: mod must be one row [1,6H]"
+            rows = Rows.from_layout(layout)
+            x2d = noised_ligand_angles.contiguous().float()
+        x = self.ligand_angle_emb.run(x2d, rows)
         if mod is None:
             mod = self.timestep_modulation(timestep.squeeze(dim=-1))             # [B,6H]
-        x = self.timestep_emb.run(x, None, mask, B, L, mod=mod, row_keys=lk)
-        x = bert.run_encoder(self.decoder, x, mask, B, L, enc=receptor.encoder_states,
-                             enc_mask=receptor.mask, Lk=receptor.L, cross_kv=receptor.cross_kv, row_keys=lk)
-        return self.angles_predictor.run(x).view(B, L, -1)
-
-    def _decode_packed(self, timestep, x_packed, receptor, mod, layout):
-        require_gpu(x_packed)
-        if receptor.layout is None:
-            raise ValueError("a packed decode needs the pocket packed as well: encode_receptor(..., layout=)")
-        assert x_packed.dim() == 2 and x_packed.shape[0] == layout.rows, (tuple(x_packed.shape), layout.rows)
-        if mod is None:
-            t = timestep.reshape(-1)
-            assert bool((t == t[0]).all()), "a packed batch shares one timestep"
-            mod = self.timestep_modulation(t[:1])
-        assert mod.shape[0] == 1, "a packed batch shares one timestep: mod must be one row [1,6H]"
-        x = self.ligand_angle_emb.run(x_packed.contiguous().float())
-        x = self.timestep_emb.run(x, None, None, 1, layout.rows, mod=mod, layout=layout)
-        x = bert.run_encoder(self.decoder, x, None, 1, layout.rows, enc=receptor.encoder_states,
-                             cross_kv=receptor.cross_kv, layout=layout, enc_layout=receptor.layout)
-        return self.angles_predictor.run(x)
+        x = self.timestep_emb.run(x, None, rows, mod=mod)
+        x = bert.run_encoder(self.decoder, x, rows, enc=receptor.encoder_states, enc_rows=receptor.rows,
+                             cross_kv=receptor.cross_kv)
+        return self.angles_predictor.run(x).view(*noised_ligand_angles.shape[:-1], -1)    # [B,L,F], or packed [rows,F]
 
     def forward(self, timestep, noised_ligand_angles, ligand_attention_masks,
                 receptor_seq, receptor_angles, receptor_attention_masks,

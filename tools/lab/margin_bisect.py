@@ -12,6 +12,7 @@ from oracle import structure as ostr, bert as obert
 pkg = ge.load_package()
 from e3diff_amd import ops, bert
 from e3diff_amd.blocks import flat2d
+from e3diff_amd.packing import Rows
 from e3diff_amd.structure_model.model import ConditionalBertForDiffusionBase
 from e3diff_amd.bert import BertConfig
 DEV = "cuda:0"
@@ -96,27 +97,28 @@ if os.environ.get("CPU32", "1") == "1":
     print("cpu32", " ".join(f"{n}:{e:.1e}" for n, e in row), flush=True)
 print("=== teacher-forced per stage (input = fp64 oracle's, cast to fp32)", flush=True)
 G = lambda v: v.float().to(DEV)
-lm, rm = d["ligand_attn_mask"].contiguous(), d["receptor_attn_mask"].contiguous()
+lm, rm = (Rows.from_mask(d[k].contiguous().float()) for k in ("ligand_attn_mask", "receptor_attn_mask"))
+no_drop = bert.Drop(0.0, 0.0)
 for mode in MODES:
     ops.set_gemm_mode(mode); ops.set_attn_mode(mode)
     row = []
     with torch.no_grad():
         (a, s), y = stages["receptor_emb"]
-        got = model.receptor_emb.run(flat2d(G(a)), flat2d(G(s)), rm, B, L)
+        got = model.receptor_emb.run(flat2d(G(a)), flat2d(G(s)), rm)
         row.append(("receptor_emb", err(got, y, mr)))
         for i in range(12):
             xi, y = stages[f"enc{i}"]
-            got = bert.run_layer(model.encoder.layer[i], flat2d(G(xi)), rm, B, L)
+            got = bert.run_layer(model.encoder.layer[i], flat2d(G(xi)), rm, no_drop)
             row.append((f"enc{i}", err(got, y, mr)))
         (a, c), y = stages["timestep_emb"]
-        got = model.timestep_emb.run(flat2d(G(a)), G(c.squeeze(1)).contiguous(), lm, B, L)
+        got = model.timestep_emb.run(flat2d(G(a)), G(c.squeeze(1)).contiguous(), lm)
         row.append(("timestep_emb", err(got, y, m)))
         encg = flat2d(G(enc))
         for i in range(12):
             xi, y = stages[f"dec{i}"]
             layer = model.decoder.layer[i]
             kv = bert.project_cross_kv(layer.crossattention, encg)
-            got = bert.run_layer(layer, flat2d(G(xi)), lm, B, L, kv, rm, L)
+            got = bert.run_layer(layer, flat2d(G(xi)), lm, no_drop, kv, rm)
             row.append((f"dec{i}", err(got, y, m)))
         xi, y = stages["predictor"]
         got = model.angles_predictor.run(flat2d(G(xi)))
