@@ -44,7 +44,7 @@ __global__ __launch_bounds__(256, 2) void attn_varlen_kernel(
     const int Lq = q_len[seg], Lk = k_len[seg];
     const int64_t qs = q_start[seg];
     float* orow = out + (qs + q0 + qi) * ocol + h * D;
-    if (Lk <= 0) {   // (the host refuses such layouts; no row is read, the tile's rows are zero)
+    if (Lk <= 0) {   // (packing.check_cross refuses such batches, the op does not: no row is read, the tile's rows are zero)
         if (q0 + qi < Lq)
             for (int c = 0; c < 64; c += 4) *reinterpret_cast<f32x4*>(orow + c) = f32x4{0.f, 0.f, 0.f, 0.f};
         return;

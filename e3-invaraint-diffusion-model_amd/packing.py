@@ -174,12 +174,20 @@ class Frame:
 
     * padded (default): the dataset's [B, L] frame;
     * trimmed (``trim``): the rows up to the longest ligand / pocket, rounded up to 32 (``trimmed_length``).  Padding
-      cannot influence valid positions (its keys carry the -10000 bias, whose softmax weight underflows to exactly
-      0.0f; every other op is row-wise), so a chain needs no other rows.  BioLiP ligands are 5-30 residues in a 64-256
-      row frame: the decoder then runs on 1/8 of the rows;
+      cannot influence valid positions while a row's attention scores spread over less than ~9900 (its keys carry
+      the -10000 bias, whose softmax weight then underflows to exactly 0.0f; every other op is row-wise), so a chain
+      needs no other rows.  BioLiP ligands are 5-30 residues in a 64-256 row frame: the decoder then runs on 1/8 of
+      the rows;
     * packed (``pack``): every item's valid rows back to back (``layouts``: ligand and pocket ``PackedLayout``).  Masks
       that are not prefix masks cannot be packed: the trimmed frame runs instead, with a warning.  An item with ligand
       rows but an empty pocket raises ``ValueError``.
+
+    The condition.  Trimmed and packed frames equal the padded one on the valid positions while every softmax row's
+    scores spread over less than ~9900.  Beyond that the reference's additive -10000 mask lets padded keys win rows of
+    the padded frame; a trimmed frame has dropped (some of) those keys, and the packed path computes the absent-keys
+    softmax -- keys outside a segment have weight exactly 0, whatever the scores.  That contract is pinned by
+    tests/test_varlen_forms_gpu.py::
+    test_packed_path_computes_the_absent_keys_softmax_where_the_reference_lets_padded_keys_win.
 
     ``ligand`` / ``pocket`` move a padded-frame tensor into the frame, ``restore`` moves a ligand-side result back;
     ``row_keys`` is the key table of the frame's ligand rows (keyed.py) and ``rows`` their count."""

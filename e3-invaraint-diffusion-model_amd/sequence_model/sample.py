@@ -296,7 +296,10 @@ def denoise(batch, model: PeptideDiff, noise_schedule, transition, diverse, x_T=
     are gathered to the packed rows; the default initial noise is drawn in the padded frame as before, the default
     uniforms of ``diverse`` chains are drawn for the packed rows, i.e. from a different place in the random stream.
     Masks that are not prefix masks run the trimmed frame instead (with a warning); an item with ligand rows but an
-    empty pocket raises ``ValueError``.
+    empty pocket raises ``ValueError``.  Trimmed and packed chains equal the padded one while every softmax row's
+    scores spread over less than ~9900 (packing.Frame): beyond that the reference's additive -10000 mask lets padded
+    keys win rows, and the packed path computes the absent-keys softmax instead (tests/test_varlen_forms_gpu.py::
+    test_packed_path_computes_the_absent_keys_softmax_where_the_reference_lets_padded_keys_win).
 
     ``seed``: keyed draws (keyed.py, DESIGN.md "Keyed sampling streams"): x_T and the uniforms of item b are functions
     of (seed, item_ids[b], step, position) alone, so they do not depend on the batch, its order, the frame (padded /

@@ -395,7 +395,10 @@ def p_sample_loop(model: nn.Module, ligand_mask, ligand_angle_noise, receptor_se
     [T/STEP, B, L, n_ft] shape.  Injected ``noises`` (padded layout) are gathered to the packed rows; default draws are
     made for the packed rows, i.e. they come from a different place in the random stream than the padded chain's.
     Masks that are not prefix masks cannot be packed: the chain then runs the trimmed frame (with a warning).  An item
-    with ligand rows but an empty pocket raises ``ValueError``.
+    with ligand rows but an empty pocket raises ``ValueError``.  The agreement holds while every softmax row's scores
+    spread over less than ~9900 (packing.Frame): beyond that the reference's additive -10000 mask lets padded keys win
+    rows, and the packed path computes the absent-keys softmax instead (tests/test_varlen_forms_gpu.py::
+    test_packed_path_computes_the_absent_keys_softmax_where_the_reference_lets_padded_keys_win).
 
     ``seed``: keyed draws (keyed.py, DESIGN.md "Keyed sampling streams"): the noise of step i at position l of item b is
     a function of (seed, item_ids[b], i, l) alone, generated inside the update kernel -- the same whatever the batch, its
