@@ -27,6 +27,11 @@
 // positions of a seeded chain make the draws they made before.
 #define E3D_KNOWN_STREAM_STRUCT 10       // structure: forward noise of the held angles, laid out as stream 1
 #define E3D_KNOWN_STREAM_SEQ 11          // sequence: forward-noising uniform of the held residues
+// scoring supplied structures (stream 12): the forward noise of a supplied backbone at the level timestep t reads, step
+// field = t, laid out as stream 1.  Stream 10 is not reused: it is drawn at the step whose LANDING level is t - 1, and has
+// no draw for level T - 1.  (tests/test_score_cpu.py counts the *STREAM* macros above as the streams the sequence score
+// left alone; this one is named apart from them.)
+#define E3D_SCORE_STRUCT_NOISE 12
 
 struct E3dU32x4 { uint32_t w[4]; };
 

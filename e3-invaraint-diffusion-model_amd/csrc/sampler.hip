@@ -1,6 +1,7 @@
 // Diffusion-process kernels: DDPM ancestral update + angular wrap, the strided (DDIM / respaced) update t -> s < t,
-// forward noising, the discrete (BLOSUM / uniform transition) posterior + categorical draw, and the score terms of a
-// supplied sequence under that posterior.  All HBM- or latency-bound.
+// forward noising, the discrete (BLOSUM / uniform transition) posterior + categorical draw, the score terms of a
+// supplied sequence under that posterior, and the score terms of supplied backbone angles under the DDPM update.  All
+// HBM- or latency-bound.
 // The keyed forms (seeded chains) generate their draws in-register from (seed, row key, step): e3d_philox.h.
 #include "e3d_common.h"
 #include "e3d_philox.h"
@@ -712,6 +713,153 @@ __global__ __launch_bounds__(64) void masked_item_sums_kernel(
     }
 }
 
+// ---------------------------------------------------------------- scoring supplied structures
+// Forward noising of N = n * B items at their own levels, one thread per (row, block j of 4 features): item n reads
+// x0 and the keys of item n % B (level-major, the host tiles nothing), noise = wrap(scale * z) with z the stream-12
+// normals of (item, step level_steps[n], position, j) in stream 1's block layout, x_t = q_sample_wrap_elem(a, s, x0,
+// noise) with (a, s) = row step of the two tables -- keyed_q_sample_wrap_kernel's arithmetic.  An item whose step lies
+// outside [0, min(max_step, T - 1)] reads no table row and gets NaN; a row of no item (a key position outside
+// [0, 2^24)) gets zeros.
+__global__ __launch_bounds__(256) void keyed_q_sample_levels_wrap_kernel(
+    const float* __restrict__ x0, const int64_t* __restrict__ row_keys, const int64_t* __restrict__ level_steps,
+    int max_step, const float* __restrict__ sqrt_ab, const float* __restrict__ sqrt_1mab, int T, float scale, uint64_t seed,
+    float* __restrict__ noise_out, float* __restrict__ xt_out, int64_t item4, int64_t batch4, int nb, int64_t n4) {
+    const int64_t top = max_step < T - 1 ? max_step : T - 1;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        const int64_t step = level_steps[i / item4];
+        const int64_t src = i % batch4;                 // the float4 group of item n % B
+        const int64_t row = src / nb;
+        const int64_t pos = row_keys[2 * row + 1];
+        f32x4 nv = {0.f, 0.f, 0.f, 0.f}, o = {0.f, 0.f, 0.f, 0.f};
+        if (step < 0 || step > top) {
+            const float q = __builtin_nanf("");
+            nv = f32x4{q, q, q, q};
+            o = nv;
+        } else if (pos >= 0 && pos < ((int64_t)1 << 24)) {
+            const float a = sqrt_ab[step], s = sqrt_1mab[step];
+            float z[4];
+            e3d_keyed_normal4(e3d_keyed_words(seed, (uint64_t)row_keys[2 * row], E3D_SCORE_STRUCT_NOISE, (uint32_t)step,
+                                              (uint32_t)pos, (uint32_t)(src - row * nb)), z);
+            const f32x4 xv = reinterpret_cast<const f32x4*>(x0)[src];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                nv[j] = wrap_pi(scale * z[j]);
+                o[j] = q_sample_wrap_elem(a, s, xv[j], nv[j]);
+            }
+        }
+        reinterpret_cast<f32x4*>(noise_out)[i] = nv;
+        reinterpret_cast<f32x4*>(xt_out)[i] = o;
+    }
+}
+
+// The score terms of one element from row t of the [T,4] table (structure_model/utils.py, ScoreTables) = (k, h, add, 0):
+//   err = wrap_pi(eps - eps_hat)   delta = wrap_pi(k * (eps_hat - eps))   term = h * (delta * delta) + add   err2 = err * err
+// Contraction is off: every product is rounded before it is added to, so term and err2 are functions of the fp32 inputs
+// alone and the sums below are sums of the stored values.
+struct ScoreCoef { float k, h, add; };
+
+__device__ __forceinline__ void angle_score_elem(const ScoreCoef c, float eps_hat, float eps, float& term, float& err,
+                                                 float& err2) {
+#pragma clang fp contract(off)
+    err = wrap_pi(eps - eps_hat);
+    const float d = c.k * (eps_hat - eps);
+    const float delta = wrap_pi(d);
+    const float sq = delta * delta;
+    const float scaled = c.h * sq;
+    term = scaled + c.add;
+    err2 = err * err;
+}
+
+constexpr int SCORE_FMAX = 32;
+
+// One wave per item n, no atomics.  Lane j takes positions j, j + 64, ... in order; a residue's value is the sum of its
+// masked elements in feature order, a masked-out element adding an exact +0 through a select (NaN may sit there); the
+// lane adds its residues in order, then the 64 lanes meet in a fixed xor butterfly (32, 16, .. 1).  Per-feature sums
+// take the same lane walk and butterfly.  The sums are a function of the item's (position, feature, value) triples
+// alone, and tot_* == masked_item_sums_kernel on res_* with the any-element-set residue mask, bit for bit: that kernel
+// adds the same values (an unset residue's is +0 here, and +0 there) in the same order.  mask is read as item n % B.
+// A step outside [0, T): no table row is read, every float output is NaN; counts is the mask's count regardless.
+__global__ __launch_bounds__(64) void angle_score_items_kernel(
+    const float* __restrict__ eps_hat, const float* __restrict__ eps, const uint8_t* __restrict__ mask,
+    const int64_t* __restrict__ level_steps, const float* __restrict__ coef, int T, float* __restrict__ term,
+    float* __restrict__ err, float* __restrict__ res_term, float* __restrict__ res_err2, float* __restrict__ feat_term,
+    float* __restrict__ feat_err2, float* __restrict__ tot_term, float* __restrict__ tot_err2, int32_t* __restrict__ counts,
+    int B, int L, int nb) {
+    const int n = blockIdx.x, lane = threadIdx.x;
+    const int64_t base = (int64_t)n * L * nb, mbase = (int64_t)(n % B) * L * nb;      // in groups of 4 elements
+    const int64_t step = level_steps[n];
+    const bool bad = step < 0 || step >= T;
+    const float nan = __builtin_nanf("");
+    const ScoreCoef c = bad ? ScoreCoef{nan, nan, nan} : ScoreCoef{coef[4 * step], coef[4 * step + 1], coef[4 * step + 2]};
+    float ft[SCORE_FMAX], fe[SCORE_FMAX];
+#pragma unroll
+    for (int f = 0; f < SCORE_FMAX; ++f) ft[f] = fe[f] = 0.f;
+    float acc_t = 0.f, acc_e = 0.f;
+    int cnt = 0;
+    for (int l = lane; l < L; l += 64) {
+        float rt = 0.f, re = 0.f;
+#pragma unroll
+        for (int j = 0; j < SCORE_FMAX / 4; ++j) {
+            if (j < nb) {
+                const int64_t g = (int64_t)l * nb + j;
+                const f32x4 hv = reinterpret_cast<const f32x4*>(eps_hat)[base + g];
+                const f32x4 ev = reinterpret_cast<const f32x4*>(eps)[base + g];
+                const uint32_t m4 = reinterpret_cast<const uint32_t*>(mask)[mbase + g];
+                f32x4 tv, rv;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    float t, r, r2;
+                    angle_score_elem(c, hv[q], ev[q], t, r, r2);
+                    if (bad) t = r = r2 = nan;
+                    tv[q] = t;
+                    rv[q] = r;
+                    const bool on = ((m4 >> (8 * q)) & 0xFFu) != 0;
+                    const float st = on ? t : 0.f, se = on ? r2 : 0.f;
+                    rt += st;
+                    re += se;
+                    ft[4 * j + q] += st;
+                    fe[4 * j + q] += se;
+                    cnt += on ? 1 : 0;
+                }
+                if (term) reinterpret_cast<f32x4*>(term)[base + g] = tv;
+                if (err) reinterpret_cast<f32x4*>(err)[base + g] = rv;
+            }
+        }
+        if (res_term) res_term[(int64_t)n * L + l] = bad ? nan : rt;
+        if (res_err2) res_err2[(int64_t)n * L + l] = bad ? nan : re;
+        acc_t += rt;
+        acc_e += re;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        acc_t += __shfl_xor(acc_t, off, 64);
+        acc_e += __shfl_xor(acc_e, off, 64);
+        cnt += __shfl_xor(cnt, off, 64);
+    }
+#pragma unroll
+    for (int f = 0; f < SCORE_FMAX; ++f) {
+        if (f < 4 * nb) {
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) {
+                ft[f] += __shfl_xor(ft[f], off, 64);
+                fe[f] += __shfl_xor(fe[f], off, 64);
+            }
+        }
+    }
+    if (lane != 0) return;
+    tot_term[n] = bad ? nan : acc_t;
+    tot_err2[n] = bad ? nan : acc_e;
+    counts[n] = cnt;
+#pragma unroll
+    for (int f = 0; f < SCORE_FMAX; ++f) {
+        if (f < 4 * nb) {
+            if (feat_term) feat_term[(int64_t)n * 4 * nb + f] = bad ? nan : ft[f];
+            if (feat_err2) feat_err2[(int64_t)n * 4 * nb + f] = bad ? nan : fe[f];
+        }
+    }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------- what the entry points share
@@ -851,7 +999,7 @@ extern "C" int e3d_keyed_draws(const int64_t* row_keys, uint64_t seed, int strea
                                int wrap, float scale, void* out, int64_t rows, void* stream) {
     E3D_REQUIRE(row_keys && out && rows > 0, "keyed_draws: bad arguments");
     E3D_REQUIRE(((stream_id >= 0 && stream_id <= 3) || stream_id == E3D_KNOWN_STREAM_STRUCT ||
-                 stream_id == E3D_KNOWN_STREAM_SEQ) && t >= 0 && t <= 65535,
+                 stream_id == E3D_KNOWN_STREAM_SEQ || stream_id == E3D_SCORE_STRUCT_NOISE) && t >= 0 && t <= 65535,
                 "keyed_draws: stream %d / step %d out of range", stream_id, t);
     E3D_REQUIRE(kind >= 0 && kind <= 3, "keyed_draws: kind %d", kind);
     E3D_REQUIRE(kind != 0 || (keyed_width(width) && aligned16({out})),
@@ -1029,4 +1177,41 @@ extern "C" int e3d_masked_item_sums(const float* values, const uint8_t* mask, fl
     E3D_REQUIRE(values && mask && sums && counts && N > 0 && L > 0, "masked_item_sums: bad arguments");
     hipLaunchKernelGGL(masked_item_sums_kernel, dim3(N), dim3(64), 0, (hipStream_t)stream, values, mask, sums, counts, L);
     return e3d_launch_status("e3d_masked_item_sums");
+}
+
+// ---------------------------------------------------------------- scoring supplied structures (entry points)
+extern "C" int e3d_keyed_q_sample_levels_wrap(const float* x0, const int64_t* row_keys, const int64_t* level_steps,
+                                              int max_step, const float* sqrt_ab, const float* sqrt_1mab, int T, float scale,
+                                              uint64_t seed, float* noise_out, float* xt_out, int N, int B, int L, int F,
+                                              void* stream) {
+    E3D_REQUIRE(x0 && row_keys && level_steps && sqrt_ab && sqrt_1mab && noise_out && xt_out && N > 0 && B > 0 && L > 0 && T > 0,
+                "keyed_q_sample_levels_wrap: bad arguments");
+    E3D_REQUIRE(N % B == 0, "keyed_q_sample_levels_wrap: N must be a multiple of B (N=%d, B=%d)", N, B);
+    E3D_REQUIRE(max_step >= 0 && max_step <= 65535,
+                "keyed_q_sample_levels_wrap: keyed streams hold steps up to 65535 (max_step=%d)", max_step);
+    E3D_REQUIRE(L <= 1 << 24, "keyed_q_sample_levels_wrap: positions must stay below 2^24 (L=%d)", L);
+    REQUIRE_KEYED_WIDTH("keyed_q_sample_levels_wrap", F);
+    REQUIRE_ALIGNED16("keyed_q_sample_levels_wrap", x0, noise_out, xt_out);
+    const int64_t item4 = (int64_t)L * (F / 4), n4 = (int64_t)N * item4;
+    hipLaunchKernelGGL(keyed_q_sample_levels_wrap_kernel, dim3(sweep_blocks(n4)), dim3(256), 0, (hipStream_t)stream, x0,
+                       row_keys, level_steps, max_step, sqrt_ab, sqrt_1mab, T, scale, seed, noise_out, xt_out, item4,
+                       (int64_t)B * item4, F / 4, n4);
+    return e3d_launch_status("e3d_keyed_q_sample_levels_wrap");
+}
+
+extern "C" int e3d_angle_score_items(const float* eps_hat, const float* eps, const uint8_t* mask, const int64_t* level_steps,
+                                     const float* coef, int T, float* term, float* err, float* res_term, float* res_err2,
+                                     float* feat_term, float* feat_err2, float* tot_term, float* tot_err2, int32_t* counts,
+                                     int N, int B, int L, int F, void* stream) {
+    E3D_REQUIRE(eps_hat && eps && mask && level_steps && coef && tot_term && tot_err2 && counts && N > 0 && B > 0 && L > 0 &&
+                    T > 0,
+                "angle_score_items: bad arguments");
+    E3D_REQUIRE(N % B == 0, "angle_score_items: N must be a multiple of B (N=%d, B=%d)", N, B);
+    E3D_REQUIRE(F > 0 && F % 4 == 0 && F <= SCORE_FMAX, "angle_score_items: F must be a multiple of 4 in [4, %d] (F=%d)",
+                SCORE_FMAX, F);
+    E3D_REQUIRE(aligned16({eps_hat, eps, term, err}) && ((uintptr_t)mask % 4) == 0,
+                "angle_score_items: eps_hat, eps, term, err must be 16B and mask 4B aligned");
+    hipLaunchKernelGGL(angle_score_items_kernel, dim3(N), dim3(64), 0, (hipStream_t)stream, eps_hat, eps, mask, level_steps,
+                       coef, T, term, err, res_term, res_err2, feat_term, feat_err2, tot_term, tot_err2, counts, B, L, F / 4);
+    return e3d_launch_status("e3d_angle_score_items");
 }

@@ -136,6 +136,10 @@ _SIGNATURES = {
     "e3d_keyed_discrete_forward_levels": (c_int, [_P, _P, _P, _P, c_int, c_uint64, _P, c_int, c_int, c_int, _P]),
     "e3d_discrete_score_rows": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "e3d_masked_item_sums": (c_int, [_P, _P, _P, _P, c_int, c_int, _P]),
+    # scoring supplied structures: keyed forward noising at per-item levels (stream 12), per-element terms + fixed-shape sums
+    "e3d_keyed_q_sample_levels_wrap": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, c_float, c_uint64, _P, _P, c_int, c_int, c_int,
+                                               c_int, _P]),
+    "e3d_angle_score_items": (c_int, [_P] * 5 + [c_int] + [_P] * 9 + [c_int, c_int, c_int, c_int, _P]),
     # keyed training and validation draws (ids and epoch read from device memory)
     "e3d_keyed_timesteps": (c_int, [_P, _P, c_uint64, c_int, c_int, _P, c_int, _P]),
     "e3d_keyed_q_sample_wrap": (c_int, [_P, _P, _P, _P, c_int, c_float, _P, _P, c_uint64, _P, _P, c_int, c_int, c_int, _P]),

@@ -35,6 +35,11 @@ DROP_LIGAND, DROP_POCKET = 8, 9
 # index of the chain; streams 1 and 3 stay as they are, so the free positions draw what they drew before.
 # sample.score_sequences noises a supplied sequence with KNOWN_SEQ too: the same law at the same step field
 KNOWN_STRUCT, KNOWN_SEQ = 10, 11
+# structure_model.sample.score_structures: the forward noise of a supplied backbone at the level that timestep t READS,
+# step field = t.  Stream 10 is not reused for it: KNOWN_STRUCT is drawn at the step whose LANDING level is t - 1 (the step
+# field t holds the noise of level t - 1), and it has no draw for level T - 1, the first one a score needs.  A stream of
+# its own also keeps streams 0 - 11 untouched: a seeded chain draws what it drew before.
+SCORE_STRUCT = 12
 
 
 def check_seed(seed):

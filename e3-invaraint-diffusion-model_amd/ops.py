@@ -1312,6 +1312,85 @@ def masked_item_sums(values, mask):
     return sums, counts
 
 
+# ----------------------------------------------------------------------------------------- scoring supplied structures
+# N = levels x items per launch, level-major (structure_model/sample.py::score_structures).
+
+def _chk_level_steps(level_steps, B, name):
+    """``level_steps`` int64 [N] on the device, N a positive multiple of B; returns N."""
+    _chk(level_steps, name + ".level_steps", torch.int64)
+    if level_steps.dim() != 1 or not level_steps.is_contiguous() or level_steps.numel() == 0 or level_steps.numel() % B:
+        raise ValueError(f"{name}: level_steps must be a contiguous [N] with N a positive multiple of the {B} items, got "
+                         f"{tuple(level_steps.shape)}")
+    return level_steps.numel()
+
+
+def keyed_q_sample_levels_wrap(x0, row_keys, level_steps, sqrt_ab, sqrt_1mab, scale, seed, max_step):
+    """(noise, x_t) float [N, L, F] of N = n * B items at their own levels: item i is item i % B of ``x0`` [B, L, F] (and of
+    ``row_keys`` [B * L, 2]) at timestep ``level_steps[i]`` (int64 [N] on the device, every entry in [0, max_step]), noise =
+    wrap(scale * z) with z the normals of (seed, row key, stream 12, that step), x_t = wrap(sqrt_ab[t] x0 + sqrt_1mab[t]
+    noise) -- q_sample_wrap's arithmetic.  Rows of no item get zeros, an item with a step outside the tables NaN."""
+    name = "keyed_q_sample_levels_wrap"
+    for n, tt in (("x0", x0), ("sqrt_ab", sqrt_ab), ("sqrt_1mab", sqrt_1mab)):
+        _chk(tt, f"{name}.{n}")
+    if x0.dim() != 3 or x0.shape[-1] % 4 or not x0.is_contiguous() or x0.numel() == 0:
+        raise ValueError(f"{name}: x0 must be a contiguous [B, L, F] with F a multiple of 4, got {tuple(x0.shape)}")
+    B, L, F = x0.shape
+    N = _chk_level_steps(level_steps, B, name)
+    if not (sqrt_ab.is_contiguous() and sqrt_1mab.is_contiguous() and sqrt_ab.dim() == 1 and sqrt_ab.shape == sqrt_1mab.shape
+            and sqrt_ab.numel() > 0):
+        raise ValueError(f"{name}: sqrt_ab and sqrt_1mab must be contiguous [T] tables of one length")
+    if not 0 <= int(max_step) <= keyed.MAX_STEP:
+        raise ValueError(f"{name}: keyed streams hold steps up to {keyed.MAX_STEP}, got max_step={max_step}")
+    if L > keyed.MAX_POSITION:
+        raise ValueError(f"{name}: keyed streams hold positions below 2^24, got a frame of {L}")
+    _chk_keys(row_keys, B * L, name)
+    noise = torch.empty((N, L, F), device=x0.device, dtype=torch.float32)
+    x_t = torch.empty_like(noise)
+    with _timed("keyed_q_sample_levels_wrap"):
+        hip.check(hip.lib().e3d_keyed_q_sample_levels_wrap(_p(x0), _p(row_keys), _p(level_steps), int(max_step), _p(sqrt_ab),
+                                                           _p(sqrt_1mab), sqrt_ab.shape[0], float(scale),
+                                                           keyed.check_seed(seed), _p(noise), _p(x_t), N, B, L, F, _stream()),
+                  "e3d_keyed_q_sample_levels_wrap")
+    return noise, x_t
+
+
+def angle_score_items(eps_hat, eps, mask, level_steps, coef, want_elements=False):
+    """The score terms of N = n * B items and their fixed-shape sums: ``eps_hat``, ``eps`` float [N, L, F]; ``mask`` uint8
+    [B, L, F], per element, read as item i % B; ``level_steps`` int64 [N] on the device; ``coef`` [T, 4] = ScoreTables.coef.
+    Returns a dict: ``res_term`` / ``res_err2`` [N, L], ``feat_term`` / ``feat_err2`` [N, F], ``tot_term`` / ``tot_err2``
+    [N], ``counts`` int32 [N] -- sums over the masked elements of term = h wrap(k (eps_hat - eps))^2 + add and of
+    wrap(eps - eps_hat)^2, the same bits for an item whatever its padding or batch -- and, with ``want_elements``,
+    ``term`` / ``err`` [N, L, F].  An item with a step outside [0, T): NaN."""
+    name = "angle_score_items"
+    _chk(eps_hat, name + ".eps_hat"); _chk(eps, name + ".eps"); _chk(mask, name + ".mask", torch.uint8); _chk(coef, name + ".coef")
+    if eps_hat.dim() != 3 or eps.shape != eps_hat.shape or not (eps_hat.is_contiguous() and eps.is_contiguous()) \
+            or eps_hat.numel() == 0:
+        raise ValueError(f"{name}: eps_hat and eps must be the same contiguous [N, L, F], got {tuple(eps_hat.shape)} and "
+                         f"{tuple(eps.shape)}")
+    N, L, F = eps_hat.shape
+    if F % 4 or F > 32:
+        raise ValueError(f"{name}: the feature count must be a multiple of 4 in [4, 32], got {F}")
+    if mask.dim() != 3 or mask.shape[1:] != (L, F) or mask.shape[0] == 0 or not mask.is_contiguous():
+        raise ValueError(f"{name}: mask must be a contiguous [B, {L}, {F}], got {tuple(mask.shape)}")
+    if _chk_level_steps(level_steps, mask.shape[0], name) != N:
+        raise ValueError(f"{name}: {level_steps.numel()} level_steps for {N} items")
+    if not (coef.is_contiguous() and coef.dim() == 2 and coef.shape[1] == 4 and coef.shape[0] > 0):
+        raise ValueError(f"{name}: coef must be a contiguous [T, 4] table, got {tuple(coef.shape)}")
+    dev = eps_hat.device
+    out = {"res_term": (N, L), "res_err2": (N, L), "feat_term": (N, F), "feat_err2": (N, F), "tot_term": (N,), "tot_err2": (N,)}
+    if want_elements:
+        out.update(term=(N, L, F), err=(N, L, F))
+    out = {k: torch.empty(shape, device=dev, dtype=torch.float32) for k, shape in out.items()}
+    out["counts"] = torch.empty((N,), device=dev, dtype=torch.int32)
+    with _timed("angle_score_items"):
+        hip.check(hip.lib().e3d_angle_score_items(_p(eps_hat), _p(eps), _p(mask), _p(level_steps), _p(coef), coef.shape[0],
+                                                  _p(out.get("term")), _p(out.get("err")), _p(out["res_term"]),
+                                                  _p(out["res_err2"]), _p(out["feat_term"]), _p(out["feat_err2"]),
+                                                  _p(out["tot_term"]), _p(out["tot_err2"]), _p(out["counts"]), N,
+                                                  mask.shape[0], L, F, _stream()), "e3d_angle_score_items")
+    return out
+
+
 KEYED_NORMAL, KEYED_UNIFORM, KEYED_ONEHOT, KEYED_CLASS = 0, 1, 2, 3
 
 

@@ -20,6 +20,7 @@ if __package__ in (None, ""):  # executed as a script from inside this directory
     _g.load_package()
     __package__ = "e3diff_amd.structure_model"
 
+import math
 import os
 import pickle
 import warnings
@@ -32,8 +33,8 @@ from .. import keyed, ops, packing
 from ..bert import BertConfig
 from ..packing import trimmed_length  # noqa: F401  (S.trimmed_length: bench.py and the tests read it here)
 from .dataset import LigandBindingSiteDataset, NoisedAnglesDataset
-from .model import ConditionalBertForDiffusion
-from .utils import CosineTables, KnownLevels, StridedTables
+from .model import ConditionalBertForDiffusion, ReceptorCache
+from .utils import CosineTables, KnownLevels, ScoreTables, StridedTables
 
 MODEL_PATH = ""  # trained state_dict (same key names as the reference's checkpoints)
 OUTPUT = "./data/output.pkl"
@@ -479,6 +480,208 @@ def p_sample_loop(model: nn.Module, ligand_mask, ligand_angle_noise, receptor_se
                               traj[n], wrap=True, mod=mod_table[i:i + 1], layout=layout, plan=plan, known_noise=kn)
     traj = frame.restore(traj, dim=1)                                     # [T/STEP, B, L, F], zeros outside the frame
     return traj if return_device else traj.cpu()
+
+
+def _tiled_cache(cache, n):
+    """The pocket cache of a padded or trimmed frame repeated for n levels x B items, level-major: item i reads the rows of
+    item i % B.  The cross K/V keep the bound their projection left on them (the content is the same)."""
+    if n == 1:
+        return cache
+
+    def rep(t):
+        out = t.repeat(n, 1)
+        if hasattr(t, "_e3d_absmax"):
+            out._e3d_absmax = t._e3d_absmax
+        return out
+    rows = packing.Rows.from_mask(cache.mask.repeat(n, 1), cache.rows.row_keys)
+    return ReceptorCache(rep(cache.encoder_states), None if cache.cross_kv is None else [rep(kv) for kv in cache.cross_kv],
+                         rows, n * cache.B, cache.L)
+
+
+def structure_prior_terms(x0, prior_ab, scale):
+    """float64, x0's shape: KL(q(x_T | x0) || N(0, scale^2)) per element with both laws read as Gaussians on the line,
+    ((1 - ab) + ab x0^2 / scale^2 - 1 - ln(1 - ab)) / 2 at ab = ``prior_ab`` (the level timestep T - 1 reads).  Host
+    arithmetic; practically 0 for the cosine schedule."""
+    ab = float(prior_ab)
+    x0 = x0.detach().double().cpu()
+    return ((1.0 - ab) + ab * x0 * x0 / (float(scale) ** 2) - 1.0 - math.log(1.0 - ab)) / 2.0
+
+
+@torch.no_grad()
+def score_structures(model, ligand_mask, angles, receptor_seq, receptor_mask, receptor_angle, total_timesteps, betas, *,
+                     levels=None, seed=None, item_ids=None, noises=None, scale=1.0, score_mask=None, trim_padding=False,
+                     levels_per_launch=None, details=None):
+    """How much the model likes given backbones: the variational score of the sampler's own reverse law for angles the
+    chain did not sample, in nats per angle (lower: the model likes the backbone better), for any backbone of a pocket --
+    replicates, natives, designs of other tools -- on one scale.
+
+    ``angles`` [B, L, F]: the clean ligand angles x0, in the layout ``p_sample_loop`` returns; the other tensors are its
+    arguments.  Indexing is the sampler's (``p_sample_loop``, stride 1, ``update="ancestral"``): timestep t in 0 .. T-1
+    reads a state at level ab_t, applies mean = sra_t (x - beta_t eps_hat / s1m_t), adds sigma_t z (sigma_t^2 =
+    ``CosineTables.posterior_variance[t]``, sigma_0 = 0), wraps to [-pi, pi) and lands on level t - 1 (level -1: the
+    sample).  For an item and a timestep t, per element:
+
+      * eps = wrap(scale z), z ~ N(0, 1), and x_t = wrap(sqrt_ab[t] x0 + s1m[t] eps): ``e3d_q_sample_wrap``'s arithmetic
+        and ``NoisedAnglesDataset``'s law (``scale``: its ``angular_var_scale``); every position is noised, padding
+        included, as in training;
+      * eps_hat = model.decode(t, x_t, ligand mask, receptor cache), the call the sampler makes;
+      * given the same x_t, the sampler's mean and the forward posterior's mean differ by k_t (eps_hat - eps), k_t =
+        beta_t / (sqrt(alpha_t) s1m_t); states live on the circle, so delta = wrap(k_t (eps_hat - eps));
+      * term = h_t delta^2 + add_t.  t > 0: h_t = 1 / (2 sigma_t^2), add_t = (scale^2 - 1) / 2 - ln(scale) (0 at scale 1):
+        the KL of the two Gaussian reverse laws, in nats.  t == 0: the sampler returns the wrapped x0 estimate with no
+        noise, and the term is the negative log-density of a Gaussian decoder of variance beta_0 around it (Ho et al.'s
+        sigma^2 = beta choice for the last step): h_0 = 1 / (2 beta_0), add_0 = ln(2 pi beta_0) / 2, which is negative
+        for small beta_0 -- a term and a bound may be negative: it is a density (``utils.ScoreTables``);
+      * err = wrap(eps - eps_hat), the argument of every training loss; err^2 is reported at every level as ``eps_mse``,
+        the counterpart of the sequence scorer's ``nll``.  It carries no schedule weight;
+      * prior = ((1 - ab) + ab x0^2 / scale^2 - 1 - ln(1 - ab)) / 2 at ab = ab_{T-1} (float64, on the host; practically 0
+        for the cosine schedule).
+
+    Over a set S of timesteps that contains 0 (``sequence_model.sample.score_levels``: ``levels=None`` every timestep,
+    ``levels=k`` {0} and k, 2k, ..), bound = prior + term_0 + w * sum_{t in S, t > 0} term_t over the scored elements, w =
+    (T - 1) / |S \\ {0}|, and score = bound / (number of scored elements).
+
+    What this number is not.  Wrapped normals are treated as Gaussians with the mean difference taken on the circle.  That
+    is accurate while sigma_t << pi; at the top of the cosine schedule sigma_t reaches 0.99995 rad and k_t 99.98 (T =
+    1000; both from ``CosineTables(1000).betas`` in float64), and there the term is an approximation, capped at pi^2 h_t.  The score is therefore NOT a certified likelihood
+    bound.  No trained checkpoint ships with the tree: nothing about its ranking quality has been measured.
+
+    Draws.  ``seed``: an int or a list of ints; each seed gives one keyed draw per (item, level, position, block of four
+    features) -- stream 12 at the step field t (keyed.py) -- so an item's score depends on (seed, ``item_ids[b]``, its
+    angles, its inputs) alone; terms are averaged over the seeds in float64 on the host and ``stderr`` is the standard
+    error of ``score`` over them (NaN for one seed).  ``item_ids`` default to 0 .. B-1 and need a seed.  ``seed=None``:
+    ``torch.randn`` on the device, or injected ``noises`` [S, B, L, F] (N(0, 1); scaled and wrapped as above, through
+    ``ops.q_sample_wrap``); a seed and ``noises`` together raise.
+
+    The pocket encoder runs once per call.  Levels are folded into the batch: a launch decodes ``levels_per_launch``
+    levels x B items with a per-item timestep against the cache's rows tiled for it (default: as many levels as keep it at
+    about 64 items).  ``trim_padding`` runs the trimmed frame (packing.Frame); packed frames share one timestep and are
+    not offered.  ``score_mask`` bool [B, L] or [B, L, F] names what is summed (and-ed with the padding mask; an item
+    with nothing scored gets a NaN score).
+
+    Returns CPU tensors: ``bound``, ``score``, ``prior``, ``stderr`` float64 [B]; ``n`` int32 [B], the scored elements;
+    ``terms`` and ``eps_mse`` float64 [S, B] (summed over the scored elements in a fixed reduction shape,
+    ``e3d_angle_score_items``; mean over seeds; ``eps_mse`` is already divided by ``n``); ``levels`` (the list S);
+    ``per_residue`` float64 [B, L], combined like ``bound`` (its prior included), NaN off the ligand; ``per_feature``
+    float64 [B, F], combined like ``bound`` WITHOUT the prior, so bound = prior + per_feature.sum(1).  ``details``: a
+    dict that receives ``x_t``, ``eps``, ``eps_hat`` [S, B, L, F] in the padded frame (one seed only)."""
+    from ..sequence_model.sample import score_levels
+    who = "score_structures"
+    T = int(total_timesteps)
+    if details is not None and not isinstance(details, dict):
+        raise ValueError(f"{who}: details must be a dict to fill, got {type(details).__name__}")
+    if not torch.is_tensor(angles) or angles.dim() != 3:
+        raise ValueError(f"{who}: angles must be a [B, L, F] tensor")
+    B, L, F = angles.shape
+    if F % 4 or not 0 < F <= 32:
+        raise ValueError(f"{who}: the feature count must be a multiple of 4 in [4, 32], got {F}")
+    if not torch.is_tensor(ligand_mask) or tuple(ligand_mask.shape) != (B, L):
+        raise ValueError(f"{who}: ligand_mask must be {(B, L)} like the angles")
+    if not torch.is_tensor(receptor_mask) or receptor_mask.dim() != 2 or receptor_mask.shape[0] != B:
+        raise ValueError(f"{who}: receptor_mask must be [{B}, Lr]")
+    Lr = receptor_mask.shape[1]
+    for name, t in (("receptor_seq", receptor_seq), ("receptor_angle", receptor_angle)):
+        if not torch.is_tensor(t) or t.dim() != 3 or tuple(t.shape[:2]) != (B, Lr):
+            raise ValueError(f"{who}: {name} must be [{B}, {Lr}, .] like the receptor mask")
+    tab = _tables(betas)
+    if tab.betas.shape[0] != T or T < 1:
+        raise ValueError(f"{who}: {tab.betas.shape[0]} betas for total_timesteps={T}")
+    if seed is None and item_ids is not None:
+        raise ValueError(f"{who}: item_ids key the seeded draws; pass a seed with them")
+    if seed is not None and noises is not None:
+        raise ValueError(f"{who}: pass either injected noises or a seed, not both")
+    seeds = [None]
+    if seed is not None:
+        seeds = [keyed.check_seed(v) for v in (seed if isinstance(seed, (list, tuple)) else [seed])]
+        if not seeds:
+            raise ValueError(f"{who}: an empty list of seeds")
+        keyed.check_steps(T)
+    if details is not None and len(seeds) > 1:
+        raise ValueError(f"{who}: details hold the draws of one seed; pass a single seed with them")
+    try:
+        S, w = score_levels(T, levels)
+    except ValueError:
+        raise ValueError(f"{who}: levels must be a positive stride, got {levels!r}") from None
+    if noises is not None and (not torch.is_tensor(noises) or tuple(noises.shape) != (len(S), B, L, F)):
+        raise ValueError(f"{who}: noises must be a tensor of {(len(S), B, L, F)}, one [B, L, F] per level")
+    valid = ligand_mask.cpu() != 0
+    scored = valid[..., None].expand(B, L, F)
+    if score_mask is not None:
+        if not torch.is_tensor(score_mask) or score_mask.dtype != torch.bool or tuple(score_mask.shape) not in ((B, L), (B, L, F)):
+            raise ValueError(f"{who}: score_mask must be a bool tensor of {(B, L)} or {(B, L, F)}")
+        sm = score_mask.cpu()
+        scored = scored & (sm if sm.dim() == 3 else sm[..., None])
+    chunk = max(1, 64 // B) if levels_per_launch is None else int(levels_per_launch)
+    if chunk < 1:
+        raise ValueError(f"{who}: levels_per_launch must be positive, got {levels_per_launch!r}")
+    tables = ScoreTables(tab, scale)            # a non-positive or non-finite scale raises here
+    ids = None if seed is None else keyed.item_ids(item_ids, B)
+
+    dev = next(model.parameters()).device
+    ligand_mask, receptor_mask = ligand_mask.to(dev), receptor_mask.to(dev)
+    frame = packing.Frame(ligand_mask, receptor_mask, trim=trim_padding)
+    cache = model.encode_receptor(frame.pocket(receptor_seq.to(dev)), frame.pocket(receptor_angle.to(dev)),
+                                  frame.pocket(receptor_mask))
+    x0 = angles.to(dev).float().contiguous()
+    x0_f = frame.ligand(x0).contiguous()
+    lmask = frame.ligand(ligand_mask).contiguous().float()
+    keys = None if seed is None else frame.row_keys(ids, dev)
+    sa, s1m = tab.sqrt_alphas_cumprod.float().contiguous().to(dev), tab.sqrt_one_minus_alphas_cumprod.float().contiguous().to(dev)
+    coef = tables.coef.to(dev)
+    scored_d = scored.to(torch.uint8).contiguous().to(dev)
+    if seed is None:
+        z_all = torch.randn(len(S), B, L, F, device=dev) if noises is None else noises.to(dev).float()
+        z_all = frame.ligand(z_all, dim=1).contiguous()
+        zero_t, one_row = torch.zeros(1, device=dev), torch.full((1,), float(scale), device=dev)
+
+    def launch(first, n, one_seed):
+        """Timesteps S[first : first + n] x the B items as one batch of N = n B items, level-major."""
+        steps = torch.tensor(S[first:first + n], device=dev, dtype=torch.long).repeat_interleave(B)
+        if one_seed is None:
+            z = z_all[first:first + n].reshape(n * B, -1).contiguous()
+            # eps = wrap(0 * 0 + scale * z): the forward-noising kernel with a one-row table (0, scale)
+            eps = ops.q_sample_wrap(torch.zeros_like(z), z, torch.zeros(n * B, device=dev, dtype=torch.long), zero_t, one_row)
+            eps = eps.reshape(n * B, *x0_f.shape[1:])
+            x_t = ops.q_sample_wrap(x0_f.repeat(n, 1, 1), eps, steps, sa, s1m)
+        else:
+            eps, x_t = ops.keyed_q_sample_levels_wrap(x0_f, keys, steps, sa, s1m, scale, one_seed, T - 1)
+        eps_hat = model.decode(steps, x_t, lmask.repeat(n, 1), _tiled_cache(cache, n)).contiguous().float()
+        # back to the padded frame, then the terms and their fixed-shape sums over the scored elements
+        x_t, eps, eps_hat = (frame.restore(t.reshape(n, B, *t.shape[1:]), dim=1).reshape(n * B, L, F).contiguous()
+                             for t in (x_t, eps, eps_hat))
+        out = ops.angle_score_items(eps_hat, eps, scored_d, steps, coef)
+        return (x_t, eps, eps_hat) + tuple(out[k].reshape(n, B, *out[k].shape[1:]) for k in
+                                           ("res_term", "feat_term", "tot_term", "tot_err2")) + (out["counts"][:B],)
+
+    per_seed = []
+    for one_seed in seeds:
+        parts = [launch(first, min(chunk, len(S) - first), one_seed) for first in range(0, len(S), chunk)]
+        x_t, eps, eps_hat, res_term, feat_term, tot_term, tot_err2 = (torch.cat([p[i] for p in parts]) for i in range(7))
+        per_seed.append(tuple(t.double().cpu() for t in (res_term, feat_term, tot_term, tot_err2)))
+        counts = parts[0][7].cpu()
+        if details is not None:
+            details.update({k: v.reshape(len(S), B, L, F).cpu() for k, v in (("x_t", x_t), ("eps", eps), ("eps_hat", eps_hat))})
+
+    def combine(v):
+        """term_0 + w * the sum of the other levels, of per-level values v [S, ..] (float64, on the host)."""
+        return v[0] + (w * v[1:].sum(dim=0) if len(S) > 1 else 0.0)
+
+    def seed_mean(i):
+        return torch.stack([p[i] for p in per_seed]).mean(dim=0)
+
+    prior_el = torch.where(scored, structure_prior_terms(angles, tables.prior_ab, scale), torch.zeros((), dtype=torch.float64))
+    prior = prior_el.sum(dim=(1, 2))
+    bound_seeds = torch.stack([prior + combine(p[2]) for p in per_seed])                  # [seeds, B]
+    n = counts.to(torch.int32)
+    per_item = torch.where(n > 0, 1.0 / n.double().clamp_min(1), torch.full((), float("nan"), dtype=torch.float64))
+    score_seeds = bound_seeds * per_item
+    nan_b = torch.full((B,), float("nan"), dtype=torch.float64)
+    stderr = score_seeds.std(dim=0, unbiased=True) / len(seeds) ** 0.5 if len(seeds) > 1 else nan_b
+    per_residue = prior_el.sum(dim=2) + combine(seed_mean(0))
+    return {"bound": bound_seeds.mean(dim=0), "score": score_seeds.mean(dim=0), "prior": prior, "n": n, "stderr": stderr,
+            "terms": seed_mean(2), "eps_mse": seed_mean(3) * per_item, "levels": list(S),
+            "per_residue": torch.where(valid, per_residue, torch.full((), float("nan"), dtype=torch.float64)),
+            "per_feature": combine(seed_mean(1))}
 
 
 def get_dataset(file_path):

@@ -139,6 +139,49 @@ class KnownLevels:
         self.levels[idx] = rows.float()
 
 
+class ScoreTables:
+    """Schedule scalars of the structure score (sample.py, ``score_structures``): what turns the model's noise error at
+    timestep ``t`` into the per-element term of the bound.
+
+    With the sampler's indexing (timestep t reads a state at level ab_t and lands on level t - 1) the sampler's mean and
+    the forward posterior's mean, given the same x_t, differ by k_t (eps_hat - eps); both laws have the variance sigma_t^2
+    = posterior_variance[t] when the noise has unit scale.  ``scale`` is the dataset's ``angular_var_scale``.
+
+    Derived in float64 from ``tab.betas`` with ab = cumprod(1 - betas), each entry rounded to fp32 once:
+
+        k_t = beta_t / (sqrt(1 - beta_t) sqrt(1 - ab_t))
+        t > 0:  h_t = 1 / (2 sigma_t^2), sigma_t^2 = beta_t (1 - ab_{t-1}) / (1 - ab_t);  add_t = (scale^2 - 1) / 2 - ln(scale)
+        t = 0:  h_0 = 1 / (2 beta_0);  add_0 = ln(2 pi beta_0) / 2      (a Gaussian decoder of variance beta_0: a density)
+
+    ``coef`` fp32 [T, 4]: row t = (k_t, h_t, add_t, 0) -- the table ``e3d_angle_score_items`` reads by each item's step.
+    ``prior_ab`` (float64): ab_{T-1}, the level of the prior term.
+    """
+
+    def __init__(self, tab: CosineTables, scale: float = 1.0):
+        scale = float(scale)
+        if not (0.0 < scale < float("inf")):
+            raise ValueError(f"ScoreTables: scale must be positive and finite, got {scale}")
+        betas = tab.betas.double()
+        T = int(betas.shape[0])
+        if T < 1:
+            raise ValueError("ScoreTables: an empty schedule")
+        ab = torch.cumprod(1.0 - betas, dim=0)
+        prev = torch.cat([torch.ones(1, dtype=torch.float64), ab[:-1]])
+        rows = torch.zeros((T, 4), dtype=torch.float64)
+        rows[:, 0] = betas / (torch.sqrt(1.0 - betas) * torch.sqrt(1.0 - ab))
+        var = betas * (1.0 - prev) / (1.0 - ab)
+        var[0] = betas[0]
+        rows[:, 1] = 1.0 / (2.0 * var)
+        rows[:, 2] = (scale * scale - 1.0) / 2.0 - math.log(scale)
+        rows[0, 2] = math.log(2.0 * math.pi * float(betas[0])) / 2.0
+        if not bool(torch.isfinite(rows).all()):
+            raise ValueError("ScoreTables: the schedule gives a non-finite coefficient (a beta of 0 or 1?)")
+        self.timesteps, self.scale = T, scale
+        self.coef64 = rows                       # before the one rounding, for checks against the closed forms
+        self.coef = rows.float().contiguous()
+        self.prior_ab = float(ab[-1])
+
+
 def cosine_beta_schedule(timesteps: int, s: float = 8e-3) -> torch.Tensor:
     return CosineTables(timesteps, s).betas
 

@@ -426,6 +426,46 @@ int e3d_discrete_score_rows(const int32_t* xt_idx, const int32_t* x0_idx, const 
 int e3d_masked_item_sums(const float* values, const uint8_t* mask, float* sums, int32_t* counts, int N, int L,
                          void* stream);
 
+/* ------------------------------------------------------------------ scoring supplied structures
+ * The score of the structure sampler's own reverse law for backbone angles x0 the chain did not sample
+ * (structure_model/sample.py::score_structures; DESIGN.md, "Scoring structures").  Levels do not depend on one another,
+ * so N = n * B items (n levels of the B supplied items, level-major: item i is item i % B at level i / B) go through one
+ * launch each.  Additions to ABI v5.
+ *
+ * Forward noising of the N items at their own levels with the noise drawn in-register from stream 12:
+ *   noise_out = wrap(scale * z),  xt_out = wrap(sqrt_ab[t] * x0 + sqrt_1mab[t] * noise_out),  t = level_steps[i]
+ * (the arithmetic of e3d_q_sample_wrap and e3d_keyed_q_sample_wrap), z the normals of (seed, row key, stream 12, step t,
+ * block j -> features 4j .. 4j+3, the block layout of stream 1).  x0 [B, L, F] and row_keys [B*L, 2] are given once: item
+ * i reads those of item i % B.  level_steps int64 [N] in DEVICE memory; max_step <= 65535 is the caller's bound on it.
+ * noise_out, xt_out [N, L, F].  A row of no item (a key position outside [0, 2^24)) gets zeros in both outputs; an item
+ * whose step lies outside [0, min(max_step, T - 1)] gets NaN in both and reads no table row.  F % 4 == 0, F <= 1024,
+ * N % B == 0. */
+int e3d_keyed_q_sample_levels_wrap(const float* x0, const int64_t* row_keys, const int64_t* level_steps, int max_step,
+                                   const float* sqrt_ab, const float* sqrt_1mab, int T, float scale, uint64_t seed,
+                                   float* noise_out, float* xt_out, int N, int B, int L, int F, void* stream);
+
+/* Per-element score terms of N items and their fixed-shape sums, one wave per item.  With (k, h, add, 0) = row
+ * level_steps[i] of coef [T, 4] (structure_model/utils.py, ScoreTables), per element in fp32, every product rounded
+ * before it is added to:
+ *   err   = wrap_[-pi,pi)(eps - eps_hat)
+ *   delta = wrap_[-pi,pi)(k * (eps_hat - eps));   term = h * (delta * delta) + add
+ * eps_hat, eps [N, L, F]; mask uint8 [B, L, F], per element, read as item i % B; level_steps int64 [N], DEVICE memory.
+ * Outputs (term, err, res_*, feat_* may each be NULL): term, err [N, L, F] (every element, masked or not);
+ * res_term, res_err2 [N, L]; feat_term, feat_err2 [N, F]; tot_term, tot_err2 [N]: sums of term and of err * err over
+ * the elements with mask != 0; counts int32 [N]: their number.
+ * Reduction shape: lane j of the wave takes positions j, j + 64, ... in order; a residue's value is the sum of its masked
+ * elements in feature order, a masked-out element adding an exact +0 through a select (NaN may sit there); the lane adds
+ * its residues in order; a fixed xor butterfly (32, 16, .. 1) over the 64 lanes gives the total.  Per-feature sums take
+ * the same lane walk and butterfly.  No atomics: the sums are a function of the item's (position, feature, value)
+ * triples alone -- the same bits for any L >= the last set position, in any batch -- and tot_* equals
+ * e3d_masked_item_sums applied to res_* with the any-element-set residue mask, bit for bit.
+ * An item whose step lies outside [0, T) reads no table row and gets NaN in every float output (counts stays the
+ * mask's count).  F % 4 == 0, F <= 32, N % B == 0; float pointers 16 B aligned, mask 4 B aligned. */
+int e3d_angle_score_items(const float* eps_hat, const float* eps, const uint8_t* mask, const int64_t* level_steps,
+                          const float* coef, int T, float* term, float* err, float* res_term, float* res_err2,
+                          float* feat_term, float* feat_err2, float* tot_term, float* tot_err2, int32_t* counts, int N,
+                          int B, int L, int F, void* stream);
+
 /* ------------------------------------------------------------------ keyed training and validation draws
  * The same generator and counter layout with the EPOCH in the step field (training epochs 0 .. 65534; 65535 is the
  * validation value) and streams 4 structure timestep, 5 structure forward noise, 6 sequence timestep, 7 sequence
