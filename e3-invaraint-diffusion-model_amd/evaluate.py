@@ -15,6 +15,11 @@ theta1 and theta3 on the residue they place (biolip.py); the datasets label thes
 tau, CA:C:1N, 1C:N:CA, CA:C:O) and the samplers produce the same columns; the NeRF builder (csrc/nerf.hip) WANTS
 the labelled meaning, with omega, tau and 1C:N:CA on the PREVIOUS residue.  ``builder_angles_from_stored`` is the map;
 ``create_pdb.py`` keeps feeding the columns as labelled, as the reference does.
+
+WITHOUT A NATIVE (design mode) none of the above applies; ``describe_samples`` says what each backbone IS instead --
+secondary structure, backbone hydrogen bonds, clashes, size -- through ONE call of ``e3d_backbone_geometry``
+(csrc/backbone_geometry.hip: Kabsch & Sander's rules in float64, a thread per residue; its header states the rules and the
+three differences from DSSP).  Agreement with the mkdssp program has not been measured.
 """
 import numpy as np
 import torch
@@ -286,3 +291,162 @@ def evaluate_samples(replicates, dataset, convention="stored", clash_cutoff=DEFA
         return rows
     placed = placed.cpu().numpy()
     return rows, [[placed[i * n_rep + r, :lens[i]].reshape(-1, 3) for r in range(n_rep)] for i in range(P)]
+
+
+# ------------------------------------------------------------------------------------------------ description without a native
+SS_HELIX, SS_STRAND = (0, 3, 4), (1, 2)      # H, G, I and B, E as indices into biolip.SS_VOCAB
+DEFAULT_CONTACT_CLASH = 2.5    # Angstrom between backbone atoms of residues at least two apart: a choice, not a standard
+GEOMETRY_KEYS = ("ss", "acc_rel", "acc_e", "don_rel", "don_e", "kappa", "clash", "hbonds", "status")
+
+
+def backbone_geometry(coords, off, is_pro=None, clash_cutoff=DEFAULT_CONTACT_CLASH, max_peptide_bond=2.5):
+    """coords [R,4,3] (N, CA, C, O per residue, all structures back to back), off [n_structs+1] (residue offsets,
+    off[0] = 0), is_pro [R] (non-zero: a proline, no amide hydrogen) or None -> a dict of device tensors, one row per
+    residue: ``ss`` u8 (index into ``biolip.SS_VOCAB``), ``acc_rel`` i32 [R,2] / ``acc_e`` f64 [R,2] (the two best
+    acceptors of its N-H, relative index and kcal/mol), ``don_rel`` / ``don_e`` (of its C=O), ``kappa`` f64 (degrees, NaN
+    where undefined), ``clash`` i32, ``hbonds`` i32 (acceptors of its N-H with E < -0.5), ``status`` i32 (0 ok, 1 a
+    non-finite coordinate, 3 held by no structure with good offsets).  The export itself (csrc/backbone_geometry.hip
+    states the rules and the three differences from DSSP); inputs are converted to contiguous float64 / int32 / uint8."""
+    tensors = (coords, off) + (() if is_pro is None else (is_pro,))
+    _require_cuda("backbone_geometry", *tensors)
+    R, n_structs = coords.shape[0], off.shape[0] - 1
+    assert tuple(coords.shape) == (R, 4, 3) and off.dim() == 1 and (is_pro is None or tuple(is_pro.shape) == (R,)), \
+        (coords.shape, off.shape, None if is_pro is None else is_pro.shape)
+    x, o = coords.contiguous().double(), off.to(torch.int32).contiguous()
+    pro = None if is_pro is None else (is_pro != 0).to(torch.uint8).contiguous()
+    new = lambda shape, dtype: torch.empty(shape, device=x.device, dtype=dtype)  # noqa: E731
+    out = {"ss": new((R,), torch.uint8), "acc_rel": new((R, 2), torch.int32), "acc_e": new((R, 2), torch.float64),
+           "don_rel": new((R, 2), torch.int32), "don_e": new((R, 2), torch.float64), "kappa": new((R,), torch.float64),
+           "clash": new((R,), torch.int32), "hbonds": new((R,), torch.int32), "status": new((R,), torch.int32)}
+    hip.check(hip.lib().e3d_backbone_geometry(x.data_ptr(), o.data_ptr(), None if pro is None else pro.data_ptr(),
+                                              *(out[k].data_ptr() for k in GEOMETRY_KEYS), n_structs, R,
+                                              float(clash_cutoff), float(max_peptide_bond),
+                                              torch.cuda.current_stream().cuda_stream), "e3d_backbone_geometry")
+    return out
+
+
+def _last_step(a):
+    a = np.asarray(a, dtype=np.float32)
+    return a[-1] if a.ndim == 3 else a
+
+
+def describe_samples(replicates, dataset=None, sequences=None, convention="stored", device="cuda",
+                     clash_cutoff=DEFAULT_CONTACT_CLASH, max_peptide_bond=2.5, _build=None, _geometry=None):
+    """What R replicates of P pockets ARE, without a native: secondary structure, backbone hydrogen bonds, clashes, size.
+
+    replicates: what ``evaluate_samples`` takes, R lists of P arrays [l_i,8] or [T,l_i,8] (the last step is taken).
+    dataset: optional.  With one, item i belongs to its record i (as in ``evaluate_samples``), rows carry
+        ``structure_ids``, and the native's own description -- built from ``angle_features[ligand_mask]``, prolines from
+        ``amino_acid`` -- is added as ``native``.  Design mode has none: leave it out.
+    sequences: optional [R][P] strings, e.g. the sequence sampler's designs; a 'P' marks a proline, which donates no
+        hydrogen bond.  A string whose length is not its chain's raises ValueError.
+    convention: as in ``evaluate_samples``.
+    ONE NeRF launch and ONE ``backbone_geometry`` call serve all chains; the sums per chain and the profile per pocket are
+    batched index sums on the device, nothing is launched per chain.
+
+    Returns one plain dict per pocket: ``index``, ``ligand_length``, ``structure_ids`` (with a dataset), and per replicate
+    [R]: ``ss`` (a string over ``biolip.SS_VOCAB``), ``helix_fraction`` (H + G + I), ``strand_fraction`` (E + B), ``hbonds``
+    (pairs with E < -0.5), ``clashes`` (backbone atom pairs of residues at least two apart closer than ``clash_cutoff``),
+    ``radius_of_gyration`` and ``end_to_end`` (C-alpha, Angstrom); ``ss_profile`` [l][8], the frequency of each letter
+    over the replicates at each position; ``native``, the same seven entries for the native chain.
+    The letters follow csrc/backbone_geometry.hip, which differs from DSSP in three stated ways; agreement with mkdssp
+    is not measured, and nothing here says whether a sample is GOOD."""
+    if convention not in ("stored", "labelled"):
+        raise ValueError(f"convention = {convention!r}: 'stored' or 'labelled'")
+    from .biolip import SS_VOCAB
+    build = _build or (lambda a, l: _device_build(a, l, device))
+    geometry = _geometry or backbone_geometry
+    n_rep = len(replicates)
+    P = len(replicates[0]) if n_rep else 0
+    records = _records_of(dataset) if dataset is not None else None
+    if n_rep < 1 or P < 1 or any(len(r) != P for r in replicates) or (records is not None and P > len(records)):
+        raise ValueError("replicates must be a non-empty list of equally long sampler outputs, no longer than the dataset")
+    if sequences is not None and (len(sequences) != n_rep or any(len(s) != P for s in sequences)):
+        raise ValueError(f"sequences must be [{n_rep}][{P}] strings, one per replicate and pocket")
+
+    # ---- every chain of the call: the replicates pocket-major, then the natives
+    chains, pro, lens = [], [], []
+    for i in range(P):
+        lens.append(_last_step(replicates[0][i]).shape[0])
+        if lens[i] < 1:
+            raise ValueError(f"pocket {i}: an empty chain")
+        for r in range(n_rep):
+            a = _last_step(replicates[r][i])
+            if a.shape != (lens[i], 8):
+                raise ValueError(f"pocket {i}, replicate {r}: angles {a.shape}, replicate 0 has {(lens[i], 8)}")
+            seq = "" if sequences is None else str(sequences[r][i])
+            if sequences is not None and len(seq) != lens[i]:
+                raise ValueError(f"pocket {i}, replicate {r}: the chain has {lens[i]} residues, the sequence {len(seq)}")
+            chains.append(a)
+            pro.append(np.frombuffer(seq.encode(), dtype=np.uint8) == ord("P") if seq else np.zeros(lens[i], dtype=bool))
+    for i in range(P if records is not None else 0):
+        lig = records[i]["ligand_mask"]
+        native = np.asarray(records[i]["angle_features"][lig], dtype=np.float32)
+        if native.shape != (lens[i], 8):
+            raise ValueError(f"pocket {i}: angles {(lens[i], 8)}, the record's ligand has {native.shape}")
+        chains.append(native)
+        pro.append(np.array([a == "P" for a, m in zip(records[i]["amino_acid"], lig.tolist()) if m], dtype=bool))
+    C, L = len(chains), max(lens)
+    batch = np.zeros((C, L, 8), dtype=np.float32)
+    for c, a in enumerate(chains):
+        batch[c, :a.shape[0]] = a
+    if convention == "stored":                  # on the padded batch at once: the entries it misses past a chain's end are
+        batch = builder_angles_from_stored(batch)    # zeros either way, and rows past the end stay zero
+    chain_len = torch.tensor([l for l in lens for _ in range(n_rep)] + (lens if records is not None else []), dtype=torch.int32)
+    coords = build(torch.from_numpy(batch), chain_len)                       # [C, L, 4, 3] float64
+    dev = coords.device
+    flat, atom_off = flatten_by_lengths(coords, chain_len)
+    flat, off = flat.reshape(-1, 4, 3), atom_off // 4
+    geo = geometry(flat, off, torch.from_numpy(np.concatenate(pro)).to(dev), clash_cutoff, max_peptide_bond)
+
+    # ---- sums per chain and the profile per pocket: index sums over all residues at once
+    lens_d = chain_len.to(dev).long()
+    chain_of = torch.repeat_interleave(torch.arange(C, device=dev), lens_d)
+    first = off[:-1].long()
+
+    def per_chain(values):
+        return torch.zeros((C,) + tuple(values.shape[1:]), device=dev, dtype=torch.float64).index_add_(0, chain_of,
+                                                                                                       values.double())
+    ss = geo["ss"].long()
+    onehot = torch.nn.functional.one_hot(ss, len(SS_VOCAB)).double()
+    counts = per_chain(onehot)
+    n = lens_d.double()
+    ca = flat[:, 1]
+    spread = ca - (per_chain(ca) / n[:, None])[chain_of]
+    rg = (per_chain((spread * spread).sum(-1)) / n).sqrt()
+    ends = (ca[first + lens_d - 1] - ca[first]).norm(dim=-1)
+    helix, strand = counts[:, list(SS_HELIX)].sum(-1) / n, counts[:, list(SS_STRAND)].sum(-1) / n
+    hbonds, clashes = per_chain(geo["hbonds"]), per_chain(geo["clash"]) / 2
+    # position p of pocket i, over its replicates: row pocket_first[i] + p of the profile
+    pocket_first = np.cumsum([0] + lens)
+    n_sampled = n_rep * int(pocket_first[-1])
+    pocket_of = torch.repeat_interleave(torch.arange(P, device=dev), torch.tensor(lens, device=dev) * n_rep)
+    start = torch.from_numpy(pocket_first[:-1]).to(dev)
+    row = start[pocket_of] + (torch.arange(n_sampled, device=dev) - first[chain_of[:n_sampled]])
+    profile = torch.zeros((int(pocket_first[-1]), len(SS_VOCAB)), device=dev, dtype=torch.float64)
+    profile = (profile.index_add_(0, row, onehot[:n_sampled]) / n_rep).cpu()
+
+    letters = np.frombuffer(SS_VOCAB.encode(), dtype=np.uint8)[geo["ss"].cpu().numpy()].tobytes().decode()
+    starts = off.cpu().tolist()
+    cols = {"helix_fraction": helix, "strand_fraction": strand, "hbonds": hbonds, "clashes": clashes,
+            "radius_of_gyration": rg, "end_to_end": ends}
+    cols = {k: v.cpu().tolist() for k, v in cols.items()}
+
+    def entry(c):
+        out = {"ss": letters[starts[c]:starts[c + 1]]}
+        for k, v in cols.items():
+            out[k] = int(round(v[c])) if k in ("hbonds", "clashes") else float(v[c])
+        return out
+
+    rows = []
+    for i in range(P):
+        per = [entry(i * n_rep + r) for r in range(n_rep)]
+        row_i = {"index": i, "ligand_length": lens[i]}
+        if records is not None:
+            row_i["structure_ids"] = dict(records[i]["structure_ids"])
+        row_i.update({k: [e[k] for e in per] for k in per[0]})
+        row_i["ss_profile"] = profile[pocket_first[i]:pocket_first[i + 1]].tolist()
+        if records is not None:
+            row_i["native"] = entry(P * n_rep + i)
+        rows.append(row_i)
+    return rows

@@ -9,7 +9,8 @@ builds schema-valid records (``biolip.validate_record``) from PDB files with two
     e3d_contact_residues   receptor residues with a heavy atom within ``cutoff`` of a ligand heavy atom (one launch)
 
 What a record built here does NOT carry: DSSP's ``secondary_structure`` (all '-') and ``numerical_features`` (zeros);
-no dataset or model of this package reads them.
+no dataset or model of this package reads them.  ``secondary_structure=True`` fills the first from the backbone with
+``evaluate.backbone_geometry`` (csrc/backbone_geometry.hip: Kabsch & Sander's rules, three stated differences from DSSP).
 
 The pocket by contact is a CHOICE, not BioLiP's rule: BioLiP's binding-site annotation uses van-der-Waals radii;
 here a receptor residue is in the pocket when any of its heavy atoms lies within ``cutoff`` (default 4.0 Angstrom) of
@@ -272,9 +273,24 @@ def _device_contacts(pairs, device, cutoff):
     return [np.nonzero(hit[a:b])[0].tolist() for a, b in zip(row0[:-1], row0[1:])]
 
 
+def _device_secondary_structure(complexes, records, device):
+    """Fill ``secondary_structure`` of each record from the backbone of its own rows: ONE ``evaluate.backbone_geometry``
+    call over all complexes, each complex one structure -- the receptor's kept rows, then the ligand's, as the record lays
+    them out.  Chain ends and gaps are found by the kernel's peptide-bond test, so bridges between the two chains count;
+    prolines come from the residue names.  Design-mode placeholders have no coordinates and keep '-'."""
+    from .evaluate import backbone_geometry           # evaluate imports this module
+    rows = [np.concatenate([c.backbone[1:-1] for c in pair if c is not None]).astype(np.float64) for pair in complexes]
+    pro = np.concatenate([np.array([ch == "P" for c in pair if c is not None for ch in c.seq[1:-1]], dtype=np.uint8)
+                          for pair in complexes])
+    off = np.cumsum([0] + [len(r) for r in rows]).astype(np.int32)
+    ss = backbone_geometry(*(torch.from_numpy(a).to(device) for a in (np.concatenate(rows), off, pro)))["ss"].cpu().tolist()
+    for rec, a, b in zip(records, off[:-1], off[1:]):
+        rec["secondary_structure"][:b - a] = [biolip.SS_VOCAB[v] for v in ss[a:b]]
+
+
 def record_from_chains(receptor, ligand=None, *, pocket=None, cutoff=DEFAULT_CUTOFF, ligand_length=None,
                        reference_pocket_shift=True, angles=None, status=None, pdb_id="", device="cuda",
-                       max_peptide_bond=MAX_PEPTIDE_BOND):
+                       max_peptide_bond=MAX_PEPTIDE_BOND, secondary_structure=False):
     """One schema-valid BioLiP record from parsed chains, laid out as the reference's ``create_data`` does: the first and
     last residue of each chain dropped, receptor first then ligand, ``coors`` = C-alpha, ``secondary_structure`` all '-',
     ``numerical_features`` zeros, ``angle_features`` in stored column order, ``edge_index`` = ligand x pocket int64 [2,E].
@@ -289,6 +305,10 @@ def record_from_chains(receptor, ligand=None, *, pocket=None, cutoff=DEFAULT_CUT
     angles: ``(receptor_angles [n,8], ligand_angles [m,8] or None)`` for the UNTRIMMED chains in stored column order,
         instead of the kernel's (``status``: the matching status arrays, optional); with an explicit ``pocket`` no GPU is
         touched.
+    secondary_structure: False (default) leaves ``secondary_structure`` all '-', as before.  True fills it with the
+        letters of csrc/backbone_geometry.hip (Kabsch & Sander's rules with three stated differences from DSSP; not
+        compared with mkdssp), the whole complex being one structure; ``numerical_features`` stays zeros either way
+        (relative accessibility needs side chains).  Needs the GPU.
     Raises ValueError for a ligand shorter than 5 residues after trimming (not in design mode) and for a kept residue whose
     angles are undefined (status bit 1); warns for a chain break (status bit 2)."""
     if ligand is None and pocket is None:
@@ -308,13 +328,16 @@ def record_from_chains(receptor, ligand=None, *, pocket=None, cutoff=DEFAULT_CUT
         positions = _device_contacts([(receptor, ligand)], device, cutoff)[0]
     rec = _assemble(receptor, ligand, per_chain[0][0], per_chain[1][0] if ligand is not None else None, positions,
                     ligand_length, reference_pocket_shift, pdb_id)
+    if secondary_structure:
+        _device_secondary_structure([(receptor, ligand)], [rec], device)
     biolip.validate_record(rec)
     return rec
 
 
 def records_from_pdb_files(jobs, device="cuda", *, cutoff=DEFAULT_CUTOFF, reference_pocket_shift=True,
-                           max_peptide_bond=MAX_PEPTIDE_BOND):
-    """Featurize many files with ONE angle launch and ONE contact launch over all chains of all files.
+                           max_peptide_bond=MAX_PEPTIDE_BOND, secondary_structure=False):
+    """Featurize many files with ONE angle launch and ONE contact launch over all chains of all files; with
+    ``secondary_structure`` one more call assigns every record's letters (``record_from_chains``).
 
     jobs: dicts with ``path`` (or PDB text), ``receptor`` (chain id) and either ``ligand`` (chain id) or ``ligand_length``
     plus ``pocket``; optional ``pocket`` (list of (resseq, icode)) with a ligand too, and ``pdb_id`` (default: the file's
@@ -345,8 +368,11 @@ def records_from_pdb_files(jobs, device="cuda", *, cutoff=DEFAULT_CUTOFF, refere
         positions = contacts[i] if i in contacts else _pocket_positions(receptor, job["pocket"])
         rec = _assemble(receptor, ligand, rec_ang, lig_ang, positions, job.get("ligand_length"), reference_pocket_shift,
                         pdb_id)
-        biolip.validate_record(rec, i)
         records.append(rec)
+    if secondary_structure:
+        _device_secondary_structure([p[1:3] for p in parsed], records, device)
+    for i, rec in enumerate(records):
+        biolip.validate_record(rec, i)
     return records
 
 

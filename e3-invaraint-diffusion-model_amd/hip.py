@@ -6,7 +6,7 @@ The library is the product's only compute path: there is no CPU or eager-PyTorch
 """
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_int64, c_uint32, c_uint64, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_uint32, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("E3D_HIP_LIB", os.path.join(_HERE, "libe3d_hip.so"))   # override: kernel experiments
@@ -161,6 +161,8 @@ _SIGNATURES = {
     "e3d_contact_residues": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P]),
     # rigid superposition of structure pairs (evaluate.py)
     "e3d_superpose_pairs": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    # secondary structure, hydrogen bonds, bends and clashes of backbones (evaluate.py, featurize.py)
+    "e3d_backbone_geometry": (c_int, 12 * [_P] + [c_int, c_int, c_double, c_double, _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

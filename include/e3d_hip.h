@@ -889,6 +889,52 @@ int e3d_contact_residues(const float* rec_xyz, const int32_t* rec_row, const int
 int e3d_superpose_pairs(const double* xyz, const int32_t* off, const int32_t* mob, const int32_t* ref, double* msd,
                         double* rot, double* trans, int32_t* status, int n_structs, int n_atoms, int n_pairs, void* stream);
 
+/* ---- backbone geometry: secondary structure, hydrogen bonds, bends, clashes (evaluate.py, featurize.py; an addition to
+ * ABI v5)
+ * Describes backbones that have no native to be compared with, after Kabsch & Sander (Biopolymers 22, 2577 (1983)), from
+ * N, CA, C, O alone, for all structures of a call at once.
+ *   coords fp64 [n_residues,4,3]: N, CA, C, O per residue, all structures back to back; off int32 [n_structs+1]: structure
+ *   s holds residues off[s] .. off[s+1]-1 (the convention of e3d_superpose_pairs, in residues); is_pro uint8 [n_residues]
+ *   or null (no proline): a proline has no amide hydrogen.  All on the device.
+ *   Per residue: ss uint8, the index into "HBEGITS-"; acc_rel int32 [.,2] and acc_e fp64 [.,2], the two lowest-energy
+ *   acceptors a of this residue's N-H as (a - d, E) (DSSP's N-H-->O columns); don_rel, don_e likewise the donors d of
+ *   its C=O as (d - a, E) (O-->H-N); only E < 0 counts, ties go to the lower index, an absent partner is 0 with 0.0;
+ *   kappa fp64 in degrees (NaN where undefined); clash int32; hbonds int32, the acceptors of its N-H with E < -0.5;
+ *   status int32: 0 ok, 1 a non-finite coordinate, 3 held by no structure with good offsets.
+ * Rules (every index inside the residue's own structure; restated in float64 numpy by tests/dssp_ref.py):
+ *   valid(i): all twelve coordinates finite; a residue that is not valid takes part in nothing, breaks contiguity, gets '-'.
+ *   bonded(i): i not the first of its structure, valid(i-1), valid(i), |C[i-1] - N[i]| <= max_peptide_bond.
+ *   contig(a, b): bonded(k) for all a < k <= b.
+ *   H[i] = N[i] + unit(C[i-1] - O[i-1]); exists iff bonded(i), i no proline, |C[i-1] - O[i-1]| > 0.
+ *   E(a, d), C=O of a accepting N-H of d: defined iff |a - d| >= 2, valid(a), H[d] exists and |CA[a] - CA[d]| < 9.0;
+ *     27.888 (1/|O_a N_d| + 1/|C_a H_d| - 1/|O_a H_d| - 1/|C_a N_d|), floored at -9.9; -9.9 when one of the four distances is
+ *     below 0.5.  hbond(a, d) := E(a, d) < -0.5.
+ *   n-turn at i (n = 3, 4, 5): contig(i, i+n) and hbond(i, i+n).
+ *   H on s .. s+3 when the 4-turns at s-1 and s exist; G on s .. s+2 (3-turns) only if none of the three is H, B or E;
+ *   I on s .. s+4 (5-turns) only if none of the five is H, B, E or G.
+ *   bridge(i, j): contig(i-1, i+1), contig(j-1, j+1), |i - j| >= 3; parallel if [hbond(i-1, j) and hbond(j, i+1)] or
+ *     [hbond(j-1, i) and hbond(i, j+1)]; antiparallel if [hbond(i, j) and hbond(j, i)] or [hbond(i-1, j+1) and
+ *     hbond(j-1, i+1)].  E: a bridge of type t with some j whose neighbour (i+-1, j+-1) (parallel) or (i+-1, j-+1)
+ *     (antiparallel) is a bridge of type t too; B: a bridge, but none with such a neighbour.
+ *   T: residues k+1 .. k+n-1 of an n-turn at k.  S: contig(i-2, i+2) and kappa(i) > 70 degrees, kappa the angle between
+ *     CA[i] - CA[i-2] and CA[i+2] - CA[i] as atan2(|u x w|, u . w).  Priority H, B, E, G, I, T, S, '-'.
+ *   clash[i]: atom pairs (atom of i, atom of j), j in the same structure, |i - j| >= 2, both valid, closer than
+ *     clash_cutoff -- the caller's choice, not a standard.  A structure's clash number is half the sum over its residues.
+ * THREE DIFFERENCES FROM DSSP: turns and bridges test the full relation E < -0.5, not DSSP's two best partners per side;
+ * pairs with |a - d| = 1 have no energy; energies are not rounded to 0.001.  No beta-bulges, no sheet labels.  Agreement
+ * with the mkdssp program has not been measured.
+ * A residue's results depend on its own structure's coordinates alone, not on the structure's place in the call.  All
+ * arithmetic float64; one call, five launches on one stream, no atomics, no host synchronisation, fixed loop bounds.
+ * Offsets are checked on the device: a structure with off[s] < 0, off[s+1] > n_residues or off[s+1] < off[s] is skipped,
+ * nothing is read through its offsets, and residues that no good structure holds get status 3, '-', absent partners, NaN
+ * kappa and zero counts.  Structures that overlap are memory-safe and otherwise undefined.
+ * Validates before any launch: coords, off and every output non-null; n_structs, n_residues > 0; clash_cutoff and
+ * max_peptide_bond > 0 and finite. */
+int e3d_backbone_geometry(const double* coords, const int32_t* off, const uint8_t* is_pro, uint8_t* ss, int32_t* acc_rel,
+                          double* acc_e, int32_t* don_rel, double* don_e, double* kappa, int32_t* clash, int32_t* hbonds,
+                          int32_t* status, int n_structs, int n_residues, double clash_cutoff, double max_peptide_bond,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

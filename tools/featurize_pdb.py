@@ -37,6 +37,9 @@ def parse_args(argv=None):
     ap.add_argument("--named-pocket", action="store_true",
                     help="mark the pocket residues actually named (default: the reference's shift by one residue, which the "
                          "published checkpoints were trained on; featurize.py)")
+    ap.add_argument("--dssp", action="store_true",
+                    help="fill secondary_structure from the backbone (featurize.py: Kabsch & Sander's rules on the GPU, not "
+                         "the mkdssp program; default: all '-')")
     ap.add_argument("-o", "--output", required=True)
     args = ap.parse_args(argv)
     if args.ligand is None and (args.pocket is None or args.ligand_length is None):
@@ -55,7 +58,7 @@ def main(argv=None):
     __graft_entry__.load_package()
     from e3diff_amd import featurize
     records = featurize.records_from_pdb_files(jobs_from_args(args), "cuda:0", cutoff=args.cutoff,
-                                               reference_pocket_shift=not args.named_pocket)
+                                               reference_pocket_shift=not args.named_pocket, secondary_structure=args.dssp)
     featurize.write(args.output, records)
     for r in records:
         n_lig, n_poc = int(r["ligand_mask"].sum()), int(r["pocket_mask"].sum())
