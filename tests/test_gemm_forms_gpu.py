@@ -13,32 +13,41 @@ operand runs the 3-term bf16 kernels, so 19 there is asserted bit-identical to 6
 ====================  ========  ===============================  ==================================  ===========================================
 layout (A, B)         NS, type  instantiation (tile)             forced by                           launch line / test id
 ====================  ========  ===============================  ==================================  ===========================================
-forward (row, row)    1 bf16    general form 1 (256x128)         pref 0, form 1                      gemm_split.hip:1137  test_forward_general_form[bf16-1]
-forward               1 bf16    general form 2 (128x128, 4 wv)   pref 0, form 2                      gemm_split.hip:1128  test_forward_general_form[bf16-2]
-forward               1 bf16    general form 3 (128x128, 8 wv)   pref 0, form 3 (or 4)               gemm_split.hip:1125  test_forward_general_form[bf16-3]
-forward               1 bf16    256x256 interleaved              pref 3, >= 160 tiles                gemm_split.hip:1078  test_forward_256x256[bf16-interleaved]
-forward               1 bf16    256x256 classic (2 buffers)      pref 1, >= 256 tiles                gemm_split.hip:1082  test_forward_256x256[bf16-classic]
-forward               2 bf16    general form 1 / 2 / 3           pref 0, form 1 / 2 / 3              1137 / 1128 / 1125   test_forward_general_form[bf16x3-1..3]
-forward               2 bf16    general form 4 (128x64, 4 wv)    pref 0, form 4                      gemm_split.hip:1116  test_forward_general_form[bf16x3-4]
-forward               2 bf16    persistent 256x256               pref 5, M % 256 == N % 256 == 0     gemm_split.hip:1072  test_forward_persistent[bf16x3]
-forward               2 bf16    256x256 interleaved              pref 3, >= 256 tiles                gemm_split.hip:1074  test_forward_256x256[bf16x3-interleaved]
-forward               2 bf16    256x256 classic (2 buffers)      pref 1, >= 256 tiles                gemm_split.hip:1082  test_forward_256x256[bf16x3-classic]
-forward               2 fp16    general form 1 / 2 / 3 / 4       pref 0, form 1 / 2 / 3 / 4          1137/1128/1125/1116  test_forward_general_form[f16x3-1..4]
-forward               2 fp16    persistent 256x256               pref 5, M % 256 == N % 256 == 0     gemm_split.hip:1072  test_forward_persistent[f16x3]
-forward               2 fp16    256x256 interleaved / classic    pref 3 / pref 1, >= 256 tiles       1074 / 1082          test_forward_256x256[f16x3-*]
-forward               3 bf16    general form 1 / 2               pref 0, form 1 / 2                  1137 / 1128          test_forward_general_form[bf16x6-1..2]
-forward               3 bf16    256x256 classic (1 buffer)       pref 1, >= 256 tiles                gemm_split.hip:1082  test_forward_256x256[bf16x6-classic]
+forward (row, row)    1 bf16    general form 1 (256x128)         pref 0, form 1                      1228 > 1269          test_forward_general_form[bf16-1]
+forward               1 bf16    general form 2 (128x128, 4 wv)   pref 0, form 2                      1219 > 1269          test_forward_general_form[bf16-2]
+forward               1 bf16    general form 3 (128x128, 8 wv)   pref 0, form 3 (or 4)               1216 > 1269          test_forward_general_form[bf16-3]
+forward               1 bf16    256x256 interleaved              pref 3, >= 160 tiles                1169 > 1116          test_forward_256x256[bf16-interleaved]
+forward               1 bf16    256x256 classic (2 buffers)      pref 1, >= 256 tiles                1173 > 1116          test_forward_256x256[bf16-classic]
+forward               2 bf16    general form 1 / 2 / 3           pref 0, form 1 / 2 / 3              1228/1219/1216 > 1269  test_forward_general_form[bf16x3-1..3]
+forward               2 bf16    general form 4 (128x64, 4 wv)    pref 0, form 4                      1207 > 1269          test_forward_general_form[bf16x3-4]
+forward               2 bf16    persistent 256x256               pref 5, M % 256 == N % 256 == 0     1163 > 1099          test_forward_persistent[bf16x3]
+forward               2 bf16    256x256 interleaved              pref 3, >= 256 tiles                1165 > 1116          test_forward_256x256[bf16x3-interleaved]
+forward               2 bf16    256x256 classic (2 buffers)      pref 1, >= 256 tiles                1173 > 1116          test_forward_256x256[bf16x3-classic]
+forward               2 fp16    general form 1 / 2 / 3 / 4       pref 0, form 1 / 2 / 3 / 4          1228/1219/1216/1207 > 1269  test_forward_general_form[f16x3-1..4]
+forward               2 fp16    persistent 256x256               pref 5, M % 256 == N % 256 == 0     1163 > 1099          test_forward_persistent[f16x3]
+forward               2 fp16    256x256 interleaved / classic    pref 3 / pref 1, >= 256 tiles       1165 / 1173 > 1116   test_forward_256x256[f16x3-*]
+forward               3 bf16    general form 1 / 2               pref 0, form 1 / 2                  1228 / 1219 > 1269   test_forward_general_form[bf16x6-1..2]
+forward               3 bf16    256x256 classic (1 buffer)       pref 1, >= 256 tiles                1173 > 1116          test_forward_256x256[bf16x6-classic]
 forward, exact fp32   --        gemm_nt_f32 (128x128)            its one kernel                      gemm_f32.hip:173     test_forward_exact_f32
-input grad (row, KM)  1, 2 bf16 general form 1 / 2 / 3           form 1 / 2 / 3                      1137 / 1128 / 1125   test_kmajor_general_form[dgrad-bf16*-*]
-input grad (row, KM)  3 bf16    general form 1 / 2 (t 6 and 19)  form 1 / 2                          1137 / 1128          test_kmajor_general_form[dgrad-bf16x6-*]
-(KM, row)             1,2,3     general form 1 / 2               form 1 / 2                          1137 / 1128          test_kmajor_general_form[kmaj_row-*]
-wgrad (KM, KM)        1,2,3     form 1, transposing staging      form 1; quads, 16-B aligned         gemm_split.hip:1135  test_weight_gradient_form[*-tr]
-wgrad (KM, KM)        1,2,3     form 1, dword staging            form 1; B at a 1-float offset       gemm_split.hip:1137  test_weight_gradient_form[*-dword]
-wgrad (KM, KM)        1,2,3     form 2 (128x128)                 form 2                              gemm_split.hip:1128  test_weight_gradient_form[*-form2]
-wgrad (KM, KM)        1,2,3     split-K of each of the three     few tiles, tokens >= 1024           gemm_split.hip:1158  test_weight_gradient_form[*] (K = 4001, 1061)
+input grad (row, KM)  1, 2 bf16 general form 1 / 2 / 3           form 1 / 2 / 3                      1228/1219/1216 > 1269  test_kmajor_general_form[dgrad-bf16*-*]
+input grad (row, KM)  3 bf16    general form 1 / 2 (t 6 and 19)  form 1 / 2                          1228 / 1219 > 1269   test_kmajor_general_form[dgrad-bf16x6-*]
+(KM, row)             1,2,3     general form 1 / 2               form 1 / 2                          1228 / 1219 > 1269   test_kmajor_general_form[kmaj_row-*]
+wgrad (KM, KM)        1,2,3     form 1, transposing staging      form 1; quads, 16-B aligned         1226 > 1269          test_weight_gradient_form[*-tr]
+wgrad (KM, KM)        1,2,3     form 1, dword staging            form 1; B at a 1-float offset       1228 > 1269          test_weight_gradient_form[*-dword]
+wgrad (KM, KM)        1,2,3     form 2 (128x128)                 form 2                              1219 > 1269          test_weight_gradient_form[*-form2]
+wgrad (KM, KM)        1,2,3     split-K of each of the three     few tiles, tokens >= 1024           1249 > 1269 (grid y) test_weight_gradient_form[*] (K = 4001, 1061)
+wgrad, grouped        1,2,3     gemm_wgrad_grouped_kernel, TR    quads, aligned, in span             1397 / 1401 / 1405   test_wgrad_forms_gpu.py::test_reduction_edges[grouped-*-tr], test_output_edges[grouped-*-tr]
+wgrad, grouped        1,2,3     the same, dword staging          one predicate term turned           1398 / 1402 / 1406   test_wgrad_forms_gpu.py::test_reduction_edges[grouped-*-dword], test_staging_predicate[*-grouped-*]
+wgrad, ragged         1,2,3     gemm_wgrad_ragged_kernel, TR     EVERY problem eligible              1449 / 1453 / 1457   test_wgrad_forms_gpu.py::test_reduction_edges[ragged-*-tr], test_problem_table[*-ragged-*]
+wgrad, ragged         1,2,3     the same, dword staging          ONE odd problem (first or last)     1450 / 1454 / 1458   test_wgrad_forms_gpu.py::test_reduction_edges[ragged-*-dword], test_staging_predicate[*-ragged-*]
 skinny                2 bf16/fp16  32x32 per wave, K slices      plan (1, 2^20) / (64, 16) / (0, 0)  gemm_skinny.hip:265  test_skinny[*-one|max|default]
 skinny + residual LN  2 bf16/fp16  the same + LayerNorm finish   plan (1, 2^20) / (64, 16) / (0, 0)  gemm_skinny.hip:357  test_skinny_residual_layernorm[*]
 ====================  ========  ===============================  ==================================  ===========================================
+
+Launch lines are those of csrc/gemm_split.hip unless a file is named: ``a > b`` = the branch of ``launch()`` (line a) that
+selects the form and the ``hipLaunchKernelGGL`` it ends in (1099: persistent, 1116: 256x256, 1269: general kernel, where
+split-K is the grid's y extent).  The two batched weight-gradient families (one launch site per NS and staging) have a
+forms file of their own, tests/test_wgrad_forms_gpu.py.
 
 Edges every instantiation sees (where its layout allows them): M = tile rows - 1, tile rows + 1 and a single row (the
 transposing weight-gradient staging needs M % 4 == 0: tile rows -/+ 4 there; the persistent kernel needs M % 256 == 0);
