@@ -1,5 +1,5 @@
-// Diffusion-process kernels: DDPM ancestral update + angular wrap, the strided (DDIM / respaced) update t -> s < t,
-// forward noising, the discrete (BLOSUM / uniform transition) posterior + categorical draw, the score terms of a
+// Diffusion-process kernels: DDPM ancestral update + angular wrap, the strided (DDIM / respaced) update t -> s < t and
+// its second-order multistep form, forward noising, the discrete (BLOSUM / uniform transition) posterior + categorical draw, the score terms of a
 // supplied sequence under that posterior, and the score terms of supplied backbone angles under the DDPM update.  All
 // HBM- or latency-bound.
 // The keyed forms (seeded chains) generate their draws in-register from (seed, row key, step): e3d_philox.h.
@@ -169,6 +169,69 @@ __global__ __launch_bounds__(256) void strided_step_wrap_kernel(
     // tail (n % 4)
     const int64_t r = n4 * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r < n) out[r] = strided_elem(c, x[r], eps_hat[r], noisy ? d.noise[r] : 0.f, noisy, wrap, wrap_x0);
+}
+
+// ---------------------------------------------------------------- multistep (DPM-Solver++ 2M) update
+// The strided update at eta = 0 plus one term that extrapolates with the x0 estimate the previous step stored (Lu et al.
+// 2022, the second-order multistep rule in its data-prediction form; the weight is capped, see MultistepTables):
+//   x0 = (x - s1m e) rsa;  wrap_x0: x0 = wrap_pi(x0);  v = a_s x0 + c_dir e
+//   c_1 != 0:  d = x0 - prev;  wrap: d = wrap_pi(d);  v += c_1 d          hist = x0;  out = wrap ? wrap_pi(v) : v
+// Row t of the [T,8] table (structure_model/utils.py, MultistepTables) = (s1m, rsa, a_s, c_dir, c_1, 0, 0, 0).  The
+// expressions up to v are strided_elem's without its noise term, fmaf for fmaf: a row with c_1 == 0 gives its bits.
+struct MultistepCoef { float s1m, rsa, a_s, c_dir, c_1; };
+
+__device__ __forceinline__ float multistep_elem(const MultistepCoef c, float x, float e, float prev, bool extrapolate,
+                                                int wrap, int wrap_x0, float& hist) {
+    float x0 = fmaf(-c.s1m, e, x) * c.rsa;
+    if (wrap_x0) x0 = wrap_pi(x0);
+    float v = fmaf(c.a_s, x0, c.c_dir * e);
+    if (extrapolate) {
+        float d = x0 - prev;
+        if (wrap) d = wrap_pi(d);   // the state lives on the circle: so does the difference of two estimates of it
+        v = fmaf(c.c_1, d, v);
+    }
+    hist = x0;
+    return wrap ? wrap_pi(v) : v;
+}
+
+// ``out`` may be ``x`` and ``hist_out`` may be ``hist_in``: every element is read before it is written, by the thread
+// that writes it.  A row with c_1 == 0 (the first and the last visited timestep) reads nothing through hist_in.  A step
+// index outside [0, T): no table row is read, both outputs are NaN.
+__global__ __launch_bounds__(256) void multistep_step_wrap_kernel(
+    const float* x, const float* __restrict__ eps_hat, const float* hist_in, const float* __restrict__ coef_table,
+    const int64_t* __restrict__ t_dev, int T, int wrap, int wrap_x0, float* out, float* hist_out, int64_t n4, int64_t n) {
+    const int64_t t = t_dev[0];
+    if (t < 0 || t >= T) {
+        strided_fill_nan(out, n4, n);
+        strided_fill_nan(hist_out, n4, n);
+        return;
+    }
+    const float* r = coef_table + 8 * t;
+    const MultistepCoef c{r[0], r[1], r[2], r[3], r[4]};
+    const bool extrapolate = c.c_1 != 0.f;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        const f32x4 xv = reinterpret_cast<const f32x4*>(x)[i];
+        const f32x4 ev = reinterpret_cast<const f32x4*>(eps_hat)[i];
+        f32x4 pv = {0.f, 0.f, 0.f, 0.f};
+        if (extrapolate) pv = reinterpret_cast<const f32x4*>(hist_in)[i];
+        f32x4 o, h;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float hj;
+            o[j] = multistep_elem(c, xv[j], ev[j], pv[j], extrapolate, wrap, wrap_x0, hj);
+            h[j] = hj;
+        }
+        reinterpret_cast<f32x4*>(out)[i] = o;
+        reinterpret_cast<f32x4*>(hist_out)[i] = h;
+    }
+    // tail (n % 4)
+    const int64_t q = n4 * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q < n) {
+        float hq;
+        out[q] = multistep_elem(c, x[q], eps_hat[q], extrapolate ? hist_in[q] : 0.f, extrapolate, wrap, wrap_x0, hq);
+        hist_out[q] = hq;
+    }
 }
 
 // q(x_t | x_0) of one element: wrap(a_t x0 + s_t noise); shared by the buffer form and the keyed form
@@ -919,6 +982,18 @@ extern "C" int e3d_strided_step_wrap(const float* x, const float* eps_hat, const
     hipLaunchKernelGGL(strided_step_wrap_kernel<false>, dim3(sweep_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, x,
                        eps_hat, buffer_draws(noise), coef_table, t_dev, T, wrap, wrap_x0, out, n / 4, n);
     return e3d_launch_status("e3d_strided_step_wrap");
+}
+
+extern "C" int e3d_multistep_step_wrap(const float* x, const float* eps_hat, const float* hist_in, const float* coef_table,
+                                       const int64_t* t_dev, int T, int wrap, int wrap_x0, float* out, float* hist_out,
+                                       int64_t n, void* stream) {
+    E3D_REQUIRE(x && eps_hat && hist_in && coef_table && t_dev && out && hist_out && n > 0 && T > 0,
+                "multistep_step_wrap: bad arguments");
+    E3D_REQUIRE(out != hist_out, "multistep_step_wrap: out and hist_out must be two buffers");
+    REQUIRE_ALIGNED16("multistep_step_wrap", x, eps_hat, hist_in, out, hist_out);
+    hipLaunchKernelGGL(multistep_step_wrap_kernel, dim3(sweep_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, x, eps_hat,
+                       hist_in, coef_table, t_dev, T, wrap, wrap_x0, out, hist_out, n / 4, n);
+    return e3d_launch_status("e3d_multistep_step_wrap");
 }
 
 extern "C" int e3d_q_sample_wrap(const float* x0, const float* noise, const int64_t* t,

@@ -122,6 +122,8 @@ _SIGNATURES = {
     # strided (DDIM / respaced) structure update: [T,8] coefficient table, step index on the device
     "e3d_strided_step_wrap": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P, c_int64, _P]),
     "e3d_keyed_strided_step_wrap": (c_int, [_P, _P, _P, _P, c_int, _P, c_uint64, c_int, c_int, _P, c_int64, c_int, _P]),
+    # multistep (DPM-Solver++ 2M) structure update: the strided arguments plus the x0 history in and out (an addition)
+    "e3d_multistep_step_wrap": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, c_int64, _P]),
     # partial redesign: held positions overwritten in place after the update (additions, no signature changed)
     "e3d_known_compose_wrap": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_float, c_int64, _P]),
     "e3d_keyed_known_compose_wrap": (c_int, [_P, _P, _P, _P, _P, c_int, c_float, _P, c_uint64, c_int64, c_int, _P]),

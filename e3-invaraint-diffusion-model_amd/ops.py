@@ -985,6 +985,23 @@ def strided_step_wrap(x, eps_hat, noise, coef_table, t_dev, wrap=True, wrap_x0=F
     return out
 
 
+def multistep_step_wrap(x, eps_hat, hist, coef_table, t_dev, wrap=True, wrap_x0=False, out=None):
+    """The second-order multistep update t -> successor(t) (DPM-Solver++ 2M, capped weight): the strided update at
+    eta == 0 plus c_1 * (x0 - hist), with the coefficients in row ``t_dev[0]`` of ``coef_table`` [T,8]
+    (structure_model.utils.MultistepTables.coef).  ``hist``: the x0 estimate the previous step stored, like ``x``; it is
+    updated in place with this step's estimate, and a row with c_1 == 0 does not read it.  ``wrap``: the difference of the
+    two estimates is taken on the circle, like the state.  Draws nothing.  ``out`` may be ``x``; returns ``out``."""
+    out = _chk_update("multistep_step_wrap", x, eps_hat, None, coef_table, 8, t_dev, out)
+    _chk(hist, "multistep_step_wrap.hist")
+    assert hist is not None and hist.is_contiguous() and hist.shape == x.shape
+    assert hist.data_ptr() != out.data_ptr() and hist.data_ptr() != x.data_ptr()
+    with _timed("multistep_step_wrap"):
+        hip.check(hip.lib().e3d_multistep_step_wrap(_p(x), _p(eps_hat), _p(hist), _p(coef_table), _p(t_dev),
+                                                    coef_table.shape[0], int(wrap), int(wrap_x0), _p(out), _p(hist),
+                                                    x.numel(), _stream()), "e3d_multistep_step_wrap")
+    return out
+
+
 def q_sample_wrap(x0, noise, t, sqrt_ab, sqrt_1mab):
     for n, tt in (("x0", x0), ("noise", noise), ("sqrt_ab", sqrt_ab), ("sqrt_1mab", sqrt_1mab)):
         _chk(tt, "q_sample_wrap." + n)

@@ -9,7 +9,9 @@ reference's structure_model/sample.py, restructured for the device:
 
 Beyond the reference: ``update="strided"`` (``UPDATE``) visits every STEP-th timestep with the schedule-consistent
 DDIM / respaced-ancestral update of Song et al. 2021 (``e3d_strided_step_wrap``, ``utils.StridedTables``) instead of
-applying one-step coefficients to a STEP-wide jump.
+applying one-step coefficients to a STEP-wide jump, and ``update="multistep"`` visits the same timesteps with the
+second-order multistep update DPM-Solver++(2M) of Lu et al. 2022 (``e3d_multistep_step_wrap``, ``utils.MultistepTables``):
+the same one decoder forward per step, the previous step's x0 estimate kept in a history buffer, no random numbers.
 
 Run as ``python sample.py`` from this directory after editing the constants, like the reference.
 """
@@ -34,7 +36,7 @@ from ..bert import BertConfig
 from ..packing import trimmed_length  # noqa: F401  (S.trimmed_length: bench.py and the tests read it here)
 from .dataset import LigandBindingSiteDataset, NoisedAnglesDataset
 from .model import ConditionalBertForDiffusion, ReceptorCache
-from .utils import CosineTables, KnownLevels, ScoreTables, StridedTables
+from .utils import CosineTables, KnownLevels, MultistepTables, ScoreTables, StridedTables
 
 MODEL_PATH = ""  # trained state_dict (same key names as the reference's checkpoints)
 OUTPUT = "./data/output.pkl"
@@ -53,6 +55,9 @@ ARITHMETIC = "f16x3"
 # variance of the respaced chain.  WRAP_X0 (E3D_SAMPLE_WRAP_X0=1): wrap the x0 estimate to [-pi, pi), the angle analogue
 # of clip_denoised -- 1/sqrt(ab_t) reaches 6.4e4 at t = 999 of the cosine schedule.  Sample quality under striding has
 # not been measured here (no trained checkpoint ships with the tree): tools/evaluate_samples.py measures it.
+# "multistep" (E3D_SAMPLE_UPDATE=multistep): the second-order multistep jump between the same visited timesteps
+# (DPM-Solver++ 2M with a capped weight; utils.MultistepTables) -- DDIM's cost per step and no draws; ETA must stay 0,
+# WRAP_X0 applies.  Its sample quality is unmeasured too; its solver error on an exactly solvable model is in DESIGN.md.
 UPDATE = os.environ.get("E3D_SAMPLE_UPDATE", "ancestral")
 ETA = float(os.environ.get("E3D_SAMPLE_ETA", "0"))
 WRAP_X0 = os.environ.get("E3D_SAMPLE_WRAP_X0", "0") == "1"
@@ -101,7 +106,7 @@ def _tables(betas):
 def p_sample(model, ligand_mask, ligand_angle_noise, receptor_seq, receptor_mask, receptor_angle,
              timestep, betas, noise=None, receptor_cache=None, out=None, wrap=False, seed=None,
              item_ids=None, strided=None, wrap_x0=False, known=None, known_mask=None, known_noise=None,
-             known_levels=None, known_scale=1.0) -> torch.Tensor:
+             known_levels=None, known_scale=1.0, multistep=None, history=None) -> torch.Tensor:
     """One reverse step x_t -> x_{t-1} (reference sample.py:55-99).  Like the reference's
     p_sample the result is NOT wrapped unless ``wrap=True`` (p_sample_loop's sample.py:140-142
     fused into the same kernel).
@@ -113,6 +118,9 @@ def p_sample(model, ligand_mask, ligand_angle_noise, receptor_seq, receptor_mask
     0 .. B-1; see keyed.py); exclusive with ``noise``.
     ``strided``: a StridedTables -- the step goes from ``timestep`` straight to its successor in that table's order with
     the DDIM / respaced update (``wrap_x0``: wrap the x0 estimate); eta == 0 draws nothing.
+    ``multistep``: a MultistepTables -- the same jump with the second-order multistep update (``wrap_x0`` as above; no
+    draws; exclusive with ``strided``).  ``history`` [B,L,F] on the device: the x0 estimate the previous step of the chain
+    stored, overwritten in place with this step's; the first and the last visited timestep do not read it.
     ``known`` [B,L,F] + ``known_mask`` (bool [B,L] or [B,L,F]) + ``known_levels`` (a KnownLevels of the chain's order):
     the held positions of the result are overwritten with the forward-noised copy of ``known`` at the level the step lands
     on (``p_sample_loop``, "partial redesign"); ``known_noise`` injects its N(0,1) draw, a ``seed`` keys it (stream 10).
@@ -127,9 +135,11 @@ def p_sample(model, ligand_mask, ligand_angle_noise, receptor_seq, receptor_mask
     elif item_ids is not None:
         raise ValueError("p_sample: item_ids key the seeded draws; pass a seed with them")
     plan = step_plan(betas, x.device, strided=strided, wrap_x0=wrap_x0, row_keys=row_keys, seed=seed, known=x0,
-                     known_mask=m8, known_levels=known_levels, known_scale=known_scale)
+                     known_mask=m8, known_levels=known_levels, known_scale=known_scale, multistep=multistep)
+    if (multistep is None) != (history is None):
+        raise ValueError("p_sample: multistep=MultistepTables(...) and history (the previous x0 estimate) go together")
     return _reverse_step(model, ligand_mask, x, receptor_seq, receptor_mask, receptor_angle, timestep, betas, noise,
-                         receptor_cache, out, wrap=wrap, plan=plan, known_noise=kn)
+                         receptor_cache, out, wrap=wrap, plan=plan, known_noise=kn, history=history)
 
 
 def _known_chain(known, known_mask, known_noises, seed, ligand_mask, x, steps, who):
@@ -171,7 +181,9 @@ class StepPlan:
     sqrt_one_minus_alphas_cumprod, sigma), or ``strided.coef`` [T,8]; None where no launch of the plan reads one (the
     eager unkeyed ancestral step takes four scalars from ``tab``).  ``keyed`` = (row keys, seed): the draws are generated
     inside the kernels (keyed.py); None: noise tensors.  ``known_x0`` / ``known_mask`` (uint8) / ``known_levels`` (a
-    KnownLevels; ``levels``: its table on the device) / ``known_scale``: the held positions; ``known_x0`` None: none."""
+    KnownLevels; ``levels``: its table on the device) / ``known_scale``: the held positions; ``known_x0`` None: none.
+    ``multistep``: a MultistepTables instead of ``strided`` (``coef``: its [T,8] table).  Its update reads and rewrites
+    the chain's x0 history, which belongs to the chain and not to this record: ``update`` is handed it."""
     tab: CosineTables
     coef: torch.Tensor = None
     strided: StridedTables = None
@@ -182,10 +194,13 @@ class StepPlan:
     known_levels: KnownLevels = None
     levels: torch.Tensor = None
     known_scale: float = 1.0
+    multistep: MultistepTables = None
 
     @property
     def order(self):
         """The timesteps a chain of this plan may visit, descending: the rows of its tables that are not NaN."""
+        if self.multistep is not None:
+            return self.multistep.order
         if self.strided is not None:
             return self.strided.order
         if self.known_levels is not None:
@@ -193,8 +208,9 @@ class StepPlan:
         return range(self.tab.betas.shape[0] - 1, -1, -1)
 
     def update_draws(self, t_index):
-        """Whether the update at ``t_index`` reads a noise tensor: not keyed, not t = 0 (ancestral), not a strided sigma of 0."""
-        if self.keyed is not None:
+        """Whether the update at ``t_index`` reads a noise tensor: not keyed, not t = 0 (ancestral), not a strided sigma of
+        0, never the multistep update."""
+        if self.keyed is not None or self.multistep is not None:
             return False
         if self.strided is not None:
             return float(self.strided.coef[t_index, 4]) != 0.0
@@ -204,11 +220,16 @@ class StepPlan:
         """Whether ``compose`` at ``t_index`` reads a noise tensor: held positions, not keyed, not the clean level."""
         return self.known_x0 is not None and self.keyed is None and float(self.known_levels.levels[t_index, 1]) != 0.0
 
-    def update(self, x, eps_hat, t_dev, noise, out, wrap, t_index=None):
+    def update(self, x, eps_hat, t_dev, noise, out, wrap, t_index=None, history=None):
         """x_t -> x_{t-1} (``t_dev``: int64 on the device, the step index first).  With the host's ``t_index`` (eager) the
         draw is settled here -- none where ``update_draws`` says so, else ``noise`` or a fresh ``torch.randn_like`` -- and
-        the unkeyed ancestral update is the scalar launch; without it (captured) ``noise`` is the graph's buffer or None."""
+        the unkeyed ancestral update is the scalar launch; without it (captured) ``noise`` is the graph's buffer or None.
+        ``history``: the chain's x0 history, which a multistep plan reads and rewrites in place."""
         eps_hat = eps_hat.contiguous()
+        if self.multistep is not None:    # t -> its successor in the table's order; no draws, keyed or not
+            if history is None:
+                raise ValueError("a multistep step needs the chain's history buffer (the previous x0 estimate)")
+            return ops.multistep_step_wrap(x, eps_hat, history, self.coef, t_dev, wrap=wrap, wrap_x0=self.wrap_x0, out=out)
         if t_index is not None:
             noise = _eager_noise(x, noise, self.update_draws(t_index))
         if self.strided is not None:      # t -> its successor in the table's order
@@ -245,17 +266,23 @@ def _eager_noise(x, noise, draws):
 
 
 def step_plan(betas, dev=None, table=False, strided=None, wrap_x0=False, row_keys=None, seed=None, known=None,
-              known_mask=None, known_levels=None, known_scale=1.0):
+              known_mask=None, known_levels=None, known_scale=1.0, multistep=None):
     """The StepPlan of a chain, checked.  ``betas``: the schedule betas or a CosineTables; ``dev``: where its tables go.
     ``table``: build the [T,4] table although the eager step would not read it (a GraphedReverseStep may run the plan); a
     keyed ancestral plan has it anyway, a strided one has its own.  ``strided``: a StridedTables (+ ``wrap_x0``);
     ``row_keys`` + ``seed``: keyed draws; ``known`` + ``known_mask`` (uint8; both like the state, in the chain's frame) +
-    ``known_levels`` (a KnownLevels of the chain's order) + ``known_scale``: held positions."""
+    ``known_levels`` (a KnownLevels of the chain's order) + ``known_scale``: held positions.  ``multistep``: a
+    MultistepTables (+ ``wrap_x0``) in the place of ``strided``, not next to it; a seed then keys the held positions alone."""
     tab = _tables(betas)
-    if strided is None and wrap_x0:
-        raise ValueError("step_plan: wrap_x0 belongs to the strided update; pass strided=StridedTables(...)")
+    if strided is not None and multistep is not None:
+        raise ValueError("step_plan: strided and multistep are two update rules; pass one of them")
+    if strided is None and multistep is None and wrap_x0:
+        raise ValueError("step_plan: wrap_x0 belongs to the strided and multistep updates; pass strided=StridedTables(...) "
+                         "or multistep=MultistepTables(...)")
     if strided is not None and not isinstance(strided, StridedTables):
         raise TypeError(f"step_plan: strided must be a StridedTables, got {type(strided).__name__}")
+    if multistep is not None and not isinstance(multistep, MultistepTables):
+        raise TypeError(f"step_plan: multistep must be a MultistepTables, got {type(multistep).__name__}")
     if (row_keys is None) != (seed is None):
         raise ValueError("step_plan: keyed draws need both row_keys and a seed")
     if known is not None and not isinstance(known_levels, KnownLevels):
@@ -263,15 +290,16 @@ def step_plan(betas, dev=None, table=False, strided=None, wrap_x0=False, row_key
     if seed is not None:
         keyed.check_steps(tab.betas.shape[0])
     coef = None
-    if strided is not None:
-        coef = strided.coef.contiguous().to(dev)
+    if strided is not None or multistep is not None:
+        coef = (strided or multistep).coef.contiguous().to(dev)
     elif table or seed is not None:
         coef = torch.stack([tab.sqrt_recip_alphas, tab.betas, tab.sqrt_one_minus_alphas_cumprod, tab.sigma],
                            dim=1).float().contiguous().to(dev)
     held = {} if known is None else dict(known_x0=known.contiguous(), known_mask=known_mask.contiguous(),
                                          known_levels=known_levels, levels=known_levels.levels.to(dev),
                                          known_scale=float(known_scale))
-    return StepPlan(tab, coef, strided, bool(wrap_x0), None if seed is None else (row_keys, keyed.check_seed(seed)), **held)
+    return StepPlan(tab, coef, strided, bool(wrap_x0), None if seed is None else (row_keys, keyed.check_seed(seed)),
+                    multistep=multistep, **held)
 
 
 def keyed_x_T(seed, item_ids, L, n_ft=8, scale=1.0, device=None):
@@ -284,9 +312,10 @@ def keyed_x_T(seed, item_ids, L, n_ft=8, scale=1.0, device=None):
 
 
 def _reverse_step(model, ligand_mask, x_t, receptor_seq, receptor_mask, receptor_angle, timestep,
-                  betas, noise, receptor_cache, out, wrap, mod=None, layout=None, plan=None, known_noise=None):
+                  betas, noise, receptor_cache, out, wrap, mod=None, layout=None, plan=None, known_noise=None, history=None):
     """The eager reverse step: decode, ``plan.update``, ``plan.compose``.  ``plan`` None: the plain ancestral step from
-    ``betas``.  ``noise`` / ``known_noise``: injected draws of the update / of the held positions."""
+    ``betas``.  ``noise`` / ``known_noise``: injected draws of the update / of the held positions.  ``history``: the
+    chain's x0 history in the chain's frame (a multistep plan)."""
     plan = step_plan(betas) if plan is None else plan
     if isinstance(timestep, int):
         t_index = timestep
@@ -299,7 +328,7 @@ def _reverse_step(model, ligand_mask, x_t, receptor_seq, receptor_mask, receptor
     if receptor_cache is None:
         receptor_cache = model.encode_receptor(receptor_seq, receptor_angle, receptor_mask)
     eps_hat = model.decode(timestep, x_t, ligand_mask, receptor_cache, mod=mod, layout=layout)
-    x = plan.update(x_t.contiguous().float(), eps_hat, t_dev, noise, out, wrap, t_index)
+    x = plan.update(x_t.contiguous().float(), eps_hat, t_dev, noise, out, wrap, t_index, history)
     return plan.compose(x, t_dev, known_noise, t_index)
 
 
@@ -310,7 +339,9 @@ class GraphedReverseStep:
     bit-identical to the eager path for the same noise, or the same keys.  A keyed plan generates its draws inside the
     kernels from the step index and a strided one at eta == 0 draws nothing: no noise buffer.  Held positions add one
     launch after the update, on the same stream and on ``self.out``, and, unseeded, a second noise buffer filled inside
-    the graph; the captured step stays one serial chain.
+    the graph; the captured step stays one serial chain.  A multistep plan has no noise buffer either; its x0 history
+    (``self.history``) is owned here, lives across replays and is updated in place inside the graph.  It starts as NaN
+    and the warm-up leaves an estimate of no chain in it: the first visited timestep of a chain does not read it.
 
     Default for chains of at most packing.GRAPH_MAX_ROWS token rows (up to ~16 pockets of 64 residues),
     ``use_graph=True`` / E3D_SAMPLE_GRAPH=1 forces it, =0 turns it off.  Measured on MI355X, one 64-residue pocket
@@ -318,10 +349,10 @@ class GraphedReverseStep:
     are host-bound at 2.4 ms per step, a replay takes 1.5 ms."""
 
     def __init__(self, model, ligand_mask, cache, tab, x_like, wrap=True, draw=True, mod_table=None, layout=None,
-                 row_keys=None, seed=None, strided=None, wrap_x0=False, known=None):
+                 row_keys=None, seed=None, strided=None, wrap_x0=False, known=None, multistep=None):
         """``tab``: the chain's StepPlan (``step_plan(..., table=True)``: the other plan arguments are then not read), or
-        its schedule -- the plan is then built here from ``row_keys`` + ``seed``, ``strided`` (+ ``wrap_x0``) and ``known``
-        = (x0, uint8 mask -- both like ``x_like`` --, KnownLevels, scale), as ``step_plan`` takes them.
+        its schedule -- the plan is then built here from ``row_keys`` + ``seed``, ``strided`` or ``multistep`` (+
+        ``wrap_x0``) and ``known`` = (x0, uint8 mask -- both like ``x_like`` --, KnownLevels, scale), as ``step_plan`` takes them.
         ``draw``: the graph draws its own N(0,1) noise each replay; False: ``step`` takes the draws (parity tests) -- the
         update's and, with held positions, theirs next to it.  A keyed plan draws inside its kernels and needs ``draw``.
         ``mod_table`` [T,6H]: row t = model.timestep_modulation(t), read on the device by the step index.
@@ -329,7 +360,7 @@ class GraphedReverseStep:
         tables are device tensors fixed for the chain, so the capture holds them like any other argument."""
         dev = x_like.device
         plan = tab if isinstance(tab, StepPlan) else step_plan(tab, dev, True, strided, wrap_x0, row_keys, seed,
-                                                               *(known or (None, None, None, 1.0)))
+                                                               *(known or (None, None, None, 1.0)), multistep=multistep)
         if plan.keyed is not None and not draw:
             raise ValueError("a keyed graph draws its own noise")
         if plan.coef is None:
@@ -340,6 +371,7 @@ class GraphedReverseStep:
         # a noise buffer only where some step of the chain reads one (none: keyed draws, or strided at eta == 0)
         self.noise = torch.zeros_like(x_like) if any(map(plan.update_draws, plan.order)) else None
         self.known_noise = torch.zeros_like(x_like) if any(map(plan.compose_draws, plan.order)) else None
+        self.history = torch.full_like(x_like, float("nan")) if plan.multistep is not None else None
         # a valid row for the warm-up and the capture (unvisited rows of a strided or level table are NaN)
         self.t = torch.full((x_like.shape[0],), plan.order[-1], device=dev, dtype=torch.long)
         # The warm-up step draws from torch's generator and its state is not put back (the sequence sampler's
@@ -351,7 +383,7 @@ class GraphedReverseStep:
         eps_hat = self.model.decode(self.t, self.x, self.mask, self.cache, mod=mod, layout=self.layout)
         if self.draw and self.noise is not None:
             self.noise.normal_()
-        self.plan.update(self.x, eps_hat, self.t, self.noise, self.out, self.wrap)
+        self.plan.update(self.x, eps_hat, self.t, self.noise, self.out, self.wrap, history=self.history)
         if self.draw and self.known_noise is not None:
             self.known_noise.normal_()
         self.plan.compose(self.out, self.t, self.known_noise)
@@ -413,7 +445,15 @@ def p_sample_loop(model: nn.Module, ligand_mask, ligand_angle_noise, receptor_se
     random number is drawn and torch's generator is left alone; 1: the ancestral variance of the respaced chain),
     ``wrap_x0`` wraps each step's x0 estimate to [-pi, pi).  The last entry, t = 0, is the wrapped x0 estimate.  Seeded
     strided chains draw the same stream-1 normals at timestep t as seeded ancestral ones.  ``eta`` / ``wrap_x0`` with
-    the ancestral update raise.
+    the ancestral update raise.  "multistep" makes the same jumps with the second-order multistep update DPM-Solver++(2M)
+    (Lu et al. 2022; utils.MultistepTables, ``e3d_multistep_step_wrap``): DDIM's update with the x0 estimate extrapolated
+    from the previous step's, which the chain keeps in a history buffer in its own frame (a captured step owns one that
+    lives across replays).  The extrapolation weight is capped at 0.5, a deliberate difference from the paper (see
+    MultistepTables).  One decoder forward per step, no random number drawn, torch's generator left alone; ``wrap_x0`` as
+    for "strided"; an ``eta`` other than 0 raises.  The first entry equals that of "strided" at eta = 0, and a chain with
+    one visited timestep is the x0 estimate.  Under a ``seed`` only the held positions draw (stream 10).  On a model whose
+    probability-flow ODE has a closed form its end point is 2.3x to 134x closer to the exact one than DDIM's at 10 to 50
+    steps; sample quality has not been measured (no trained checkpoint ships with the tree).
 
     Partial redesign -- ``known`` [B, L, n_ft] + ``known_mask`` (bool [B, L]: whole residues, or [B, L, n_ft]: per
     element, e.g. hold a residue's dihedrals and free its bond angles): the masked ligand positions are held at ``known``
@@ -428,14 +468,17 @@ def p_sample_loop(model: nn.Module, ligand_mask, ligand_angle_noise, receptor_se
     they are keyed stream 10 at the step's index, and streams 0 / 1 -- the free positions' draws -- are untouched.  A mask
     with nothing set runs the chain exactly as without these arguments.  There is no resampling loop (RePaint's jumps
     back), and sample quality has not been measured here (no trained checkpoint ships with the tree)."""
-    if update not in ("ancestral", "strided"):
-        raise ValueError(f"p_sample_loop: update must be 'ancestral' or 'strided', got {update!r}")
+    if update not in ("ancestral", "strided", "multistep"):
+        raise ValueError(f"p_sample_loop: update must be 'ancestral', 'strided' or 'multistep', got {update!r}")
     if update == "ancestral" and (eta != 0.0 or wrap_x0):
-        raise ValueError("p_sample_loop: eta and wrap_x0 belong to update='strided'")
+        raise ValueError("p_sample_loop: eta belongs to update='strided', wrap_x0 to 'strided' or 'multistep'")
+    if update == "multistep" and eta != 0.0:
+        raise ValueError("p_sample_loop: update='multistep' draws nothing; eta belongs to update='strided'")
     step = STEP if step is None else step
     tab = _tables(betas)
     order = list(reversed(range(0, total_timesteps, step)))
     strided = StridedTables(tab, order, eta) if update == "strided" else None
+    multistep = MultistepTables(tab, order) if update == "multistep" else None
     x = ligand_angle_noise.contiguous().float()
     x0, m8, known_noises = _known_chain(known, known_mask, known_noises, seed, ligand_mask, x, len(order), "p_sample_loop")
     if x0 is not None and (noises is None) != (known_noises is None) and seed is None:
@@ -461,7 +504,8 @@ def p_sample_loop(model: nn.Module, ligand_mask, ligand_angle_noise, receptor_se
         known_noises = None if known_noises is None else frame.ligand(known_noises, dim=1)
     plan = step_plan(tab, x.device, table=True, strided=strided, wrap_x0=wrap_x0,
                      row_keys=None if seed is None else frame.row_keys(ids, x.device), seed=seed, known=x0, known_mask=m8,
-                     known_levels=None if x0 is None else KnownLevels(tab, order), known_scale=known_scale)
+                     known_levels=None if x0 is None else KnownLevels(tab, order), known_scale=known_scale,
+                     multistep=multistep)
     traj = torch.empty((len(order),) + tuple(x.shape), device=x.device, dtype=torch.float32)
     # what depends on the timestep alone, for the whole chain at once: row t of the table = timestep_modulation(t)
     mod_rows = model.timestep_modulation(torch.tensor(order, device=x.device, dtype=torch.long))
@@ -470,6 +514,8 @@ def p_sample_loop(model: nn.Module, ligand_mask, ligand_angle_noise, receptor_se
     graphed = packing.capture_graph(
         lambda: GraphedReverseStep(model, mask, cache, plan, x, draw=noises is None, mod_table=mod_table, layout=layout),
         frame.rows, len(order), use_graph)
+    # the eager chain's x0 history, in the chain's frame (a captured step owns its own); NaN until the first step stores one
+    history = torch.full_like(x, float("nan")) if multistep is not None and graphed is None else None
     for n, i in enumerate(order):
         kn = None if known_noises is None else known_noises[n].contiguous()
         if graphed is not None:
@@ -477,7 +523,8 @@ def p_sample_loop(model: nn.Module, ligand_mask, ligand_angle_noise, receptor_se
             traj[n].copy_(x)
         else:
             x = _reverse_step(model, mask, x, None, None, None, i, tab, None if noises is None else noises[n], cache,
-                              traj[n], wrap=True, mod=mod_table[i:i + 1], layout=layout, plan=plan, known_noise=kn)
+                              traj[n], wrap=True, mod=mod_table[i:i + 1], layout=layout, plan=plan, known_noise=kn,
+                              history=history)
     traj = frame.restore(traj, dim=1)                                     # [T/STEP, B, L, F], zeros outside the frame
     return traj if return_device else traj.cpu()
 

@@ -104,6 +104,75 @@ class StridedTables:
         return self.order[k + 1] if k + 1 < len(self.order) else -1
 
 
+class MultistepTables:
+    """Coefficients of the second-order multistep update over a subset of the timesteps: DPM-Solver++(2M) of Lu et al.
+    2022 in its data-prediction form, with the extrapolation weight capped.  One decoder forward per step, like the
+    strided update; it keeps the previous step's x0 estimate and draws nothing.
+
+    ``order``: the visited timesteps, strictly descending, as for ``StridedTables``; same successors.
+
+    With lambda(a) = ln(a / (1 - a)) / 2 (half the log-SNR) and h_k = lambda(ab_s) - lambda(ab_t) at order[k], the rule
+    replaces the x0 estimate of the eta = 0 strided (DDIM) update by x0 + w_k (x0 - x0_prev):
+
+        w_k = 0                                  at the first visited timestep (no history) and the last (h is infinite)
+        w_k = min(h_k / (2 h_{k-1}), w_max)      otherwise
+
+    ``w_max`` = 0.5 by default; None gives the paper's uncapped weight.  The cap is a deliberate difference from the
+    paper: the visited timesteps are uniform in t and beta_0 is clipped, so the jump that lands on t = 0 spans a log-SNR
+    step several times its predecessor's (w = 2.1 at T = 1000, step 100) and the uncapped rule can then be worse than
+    DDIM; 0.5 is the weight of equal steps.  ``weights`` (float64 [len(order)]) holds the w_k, so a caller sees where the
+    cap acted.
+
+    Derived in float64 from ``tab.betas`` with ab = cumprod(1 - betas), each coefficient rounded to fp32 once.  In the
+    DDIM update the x0 estimate carries the factor a_s - sqrt(ab_t) c_dir / s1m (the rest of it multiplies x), hence
+
+        c_1 = (a_s - sqrt(ab_t) c_dir / s1m) w_k
+
+    ``coef`` fp32 [T, 8]: row t = (s1m, rsa, a_s, c_dir, c_1, 0, 0, 0), the first four bit-identical to
+    ``StridedTables(tab, order, 0.0).coef`` -- the table ``e3d_multistep_step_wrap`` reads by the device step index;
+    rows of timesteps that are not visited are NaN.
+    """
+
+    def __init__(self, tab: CosineTables, order, w_max=0.5):
+        T = int(tab.betas.shape[0])
+        order = [int(t) for t in order]
+        if w_max is not None and not float(w_max) >= 0.0:
+            raise ValueError(f"MultistepTables: w_max must be None or at least 0, got {w_max}")
+        if not order:
+            raise ValueError("MultistepTables: the order of timesteps is empty")
+        if any(t < 0 or t >= T for t in order):
+            raise ValueError(f"MultistepTables: timesteps must lie in [0, {T}), got {order}")
+        if any(a <= b for a, b in zip(order, order[1:])):
+            raise ValueError(f"MultistepTables: the order must be strictly descending, got {order}")
+        ab = torch.cumprod(1.0 - tab.betas.double(), dim=0)
+        idx = torch.tensor(order, dtype=torch.long)
+        ab_t = ab[idx]
+        ab_s = torch.cat([ab[idx[1:]], torch.ones(1, dtype=torch.float64)])
+        n = len(order)
+        w = torch.zeros(n, dtype=torch.float64)
+        if n > 2:
+            lam = 0.5 * torch.log(ab_t / (1.0 - ab_t))
+            h = lam[1:] - lam[:-1]                      # h[k] of order[k], k < n - 1
+            w[1:n - 1] = h[1:] / (2.0 * h[:-1])
+            if w_max is not None:
+                w = torch.clamp(w, max=float(w_max))
+        rows = torch.zeros((n, 8), dtype=torch.float64)
+        rows[:, 0] = torch.sqrt(1.0 - ab_t)
+        rows[:, 1] = 1.0 / torch.sqrt(ab_t)
+        rows[:, 2] = torch.sqrt(ab_s)
+        rows[:, 3] = torch.sqrt(torch.clamp(1.0 - ab_s, min=0.0))
+        rows[:, 4] = (rows[:, 2] - torch.sqrt(ab_t) * rows[:, 3] / rows[:, 0]) * w
+        self.timesteps, self.order, self.w_max = T, order, None if w_max is None else float(w_max)
+        self.weights = w
+        self.coef = torch.full((T, 8), float("nan"), dtype=torch.float32)
+        self.coef[idx] = rows.float()
+
+    def successor(self, t: int) -> int:
+        """The timestep the update at ``t`` lands on; -1 after the last visited one."""
+        k = self.order.index(int(t))
+        return self.order[k + 1] if k + 1 < len(self.order) else -1
+
+
 class KnownLevels:
     """Noise levels of the held positions of a partial redesign (replacement conditioning; sample.py, ``known=``): the
     level the state is on AFTER the step at each visited timestep, whatever the update rule and the stride are.

@@ -261,6 +261,21 @@ int e3d_ddpm_step_wrap_table(const float* x, const float* eps_hat, const float* 
 int e3d_strided_step_wrap(const float* x, const float* eps_hat, const float* noise, const float* coef_table,
                           const int64_t* t_dev, int T, int wrap, int wrap_x0, float* out, int64_t n, void* stream);
 
+/* One second-order multistep update t -> s < t: DPM-Solver++(2M) of Lu et al. 2022 in its data-prediction form, with
+ * the extrapolation weight capped (structure_model/utils.py, MultistepTables).  It is the strided update at eta = 0 plus
+ * one term built from the x0 estimate that the previous step stored; it draws nothing.  Per element:
+ *   x0 = (x - s1m * eps_hat) * rsa;   wrap_x0: x0 = wrap_[-pi,pi)(x0)
+ *   v  = a_s * x0 + c_dir * eps_hat
+ *   c_1 != 0:  d = x0 - hist_in;   wrap: d = wrap_[-pi,pi)(d);   v = v + c_1 * d
+ *   hist_out = x0;   out = wrap ? wrap_[-pi,pi)(v) : v
+ * with (s1m, rsa, a_s, c_dir, c_1, 0, 0, 0) = row t_dev[0] of coef_table [T,8].  A row with c_1 == 0 (the first and the
+ * last visited timestep) reads nothing through hist_in and gives the bits of e3d_strided_step_wrap at sigma == 0.
+ * t_dev[0] outside [0, T): no table row is read and out and hist_out are NaN.  out may alias x and hist_out may alias
+ * hist_in; out and hist_out are two buffers.  All five arrays 16-byte aligned.  n = number of elements. */
+int e3d_multistep_step_wrap(const float* x, const float* eps_hat, const float* hist_in, const float* coef_table,
+                            const int64_t* t_dev, int T, int wrap, int wrap_x0, float* out, float* hist_out, int64_t n,
+                            void* stream);
+
 /* Forward noising q(x_t | x_0) with wrap (structure_model/dataset.py:211-228):
  *   out[b] = wrap(sqrt_ab[t[b]] * x0[b] + sqrt_1mab[t[b]] * noise[b]),  per = elements per item. */
 int e3d_q_sample_wrap(const float* x0, const float* noise, const int64_t* t,

@@ -96,8 +96,8 @@ def main():
     ap.add_argument("--pack", action="store_true", help="pack=True in both chains (the valid rows of every item back to back)")
     ap.add_argument("--seed", type=int, default=None, help="keyed draws in both chains, items keyed 0 .. batch-1 "
                     "(default: torch's generator)")
-    ap.add_argument("--update", choices=("ancestral", "strided"), default="ancestral", help="structure chain; strided: the DDIM / "
-                    "respaced update between visited timesteps")
+    ap.add_argument("--update", choices=("ancestral", "strided", "multistep"), default="ancestral", help="structure chain; strided: the DDIM / "
+                    "respaced update between visited timesteps; multistep: the second-order multistep update between them")
     ap.add_argument("--eta", type=float, default=0.0, help="noise scale of the strided update in [0, 1] (0: deterministic)")
     ap.add_argument("--wrap-x0", action="store_true", help="strided update: wrap the x0 estimate to [-pi, pi)")
     ap.add_argument("--stride", type=int, default=1, help="structure chain: visit every STRIDE-th timestep")

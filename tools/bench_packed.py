@@ -10,6 +10,7 @@ noise.  Then the sequence chain at tools/bench_joint.py's size (``sequence_leg``
     python tools/bench_packed.py [--steps K] [--warmup W]
     python tools/bench_packed.py --leg packed|trimmed --steps K      # only that leg's eager steps (for rocprofv3)
     python tools/bench_packed.py --update strided [--eta E] [--wrap-x0]   # the timed steps run the strided (DDIM) update
+    python tools/bench_packed.py --update multistep [--wrap-x0]           # ... the second-order multistep update
     python tools/bench_packed.py --summarize PACKED_STATS.csv TRIMMED_STATS.csv   # attention kernels of two traces
 
 ``--summarize`` reads two ``rocprofv3 --kernel-trace --stats`` kernel tables (one run per leg) and prints the attention
@@ -143,8 +144,9 @@ def main():
     ap.add_argument("--summarize", nargs=2, metavar=("PACKED_CSV", "TRIMMED_CSV"), default=None)
     ap.add_argument("--seed", type=int, default=None, help="keyed draws in the timed chains, items keyed 0 .. B-1 "
                     "(default: torch's generator)")
-    ap.add_argument("--update", choices=("ancestral", "strided"), default="ancestral", help="update kernel of the timed "
-                    "structure steps; strided: the DDIM / respaced update (table of all 1000 timesteps, as step=1)")
+    ap.add_argument("--update", choices=("ancestral", "strided", "multistep"), default="ancestral", help="update kernel of the timed "
+                    "structure steps; strided: the DDIM / respaced update, multistep: the second-order multistep update (table of all "
+                    "1000 timesteps, as step=1)")
     ap.add_argument("--eta", type=float, default=0.0, help="noise scale of the strided update in [0, 1] (0: deterministic)")
     ap.add_argument("--wrap-x0", action="store_true", help="strided update: wrap the x0 estimate to [-pi, pi)")
     args = ap.parse_args()
@@ -173,11 +175,12 @@ def main():
     model, pkg = build(device)
     from helpers import synthetic_pockets
     from e3diff_amd.structure_model import sample as S
-    from e3diff_amd.structure_model.utils import CosineTables, StridedTables, modulo_with_wrapped_range
+    from e3diff_amd.structure_model.utils import CosineTables, MultistepTables, StridedTables, modulo_with_wrapped_range
 
     pk = {k: v.to(device) for k, v in synthetic_pockets(B, L, seed=1000).items() if torch.is_tensor(v)}
     tab = CosineTables(1000)
     st = StridedTables(tab, list(reversed(range(1000))), args.eta) if args.update == "strided" else None
+    ms = MultistepTables(tab, list(reversed(range(1000)))) if args.update == "multistep" else None
     gen = torch.Generator(device=device).manual_seed(0)
     x = modulo_with_wrapped_range(torch.randn(B, L, 8, device=device, generator=gen)).contiguous()
     lm, rm = pk["ligand_attn_mask"], pk["receptor_attn_mask"]
@@ -204,19 +207,20 @@ def main():
         """The chain's StepPlan on one frame (--update, --eta, --wrap-x0, --seed)."""
         keys = frame_keys(kind)
         return S.step_plan(tab, device, table=True, strided=st, wrap_x0=args.wrap_x0, row_keys=keys,
-                           seed=None if keys is None else args.seed)
+                           seed=None if keys is None else args.seed, multistep=ms)
 
     def eager(kind, steps):
         mask, xa, cache, layout = frame(kind)
         plan = plan_of(kind)
         xb = torch.empty_like(xa)
+        history = torch.zeros_like(xa) if ms is not None else None      # the multistep chain's x0 history, in the frame
         for k_steps in (args.warmup, steps):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for j in range(k_steps):
                 i = 999 - j
                 y = S._reverse_step(model, mask, xa, None, None, None, i, tab, None, cache, xb, True,
-                                    mod=mod_table[i:i + 1], layout=layout, plan=plan)
+                                    mod=mod_table[i:i + 1], layout=layout, plan=plan, history=history)
                 xa, xb = y, xa
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0

@@ -4,6 +4,7 @@ model (encoder cached, as `structure_model/sample.py` runs it), default arithmet
 
     python tools/bench_single.py [--seq-len 64] [--steps 50] [--graph]
     python tools/bench_single.py --steps 1000 --stride 20 --update strided [--eta E] [--wrap-x0]   # 50 visited timesteps
+    python tools/bench_single.py --steps 1000 --stride 20 --update multistep [--wrap-x0]           # the same 50, second order
     python tools/bench_single.py --keep 0-31                # partial redesign: those positions held at the pocket's ligand
 """
 import argparse
@@ -110,9 +111,9 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--graph", type=int, default=None, choices=(0, 1), help="1: replay one captured HIP graph per step, 0: eager launches (default: the sampler's own choice)")
     ap.add_argument("--seed", type=int, default=None, help="keyed draws with this seed (default: torch's generator)")
-    ap.add_argument("--update", choices=("ancestral", "strided"), default="ancestral", help="strided: the DDIM / respaced update between visited timesteps")
+    ap.add_argument("--update", choices=("ancestral", "strided", "multistep"), default="ancestral", help="strided: the DDIM / respaced update between visited timesteps; multistep: the second-order multistep update between them (eta stays 0)")
     ap.add_argument("--eta", type=float, default=0.0, help="noise scale of the strided update in [0, 1] (0: deterministic)")
-    ap.add_argument("--wrap-x0", action="store_true", help="strided update: wrap the x0 estimate to [-pi, pi)")
+    ap.add_argument("--wrap-x0", action="store_true", help="strided and multistep updates: wrap the x0 estimate to [-pi, pi)")
     ap.add_argument("--stride", type=int, default=1, help="visit every STRIDE-th timestep (p_sample_loop's step)")
     ap.add_argument("--keep", default="", help="partial redesign: ligand positions held fixed, e.g. 0-31 (the ligand then fills the frame)")
     a = ap.parse_args()
