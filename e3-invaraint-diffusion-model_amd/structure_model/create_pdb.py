@@ -52,14 +52,26 @@ def backbone_from_angles(angles: torch.Tensor, lengths: torch.Tensor, center: bo
 
 def pdb_text(coords: np.ndarray) -> str:
     """[4n,3] coordinates (N, CA, C, O per residue) -> PDB text: one GLY residue per 4 atoms,
-    chain A, single N-CA-C backbone bonds, C=O, peptide bonds C(i)-N(i+1)."""
+    chain A, single N-CA-C backbone bonds, C=O, peptide bonds C(i)-N(i+1).
+
+    The records have fixed columns: serial numbers up to 99999, residue numbers up to 9999, coordinates that ``%8.3f``
+    writes in eight characters (-999.999 .. 9999.999 after rounding, finite).  Anything else raises ValueError naming the
+    value -- a wider field would shift every later column of its line."""
     assert len(coords) % 4 == 0, f"Expected 4N coords, got {len(coords)}"
-    lines = []
-    for i, (x, y, z) in enumerate(np.asarray(coords, dtype=np.float64)):
-        name, element = _ATOMS[i % 4]
-        lines.append("ATOM  %5d %-4s %3s %1s%4d    %8.3f%8.3f%8.3f%6.2f%6.2f          %2s" % (
-            i + 1, (" " + name) if len(name) < 4 else name, "GLY", "A", i // 4 + 1, x, y, z, 1.0, 5.0, element))
     n_atoms = len(coords)
+    if n_atoms > 99999:
+        raise ValueError(f"{n_atoms} atoms do not fit the PDB serial-number columns (at most 99999)")
+    if n_atoms // 4 > 9999:
+        raise ValueError(f"{n_atoms // 4} residues do not fit the PDB residue-number columns (at most 9999)")
+    lines = []
+    for i, xyz in enumerate(np.asarray(coords, dtype=np.float64)):
+        name, element = _ATOMS[i % 4]
+        fields = ["%8.3f" % v for v in xyz]
+        for v, field in zip(xyz, fields):
+            if len(field) != 8 or not np.isfinite(v):
+                raise ValueError(f"coordinate {float(v)!r} of atom {i + 1} does not fit the PDB column %8.3f")
+        lines.append("ATOM  %5d %-4s %3s %1s%4d    %s%6.2f%6.2f          %2s" % (
+            i + 1, (" " + name) if len(name) < 4 else name, "GLY", "A", i // 4 + 1, "".join(fields), 1.0, 5.0, element))
     bonds = {k: [] for k in range(1, n_atoms + 1)}
     for r in range(n_atoms // 4):
         n, ca, c, o = (4 * r + k for k in (1, 2, 3, 4))
