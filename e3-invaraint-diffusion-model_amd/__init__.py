@@ -6,7 +6,7 @@ the C-ABI of include/e3d_hip.h (csrc/, loaded by hip.py).  No CPU fallback.
 """
 from . import hip  # noqa: F401
 
-__all__ = ["hip", "ops", "bert", "blocks", "training", "optim", "sharding", "autograd", "biolip", "featurize", "evaluate", "packing", "design", "structure_model", "sequence_model", "DesignControls", "score_sequences", "score_structures"]
+__all__ = ["hip", "ops", "bert", "blocks", "training", "optim", "sharding", "autograd", "biolip", "featurize", "evaluate", "packing", "design", "similarity", "structure_model", "sequence_model", "DesignControls", "score_sequences", "score_structures"]
 
 
 def __getattr__(name):

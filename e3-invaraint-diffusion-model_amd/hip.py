@@ -165,6 +165,9 @@ _SIGNATURES = {
     "e3d_superpose_pairs": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
     # secondary structure, hydrogen bonds, bends and clashes of backbones (evaluate.py, featurize.py)
     "e3d_backbone_geometry": (c_int, 12 * [_P] + [c_int, c_int, c_double, c_double, _P]),
+    # local alignment of sequence sets (similarity.py)
+    "e3d_align_workspace_bytes": (c_int64, [c_int, c_int]),
+    "e3d_align_pairs": (c_int, 9 * [_P] + [c_int64] + 7 * [c_int] + [_P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

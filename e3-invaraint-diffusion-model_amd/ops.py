@@ -1505,3 +1505,42 @@ def keyed_discrete_q_sample(x0_idx, qtb, item_ids, epoch, seed):
         hip.check(hip.lib().e3d_keyed_discrete_q_sample(_p(x0_idx), _p(qtb), _p(item_ids), _p(epoch), keyed.check_seed(seed),
                                                         _p(out), B, L, C, _stream()), "e3d_keyed_discrete_q_sample")
     return out
+
+
+# ---------------------------------------------------------------------------------------------- sequence alignment
+# csrc/seq_align.hip.  Queries longer than 32 residues hand a strip's last row on through a workspace of 1 MiB slots, one
+# per wave in flight: as many as there are (long query, 64 targets) items, 1024 at the most.  It is a plain allocation
+# of the call, handed back to torch's allocator on return (stream-ordered, so the launch that uses it is safe); calls
+# whose queries all fit one strip fetch none.
+ALIGN_SLOT_BYTES = 1 << 20
+ALIGN_STRIP = 32
+
+
+def align_pairs(q_codes, q_off, t_codes, t_off, subst, gap_open=11, gap_extend=1, upper_only=False, out=None,
+                long_queries=None):
+    """Local alignment (Smith-Waterman, affine gaps) of every query with every target: ``e3d_align_pairs`` as it is.
+    q_codes / t_codes u8 (indices into ``AA_VOCAB``, packed), q_off / t_off i32 [n+1], subst i8 [20,20]; returns
+    (score, matches, columns), i32 [Q,T] each -- or fills ``out``, three contiguous i32 [Q,T] tensors.  Bad sequences
+    give -2 and, with ``upper_only``, pairs t <= q give -1 (include/e3d_hip.h).  Targets are taken in the order given.
+    ``long_queries``: how many queries are longer than 32 residues, when the caller knows (True: some).  0 / False: no
+    workspace is fetched, and a longer query would count as a bad sequence; None: every query may be, unless all
+    codes together fit one strip."""
+    _chk(q_codes, "q_codes", torch.uint8); _chk(t_codes, "t_codes", torch.uint8); _chk(subst, "subst", torch.int8)
+    _chk(q_off, "q_off", torch.int32); _chk(t_off, "t_off", torch.int32)
+    Q, T = q_off.numel() - 1, t_off.numel() - 1
+    assert all(x.is_contiguous() for x in (q_codes, q_off, t_codes, t_off, subst)) and subst.numel() == 400
+    dev = q_codes.device
+    if out is None:
+        out = tuple(torch.empty((Q, T), device=dev, dtype=torch.int32) for _ in range(3))
+    for o in out:
+        _chk(o, "out", torch.int32)
+        assert o.is_contiguous() and tuple(o.shape) == (Q, T), (o.shape, o.stride())
+    if long_queries is None:
+        long_queries = q_codes.numel() > ALIGN_STRIP
+    n_long = Q if long_queries is True else min(int(long_queries), Q)
+    ws = torch.empty(hip.lib().e3d_align_workspace_bytes(n_long, T), dtype=torch.uint8, device=dev) if n_long else None
+    hip.check(hip.lib().e3d_align_pairs(_p(q_codes), _p(q_off), _p(t_codes), _p(t_off), _p(subst), *(_p(o) for o in out),
+                                        _p(ws), 0 if ws is None else ws.numel(), Q, T, q_codes.numel(), t_codes.numel(),
+                                        int(gap_open), int(gap_extend), int(bool(upper_only)), _stream()),
+              "e3d_align_pairs")
+    return tuple(out)

@@ -21,7 +21,7 @@ from torch.utils.data import DataLoader
 
 from .. import keyed, ops, packing
 from ..bert import BertConfig
-from .dataset import AA_VOCAB, LigandBindingSiteDataset
+from .dataset import AA_VOCAB, SPLIT_FILE, LigandBindingSiteDataset
 from .model import PeptideDiff, onehot_to_index
 from .utils import BlosumTransition, DiscreteUniformTransition, PredefinedNoiseScheduleDiscrete  # noqa: F401
 
@@ -73,7 +73,8 @@ CONFIG = {
 
 
 def get_dataloader(file_path):
-    ds = LigandBindingSiteDataset(file_path, "test", CONFIG["max_seq_len"], CONFIG["pocket_ext"])
+    ds = LigandBindingSiteDataset(file_path, "test", CONFIG["max_seq_len"], CONFIG["pocket_ext"],
+                                  split_file=SPLIT_FILE or None)   # E3D_SPLIT_FILE
     return DataLoader(dataset=ds, batch_size=CONFIG["batch_size"], shuffle=False, num_workers=THREAD_NUM)
 
 

@@ -21,7 +21,7 @@ from torch.utils.data.distributed import DistributedSampler
 
 from .. import training
 from ..bert import BertConfig
-from .dataset import LigandBindingSiteDataset
+from .dataset import SPLIT_FILE, LigandBindingSiteDataset
 from .model import PeptideDiff
 
 MODEL_PATH = ""
@@ -66,7 +66,8 @@ def get_dataloader(file_path, records=None, seed=None):
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     out = []
     for split, shuffle in (("train", True), ("validation", False)):
-        ds = LigandBindingSiteDataset(file_path, split, CONFIG["max_seq_len"], CONFIG["pocket_ext"], records=records)
+        ds = LigandBindingSiteDataset(file_path, split, CONFIG["max_seq_len"], CONFIG["pocket_ext"], records=records,
+                                      split_file=SPLIT_FILE or None)
         if seed is not None:
             ds = training.ItemIdDataset(ds)
         sampler = DistributedSampler(ds, num_replicas=world, rank=rank, shuffle=shuffle) if world > 1 else None

@@ -6,6 +6,8 @@ The tensor layout of an item is the drop-in contract with the reference
 reference's per-item host path (DataLoader workers); ``noise_batch_on_device`` is the batched HIP
 path for training loops that already hold the batch in HBM.
 """
+import json
+import os
 import random
 from typing import Dict, Optional
 
@@ -20,6 +22,30 @@ from .utils import CosineTables, modulo_with_wrapped_range
 RANDOM_SEED = 0
 AA_VOCAB = "ACDEFGHIKLMNPQRSTVWY"
 SS_VOCAB = "HBEGITS-"
+# A split file (tools/split_dataset.py) for the training and sampling entry points; read once, at import.  Empty: the
+# reference's random 80/10/10.
+SPLIT_FILE = os.environ.get("E3D_SPLIT_FILE", "")
+SPLIT_NAMES = ("train", "validation", "test")
+
+
+def split_key(record):
+    ids = record["structure_ids"]
+    return f"{ids['pdb_id']}:{ids['receptor_chain']}:{ids['ligand_chain']}"
+
+
+def read_split_file(path, records):
+    """The split name of every record, in order, from a JSON file {"records": [[key, split], ...]} whose keys
+    ("pdb_id:receptor_chain:ligand_chain") must be those of ``records``, one for one and in the same order."""
+    with open(path) as f:
+        rows = json.load(f)["records"]
+    if len(rows) != len(records):
+        raise ValueError(f"{path}: {len(rows)} entries for {len(records)} records")
+    for i, (row, rec) in enumerate(zip(rows, records)):
+        if row[0] != split_key(rec):
+            raise ValueError(f"{path}: entry {i} is {row[0]!r}, record {i} is {split_key(rec)!r}")
+        if row[1] not in SPLIT_NAMES:
+            raise ValueError(f"{path}: entry {i} ({row[0]}) names the split {row[1]!r}, not one of {SPLIT_NAMES}")
+    return [row[1] for row in rows]
 
 
 def _one_hot(symbols, vocab):
@@ -42,9 +68,12 @@ class LigandBindingSiteDataset(Dataset):
     with_ligand_seq = False  # the sequence model's dataset adds "ligand_seq"
 
     def __init__(self, filepath: str, split: Optional[str], max_len: int = 64, pocket_ext: int = 1,
-                 records=None) -> None:
+                 records=None, split_file: Optional[str] = None) -> None:
         """filepath: a ``biolip.pt`` (torch.save of list[dict], clean_data/data_preprocessing.py:880-892);
-        split: "train" | "validation" | "test" | None; ``records`` bypasses the file (synthetic data)."""
+        split: "train" | "validation" | "test" | None; ``records`` bypasses the file (synthetic data).
+        split_file: a JSON file of tools/split_dataset.py that names the split of every record, in file order (splits
+        by sequence cluster, similarity.py); the dataset then holds the records it assigns to ``split`` instead of a
+        slice of the random 80/10/10.  None: the splits are what they always were."""
         super().__init__()
         self.max_len, self.pocket_ext = max_len, pocket_ext
         if records is None:
@@ -54,7 +83,23 @@ class LigandBindingSiteDataset(Dataset):
         for d in self.data:
             d["amino_acid"] = _one_hot("".join(d["amino_acid"]), AA_VOCAB)
             d["secondary_structure"] = _one_hot("".join(d["secondary_structure"]), SS_VOCAB)
-        self._split_data(split)
+        if split_file:
+            self._split_by_file(split, split_file)
+        else:
+            self._split_data(split)
+
+    def _split_by_file(self, split_name, split_file):
+        """Keep the records ``split_file`` gives to ``split_name``.  The shuffle is the one of ``_split_data``, call for
+        call, so the order within a split is deterministic and the global ``random`` stream is left as it always was."""
+        names = read_split_file(split_file, self.data)
+        for d, name in zip(self.data, names):
+            d["_split"] = name
+        random.seed(RANDOM_SEED)
+        random.shuffle(self.data)
+        if split_name is not None:
+            self.data = [d for d in self.data if d["_split"] == split_name]
+        for d in self.data:
+            del d["_split"]
 
     def _split_data(self, split_name):
         random.seed(RANDOM_SEED)

@@ -34,7 +34,7 @@ from torch import nn
 from .. import keyed, ops, packing
 from ..bert import BertConfig
 from ..packing import trimmed_length  # noqa: F401  (S.trimmed_length: bench.py and the tests read it here)
-from .dataset import LigandBindingSiteDataset, NoisedAnglesDataset
+from .dataset import SPLIT_FILE, LigandBindingSiteDataset, NoisedAnglesDataset
 from .model import ConditionalBertForDiffusion, ReceptorCache
 from .utils import CosineTables, KnownLevels, MultistepTables, ScoreTables, StridedTables
 
@@ -732,7 +732,8 @@ def score_structures(model, ligand_mask, angles, receptor_seq, receptor_mask, re
 
 
 def get_dataset(file_path):
-    ds = LigandBindingSiteDataset(file_path, "test", CONFIG["max_seq_len"], CONFIG["pocket_ext"])
+    ds = LigandBindingSiteDataset(file_path, "test", CONFIG["max_seq_len"], CONFIG["pocket_ext"],
+                                  split_file=SPLIT_FILE or None)   # E3D_SPLIT_FILE
     return NoisedAnglesDataset(ds, timesteps=CONFIG["timesteps"])
 
 

@@ -20,7 +20,7 @@ from torch.utils.data.distributed import DistributedSampler
 
 from .. import training
 from ..bert import BertConfig
-from .dataset import LigandBindingSiteDataset, NoisedAnglesDataset
+from .dataset import SPLIT_FILE, LigandBindingSiteDataset, NoisedAnglesDataset
 from .model import ConditionalBertForDiffusion
 
 MODEL_PATH = ""          # where the final state_dict is written
@@ -72,7 +72,8 @@ def get_dataloader(file_path, records=None, seed=None):
     seed = SEED if seed is None else seed
     out = []
     for split, shuffle in (("train", True), ("validation", False)):
-        ds = LigandBindingSiteDataset(file_path, split, CONFIG["max_seq_len"], CONFIG["pocket_ext"], records=records)
+        ds = LigandBindingSiteDataset(file_path, split, CONFIG["max_seq_len"], CONFIG["pocket_ext"], records=records,
+                                      split_file=SPLIT_FILE or None)
         ds = NoisedAnglesDataset(ds, timesteps=CONFIG["timesteps"])
         if seed is not None:
             ds = training.ItemIdDataset(ds, skip_noising=True)

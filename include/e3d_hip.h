@@ -950,6 +950,46 @@ int e3d_backbone_geometry(const double* coords, const int32_t* off, const uint8_
                           int32_t* status, int n_structs, int n_residues, double clash_cutoff, double max_peptide_bond,
                           void* stream);
 
+/* ---- local alignment of sequence sets (similarity.py; an addition to ABI v5)
+ * Smith-Waterman with affine gaps (Gotoh) of every query with every target, in integers: per pair the score of the best
+ * local alignment and two counters of the path that produced it, from which the caller forms an identity.  No traceback.
+ *   q_codes uint8 [n_q_codes], q_off int32 [n_q+1]: query s holds codes q_off[s] .. q_off[s+1]-1, packed back to back (the
+ *   convention of e3d_backbone_geometry); t_codes, t_off [n_t+1] likewise.  A code is an index 0..19 into
+ *   "ACDEFGHIKLMNPQRSTVWY".  subst int8 [20*20]: the substitution matrix in that order, the caller's choice (similarity.py
+ *   passes BLOSUM62).  score, matches, columns int32 [n_q, n_t], row-major.  All on the device.
+ *   Query a[1..m], target b[1..n], go = gap_open, ge = gap_extend; a gap of k columns costs go + k ge (blastp's convention):
+ *     E[i][j] = max(H[i][j-1] - (go+ge), E[i][j-1] - ge)        the column consumes b_j only
+ *     F[i][j] = max(H[i-1][j] - (go+ge), F[i-1][j] - ge)        the column consumes a_i only
+ *     H[i][j] = max(0, H[i-1][j-1] + S[a_i][b_j], E[i][j], F[i][j])
+ *   H[0][*] = H[*][0] = 0; E and F are minus infinity on the boundary (int32 arithmetic, nothing wraps).
+ *   H, E and F each carry the counters of the path behind their value: matches, the diagonal columns with a_i == b_j, and
+ *   columns, all columns, gaps included.  TIE RULES (identity depends on which co-optimal alignment is taken): E and F, on
+ *   equal value opening from H wins over extending; H, the diagonal wins over E and E over F, a later candidate replaces an
+ *   earlier one only if strictly greater; a winner <= 0 makes the cell (0, 0, 0).  The pair's result is the cell with the
+ *   largest H, among equals the smallest i, then the smallest j; a pair with no positive cell gives (0, 0, 0).
+ *   tests/align_ref.py restates this in Python.
+ *   Lengths 1 .. E3D_ALIGN_MAX_LEN; scores then stay below 2^14 for matrix entries up to 11 and counters below 2^16.
+ *   upper_only != 0: pairs with t <= q are not looked at and are written (-1, -1, -1), whatever their sequences are (a set
+ *   against itself).
+ *   Checked on the device: a sequence whose offsets are out of order or outside [0, n_codes], whose length is 0 or above
+ *   the cap, or that holds a code >= 20 is never read through, and every pair it takes part in is written (-2, -2, -2);
+ *   nothing faults, nothing outside [n_q, n_t] is written.  Offsets that make sequences overlap are memory-safe.
+ *   workspace: queries longer than 32 residues need one: any whole number of 1 MiB slots, each serves one wave at a time
+ *   (e3d_align_workspace_bytes(n_q, n_t) is the size that keeps the device busy), not shared between calls that may run
+ *   concurrently.  Null, or smaller than a slot: the cap on QUERY length of this call is 32, and a longer query is a bad
+ *   sequence like one above E3D_ALIGN_MAX_LEN (targets are not affected).
+ *   A pair's three numbers depend on its two sequences, the matrix and the gap costs only -- not on n_q, n_t, its place or
+ *   its neighbours.  One lane per pair, the lanes of a wave share the query and take consecutive targets: sort the targets
+ *   by length for speed (any order is correct).  Two launches on one stream, no atomics, no host synchronisation.
+ * Validates before any launch: every pointer but workspace non-null; n_q, n_t > 0; n_q_codes, n_t_codes >= 0;
+ * gap_open >= 0, gap_extend >= 1, gap_open + gap_extend <= 127. */
+#define E3D_ALIGN_MAX_LEN 1024
+int64_t e3d_align_workspace_bytes(int n_q, int n_t);
+int e3d_align_pairs(const uint8_t* q_codes, const int32_t* q_off, const uint8_t* t_codes, const int32_t* t_off,
+                    const int8_t* subst, int32_t* score, int32_t* matches, int32_t* columns, void* workspace,
+                    int64_t workspace_bytes, int n_q, int n_t, int n_q_codes, int n_t_codes, int gap_open, int gap_extend,
+                    int upper_only, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
